@@ -11,8 +11,13 @@ s mod G.  Every stream keeps `--slots` consecutive frames resident in HBM and th
 per-step working set (>= 4 x ~110 MB of raw features + the stereo sets and scratch) does not fit the 256 MB Infinity Cache.
 Prints ONE JSON line (rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--slots S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--slots S] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times exactly K steps once and prints the line.  `--full` adds everything else the benchmark
+measures or checks, after the timed region: the region repeated (`--repeats`, median), rocm-smi clocks, per-stage and roofline
+passes, the oracle parity sample, the extra legs, the CPU baselines and the full record in bench_extras.json.  `--dump-outputs DIR`
+writes the results of the last timed step as DIR/<name>.npy (the inputs are seeded: the same arguments give the same streams).
 
 `--gpus N` without a torch.distributed environment re-executes itself under torch.distributed.run with N ranks (one
 process per GPU, RCCL).  Multi-GPU: the path has no exchange step — the only collectives are the timing barrier and the
@@ -116,7 +121,7 @@ def _gen_stream(args):
 
 def generate_streams(seq_ids, replicas, n_frames, n_pts, n_lines, cluster_kw=None):
     jobs = [(s, r, n_frames, n_pts, n_lines, cluster_kw) for s, r in zip(seq_ids, replicas)]
-    nproc = min(32, os.cpu_count() or 1, max(1, len(jobs) // 8))
+    nproc = min(16, os.cpu_count() or 1, max(1, len(jobs) // 8))   # (at most 16 workers, as for the configs[3] sequences)
     if nproc <= 1:
         return [_gen_stream(j) for j in jobs]
     import multiprocessing as mp
@@ -773,6 +778,35 @@ def configs3_leg(local_rank, seqs, B=512, steps=10):
                    "only as the fallback of :359")
     return out
 
+
+def headline_record(args, world, backend, frames_total, dt, rep_dt, per_rank, streams, ok_frac):
+    """The record of the timed region: the contract's keys and the workload — all a run without --full reports."""
+    B, S = len(streams), len(streams[0])
+    n_kp = np.array([[len(st[k]["kp_l"]) + len(st[k]["kp_r"]) for k in range(S)] for st in streams], np.float64)  # [B][S]
+    resident_mb = S * B * (2 * 2048 * (8 + 32) + 2048 * 4 + 2 * 512 * (16 + 32) + 512 * 4) / 1e6
+    return {
+        "metric": "stereo frames/s (match+optimizePose)", "value": frames_total / dt, "unit": "frame-pairs/s",
+        "n_gpus": world, "rccl_ranks": world, "collective_backend": ("rccl" if backend == "nccl" else backend), "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "repeats": {"n": len(rep_dt), "statistic": "median", "value_min": frames_total / max(rep_dt), "value_max": frames_total / min(rep_dt),
+                    "ms_per_step_all": [d / args.steps * 1e3 for d in rep_dt]},
+        "parity_sampled": None,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/fp4+f64", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[2]: KITTI-00-shaped stereo with points + lines (ORB + LBD rows), grid-windowed stereo "
+                               "match (points and lines) + f2f brute-force mutual-NNR match (points and lines) + full GN optimizePose "
+                               "(config_kitti.yaml), device-resident per-frame pipeline; the streams cycle through the 8 sequence ids / 3 "
+                               "KITTI calibrations of configs[4] (sequence s on rank s mod G)",
+                   "streams_per_gpu": B, "resident_frames_per_stream": S, "slot_order": "ping-pong",
+                   "resident_raw_features_MB_per_gpu": resident_mb,
+                   "keypoints_per_image": float(n_kp.mean() / 2), "keylines_per_image": float(np.mean([len(st[0]["kl_l"]) for st in streams])),
+                   "cameras": "kitti00-02 (seq 0-2), kitti03 (seq 3), kitti04-10 (seq 4-7)",
+                   "parallelism": f"seq-shard x{world}", "committed_pose_fraction": ok_frac},
+        "per_rank_frame_pairs_per_s": per_rank if world > 1 else None,
+        # (the driver computes scaling efficiency itself; this is a convenience when the N = 1 value of the same box is handed in)
+        "scaling_efficiency_vs_n1": (frames_total / dt / (world * float(os.environ["STVO_N1_VALUE"]))
+                                     if world > 1 and os.environ.get("STVO_N1_VALUE") else None),
+    }
+
+
 SHORT_LINE_MAX = 6000   # bytes: the driver keeps a bounded tail of stdout — round 5's 20 KB line was recorded as "parsed": null
 
 
@@ -879,6 +913,26 @@ def write_extras(full, path=None):
     return written
 
 
+DUMP_MAX_BYTES = 63 * 10**6   # (--dump-outputs writes at most 64 MB, the .npy headers included)
+
+
+def dump_outputs(out_dir, res, counts, suffix=""):
+    """--dump-outputs: the last timed step's stvo_seq_read results — every field of the pose record of every stream and the
+    per-stream set sizes (stereo points, stereo lines, matched points, matched lines) — as float64 arrays, one DIR/<name>.npy each.
+    Past DUMP_MAX_BYTES in all, a fixed seeded sample of the streams is written, with their indices in stream_index.npy."""
+    arrays = {name: res[name].astype(np.float64) for name in res.dtype.names}
+    arrays["counts"] = counts.astype(np.float64)
+    n = len(counts)
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // (row_bytes + 8), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["stream_index"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -892,15 +946,24 @@ def main():
     ap.add_argument("--lines", type=int, default=85, help="3-D segments per stream; + 20 %% distractors ~ 100 key-lines per image")
     ap.add_argument("--max-keylines", type=int, default=128,
                     help="key-line capacity per image of the pipeline (config_kitti.yaml: lsd_nfeatures 100; the library allows up to 512)")
-    ap.add_argument("--repeats", type=int, default=5, help="the timed region (exactly --steps steps between barriers) is repeated this often; value = median")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle parity sample after the timed region (counter passes: every dispatch costs seconds)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-clocks", action="store_true", help="skip the rocm-smi clock sample (it keeps enqueueing steps until rocm-smi answers: counter passes, where every dispatch costs seconds)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the latency / configs[1] / correlated-descriptor legs")
-    ap.add_argument("--print-extras", action="store_true", help="also print the full record (bench_extras.json) on stderr")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region (exactly --steps steps between barriers) is repeated this often; value = median "
+                    "(default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: repeated timed regions, the rocm-smi clock sample, the per-stage "
+                    "and roofline passes, the oracle parity sample, the extra legs, the CPU baselines and bench_extras.json.  Without it a run sets up, "
+                    "warms up, times --steps steps once and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (the pose results and set sizes a "
+                    "caller of stvo_seq_read receives, one float64 .npy per field) into DIR")
+    ap.add_argument("--no-parity", action="store_true", help="(--full) skip the oracle parity sample after the timed region (counter passes: every dispatch costs seconds)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
+    ap.add_argument("--no-clocks", action="store_true", help="(--full) skip the rocm-smi clock sample (it keeps enqueueing steps until rocm-smi answers: counter passes, where every dispatch costs seconds)")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the latency / configs[1] / correlated-descriptor legs")
+    ap.add_argument("--print-extras", action="store_true", help="(--full) also print the full record (bench_extras.json) on stderr")
     ap.add_argument("--streams-cache", default=None, help="pickle file for the synthetic streams of rank 0: written when absent, read when present — counter passes "
                     "(rocprofv3 --pmc) then start without forking generator processes under the profiler, which is where they tend to hang on this pool")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    extras = args.full and not args.no_extras
 
     # ---- `--gpus N` from a plain `python bench.py`: spawn N ranks (one process per GPU) under torch.distributed.run
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -934,10 +997,10 @@ def main():
             with open(cache, "wb") as f:
                 pickle.dump(streams, f, protocol=4)
     streams_cl = None
-    if rank == 0 and world == 1 and not args.no_extras:   # the same streams with clustered landmark descriptors (value_clustered)
+    if rank == 0 and world == 1 and extras:   # the same streams with clustered landmark descriptors (value_clustered)
         streams_cl = generate_streams(seq_ids, replicas, S, args.points, args.lines, cluster_kw=CORRELATED_MODELS["clustered"])
     c3_seqs = None
-    if rank == 0 and world == 1 and not args.no_extras:   # configs[3] sequences, also before the GPU is touched (fork)
+    if rank == 0 and world == 1 and extras:   # configs[3] sequences, also before the GPU is touched (fork)
         import multiprocessing as mp_
         with mp_.get_context("fork").Pool(min(16, os.cpu_count() or 1)) as pool:
             c3_seqs = pool.map(_gen_configs3, [(k, 5) for k in range(64)])
@@ -1002,20 +1065,25 @@ def main():
     # reporting only: every rank's own rate (its frame pairs / its own median time), gathered to rank 0
     per_rank = shard.gather_scalars(dist, B * args.steps / float(np.median(rep_dt_local)), device=agg_dev)
 
+    res, counts = pipe.read()   # the results of the last timed step, as a caller of the path receives them
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, counts, suffix=f".rank{rank}" if world > 1 else "")
+
     clocks = None
-    if rank == 0 and not args.no_clocks:   # outside the timed region: a few hundred more steps while rocm-smi takes its sample
+    if rank == 0 and args.full and not args.no_clocks:   # outside the timed region: a few hundred more steps while rocm-smi takes its sample
         def _work():
             nonlocal last_slot
             for _ in range(8):
                 last_slot = next(order); pipe.step_dev(last_slot)
             ctx.synchronize()
         clocks = gpu_clocks_under_load(_work, card=local_rank)
-
-    res, counts = pipe.read()   # sanity: the timed work produced real poses
-    ok_frac = float((res["status"] == 0).mean())
+        res, counts = pipe.read()
+    ok_frac = float((res["status"] == 0).mean())   # sanity: the timed work produced real poses
 
     out = None
-    if rank == 0:
+    if rank == 0 and not args.full:   # the headline alone
+        out = headline_record(args, world, backend, frames_total, dt, rep_dt, per_rank, streams, ok_frac)
+    elif rank == 0:
         # ---- per-kernel figures, measured LIVE behind the timed region, same streams, same slot order, hipEvent pairs on the stream the
         # kernels run on.  Two passes.  (B) counting pass: an event pair around EVERY stage and a read after every step -> `stage_ms`
         # (bench_extras.json only: the markers change what runs beside what) and the set sizes / match counts / evaluations of every slot
@@ -1133,28 +1201,10 @@ def main():
                                     "8 (N1 + N2) + 4 N1 bytes in, 48 bytes per stereo point out: a 16-byte compact record + the descriptor row)" if fused_tail else "") +
                                  "; ~16 k candidate pairs per frame — bound by LDS gathers and the issue of the per-thread sort / chain code "
                                  "at 4 waves per SIMD (one workgroup per CU), not by HBM"}
-        resident_mb = S * B * (2 * 2048 * (8 + 32) + 2048 * 4 + 2 * 512 * (16 + 32) + 512 * 4) / 1e6
-        out = {
-            "metric": "stereo frames/s (match+optimizePose)", "value": frames_total / dt, "unit": "frame-pairs/s",
-            "n_gpus": world, "rccl_ranks": world, "collective_backend": ("rccl" if backend == "nccl" else backend), "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "repeats": {"n": len(rep_dt), "statistic": "median", "value_min": frames_total / max(rep_dt), "value_max": frames_total / min(rep_dt),
-                        "ms_per_step_all": [d / args.steps * 1e3 for d in rep_dt]},
-            "parity_sampled": parity,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/fp4+f64", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[2]: KITTI-00-shaped stereo with points + lines (ORB + LBD rows), grid-windowed stereo "
-                                   "match (points and lines) + f2f brute-force mutual-NNR match (points and lines) + full GN optimizePose "
-                                   "(config_kitti.yaml), device-resident per-frame pipeline; the streams cycle through the 8 sequence ids / 3 "
-                                   "KITTI calibrations of configs[4] (sequence s on rank s mod G)",
-                       "streams_per_gpu": B, "resident_frames_per_stream": S, "slot_order": "ping-pong",
-                       "resident_raw_features_MB_per_gpu": resident_mb,
-                       "keypoints_per_image": float(n_kp.mean() / 2), "keylines_per_image": float(np.mean([len(st[0]["kl_l"]) for st in streams])),
-                       "mean_stereo_points": n2_l / B, "mean_matched_points": np_l / B, "mean_matched_lines": nl_l / B,
-                       "cameras": "kitti00-02 (seq 0-2), kitti03 (seq 3), kitti04-10 (seq 4-7)",
-                       "parallelism": f"seq-shard x{world}", "committed_pose_fraction": ok_frac},
-            "per_rank_frame_pairs_per_s": per_rank if world > 1 else None,
-            # (the driver computes scaling efficiency itself; this is a convenience when the N = 1 value of the same box is handed in)
-            "scaling_efficiency_vs_n1": (frames_total / dt / (world * float(os.environ["STVO_N1_VALUE"]))
-                                         if world > 1 and os.environ.get("STVO_N1_VALUE") else None),
+        out = headline_record(args, world, backend, frames_total, dt, rep_dt, per_rank, streams, ok_frac)
+        out["parity_sampled"] = parity
+        out["config"].update({"mean_stereo_points": n2_l / B, "mean_matched_points": np_l / B, "mean_matched_lines": nl_l / B})
+        out.update({
             "roofline": roofline, "roofline_pose": roofline_pose, "roofline_grid_scan": roofline_grid, "gpu_clocks": clocks,
             "stage_ms": dict(stage_ms_full, steps_timed=n_timed_full,
                              note="stereo_points_stage = cells + grid matcher (with the tail of the association as its last phase) of the "
@@ -1164,10 +1214,10 @@ def main():
                                   "with the point matcher: 0.14 ms alone, while in the timed region — fork behind the cells kernel, no markers — "
                                   "they run beside the forward scan and stretch IT), so the stages do not add up to ms_per_step: "
                                   "profiles/<tag>_step_timeline.txt has the dispatches of the timed region itself"),
-        }
+        })
     pipe.close()
     ctx.close()
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras:
         def extra(name, leg, *a, **kw):
             """The extra legs run after the timed region of the headline: one that fails is reported in its own key and must not
             cost the line (the headline, roofline and cpu_baseline objects above / below do not depend on them)."""
@@ -1199,7 +1249,7 @@ def main():
         extra("images_to_poses_with_lines", images_leg, local_rank, B=3072, steps=3, lines=True)  # (the headline's stream count: 6144 images per step — 7.9 k pairs/s at 2048 streams, 9.2 k here, 9.0 k at 4096)
         # the reference application's own case (app/imagesStVO.cpp: ONE stereo pair per step, key-points + key-lines): latency, not throughput
         extra("one_stereo_pair_with_lines", images_leg, local_rank, B=1, steps=12, lines=True)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.points, args.lines)
         out["cpu_baseline_fanout"] = cpu_baseline_fanout(args.points, args.lines)
         out["cpu_baseline_threads"] = cpu_baseline_threads(args.points, args.lines)
@@ -1225,10 +1275,11 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0:
+    if rank == 0 and args.full:
         out["extras_file"] = write_extras(out)
         if args.print_extras:   # the full record on an EARLIER line of stderr; stdout carries the one short line only
             print("bench_extras: " + json.dumps(out), file=sys.stderr)
+    if rank == 0:
         print(short_line(out), flush=True)
 
 

@@ -72,7 +72,7 @@ def test_bench_line_is_short_and_parses():
     """`python bench.py` (small batch) on the GPU: ONE stdout line, < 6 KB, with the contract's keys, a roofline measured by the light
     pass (event pairs on the three big kernels only) and the cpu_baseline object; the full record lands in bench_extras.json."""
     import json
-    out = _run_bench(["--batch", "64", "--steps", "2", "--warmup", "1", "--repeats", "2", "--no-extras", "--no-clocks"])
+    out = _run_bench(["--full", "--batch", "64", "--steps", "2", "--warmup", "1", "--repeats", "2", "--no-extras", "--no-clocks"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "roofline_pose", "roofline_grid_scan", "cpu_baseline", "parity_sampled"):
         assert k in out, k
@@ -87,7 +87,7 @@ def test_bench_line_is_short_and_parses():
 def test_bench_eight_ranks_gloo_on_one_gpu():
     """`python bench.py --gpus 8` as an 8-GPU node would run it (8 ranks, sequence s on rank s, 16 streams per rank), over gloo on this
     box's one GPU: n_gpus == 8, whole-job value, one rate per rank."""
-    out = _run_bench(["--gpus", "8", "--batch", "16", "--steps", "2", "--warmup", "1", "--repeats", "1", "--no-extras", "--no-cpu-baseline", "--no-clocks"],
+    out = _run_bench(["--full", "--gpus", "8", "--batch", "16", "--steps", "2", "--warmup", "1", "--repeats", "1", "--no-extras", "--no-cpu-baseline", "--no-clocks"],
                      env_extra={"STVO_BENCH_BACKEND": "gloo", "STVO_N1_VALUE": "100000"})
     assert out["n_gpus"] == 8 and out["rccl_ranks"] == 8 and out["scaling"] == "weak"
     assert len(out["per_rank_frame_pairs_per_s"]) == 8 and all(v > 0 for v in out["per_rank_frame_pairs_per_s"])
@@ -95,3 +95,26 @@ def test_bench_eight_ranks_gloo_on_one_gpu():
     assert abs(out["value"] - frames / (out["ms_per_step"] * 1e-3 * 2)) / out["value"] < 1e-4
     assert out["scaling_efficiency_vs_n1"] == pytest.approx(out["value"] / 8e5, rel=1e-4)
     assert out["parity_sampled"]["ok"]
+
+
+def test_bench_plain_run_times_its_steps_once_and_dumps_the_last_step(tmp_path):
+    """`python bench.py` without --full: exactly --steps timed steps (one region), the contract's keys, no per-kernel passes, parity
+    sample, CPU baseline or extras file; --dump-outputs writes the last timed step's results, and a second run with the same
+    arguments (same seeded streams) writes the same arrays."""
+    import glob
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        out = _run_bench(["--batch", "64", "--steps", "3", "--warmup", "2", "--dump-outputs", str(d)])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in out, key
+        assert out["steps"] == 3 and out["warmup"] == 2 and out["repeats"]["n"] == 1 and out["higher_is_better"] is True
+        assert abs(out["value"] - 64 / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-4
+        assert "roofline" not in out and "cpu_baseline" not in out and out["parity_sampled"] is None and out["extras_file"] is None
+        dumps.append({os.path.basename(f): np.load(f) for f in glob.glob(str(d / "*.npy"))})
+    a, b = dumps
+    assert {"T.npy", "status.npy", "iters.npy", "counts.npy"} <= set(a) and set(a) == set(b)
+    assert all(v.dtype == np.float64 and len(v) == 64 for v in a.values())
+    assert (a["status.npy"] == 0).mean() > 0.9 and (a["counts.npy"][:, 2] > 0).all()
+    for name in a:
+        assert np.array_equal(a[name], b[name], equal_nan=True), name

@@ -6,7 +6,7 @@ for spec in "$@"; do
   lib=${spec%%:*}; envs=""
   if [[ "$spec" == *:* ]]; then envs=$(echo "${spec#*:}" | tr ',' ' '); fi
   echo "== $spec"
-  env $envs STVO_LIB=$PWD/tools/ab/$lib.so timeout 300 python bench.py --no-extras --no-cpu-baseline --no-clocks ${AB_ARGS:-} 2>/dev/null | python -c "
+  env $envs STVO_LIB=$PWD/tools/ab/$lib.so timeout 300 python bench.py --full --no-extras --no-cpu-baseline --no-clocks ${AB_ARGS:-} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split('\n')[-1]); r=d['repeats']
 print(round(d['value']), r['value_min'], r['value_max'], d['ms_per_step'], 'K1m', d['roofline']['avg_launch_ms'], 'pose', d['roofline_pose']['avg_launch_ms'], 'grid', d['roofline_grid_scan']['avg_launch_ms'], 'parity', d['parity_sampled'].get('ok'))"
