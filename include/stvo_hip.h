@@ -327,6 +327,32 @@ int stvo_keylines_xy_dev(stvo_ctx* ctx, int B, int stride, const stvo_keyline* l
  * segments [B][cap][4], n_segments [B] (all found; at most cap stored) */
 int stvo_lsd_segments(stvo_lsd* lsd, const uint8_t* images, float* segments, int cap, int32_t* n_segments);
 
+/* ---- stereo rectification (input preparation of Dataset::nextFrame, src/dataset.cpp:147-157) ---------------------------- */
+
+/* Replaces the rectification half of  PinholeStereoCamera(const string& params_file)  (src/pinholeStereoCamera.cpp:30-125):
+ * stereoRectify(CALIB_ZERO_DISPARITY, alpha 0) in the form of OpenCV 3.4's cvStereoRectify, then initUndistortRectifyMap (rad-tan)
+ * or fisheye::initUndistortRectifyMap per side, CV_16SC2 maps (DESIGN.md §9 states the form and what stays unpinned).  Host only,
+ * no device needed.  map1 [2][rows][cols][2] int16 (integer source position) and map2 [2][rows][cols] uint16 (5-bit fractions,
+ * iv & 31) * 32 + (iu & 31)), left side first; either may be NULL.  Form KITTI: both sides hold the left map (:119-120). */
+int stvo_rectify_compute(const stvo_rect_calib* calib, stvo_rect_camera* out, int16_t* map1, uint16_t* map2);
+
+/* Replaces  PinholeStereoCamera::rectifyImagesLR / rectifyImage  (src/pinholeStereoCamera.cpp:196-208): cv::remap(INTER_LINEAR,
+ * BORDER_CONSTANT 0) of 8-bit images with the CV_16SC2 maps, bit for bit, or a copy when dist is 0.  One rectifier serves up to
+ * B stereo pairs per call; the maps stay resident in HBM. */
+typedef struct stvo_rectify stvo_rectify;
+int stvo_rectify_create(stvo_ctx* ctx, int B, const stvo_rect_calib* calib, stvo_rectify** out);
+/* Caller-made maps (own calibration tools): map1 / map2 as stvo_rectify_compute writes them, both sides; dist = 1. */
+int stvo_rectify_create_from_maps(stvo_ctx* ctx, int B, int cols, int rows, const int16_t* map1, const uint16_t* map2,
+                                  stvo_rectify** out);
+int stvo_rectify_destroy(stvo_rectify* rect);
+int stvo_rectify_camera(const stvo_rectify* rect, stvo_rect_camera* out);
+/* n (1 .. B) pairs: src_l / dst_l hold n left images and src_r / dst_r n right images, rows * cols bytes apart; the left map applies
+ * to the left images, the right map to the right ones.  A destination that overlaps any source is STVO_ERR_INVALID_ARG.
+ * Host buffers, synchronises. */
+int stvo_rectify_images(stvo_rectify* rect, int n, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l, uint8_t* dst_r);
+/* The same with DEVICE pointers, enqueued on the context's stream (no synchronisation). */
+int stvo_rectify_images_dev(stvo_rectify* rect, int n, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l, uint8_t* dst_r);
+
 /* ---- measurement helpers --------------------------------------------------------------------- */
 /* Times `iters` launches of the named kernel stage on the context's stream with hipEvents and
  * returns the average milliseconds per launch (used by bench.py for the roofline line).

@@ -167,6 +167,33 @@ typedef struct stvo_keyline {
     int32_t num_pixels;    /* KeyLine::numOfPixels (cv::LineIterator count): the length of the line support region */
 } stvo_keyline;
 
+/* Stereo calibration as the reference's YAML constructor reads it (src/pinholeStereoCamera.cpp:30-125), before rectification.
+ * form STVO_RECT_FORM_KITTI: cam_fx / cam_fy / cam_cx / cam_cy and cam_d0..d3 (fx, fy, cx, cy, d).  STVO_RECT_FORM_RADTAN and
+ * STVO_RECT_FORM_FISHEYE: Kl / Kr = (fx, fy, cx, cy), Dl / Dr (n_dist = 4, 5 or 8 rad-tan coefficients; 4 equidistant ones for
+ * the fisheye form, which the reference selects with a `dtype` key), R row-major, t.  b = cam_bl in every form (never derived
+ * from t).  Rl / Rr of the YAML are not read (the reference ignores them). */
+enum { STVO_RECT_FORM_KITTI = 0, STVO_RECT_FORM_RADTAN = 1, STVO_RECT_FORM_FISHEYE = 2 };
+typedef struct stvo_rect_calib {
+    int32_t form;
+    int32_t width, height;
+    int32_t n_dist;
+    double b;
+    double fx, fy, cx, cy, d[4];
+    double Kl[4], Kr[4];
+    double Dl[8], Dr[8];
+    double R[9], t[3];
+} stvo_rect_calib;
+
+/* The rectified stereo camera: R1 / R2 (3 x 3) and P1 / P2 (3 x 4) row-major as stereoRectify returns them (form KITTI: R = I and
+ * P = [fx 0 cx 0; 0 fx cy 0; 0 0 1 0] in float, src/pinholeStereoCamera.cpp:114), cam = the camera the pipeline works with
+ * (fx = P1(0,0), fy = P1(1,1), cx = P1(0,2), cy = P1(1,2), b = cam_bl; form KITTI: the intrinsics as read), dist = whether
+ * rectifyImagesLR remaps (0: it copies, :198-207). */
+typedef struct stvo_rect_camera {
+    int32_t dist, width, height, reserved;
+    double R1[9], R2[9], P1[12], P2[12];
+    stvo_cam cam;
+} stvo_rect_camera;
+
 /* Error codes of the C-ABI (0 ok, <0 error; never throws). */
 enum {
     STVO_OK = 0,

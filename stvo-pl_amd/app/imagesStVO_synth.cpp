@@ -9,6 +9,9 @@
 //                    [--keyframes]   (needNewKF / currFrameIsKF after every optimizePose, as PL-SLAM drives them)
 //                    [--device-pipeline]   (stvo_seq_*: one upload + one synchronisation per frame, state in HBM)
 //                    [--no-lines]    (Config::hasLines() = false)
+//                    [--dataset-params FILE]   (image files: the camera comes from the dataset parameter file and every raw pair is
+//                                               rectified before initialize / insertStereoPair, as Dataset::nextFrame does,
+//                                               src/dataset.cpp:147-157)
 // A sequence file that starts with "STVOIMG1" holds stereo IMAGES (n_frames, cols, rows, camera, then per frame the left and the
 // right 8-bit image): the loop then calls the reference's own entry points initialize / insertStereoPair(img_l, img_r, idx)
 // (include/stereoFrameHandler.h:44-45), whose ORB point front-end runs on the GPU (key-points only: no LSD / LBD here).
@@ -64,7 +67,7 @@ int main(int argc, char** argv) {
                      "[--mode m] [-n frames]\n";
         return -1;
     }
-    std::string preset = "kitti", cfg;
+    std::string preset = "kitti", cfg, dataset_params;
     int mode = 0, max_frames = 0, frame_offset = 0, frame_step = 1;
     bool keyframes = false;
     bool device_pipeline = false, no_lines = false;
@@ -76,6 +79,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--device-pipeline")) device_pipeline = true;
         else if (!std::strcmp(argv[i], "--keyframes")) keyframes = true;
         else if (!std::strcmp(argv[i], "--no-lines")) no_lines = true;
+        else if (!std::strcmp(argv[i], "--dataset-params") && i + 1 < argc) dataset_params = argv[++i];
         else if (!std::strcmp(argv[i], "-o") && i + 1 < argc) frame_offset = std::atoi(argv[++i]);  // imagesStVO.cpp:158-159
         else if (!std::strcmp(argv[i], "-s") && i + 1 < argc) frame_step = std::atoi(argv[++i]);    // imagesStVO.cpp:162-163
     }
@@ -106,8 +110,27 @@ int main(int argc, char** argv) {
         const int avail = n_file_frames > frame_offset ? (n_file_frames - frame_offset + frame_step - 1) / frame_step : 0;
         n_frames = (max_frames > 0 && max_frames < avail) ? max_frames : avail;
     }
+    if (!dataset_params.empty() && !image_file) {
+        std::cerr << "--dataset-params rectifies raw images: it takes an image file (STVOIMG1)" << std::endl;
+        return -1;
+    }
     std::ofstream out(argv[2], std::ios::binary);
-    PinholeStereoCamera* cam_pin = new PinholeStereoCamera(cols, rows, camv[0], camv[1], camv[2], camv[3], camv[4]);
+    PinholeStereoCamera* cam_pin = nullptr;
+    if (dataset_params.empty()) {
+        cam_pin = new PinholeStereoCamera(cols, rows, camv[0], camv[1], camv[2], camv[3], camv[4]);
+    } else {
+        try {
+            cam_pin = new PinholeStereoCamera(dataset_params);  // the camera of the file, not the one in the image file's header
+        } catch (const std::exception& e) {
+            std::cerr << e.what() << std::endl;
+            return -1;
+        }
+        if (cam_pin->getWidth() != cols || cam_pin->getHeight() != rows) {
+            std::cerr << "--dataset-params: the camera is " << cam_pin->getWidth() << " x " << cam_pin->getHeight() << ", the images "
+                      << cols << " x " << rows << std::endl;
+            return -1;
+        }
+    }
 
     if (device_pipeline) {
         // ---- the same loop on the device-resident pipeline: pose + counters per frame, Tfw composed here
@@ -238,6 +261,15 @@ int main(int argc, char** argv) {
         if (max_frames > 0 && n_done >= max_frames) break;
         ++frame_counter;
         ++n_done;
+        if (image_file && !dataset_params.empty()) {  // cam->rectifyImagesLR(img_l, img_l, img_r, img_r), src/dataset.cpp:155
+            const GrayImage rl{img_l.data(), rows, cols, (size_t)cols}, rr{img_r.data(), rows, cols, (size_t)cols};
+            try {
+                cam_pin->rectifyImagesLR(rl, img_l, rr, img_r);
+            } catch (const std::exception& e) {
+                std::cerr << e.what() << std::endl;
+                return -2;
+            }
+        }
         const GrayImage gl{img_l.data(), rows, cols, (size_t)cols}, gr{img_r.data(), rows, cols, (size_t)cols};
         if (frame_counter == 0) {
             if (image_file) StVO->initialize(gl, gr, 0);  // initialize(img_l, img_r, 0), imagesStVO.cpp:90

@@ -9,7 +9,7 @@ import subprocess
 
 import numpy as np
 
-from .ctypes_types import Cam, GridWindow, MatchParams, OptParams, PoseResult, POSE_RESULT_DTYPE
+from .ctypes_types import Cam, GridWindow, MatchParams, OptParams, PoseResult, POSE_RESULT_DTYPE, RectCalib, RectCamera
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # stvo-pl_amd/
 LIB_PATH = os.environ.get("STVO_LIB") or os.path.join(PKG_DIR, "libstvo_hip.so")   # STVO_LIB: A/B runs of two builds (developer)
@@ -24,7 +24,9 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_orb_set_pattern", "stvo_orb_get_pattern", "stvo_orb_detect", "stvo_orb_detect_dev", "stvo_orb_detect_levels",
            "stvo_orb_detect_levels_dev", "stvo_orb_set_fast_threshold", "stvo_seq_upload_dev", "stvo_lbd_create", "stvo_lbd_destroy",
            "stvo_lbd_compute", "stvo_lbd_compute_dev", "stvo_debug_reparse_env", "stvo_lsd_create", "stvo_lsd_destroy", "stvo_lsd_detect",
-           "stvo_lsd_detect_dev", "stvo_lsd_segments", "stvo_lsd_counts", "stvo_keylines_xy_dev"]
+           "stvo_lsd_detect_dev", "stvo_lsd_segments", "stvo_lsd_counts", "stvo_keylines_xy_dev", "stvo_rectify_compute",
+           "stvo_rectify_create", "stvo_rectify_create_from_maps", "stvo_rectify_destroy", "stvo_rectify_camera", "stvo_rectify_images",
+           "stvo_rectify_images_dev"]
 
 SEQ_NSTAGE = 5  # include/stvo_hip.h: STVO_SEQ_NSTAGE
 SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_check", "pose")
@@ -151,6 +153,13 @@ def load():
     L.stvo_lsd_counts.argtypes = [C.c_void_p, i32p, i32p]
     L.stvo_keylines_xy_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.stvo_seq_destroy.argtypes = [C.c_void_p]
+    L.stvo_rectify_compute.argtypes = [C.POINTER(RectCalib), C.POINTER(RectCamera), C.c_void_p, C.c_void_p]
+    L.stvo_rectify_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(RectCalib), C.POINTER(C.c_void_p)]
+    L.stvo_rectify_create_from_maps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.stvo_rectify_destroy.argtypes = [C.c_void_p]
+    L.stvo_rectify_camera.argtypes = [C.c_void_p, C.POINTER(RectCamera)]
+    L.stvo_rectify_images.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    L.stvo_rectify_images_dev.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
     L.stvo_seq_push.argtypes = [C.c_void_p, C.POINTER(FrameFeatures), C.c_void_p, i32p]
     L.stvo_seq_upload.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameFeatures)]
     L.stvo_seq_upload_dev.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameFeatures)]
@@ -584,3 +593,147 @@ class Sequences:
         ps = [C.POINTER(C.c_int32)() for _ in range(2)]
         self.ctx._chk(self.ctx.lib.stvo_seq_fetch_inliers(self.h, *[C.byref(p) for p in ps]))
         return tuple(np.ctypeslib.as_array(p, shape=sh).copy() for p, sh in zip(ps, [(self.B, K), (self.B, M)]))
+
+
+# ---- stereo rectification (stvo_rectify_*) ------------------------------------------------------------------------------------
+
+RECT_FORM_KITTI, RECT_FORM_RADTAN, RECT_FORM_FISHEYE = 0, 1, 2
+
+
+def parse_dataset_yaml(text):
+    """The YAML subset of the dataset parameter files (config/dataset_params/*.yaml of the reference): `key: value` lines, one level
+    of blocks (`cam0:`), scalars, and flow lists `[a, b, ...]` that may span lines; `#` starts a comment.  -> nested dict of str /
+    float / list of float."""
+    root, block, pending = {}, None, None
+    for raw in text.splitlines():
+        line = raw.split("#", 1)[0].rstrip()
+        if pending is not None:
+            pending[1].append(line.strip())
+            if "]" in line:
+                key, parts, target = pending
+                target[key] = [float(v) for v in " ".join(parts).strip()[1:-1].replace(",", " ").split()]
+                pending = None
+            continue
+        if not line.strip():
+            continue
+        indented = line[0] in " \t"
+        key, sep, val = line.strip().partition(":")
+        if not sep:
+            raise ValueError(f"dataset parameters: cannot read line {raw!r}")
+        key, val = key.strip(), val.strip()
+        target = block if indented and block is not None else root
+        if not indented:
+            block = None
+        if val == "":
+            if indented:
+                raise ValueError(f"dataset parameters: nested blocks are not supported ({raw!r})")
+            block = root[key] = {}
+        elif val.startswith("["):
+            if "]" in val:
+                target[key] = [float(v) for v in val[1:val.index("]")].replace(",", " ").split()]
+            else:
+                pending = (key, [val], target)
+        else:
+            try:
+                target[key] = float(val)
+            except ValueError:
+                target[key] = val
+    if pending is not None:
+        raise ValueError(f"dataset parameters: unterminated list for {pending[0]}")
+    return root
+
+
+def calib_from_params(params):
+    """The cam0 block of a parsed dataset parameter file -> RectCalib, selecting the branch the reference's constructor takes
+    (src/pinholeStereoCamera.cpp:38-125): Kl present -> rad-tan stereo (fisheye when a dtype key is present), else KITTI-style."""
+    cam = params["cam0"]
+    if cam.get("cam_model") != "Pinhole":
+        raise ValueError("dataset parameters: cam_model must be Pinhole")
+    c = RectCalib()
+    c.width, c.height, c.b = int(cam["cam_width"]), int(cam["cam_height"]), float(cam["cam_bl"])
+    if "Kl" in cam:
+        c.form = RECT_FORM_FISHEYE if "dtype" in cam else RECT_FORM_RADTAN
+        nd = len(cam["Dl"])
+        if len(cam["Dr"]) != nd or len(cam["Kl"]) != 4 or len(cam["Kr"]) != 4 or len(cam["R"]) != 9 or len(cam["t"]) != 3:
+            raise ValueError("dataset parameters: Kl / Kr need 4 values, Dl / Dr the same count, R 9 and t 3")
+        c.n_dist = nd
+        c.Kl[:], c.Kr[:] = cam["Kl"], cam["Kr"]
+        c.Dl[:nd], c.Dr[:nd] = cam["Dl"], cam["Dr"]
+        c.R[:], c.t[:] = cam["R"], cam["t"]
+    else:
+        c.form = RECT_FORM_KITTI
+        c.fx, c.fy, c.cx, c.cy = cam["cam_fx"], cam["cam_fy"], cam["cam_cx"], cam["cam_cy"]
+        c.d[:] = [cam["cam_d0"], cam["cam_d1"], cam["cam_d2"], cam["cam_d3"]]
+    return c
+
+
+def read_dataset_params(path):
+    """A dataset parameter file (euroc_params.yaml, kitti00-02.yaml, ...) -> RectCalib."""
+    with open(path) as f:
+        return calib_from_params(parse_dataset_yaml(f.read()))
+
+
+def camera_dict(rc):
+    """RectCamera -> dict of numpy arrays (R1, R2 3x3; P1, P2 3x4), the pipeline camera (fx, fy, cx, cy, b, width, height), dist."""
+    return dict(R1=np.array(rc.R1[:]).reshape(3, 3), R2=np.array(rc.R2[:]).reshape(3, 3), P1=np.array(rc.P1[:]).reshape(3, 4),
+                P2=np.array(rc.P2[:]).reshape(3, 4), dist=int(rc.dist),
+                cam=dict(fx=rc.cam.fx, fy=rc.cam.fy, cx=rc.cam.cx, cy=rc.cam.cy, b=rc.cam.b, width=rc.width, height=rc.height))
+
+
+def rectify_compute(calib, maps=True):
+    """Host-only rectification (no device): (camera_dict, map1 int16 [2, rows, cols, 2], map2 uint16 [2, rows, cols]) or, with
+    maps=False, the camera dict alone."""
+    L = load()
+    rc = RectCamera()
+    m1 = m2 = None
+    if maps:
+        m1 = np.zeros((2, calib.height, calib.width, 2), np.int16)
+        m2 = np.zeros((2, calib.height, calib.width), np.uint16)
+    rcode = L.stvo_rectify_compute(C.byref(calib), C.byref(rc), _ptr(m1) if maps else None, _ptr(m2) if maps else None)
+    if rcode != 0:
+        raise StvoError(f"stvo_rectify_compute: {L.stvo_error_string(rcode).decode()} ({rcode})")
+    return (camera_dict(rc), m1, m2) if maps else camera_dict(rc)
+
+
+class Rectifier:
+    """The GPU rectifier for up to B stereo pairs of one size (stvo_rectify_*): calib = RectCalib (read_dataset_params) or
+    maps = (map1 int16 [2, rows, cols, 2], map2 uint16 [2, rows, cols]), left side first."""
+
+    def __init__(self, ctx, B, calib=None, maps=None):
+        if (calib is None) == (maps is None):
+            raise ValueError("Rectifier: pass exactly one of calib and maps")
+        self.ctx, self.B = ctx, B
+        self.h = C.c_void_p()
+        if calib is not None:
+            ctx._chk(ctx.lib.stvo_rectify_create(ctx.h, B, C.byref(calib), C.byref(self.h)))
+        else:
+            m1 = np.ascontiguousarray(maps[0], np.int16)
+            m2 = np.ascontiguousarray(maps[1], np.uint16)
+            if m1.ndim != 4 or m1.shape[0] != 2 or m1.shape[3] != 2 or m2.shape != m1.shape[:3]:
+                raise ValueError("Rectifier: maps must be int16 [2, rows, cols, 2] and uint16 [2, rows, cols]")
+            ctx._chk(ctx.lib.stvo_rectify_create_from_maps(ctx.h, B, m1.shape[2], m1.shape[1], _ptr(m1), _ptr(m2), C.byref(self.h)))
+        rc = RectCamera()
+        ctx._chk(ctx.lib.stvo_rectify_camera(self.h, C.byref(rc)))
+        info = camera_dict(rc)
+        self.cols, self.rows, self.dist = rc.width, rc.height, info["dist"]
+        self.camera = info["cam"]  # the rectified pipeline camera (zeros for caller maps)
+        self.info = info
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.stvo_rectify_destroy(self.h)
+            self.h = None
+
+    def rectify(self, left, right):
+        """Host images uint8 [n, rows, cols] each (n <= B) -> (left, right) rectified, synchronous."""
+        left = np.ascontiguousarray(left, np.uint8).reshape(-1, self.rows, self.cols)
+        right = np.ascontiguousarray(right, np.uint8).reshape(-1, self.rows, self.cols)
+        if len(left) != len(right):
+            raise ValueError("Rectifier.rectify: as many right images as left ones")
+        out_l, out_r = np.empty_like(left), np.empty_like(right)
+        self.ctx._chk(self.ctx.lib.stvo_rectify_images(self.h, len(left), _ptr(left), _ptr(right), _ptr(out_l), _ptr(out_r)))
+        return out_l, out_r
+
+    def rectify_dev(self, n, src_l, src_r, dst_l, dst_r):
+        """Device pointers (n images each, rows * cols bytes apart); asynchronous on the context's stream."""
+        self.ctx._chk(self.ctx.lib.stvo_rectify_images_dev(self.h, n, src_l, src_r, dst_l, dst_r))

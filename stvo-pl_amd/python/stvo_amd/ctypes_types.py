@@ -86,3 +86,15 @@ def match_params(preset="kitti", **kw):
                        base["max_dist_epip"], base["min_disp"], base["line_sim_th"], base["stereo_overlap_th"],
                        base["line_horiz_th"], base["ls_min_disp_ratio"], base["orb_scale_factor"], base["lsd_scale"],
                        float(base["min_ratio_12_p"]))  # matchGrid compares with the double (src/matching.cpp:160,241)
+
+
+class RectCalib(C.Structure):  # stvo_rect_calib
+    _fields_ = [("form", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("n_dist", C.c_int32), ("b", C.c_double),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("d", C.c_double * 4),
+                ("Kl", C.c_double * 4), ("Kr", C.c_double * 4), ("Dl", C.c_double * 8), ("Dr", C.c_double * 8),
+                ("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
+class RectCamera(C.Structure):  # stvo_rect_camera
+    _fields_ = [("dist", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_int32), ("R1", C.c_double * 9),
+                ("R2", C.c_double * 9), ("P1", C.c_double * 12), ("P2", C.c_double * 12), ("cam", Cam)]

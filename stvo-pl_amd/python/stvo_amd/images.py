@@ -4,7 +4,8 @@ owns the device buffers, every computation is behind the C-ABI.
 
 Replaces, per frame and stream: StereoFrame::detectStereoPoints + matchStereoPoints (/root/reference/src/stereoFrame.cpp:88-173),
 StereoFrameHandler::f2fTracking + optimizePose (src/stereoFrameHandler.cpp:106-392); with lsd = stvo_lsd_params also
-detectStereoLineSegments + matchStereoLines (:191-243, :309-398): LSD detector, top-N cut, LBD descriptors (stvo_lsd_* / stvo_lbd_*)."""
+detectStereoLineSegments + matchStereoLines (:191-243, :309-398): LSD detector, top-N cut, LBD descriptors (stvo_lsd_* / stvo_lbd_*);
+with rectify = capi.Rectifier also the rectification of the raw pairs that Dataset::nextFrame does first (src/dataset.cpp:147-157)."""
 import ctypes as C
 
 import numpy as np
@@ -16,12 +17,18 @@ from .capi import FrameFeatures
 
 class ImagePipeline:
     def __init__(self, ctx, B, cam, mp, op, max_kp=2048, nfeatures=2000, fast_threshold=20, edge_threshold=19, device="cuda:0", nlevels=1,
-                 scale_factor=1.2, lsd=None, max_kl=128):
+                 scale_factor=1.2, lsd=None, max_kl=128, rectify=None):
         """cam: one camera dict (width / height = image size) for all B streams.  nlevels / scale_factor: Config::orbNLevels /
         orbScaleFactor (the key-point octaves travel with the key-points: sigma2 = 1 / scale^(2 level)).  lsd: capi.lsd_params(...)
-        for the key-line front-end (op.has_lines = 1, at most max_kl key-lines per image), None: key-points only (op.has_lines = 0)."""
+        for the key-line front-end (op.has_lines = 1, at most max_kl key-lines per image), None: key-points only (op.has_lines = 0).
+        rectify: a capi.Rectifier of the same context for at least B pairs of this size: enqueue first remaps the raw images into a
+        resident rectified buffer (same stream, no host synchronisation) and the detectors read that buffer; cam is then the rectified
+        camera (Rectifier.camera).  None: the images are taken as rectified."""
         self.ctx, self.B, self.K, self.M = ctx, B, max_kp, max_kl
         self.cols, self.rows = cam["width"], cam["height"]
+        self.rectify = rectify
+        if rectify is not None and (rectify.ctx is not ctx or rectify.B < B or rectify.cols != self.cols or rectify.rows != self.rows):
+            raise ValueError("ImagePipeline: the rectifier must belong to the same context, hold B pairs and match the image size")
         self.orb = capi.Orb(ctx, 2 * B, self.cols, self.rows, max_kp, nfeatures, fast_threshold, edge_threshold, nlevels, scale_factor)  # left images, then right
         if lsd is not None and (lsd.nfeatures == 0 or lsd.nfeatures > max_kl):
             import warnings
@@ -31,6 +38,7 @@ class ImagePipeline:
         self.seq = capi.Sequences(ctx, B, max_kp, max_kl if lsd is not None else 64, cam, mp, op)
         dev = torch.device(device)
         self.img = torch.zeros((2 * B, self.rows, self.cols), dtype=torch.uint8, device=dev)
+        self.rect_img = torch.zeros((2 * B, self.rows, self.cols), dtype=torch.uint8, device=dev) if rectify is not None else None
         self.kp = torch.zeros((2 * B, max_kp, 2), dtype=torch.float32, device=dev)
         self.resp = torch.zeros((2 * B, max_kp), dtype=torch.float32, device=dev)
         self.ang = torch.zeros((2 * B, max_kp), dtype=torch.float32, device=dev)
@@ -70,11 +78,16 @@ class ImagePipeline:
 
     def enqueue(self, img_ptr=None):
         """Detection + description of the 2 B resident images (or of the uint8 [2 B, rows, cols] device buffer at img_ptr: B left,
-        then B right), ingestion, one pipeline step — all asynchronous."""
-        self.orb.detect_dev(img_ptr if img_ptr is not None else self.img.data_ptr(), self.kp.data_ptr(), self.resp.data_ptr(), self.ang.data_ptr(), self.desc.data_ptr(),
+        then B right), ingestion, one pipeline step — all asynchronous.  With a rectifier the images are raw and are rectified first."""
+        ip = img_ptr if img_ptr is not None else self.img.data_ptr()
+        if self.rectify is not None:
+            side = self.B * self.rows * self.cols
+            rp = self.rect_img.data_ptr()
+            self.rectify.rectify_dev(self.B, ip, ip + side, rp, rp + side)
+            ip = rp
+        self.orb.detect_dev(ip, self.kp.data_ptr(), self.resp.data_ptr(), self.ang.data_ptr(), self.desc.data_ptr(),
                             self.n.data_ptr(), octave=self.oct.data_ptr())
         if self.lsd is not None:
-            ip = img_ptr if img_ptr is not None else self.img.data_ptr()
             self.lsd.detect_dev(ip, self.kl.data_ptr(), None, self.nl.data_ptr())
             self.lbd.compute_dev(ip, self.kl.data_ptr(), self.nl.data_ptr(), self.ldesc.data_ptr())
             self.ctx._chk(self.ctx.lib.stvo_keylines_xy_dev(self.ctx.h, 2 * self.B, self.M, self.kl.data_ptr(), self.nl.data_ptr(), self.kl_xy.data_ptr()))
