@@ -24,7 +24,8 @@ struct stvo_ctx {
     char* arena_host = nullptr;  // pinned mirror of the arena: uploads are gathered here and sent as ONE H2D copy
     size_t arena_size = 0, arena_off = 0, upload_hi = 0;
     uint32_t* probe_sink = nullptr;
-    // overlap mode: pose kernels go to aux_stream; events order them against the matching kernels
+    // overlap mode: pose kernels go to aux_stream; events order them against the matching kernels (stvo_ctx_set_overlap creates the
+    // stream and both events together)
     int overlap = 0;
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_match_done = nullptr, ev_pose_done = nullptr;

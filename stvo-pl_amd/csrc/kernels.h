@@ -294,13 +294,6 @@ struct GridBatch {
     // the one-workgroup matcher builds the grid of its frame itself as its first phase — no point_cells_kernel launch
     int fused_cells;
     PointCells cells;
-    // dyn_ctr != nullptr (persistent point matcher, pipelined steps of seq_pipeline.hip): the workgroups take their frames from the counter
-    // dyn_ctr[dyn_par] instead of by a static stride — the launch then starts beside the previous step's pose kernel, its workgroups come
-    // to their CUs one by one as that kernel's frame pairs finish, and the ones that start early take more frames.  The launch resets
-    // dyn_ctr[dyn_par ^ 1] for the next one; dyn_owner [B] remembers who took a frame (for the workgroup's own pass over misfits).
-    int32_t* dyn_ctr;
-    int32_t* dyn_owner;
-    int dyn_par;
 };
 constexpr int GRID_ELIG = 16;
 // scan_events (optional): [0] / [1] are recorded on `s` before / after the two grid_scan passes

@@ -22,7 +22,6 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
-#include <unordered_map>
 #include <vector>
 
 #include "ctx_internal.h"
@@ -609,8 +608,9 @@ struct stvo_seq {
     // ordering inside the pose kernel instead of events (kernels.h: PoseArgs::wait_flag / fetch_*), small batches only
     unsigned* d_join_flag = nullptr;     // device word the line stream's last launch of a step is followed by a signal on
     unsigned join_epoch = 0;
-    unsigned fetch_epoch = 0;            // value the pose kernel publishes in the pinned flag once the match indices are in fetch_host
+    unsigned fetch_epoch = 0;            // the last value handed to a pose kernel to publish in the pinned flag once the match indices are in fetch_host
     bool fetch_by_pose = false;          // the last step's by-products come that way (stvo_seq_fetch_matches polls the flag)
+    unsigned fetch_value = 0;            // ... and the value its pose kernel publishes
     std::vector<char> raw_split;  // per slot: its key-line arrays were copied on the line stream
     size_t raw_bytes = 0;
     stvo::SeqDev d{};          // pointers into `dev` (set = current)
@@ -626,39 +626,29 @@ struct stvo_seq {
         double *spl, *epl, *sP, *eP, *le, *s2l, *s2lm;
         uint8_t* ldesc;
         int32_t* nl;
-    } set[3];  // THREE stereo sets (round 6): step k writes set k mod 3 and reads set (k - 1) mod 3, so that the association of step k + 1
-               // (which writes set (k + 1) mod 3) may run while the pose kernel of step k still reads sets k - 1 and k (pipelined steps below)
+    } set[3];  // THREE stereo sets (round 6): step k writes set k mod 3 and reads set (k - 1) mod 3, so that the key-line stage of step
+               // k + 1 (key-line stage ahead, below), which writes set (k + 1) mod 3, may run while the pose kernel of step k still reads sets k - 1 and k
     int cur = 0;
     int prev_set() const { return (cur + 2) % 3; }
     unsigned long long *cover, *top2;
     uint32_t *elig = nullptr, *elig_l = nullptr;         // eligible pairs of the grid scans (points / lines), see GridBatch
     int32_t *elig_cnt = nullptr, *elig_cnt_l = nullptr, *govf = nullptr, *govf_l = nullptr;
     int32_t *owner2, *m12s_p, *m12s_l, *m12p, *m12l, *inlp, *inll, *counts;
-    // ---- pipelined steps (batches; STVO_SEQ_PIPE=0 switches them off): optimizePose(k) runs on the context's aux stream, and the point
-    // stream goes straight on to the stereo association of step k + 1, whose workgroups take the CUs the pose kernel's one residency round
-    // frees as its frame pairs finish (the pairs with the most evaluations are a ~20 % tail: profiles/r05_sq_counters.txt).  What makes the
-    // two independent: the third stereo set (above), a second copy of the f2f match indices (odd steps write m12p_alt / m12l_alt), and the
-    // events ev_match (point stream -> pose: the indices are complete) / ev_pose[k & 1] (pose -> the step that overwrites what it read).
-    // The ORDER in which the two become ready matters for speed only: the pose kernel's workgroups must be dispatched before the matcher's
-    // (one per CU, most of its LDS), so the point stream passes a one-thread gate kernel that leaves when the pose kernel
-    // has begun (PoseArgs::start_flag; kernels.h says why not "has been dispatched completely") — bounded, a hint: every data dependence is carried by the events.
-    int32_t *m12p_alt = nullptr, *m12l_alt = nullptr;
-    hipEvent_t ev_match = nullptr, ev_pose[2] = {nullptr, nullptr};
-    unsigned* d_pose_flag = nullptr;
-    unsigned pose_epoch = 0;
-    int32_t *d_dyn_ctr = nullptr, *d_dyn_owner = nullptr;  // GridBatch::dyn_ctr [2] / dyn_owner [B]: frame tickets of the persistent point matcher
-    long long dyn_last_frame = -2;                         // the last step whose matcher took tickets (it reset the other counter)
-    bool pose_pending[2] = {false, false};  // ev_pose[i] has been recorded and not yet waited for by the point stream
-    bool piped_last = false;                // the last step put its pose kernel on the aux stream (stvo_seq_read waits for it)
     // ---- key-line stage AHEAD (the default for batches, round 6; STVO_LINES_AHEAD=0 switches it off): the key-line kernels of step k + 1
     // (stereo association + f2f of ~100 rows per image: 1024 small workgroups each) do not depend on anything the point stream does in
     // step k + 1, so the line stream no longer waits for that step's fork event.  It waits for the fork event of step k — recorded behind
-    // optimizePose(k - 1), the last reader of the line set and of the match-index copy step k + 1 overwrites (three sets, two copies) —
-    // and passes a gate that opens when optimizePose(k) has been dispatched: the small workgroups then fill the slots that kernel's one
-    // residency round frees as its frame pairs finish, instead of sharing the issue ports with the forward scan K1m(k + 1), which they
-    // stretched by ~40 us per step.
+    // optimizePose(k - 1), the last reader of the line set and of the key-line match indices step k + 1 overwrites (three sets; odd steps
+    // write the second copy m12l_alt) — and passes a gate that opens when optimizePose(k) has been dispatched: the small workgroups then
+    // fill the slots that kernel's one residency round frees as its frame pairs finish, instead of sharing the issue ports with the forward
+    // scan K1m(k + 1), which they stretched by ~40 us per step.  The gate (launch_stream_gate) waits for PoseArgs::start_flag (kernels.h
+    // says why not "has been dispatched completely"): bounded, a hint — every data dependence is carried by the events.  The point stream
+    // needs no second copy of its match indices: the point f2f of step k + 1 follows optimizePose(k) in stream order.
+    int32_t* m12l_alt = nullptr;  // batches only
+    unsigned* d_pose_flag = nullptr;
+    unsigned pose_epoch = 0;         // the last start value handed to a pose kernel
     long long fork_rec_frame = -2;   // the last step that recorded ev_fork on the point stream
-    long long pose_flag_frame = -2;  // the last step whose pose kernel publishes its start (d_pose_flag == pose_epoch)
+    long long pose_flag_frame = -2;  // the last step whose pose kernel publishes its start (d_pose_flag reaches pose_flag_value)
+    unsigned pose_flag_value = 0;
     stvo_pose_result* results;
     char* out_host = nullptr;  // pinned: results + counts
     // second stream: the line stage (stereo association + f2f of the key-lines) is independent of the point stage
@@ -687,10 +677,6 @@ struct stvo_seq {
     char* fetch_host = nullptr;
     hipEvent_t ev_fetch = nullptr;
     size_t m12_span = 0, inl_span = 0;  // bytes of the contiguous [m12s_p | m12s_l | m12p | m12l] and [inlp | inll] blocks
-    hipEvent_t pev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // STVO_SEQ_PROF stage markers (developer aid)
-    // captured step chains, keyed by (slot, buffer parity, line-stage flags); small batches only (launch-bound)
-    bool graph_mode = false;
-    std::unordered_map<unsigned, hipGraphExec_t> graphs;
     // optional live stage timing (bench.py): event pairs around the kernels of every step, on the stream they run on
     int timing = 0;  // 1: every stage; 2: "light" — only the three big kernels of the point stream, the step otherwise as untimed
     std::vector<hipEvent_t> tev;  // STVO_SEQ_NSTAGE start/stop pairs per step, grown on demand
@@ -834,9 +820,8 @@ int stvo_seq_create_multi(stvo_ctx* ctx, int B, int max_keypoints, int max_keyli
     const size_t o_m12sp = c.take(nb * K * 4), o_m12sl = c.take(nb * M * 4), o_m12p = c.take(nb * K * 4), o_m12l = c.take(nb * M * 4),
                  o_inlp = c.take(nb * K * 4), o_inll = c.take(nb * M * 4), o_res = c.take(nb * sizeof(stvo_pose_result)),
                  o_counts = c.take(nb * 4 * 4);
-    const bool pipe_ok = B >= 64;  // (pipelined steps: batches only)
-    const size_t o_m12p_alt = c.take(pipe_ok ? nb * K * 4 : 0), o_m12l_alt = c.take(pipe_ok ? nb * M * 4 : 0);
-    const size_t o_dyn_ctr = c.take(64), o_dyn_owner = c.take(nb * 4);
+    const bool alt_l = B >= 64;  // second copy of the key-line match indices (key-line stage ahead: batches only)
+    const size_t o_m12l_alt = c.take(alt_l ? nb * M * 4 : 0);
     const size_t cap_l = nb * (size_t)M * 4;  // line f2f: up to 4 train segments
     const size_t o_cover_l = c.take(nb * (size_t)(M / 64) * M * 8), o_top2_l = c.take(nb * M * 8), o_owner_l = c.take(nb * M * 4),
                  o_knn12_l = c.take(cap_l * 8), o_knn21_l = c.take(cap_l * 8), o_cand_l = c.take(nb * M * 4),
@@ -869,21 +854,9 @@ int stvo_seq_create_multi(stvo_ctx* ctx, int B, int max_keypoints, int max_keyli
               hip_ok(ctx, hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming), "hipEventCreate seq") &&
               hip_ok(ctx, hipEventCreateWithFlags(&s->ev_cells, hipEventDisableTiming), "hipEventCreate seq") &&
               hip_ok(ctx, hipEventCreateWithFlags(&s->ev_upload, hipEventDisableTiming), "hipEventCreate seq") &&
-              hip_ok(ctx, hipEventCreateWithFlags(&s->ev_match, hipEventDisableTiming), "hipEventCreate seq") &&
-              hip_ok(ctx, hipEventCreateWithFlags(&s->ev_pose[0], hipEventDisableTiming), "hipEventCreate seq") &&
-              hip_ok(ctx, hipEventCreateWithFlags(&s->ev_pose[1], hipEventDisableTiming), "hipEventCreate seq") &&
               hip_ok(ctx, hipEventCreateWithFlags(&s->ev_stage[0], hipEventDisableTiming), "hipEventCreate seq") &&
               hip_ok(ctx, hipEventCreateWithFlags(&s->ev_stage[1], hipEventDisableTiming), "hipEventCreate seq");
     s->zero_copy = B <= 16;
-    if (ok && pipe_ok && !ctx->aux_stream) {  // pipelined steps: optimizePose on the context's aux stream (with its record arena)
-        ok = hip_ok(ctx, hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking), "hipStreamCreate aux");
-        if (ok) stvo::pose_retain_stream(ctx->aux_stream);
-    }
-    {   // graph replay of the step chain: opt-in (STVO_SEQ_GRAPH=1).  Measured on ROCm 7.2 / MI355X for one sequence: 0.290 vs
-        // 0.282 ms per frame points-only and 0.477 vs 0.310 ms with the line stage on its second stream — the graph executor
-        // adds more per-node latency than the host-side launches cost (profiles/r02_single_stream_latency.txt)
-        s->graph_mode = stvo::dbg().seq_graph != stvo::DBG_UNSET && stvo::dbg().seq_graph != 0;
-    }
     if (!ok) {
         stvo_seq_destroy(s);
         return STVO_ERR_HIP;
@@ -900,12 +873,7 @@ int stvo_seq_create_multi(stvo_ctx* ctx, int B, int max_keypoints, int max_keyli
     s->d_qtab = (double*)(D + o_qtab);
     s->d_join_flag = (unsigned*)(D + o_joinflag);
     s->d_pose_flag = (unsigned*)(D + o_poseflag);
-    s->d_dyn_ctr = (int32_t*)(D + o_dyn_ctr);
-    s->d_dyn_owner = (int32_t*)(D + o_dyn_owner);
-    if (pipe_ok) {
-        s->m12p_alt = (int32_t*)(D + o_m12p_alt);
-        s->m12l_alt = (int32_t*)(D + o_m12l_alt);
-    }
+    if (alt_l) s->m12l_alt = (int32_t*)(D + o_m12l_alt);
     {
         std::vector<double> iw(2 * nb);
         for (int b = 0; b < B; ++b) {
@@ -982,10 +950,6 @@ int stvo_seq_set_slots(stvo_seq* s, int n_slots) {
     stvo_ctx* ctx = s->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->aux_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->aux_stream));
-    // captured step graphs (STVO_SEQ_GRAPH=1) hold the raw-slot addresses of the slots they were captured for
-    for (auto& g : s->graphs) (void)hipGraphExecDestroy(g.second);
-    s->graphs.clear();
     if (s->extra_raw) {
         HIP_TRY(ctx, hipFree(s->extra_raw));
         s->extra_raw = nullptr;
@@ -1011,7 +975,6 @@ int stvo_seq_destroy(stvo_seq* s) {
     if (!s) return STVO_OK;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    if (s->ctx->aux_stream) (void)hipStreamSynchronize(s->ctx->aux_stream);
     if (s->d_prof) (void)hipFree(s->d_prof);
     if (s->d_motion_T) (void)hipFree(s->d_motion_T);
     if (s->line_stream) {
@@ -1021,16 +984,10 @@ int stvo_seq_destroy(stvo_seq* s) {
     if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
     if (s->ev_join) (void)hipEventDestroy(s->ev_join);
     if (s->ev_cells) (void)hipEventDestroy(s->ev_cells);
-    if (s->ev_match) (void)hipEventDestroy(s->ev_match);
-    for (auto e : s->ev_pose)
-        if (e) (void)hipEventDestroy(e);
     if (s->ev_upload) (void)hipEventDestroy(s->ev_upload);
     for (auto e : s->ev_stage)
         if (e) (void)hipEventDestroy(e);
-    for (auto e : s->pev)
-        if (e) (void)hipEventDestroy(e);
     for (auto e : s->tev) (void)hipEventDestroy(e);
-    for (auto& g : s->graphs) (void)hipGraphExecDestroy(g.second);
     if (s->ev_fetch) (void)hipEventDestroy(s->ev_fetch);
     if (s->fetch_host) (void)hipHostFree(s->fetch_host);
     if (s->dev) (void)hipFree(s->dev);
@@ -1043,16 +1000,6 @@ int stvo_seq_destroy(stvo_seq* s) {
 }
 
 namespace {
-
-// pipelined steps: pose kernels still in flight on the aux stream (everything they depend on was enqueued before them)
-int seq_wait_pose_stream(stvo_seq* s) {
-    stvo_ctx* ctx = s->ctx;
-    if ((s->pose_pending[0] || s->pose_pending[1] || s->piped_last) && ctx->aux_stream) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->aux_stream));
-        s->pose_pending[0] = s->pose_pending[1] = false;
-    }
-    return STVO_OK;
-}
 
 void bind_raw(stvo_seq* s, stvo::SeqDev& d, int slot) {
     char* Rw = s->raw_dev[slot];
@@ -1137,7 +1084,7 @@ int stvo_seq_upload(stvo_seq* s, int slot, const stvo_frame_features* f) {
     s->raw_split[slot] = 0;
     if (s->raw_bytes <= (size_t)4 << 20) {
         // copy kernel instead of the DMA engine: ~5 us less latency for the ~200 KB of one frame
-        if (any_lines && s->op.has_points && !s->st_dirty && !s->graph_mode && s->line_stream) {
+        if (any_lines && s->op.has_points && !s->st_dirty && s->line_stream) {
             stvo::launch_copy16(ctx->stream, H, s->raw_dev[slot], s->off_kl_l);
             stvo::launch_copy16(s->line_stream, H + s->off_kl_l, s->raw_dev[slot] + s->off_kl_l, s->raw_bytes - s->off_kl_l);
             s->raw_split[slot] = 1;
@@ -1193,9 +1140,23 @@ struct StepFlags {
     bool lines_now, lines_prev, track;
 };
 
-// Enqueues the kernel chain of one step on the context's stream (and the line stream).  No state of `s` changes here, so
-// the same code serves direct launches and stream capture into a hipGraph.
-int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, bool* forked_by_event = nullptr) {
+// What a step has published for the steps after it.  stvo_seq_step_dev commits it to `s` only when the whole step has been enqueued,
+// so that no later step waits on an event or a flag that a failed step never recorded.
+struct StepPub {
+    bool fork_recorded = false;  // ev_fork was recorded on the point stream (stvo_seq::fork_rec_frame)
+    bool pose_flagged = false;   // the pose kernel publishes its start: d_pose_flag reaches pose_flag_value (stvo_seq::pose_flag_frame)
+    unsigned pose_flag_value = 0;
+    bool line_forked = false;    // the line stream waited for an event of the point stream (stvo_seq::sl_forked_frame)
+    bool fetch_by_pose = false;  // the pose kernel hands the match indices to the host and then publishes fetch_value (stvo_seq::fetch_by_pose)
+    unsigned fetch_value = 0;
+};
+
+// Enqueues the kernel chain of one step on the context's stream and the line stream, and returns in `pub` what the step publishes.
+// Of the state of `s` it changes only: the counters the three flags' values are drawn from (pose_epoch, join_epoch, fetch_epoch) — a
+// value handed to a launch may reach the device even when a later launch of the step fails, so it is never handed out twice; later
+// steps wait only for the values committed from `pub` —, the key-line capacity of the set it builds (set_lines_cap[cur]), the
+// stage-timing events it takes, and the test hooks (last_*_grid, last_line_fused).
+int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, StepPub& pub) {
     stvo_ctx* ctx = s->ctx;
     const int B = s->B, K = s->K, M = s->M;
     hipStream_t st = ctx->stream;
@@ -1219,31 +1180,10 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, bool* forked_by
     auto mark = [&](int k, hipStream_t q) {
         if (tev && !(light && k < 2)) (void)hipEventRecord(tev[k], q);
     };
-    // ---- pipelined step (stvo_seq: "pipelined steps"): this step's pose kernel goes to the aux stream and the NEXT step's association may
-    // start beside it.  Batches on the compact-record batch kernel only; not with the by-product fetch (its copies follow the pose kernel in
-    // the point stream), the full stage timers, the host-side profile markers or graph replay.
-    // (round 6: built, parity-green, measured — no gain: the matcher's workgroups need whole CUs, which the pose kernel frees only at its very
-    //  end; profiles/r06_pipelined_steps.txt.  Opt-in: STVO_SEQ_PIPE=1, 2 = without the gate.)
-    const int pipe_sw = stvo::dbg().seq_pipe;
-    const bool piped = s->m12p_alt != nullptr && ctx->aux_stream != nullptr && !ctx->overlap && !s->fetch && !s->graph_mode && !s->pev[0] &&
-                       !(tev && !light) && !s->zero_copy && (pipe_sw == 1 || pipe_sw == 2);
-    // what a pose kernel on the aux stream still reads — the stereo set this step overwrites (it was `prev` two steps ago) and the f2f
-    // match indices of this step's parity — is free once the pose kernel of two steps ago has finished: long ago, in the steady state
-    {
-        const int par2 = s->frame_idx & 1;
-        if (s->pose_pending[par2]) {
-            HIP_TRY(ctx, hipStreamWaitEvent(st, s->ev_pose[par2], 0));
-            s->pose_pending[par2] = false;
-        }
-        if (!piped && s->pose_pending[par2 ^ 1]) {  // leaving the pipelined mode: this step's pose kernel follows the last one in stream order
-            HIP_TRY(ctx, hipStreamWaitEvent(st, s->ev_pose[par2 ^ 1], 0));
-            s->pose_pending[par2 ^ 1] = false;
-        }
-    }
-    // two copies of the f2f match indices, by the parity of the step (batches without the by-product fetch, whose copies read the first):
-    // the matches of step k + 1 may be written while optimizePose(k) reads those of step k
-    const bool alt_ok = s->m12p_alt != nullptr && !s->fetch;
-    int32_t* const m12p_use = (alt_ok && (s->frame_idx & 1)) ? s->m12p_alt : s->m12p;
+    pub = StepPub{};
+    // two copies of the key-line match indices, by the parity of the step (batches without the by-product fetch, whose copies read the
+    // first): with the key-line stage ahead, the matches of step k + 1 may be written while optimizePose(k) reads those of step k
+    const bool alt_ok = s->m12l_alt != nullptr && !s->fetch;
     int32_t* const m12l_use = (alt_ok && (s->frame_idx & 1)) ? s->m12l_alt : s->m12l;
     // ---- stereo association of the new frame into set[cur]
     stvo_seq::Set& cs = s->set[s->cur];
@@ -1262,28 +1202,23 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, bool* forked_by
     const bool par = lines_now && s->op.has_points;
     hipStream_t sl = par ? s->line_stream : st;
     // Where the line stream forks off.  Every big kernel of the point stream fills the register file of the CUs it runs on, so work
-    // of the line stream never runs BESIDE it, only instead of it.  Forked at the start of the step (default) the line kernels share
-    // the GPU with point_cells_kernel and delay the start of some of the persistent point matcher's workgroups (0.158 -> 0.198 ms
-    // per 1024 frames) but leave the key-point scan alone (0.467 ms); forked after the point stage (STVO_LINE_FORK=late) they
-    // stretch the scan instead (0.510 ms).  Measured: 1024 KITTI-shaped streams 929 k (early) vs 935 k (late) frame pairs/s, 512
-    // EuRoC-shaped streams 857 k vs 777 k, one stream 0.252 vs 0.280 ms per frame.
-    // Round 5: a third point — behind the cells kernel (STVO_LINE_FORK=mid), the default for batches: the line kernels then become
-    // ready together with the persistent point matcher, whose workgroups (already queued) take their CUs first, instead of finding four
-    // line workgroups per CU in their way.  1024 KITTI-shaped streams 0.872 -> 0.853 ms per step, 512 EuRoC-shaped 1.036 -> 1.105 M
-    // frame pairs/s; one stream is SLOWER that way (0.205 -> 0.211 ms: its line kernels lose their head start), so small batches keep
-    // the fork at the start.  STVO_LINE_FORK=start / mid / late forces one of the three.
-    const int fork_sw = stvo::dbg().line_fork_late;  // DBG_UNSET: by batch size
-    const bool late_fork = par && fork_sw == 1;
-    const bool mid_fork = par && s->op.has_points && (fork_sw == 2 || (fork_sw == stvo::DBG_UNSET && B >= 64));
-    const bool fork_free = par && s->raw_split[slot] && !s->st_dirty && !s->graph_mode;  // see stvo_seq::st_dirty
-    if (forked_by_event) *forked_by_event = par && (late_fork || mid_fork || !fork_free);
-    if (par && !late_fork && !mid_fork && !fork_free) {
+    // of the line stream never runs BESIDE it, only instead of it.  Forked at the start of the step (small batches) the line kernels
+    // share the GPU with point_cells_kernel and delay the start of some of the persistent point matcher's workgroups (0.158 -> 0.198 ms
+    // per 1024 frames) but leave the key-point scan alone (0.467 ms); forked after the point stage (measured, then removed) they
+    // stretched the scan instead (0.510 ms): 1024 KITTI-shaped streams 929 k (start) vs 935 k (after) frame pairs/s, 512 EuRoC-shaped
+    // streams 857 k vs 777 k, one stream 0.252 vs 0.280 ms per frame.
+    // Round 5: behind the cells kernel (mid), the default for batches: the line kernels then become ready together with the
+    // persistent point matcher, whose workgroups (already queued) take their CUs first, instead of finding four line workgroups per CU
+    // in their way.  1024 KITTI-shaped streams 0.872 -> 0.853 ms per step, 512 EuRoC-shaped 1.036 -> 1.105 M frame pairs/s; one
+    // stream is SLOWER that way (0.205 -> 0.211 ms: its line kernels lose their head start), so small batches keep the fork at the start.
+    const bool mid_fork = par && B >= 64;
+    const bool fork_free = par && s->raw_split[slot] && !s->st_dirty;  // see stvo_seq::st_dirty
+    pub.line_forked = par && (mid_fork || !fork_free);
+    if (par && !mid_fork && !fork_free) {
         HIP_TRY(ctx, hipEventRecord(s->ev_fork, st));
         HIP_TRY(ctx, hipStreamWaitEvent(sl, s->ev_fork, 0));
     }
     d.zero_nl = (!lines_now && s->op.has_points) ? 1 : 0;
-    if (s->pev[0]) (void)hipEventRecord(s->pev[1], st);  // pev[0] was recorded before the ingest
-    int stage_rc = STVO_OK;
     auto point_stage = [&]() -> int {
         if (s->op.has_points) {
             mark(0, st);
@@ -1316,7 +1251,7 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, bool* forked_by
             // last read two steps ago, and the line stream's work of the previous step waited for an event the point stream recorded
             // after that: sl_forked_frame), (b) the line stream has been made to wait for every upload enqueued on the point stream
             // (stvo_seq_step_dev), (c) everything else the kernel reads is the resident slot.  STVO_CELLS_AHEAD=0: in the point stream.
-            const bool cells_ahead = par && mid_fork && g.lean_cells && !g.fused_cells && (!tev || light) && !s->pev[0] && !s->graph_mode &&
+            const bool cells_ahead = mid_fork && g.lean_cells && !g.fused_cells && (!tev || light) &&
                                      s->cells_buf[0].pstart != s->cells_buf[1].pstart && s->sl_forked_frame == (long long)s->frame_idx - 1 &&
                                      stvo::dbg().cells_ahead != 0;
             // key-line stage ahead (stvo_seq: fork_rec_frame): the line stream waits for the PREVIOUS step's fork event — in front of the
@@ -1328,12 +1263,9 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, bool* forked_by
             const int la_sw = stvo::dbg().lines_ahead;
             const bool la_pays = s->pose_flag_frame == (long long)s->frame_idx - 1 && B > 2 * stvo::device_cu_count() &&
                                  std::max(s->raw_max_lines[slot], s->set_lines_cap[s->prev_set()]) <= 128;
-            const bool lines_ahead = cells_ahead && !piped && alt_ok && s->fork_rec_frame == (long long)s->frame_idx - 1 && la_sw != 0 &&
-                                     (la_sw == 1 || la_sw == 2 || la_pays);
-            // (STVO_LINES_AHEAD=2: the gate in front of the cells kernel too — experiment)
-            const bool gate_cells = lines_ahead && stvo::dbg().lines_ahead == 2 && s->pose_flag_frame == (long long)s->frame_idx - 1;
+            const bool lines_ahead = cells_ahead && alt_ok && s->fork_rec_frame == (long long)s->frame_idx - 1 && la_sw != 0 &&
+                                     (la_sw == 1 || la_pays);
             if (lines_ahead) HIP_TRY(ctx, hipStreamWaitEvent(sl, s->ev_fork, 0));
-            if (gate_cells) stvo::launch_stream_gate(sl, s->d_pose_flag, s->pose_epoch);
             if (g.fused_cells)
                 g.cells = stvo::point_cells_args(d);
             else if (g.lean_cells)
@@ -1351,20 +1283,11 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, bool* forked_by
             if (light) (void)hipEventRecord(tev[2], st);
             if (mid_fork) {
                 HIP_TRY(ctx, hipEventRecord(s->ev_fork, st));
-                if (!s->graph_mode) s->fork_rec_frame = s->frame_idx;
+                pub.fork_recorded = true;
                 if (!lines_ahead)
                     HIP_TRY(ctx, hipStreamWaitEvent(sl, s->ev_fork, 0));
-                else if (!gate_cells && s->pose_flag_frame == (long long)s->frame_idx - 1)  // the key-line kernels behind the dispatch of optimizePose(k - 1)
-                    stvo::launch_stream_gate(sl, s->d_pose_flag, s->pose_epoch);
-            }
-            // pipelined steps: the persistent matcher starts beside the previous step's pose kernel — frames by ticket (GridBatch::dyn_ctr)
-            if (piped && fl.track && g.lean_cells && !g.fused_cells && stvo::dbg().grid_dyn != 0) {
-                g.dyn_ctr = s->d_dyn_ctr;
-                g.dyn_owner = s->d_dyn_owner;
-                g.dyn_par = s->frame_idx & 1;
-                if (s->dyn_last_frame != (long long)s->frame_idx - 1)  // nobody reset this launch's counter
-                    HIP_TRY(ctx, hipMemsetAsync(s->d_dyn_ctr, 0, 2 * sizeof(int32_t), st));
-                s->dyn_last_frame = s->frame_idx;
+                else if (s->pose_flag_frame == (long long)s->frame_idx - 1)  // the key-line kernels behind the dispatch of optimizePose(k - 1)
+                    stvo::launch_stream_gate(sl, s->d_pose_flag, s->pose_flag_value);
             }
             s->last_point_grid = g;
             stvo::launch_grid_batch(st, g, false, tev ? (light ? gev_light : tev + 2) : nullptr);
@@ -1389,10 +1312,8 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, bool* forked_by
             if (g.mutual) { g.elig = s->elig_l; g.elig_cnt = s->elig_cnt_l; g.ovf = s->govf_l; }
             s->last_line_grid = g;
             // few key-lines per frame: the whole association in one workgroup per frame (STVO_LINE_FUSED=0: the general grid matcher)
-            // LDS for the lines the slot holds, not for the capacity — except under graph replay: a captured step is replayed for
-            // later uploads into the slot, whose line counts the capture cannot know, so it is sized for the capacity (and so are
-            // the caps derived from set_lines_cap below)
-            const int Mk = s->graph_mode ? M : std::min(M, std::max(64, (s->raw_max_lines[slot] + 63) & ~63));
+            // LDS for the lines the slot holds, not for the capacity
+            const int Mk = std::min(M, std::max(64, (s->raw_max_lines[slot] + 63) & ~63));
             s->set_lines_cap[s->cur] = Mk;
             const size_t lds = (size_t)Mk * stvo::LSF_BYTES_PER_LINE + 4 + (size_t)Mk * (Mk / 32) * 4;
             const int ef = stvo::dbg().line_fused;
@@ -1413,17 +1334,8 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, bool* forked_by
         }
         return STVO_OK;
     };
-    // enqueue order: STVO_LINE_FIRST=1 puts the line kernel in front of the point stage (experiment: the point matcher then starts on
-    // free CUs, the cells kernel shares them — same step time on 1024 KITTI-shaped streams, slower with hundreds of lines per image)
-    const bool line_first = par && !late_fork && stvo::dbg().line_first == 1;
-    if (line_first && (stage_rc = line_stage()) != STVO_OK) return stage_rc;
-    if ((stage_rc = point_stage()) != STVO_OK) return stage_rc;
-    if (late_fork) {
-        HIP_TRY(ctx, hipEventRecord(s->ev_fork, st));
-        HIP_TRY(ctx, hipStreamWaitEvent(sl, s->ev_fork, 0));
-    }
-    if (!line_first && (stage_rc = line_stage()) != STVO_OK) return stage_rc;
-    if (s->pev[0]) (void)hipEventRecord(s->pev[2], st);
+    TRY(point_stage());
+    TRY(line_stage());
     const bool track = fl.track;
     if (track) {
         // ---- f2fTracking: prev stereo sets vs curr stereo sets
@@ -1459,7 +1371,7 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, bool* forked_by
             }
         };
         hipEvent_t mev_light[4] = {tev ? tev[4] : nullptr, tev ? tev[5] : nullptr, nullptr, nullptr};  // (light: no pair around plan + reverse scans)
-        if (s->op.has_points) match_set(st, w, K, ps.desc, ps.n, cs.desc, cs.n, s->mp.min_ratio_12_p, m12p_use, tev ? (light ? mev_light : tev + 4) : nullptr);
+        if (s->op.has_points) match_set(st, w, K, ps.desc, ps.n, cs.desc, cs.n, s->mp.min_ratio_12_p, s->m12p, tev ? (light ? mev_light : tev + 4) : nullptr);
         small_cap = lines_cap;
         if (lines_prev && lines_now)
             match_set(sl, s->lazy_l, M, ps.ldesc, ps.nl, cs.ldesc, cs.nl, s->mp.min_ratio_12_l, m12l_use, nullptr);
@@ -1467,21 +1379,14 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, bool* forked_by
             HIP_TRY(ctx, hipMemsetAsync(m12l_use, 0xFF, (size_t)B * M * sizeof(int32_t), st));
         // Small batches (single-stream operation): the pose kernel itself waits for the line stream and hands the match indices to
         // the host — an event awaited or recorded in front of it delays its start by ~6 us each on this runtime.
-        const bool inline_sync = stvo::pose_inline_sync_ok(B) && stvo::dbg().seq_inline != 0 && !s->graph_mode && !tev && !s->pev[0] &&
-                                 (!s->fetch || (B == 1 && s->zero_copy));
-        hipStream_t sp = piped ? ctx->aux_stream : st;  // the stream of optimizePose
-        if (piped) {  // the pose kernel waits for both streams' matches; the point stream does not wait for the key-line stream at all
-            HIP_TRY(ctx, hipEventRecord(s->ev_match, st));
-            HIP_TRY(ctx, hipStreamWaitEvent(sp, s->ev_match, 0));
-        }
+        const bool inline_sync = stvo::pose_inline_sync_ok(B) && stvo::dbg().seq_inline != 0 && !tev && (!s->fetch || (B == 1 && s->zero_copy));
         if (par && inline_sync) {
             stvo::launch_stream_signal(sl, s->d_join_flag, ++s->join_epoch);
         } else if (par) {  // join before optimizePose
             HIP_TRY(ctx, hipEventRecord(s->ev_join, sl));
-            HIP_TRY(ctx, hipStreamWaitEvent(sp, s->ev_join, 0));
+            HIP_TRY(ctx, hipStreamWaitEvent(st, s->ev_join, 0));
         }
-        if (s->pev[0]) (void)hipEventRecord(s->pev[3], st);
-        s->fetch_by_pose = s->fetch && inline_sync;
+        pub.fetch_by_pose = s->fetch && inline_sync;
         if (s->fetch && !inline_sync) {
             stvo::launch_copy16(st, s->m12s_p, s->fetch_host, s->m12_span);
             HIP_TRY(ctx, hipEventRecord(s->ev_fetch, st));
@@ -1491,7 +1396,7 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, bool* forked_by
         std::memset(&a, 0, sizeof(a));
         a.B = B; a.max_pts = K; a.max_lines = M;
         a.n_prev_pts = s->op.has_points ? ps.n : nullptr;
-        a.prev_rc = ps.rc; a.curr_rc = cs.rc; a.q_tab = s->d_qtab; a.level_scale = s->mp.orb_scale_factor; a.m12p = m12p_use;
+        a.prev_rc = ps.rc; a.curr_rc = cs.rc; a.q_tab = s->d_qtab; a.level_scale = s->mp.orb_scale_factor; a.m12p = s->m12p;
         a.n_prev_lines = s->op.has_lines ? ps.nl : nullptr;
         a.prev_sP = ps.sP; a.prev_eP = ps.eP; a.prev_spl = ps.spl; a.prev_epl = ps.epl; a.prev_s2l = ps.s2lm;
         a.curr_le = cs.le; a.m12l = m12l_use;
@@ -1516,39 +1421,28 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, bool* forked_by
         }
         // single-stream operation: the eigenvalues of the committed covariance (an output only) are computed by stvo_seq_read
         a.lazy_eig = (inline_sync && s->zero_copy && stvo::dbg().pose_kernel != 4) ? 1 : 0;
-        if (s->fetch_by_pose) {
+        if (pub.fetch_by_pose) {
             a.fetch_src = reinterpret_cast<const uint4*>(s->m12s_p);
             a.fetch_dst = reinterpret_cast<uint4*>(s->fetch_host);
             a.fetch_n16 = (unsigned)(s->m12_span / 16);
             a.fetch_flag = reinterpret_cast<unsigned*>(s->fetch_host + s->m12_span + s->inl_span);
-            a.fetch_value = ++s->fetch_epoch;
+            a.fetch_value = pub.fetch_value = ++s->fetch_epoch;
         }
-        const bool flagged = s->m12p_alt != nullptr && !s->graph_mode && stvo::pose_start_flag_ok(a);  // (batches on the batch kernel)
-        const bool gated = piped && pipe_sw != 2 && flagged;
-        if (flagged) {
+        // batches on the batch kernel: the key-line stage of the next step may wait for this launch to begin
+        if (s->m12l_alt != nullptr && stvo::pose_start_flag_ok(a)) {
             a.start_flag = s->d_pose_flag;
-            a.start_value = ++s->pose_epoch;
-            s->pose_flag_frame = s->frame_idx;
+            a.start_value = pub.pose_flag_value = ++s->pose_epoch;
+            pub.pose_flagged = true;
         }
-        mark(8, sp);
-        TRY(stvo::launch_pose(sp, a));
-        mark(9, sp);
-        if (piped) {
-            const int par2 = s->frame_idx & 1;
-            HIP_TRY(ctx, hipEventRecord(s->ev_pose[par2], sp));
-            s->pose_pending[par2] = true;
-            // the point stream's next kernels (the next step's matcher) behind the start of this pose kernel
-            if (gated) stvo::launch_stream_gate(st, s->d_pose_flag, s->pose_epoch);
-        }
-        s->piped_last = piped;
-        if (s->pev[0]) (void)hipEventRecord(s->pev[4], st);
+        mark(8, st);
+        TRY(stvo::launch_pose(st, a));
+        mark(9, st);
         if (s->fetch && !inl_zero_copy) stvo::launch_copy16(st, s->inlp, s->fetch_host + s->m12_span, s->inl_span);
     } else {
         if (par) {  // first frame: nothing to track, but the main stream must still see the line stage's results
             HIP_TRY(ctx, hipEventRecord(s->ev_join, sl));
             HIP_TRY(ctx, hipStreamWaitEvent(st, s->ev_join, 0));
         }
-        s->fetch_by_pose = false;
         if (s->fetch) {
             stvo::launch_copy16(st, s->m12s_p, s->fetch_host, s->m12_span);
             HIP_TRY(ctx, hipEventRecord(s->ev_fetch, st));
@@ -1559,9 +1453,7 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, bool* forked_by
 
 }  // namespace
 
-// Runs the whole per-frame pipeline on the features resident in `slot` (asynchronous; no host transfer).  Optionally
-// (STVO_SEQ_GRAPH=1) the chain of ~25 short kernels on two streams is captured ONCE per (slot, buffer parity, line-stage
-// flags) into a hipGraph and replayed with a single launch; measured slower than direct launches, see stvo_seq_create_multi.
+// Runs the whole per-frame pipeline on the features resident in `slot` (asynchronous; no host transfer).
 int stvo_seq_step_dev(stvo_seq* s, int slot) {
     if (!s || slot < 0 || slot >= (int)s->raw_dev.size()) return STVO_ERR_INVALID_ARG;
     stvo_ctx* ctx = s->ctx;
@@ -1578,38 +1470,17 @@ int stvo_seq_step_dev(stvo_seq* s, int slot) {
             s->upload_seen = s->upload_seq;
         }
     }
-    bool forked = false;
-    // the first steps run directly (lazy one-time initialisations must not happen inside a capture); timing / fetch /
-    // profiling modes record events the host waits on, which a captured graph cannot provide
-    const bool use_graph = s->graph_mode && s->frame_idx >= 2 && !s->timing && !s->fetch && !s->pev[0] && !ctx->overlap;
-    if (use_graph) {
-        const unsigned key = (unsigned)slot | ((unsigned)s->cur << 8) | ((unsigned)fl.lines_now << 10) | ((unsigned)fl.lines_prev << 11) |
-                             ((unsigned)fl.track << 12) | ((unsigned)(s->frame_idx & 1) << 13);  // (set index 0..2, grid-buffer parity)
-        auto it = s->graphs.find(key);
-        if (it == s->graphs.end()) {
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            bool ok = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-            int rc = STVO_ERR_HIP;
-            if (ok) {
-                rc = seq_enqueue_step(s, slot, fl, &forked);
-                ok = hipStreamEndCapture(ctx->stream, &graph) == hipSuccess && rc == STVO_OK && graph != nullptr;
-            }
-            if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
-            if (graph) (void)hipGraphDestroy(graph);
-            if (!ok) {  // capture unsupported for some node: fall back to direct launches for good
-                (void)hipGetLastError();
-                s->graph_mode = false;
-                TRY(seq_enqueue_step(s, slot, fl, &forked));
-            } else {
-                it = s->graphs.emplace(key, exec).first;
-            }
-        }
-        if (s->graph_mode) HIP_TRY(ctx, hipGraphLaunch(it->second, ctx->stream));
-    } else {
-        TRY(seq_enqueue_step(s, slot, fl, &forked));
+    StepPub pub;
+    TRY(seq_enqueue_step(s, slot, fl, pub));
+    // the whole step is enqueued: what it published
+    if (pub.fork_recorded) s->fork_rec_frame = s->frame_idx;
+    if (pub.pose_flagged) {
+        s->pose_flag_frame = s->frame_idx;
+        s->pose_flag_value = pub.pose_flag_value;
     }
-    if (forked && !s->graph_mode) s->sl_forked_frame = s->frame_idx;
+    if (pub.line_forked) s->sl_forked_frame = s->frame_idx;
+    s->fetch_by_pose = pub.fetch_by_pose;
+    s->fetch_value = pub.fetch_value;
     s->st_dirty = true;
     s->set_lines[s->cur] = fl.lines_now;
     s->last_lines = fl.lines_now;
@@ -1628,7 +1499,6 @@ int stvo_seq_read(stvo_seq* s, stvo_pose_result* results, int32_t* counts) {
     const int B = s->B;
     hipStream_t st = ctx->stream;
     const stvo_seq::Set& ls = s->set[s->prev_set()];  // the set built by the last step (cur has moved on)
-    TRY(seq_wait_pose_stream(s));  // pipelined steps: the last pose kernels run on the aux stream
     if (s->d_prof && s->frame_idx > 1) {  // STVO_POSE_PROF: mean phase ticks of the last pose launch (as stvo_time_stage_dev prints them)
         HIP_TRY(ctx, hipStreamSynchronize(st));
         std::vector<long long> h((size_t)B * 16);
@@ -1706,12 +1576,12 @@ int stvo_seq_fetch_matches(stvo_seq* s, const int32_t** m12_stereo_pts, const in
         const volatile unsigned* flag = reinterpret_cast<const volatile unsigned*>(s->fetch_host + s->m12_span + s->inl_span);
         const auto t0 = std::chrono::steady_clock::now();
         bool seen = false;
-        for (unsigned spin = 0; !(seen = (*flag == s->fetch_epoch)); ++spin)
+        for (unsigned spin = 0; !(seen = (*flag == s->fetch_value)); ++spin)
             if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
         std::atomic_thread_fence(std::memory_order_acquire);
         if (!seen) {
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (*flag != s->fetch_epoch) {  // the kernel ended without publishing: it gave up waiting for the key-line stream (STVO_POSE_INTERNAL)
+            if (*flag != s->fetch_value) {  // the kernel ended without publishing: it gave up waiting for the key-line stream (STVO_POSE_INTERNAL)
                 std::snprintf(ctx->last_error, sizeof(ctx->last_error), "%s", "the pose kernel did not publish the match indices of the last step (no signal from the key-line stream)");
                 return STVO_ERR_HIP;
             }
@@ -1746,8 +1616,6 @@ int stvo_seq_set_motion_model(stvo_seq* s, int enable) {
     stvo_ctx* ctx = s->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    // (every stream a pose kernel or a captured step may still hold init_T / next_T on — the set stvo_seq_destroy waits for)
-    if (ctx->aux_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->aux_stream));
     if (s->line_stream) HIP_TRY(ctx, hipStreamSynchronize(s->line_stream));
     if (!enable) {
         if (s->d_motion_T) (void)hipFree(s->d_motion_T);
@@ -1759,8 +1627,6 @@ int stvo_seq_set_motion_model(stvo_seq* s, int enable) {
             for (int i = 0; i < 4; ++i) I[(size_t)b * 16 + i * 5] = 1.0;
         if (!upload_now(ctx, s->d_motion_T, I.data(), I.size() * sizeof(double), "hipMemcpy motion")) return STVO_ERR_HIP;
     }
-    for (auto& g : s->graphs) (void)hipGraphExecDestroy(g.second);  // captured steps hold the old init_T pointer
-    s->graphs.clear();
     return STVO_OK;
 }
 
@@ -1776,7 +1642,6 @@ int stvo_seq_get_stage_timing(stvo_seq* s, float avg_ms[STVO_SEQ_NSTAGE], int32_
     stvo_ctx* ctx = s->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    TRY(seq_wait_pose_stream(s));  // (pipelined steps: the pose kernel's pair is on the aux stream)
     double acc[STVO_SEQ_NSTAGE] = {0};
     int cnt[STVO_SEQ_NSTAGE] = {0};
     for (size_t k = 0; k + 2 * STVO_SEQ_NSTAGE <= s->tev_used; k += 2 * STVO_SEQ_NSTAGE)
@@ -1877,45 +1742,9 @@ int stvo_seq_debug_grid(stvo_seq* s, int b, int lines, int32_t* cell_start, int3
 int stvo_seq_push(stvo_seq* s, const stvo_frame_features* f, stvo_pose_result* results, int32_t* counts) {
     if (!s || !f) return STVO_ERR_INVALID_ARG;
     const int slot = s->frame_idx & 1;  // (slots beyond the first two belong to callers of upload / step_dev)
-    const bool prof = stvo::dbg().seq_prof != stvo::DBG_UNSET;  // developer aid: host-side phase times
-    if (!prof) {
-        TRY(stvo_seq_upload(s, slot, f));
-        TRY(stvo_seq_step_dev(s, slot));
-        return stvo_seq_read(s, results, counts);
-    }
-    using clk = std::chrono::steady_clock;
-    static double acc[4] = {0, 0, 0, 0}, gacc[4] = {0, 0, 0, 0};
-    static int n = 0, gn = 0;
-    if (!s->pev[0])
-        for (auto& e : s->pev) (void)hipEventCreate(&e);
-    const auto t0 = clk::now();
-    (void)hipEventRecord(s->pev[0], s->ctx->stream);
     TRY(stvo_seq_upload(s, slot, f));
-    const auto t1 = clk::now();
     TRY(stvo_seq_step_dev(s, slot));
-    const auto t2 = clk::now();
-    (void)hipStreamSynchronize(s->ctx->stream);
-    const auto t3 = clk::now();
-    const int rc = stvo_seq_read(s, results, counts);
-    const auto t4 = clk::now();
-    auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-    if (s->frame_idx > 10) {  // skip the warm-up frames
-        acc[0] += us(t0, t1); acc[1] += us(t1, t2); acc[2] += us(t2, t3); acc[3] += us(t3, t4);
-        ++n;
-        float ms[4] = {0, 0, 0, 0};
-        bool okev = true;
-        for (int k = 0; k < 4; ++k) okev = okev && hipEventElapsedTime(&ms[k], s->pev[k], s->pev[k + 1]) == hipSuccess;
-        if (okev) {
-            for (int k = 0; k < 4; ++k) gacc[k] += ms[k] * 1e3;
-            ++gn;
-        }
-        if (n % 20 == 0)
-            std::fprintf(stderr, "[seq prof] host, mean us over %d frames: pack + ingest enqueue %.1f | kernel launches %.1f | wait for GPU %.1f | "
-                                 "read-back %.1f || GPU (events): ingest %.1f | stereo stage %.1f | f2f stage %.1f | pose %.1f\n",
-                         n, acc[0] / n, acc[1] / n, acc[2] / n, acc[3] / n, gacc[0] / (gn ? gn : 1), gacc[1] / (gn ? gn : 1),
-                         gacc[2] / (gn ? gn : 1), gacc[3] / (gn ? gn : 1));
-    }
-    return rc;
+    return stvo_seq_read(s, results, counts);
 }
 
 }  // extern "C"

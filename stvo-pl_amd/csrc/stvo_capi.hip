@@ -27,12 +27,7 @@ DebugSwitches parse_switches() {
     d.pose_los = env_int("STVO_POSE_LOS");
     d.knn_mfma = env_int("STVO_KNN_MFMA");
     d.knn_nseg = env_int("STVO_KNN_NSEG");
-    d.seq_graph = env_int("STVO_SEQ_GRAPH");
-    d.seq_prof = env_int("STVO_SEQ_PROF");
     d.seq_inline = env_int("STVO_SEQ_INLINE");
-    const char* lf = std::getenv("STVO_LINE_FORK");
-    d.line_fork_late = lf ? (lf[0] == 'l' ? 1 : (lf[0] == 'm' ? 2 : 0)) : DBG_UNSET;
-    d.line_first = env_int("STVO_LINE_FIRST");
     d.cells_ahead = env_int("STVO_CELLS_AHEAD");
     d.line_fused = env_int("STVO_LINE_FUSED");
     d.match_small = env_int("STVO_MATCH_SMALL");
@@ -41,9 +36,7 @@ DebugSwitches parse_switches() {
     d.grid_fused = env_int("STVO_GRID_FUSED");
     d.grid_fused_cap = env_int("STVO_GRID_FUSED_CAP");
     d.grid_cells = env_int("STVO_GRID_CELLS");
-    d.seq_pipe = env_int("STVO_SEQ_PIPE");
     d.lines_ahead = env_int("STVO_LINES_AHEAD");
-    d.grid_dyn = env_int("STVO_GRID_DYN");
     d.lsd_grow = env_int("STVO_LSD_GROW");
     d.lsd_waves = env_int("STVO_LSD_WAVES");
     d.lsd_xcd_blocks = env_int("STVO_LSD_XCD_BLOCKS");
@@ -150,9 +143,8 @@ int stvo_ctx_destroy(stvo_ctx* ctx) {
         (void)hipStreamSynchronize(ctx->aux_stream);
         stvo::pose_release_stream(ctx->aux_stream);
         (void)hipStreamDestroy(ctx->aux_stream);
-        // (the aux stream may have been created by a sequence pipeline — pipelined steps — without the overlap mode's events)
-        if (ctx->ev_match_done) (void)hipEventDestroy(ctx->ev_match_done);
-        if (ctx->ev_pose_done) (void)hipEventDestroy(ctx->ev_pose_done);
+        (void)hipEventDestroy(ctx->ev_match_done);
+        (void)hipEventDestroy(ctx->ev_pose_done);
     }
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -183,13 +175,20 @@ int stvo_ctx_synchronize(stvo_ctx* ctx) {
 int stvo_ctx_set_overlap(stvo_ctx* ctx, int enable) {
     if (!ctx) return STVO_ERR_INVALID_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (enable && !ctx->aux_stream) {
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
-        stvo::pose_retain_stream(ctx->aux_stream);
-    }
-    if (enable && !ctx->ev_match_done) {  // (a sequence pipeline may have created the aux stream before: its pipelined steps)
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_match_done, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_pose_done, hipEventDisableTiming));
+    if (enable && !ctx->aux_stream) {  // the aux stream and its two events exist together, or none of them
+        hipEvent_t em = nullptr, ep = nullptr;
+        hipStream_t as = nullptr;
+        if (!hip_ok(ctx, hipEventCreateWithFlags(&em, hipEventDisableTiming), "hipEventCreate overlap") ||
+            !hip_ok(ctx, hipEventCreateWithFlags(&ep, hipEventDisableTiming), "hipEventCreate overlap") ||
+            !hip_ok(ctx, hipStreamCreateWithFlags(&as, hipStreamNonBlocking), "hipStreamCreate overlap")) {
+            if (em) (void)hipEventDestroy(em);
+            if (ep) (void)hipEventDestroy(ep);
+            return STVO_ERR_HIP;
+        }
+        ctx->ev_match_done = em;
+        ctx->ev_pose_done = ep;
+        ctx->aux_stream = as;
+        stvo::pose_retain_stream(as);
     }
     if (!enable && ctx->aux_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->aux_stream));
     ctx->overlap = enable ? 1 : 0;

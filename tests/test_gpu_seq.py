@@ -276,21 +276,21 @@ def test_seq_point_grid_other_formulations(oracle, switches, env):
     run_and_compare(oracle, seqs, cam, "kitti")
 
 
-@pytest.mark.parametrize("env", [
-    {"STVO_LINE_FUSED": "1", "STVO_MATCH_SMALL": "1"},    # one workgroup per frame for 200 key-lines (LDS sized for 256, opt-in above 48 KB at 320)
-    {"STVO_LINE_FUSED": "0", "STVO_MATCH_SMALL": "0"},    # the general grid matcher and match machinery for the key-lines
-    {"STVO_LINE_FUSED": "1", "STVO_LINE_FORK": "late"},   # line stream forked after the point stage
-    {"STVO_GRID_TAIL": "0"},                              # point_tail_kernel as its own launch behind the lean cells kernel
-    {"STVO_MATCH_LAZY": "1"},                             # lazy reverse check for a tiny batch (default there: both directions in one scan)
-], ids=["lines-fused", "lines-general", "late-fork", "tail-kernel", "lazy-reverse"])
-def test_seq_step_variants_line_heavy(oracle, switches, env):
+@pytest.mark.parametrize("env,max_kl", [
+    ({"STVO_LINE_FUSED": "1", "STVO_MATCH_SMALL": "1"}, 320),  # one workgroup per frame for 200 key-lines (LDS sized for 256, opt-in above 48 KB at 320)
+    ({"STVO_LINE_FUSED": "0", "STVO_MATCH_SMALL": "0"}, 320),  # the general grid matcher and match machinery for the key-lines
+    ({"STVO_LINE_FUSED": "1"}, 512),                           # the fused line kernel at a 512-line capacity
+    ({"STVO_GRID_TAIL": "0"}, 320),                            # point_tail_kernel as its own launch behind the lean cells kernel
+    ({"STVO_MATCH_LAZY": "1"}, 320),                           # lazy reverse check for a tiny batch (default there: both directions in one scan)
+], ids=["lines-fused", "lines-general", "lines-fused-cap512", "tail-kernel", "lazy-reverse"])
+def test_seq_step_variants_line_heavy(oracle, switches, env, max_kl):
     """Every launch plan the step can choose (by batch size / line count, or by a developer switch) gives the oracle's results:
     EuRoC-shaped frames with ~240 key-lines per image, two streams."""
     switches(env)
     cam = synth.EUROC_CAM
     seqs = [synth.make_stereo_sequence(740 + b, n_frames=4, n_pts=500, n_lines=200, cam=cam, depth=(1.0, 8.0),
                                        octave_probs=[.5, .25, .15, .1], outlier_frac=0.2) for b in range(2)]
-    run_and_compare(oracle, seqs, cam, "euroc", max_kl=512 if env.get("STVO_LINE_FORK") else 320)
+    run_and_compare(oracle, seqs, cam, "euroc", max_kl=max_kl)
 
 
 def test_seq_batch_line_heavy_default_plan(oracle):
@@ -447,12 +447,11 @@ def test_seq_pipeline_headline_shape_every_stream_vs_oracle(oracle, switches, po
 
 
 def test_seq_steps_back_to_back_schedules_agree(switches):
-    """Round 6: three stereo sets, two copies of the f2f match indices, and two schedules built on them — the key-line stage one step
-    AHEAD (the line stream waits for the previous step's fork event and a gate behind the dispatch of the previous pose kernel: the
-    default for > 2 x CUs streams with ~100 key-lines per image) and the pipelined steps (optimizePose on the aux stream beside the next
-    step's stereo association, the persistent point matcher taking frames by ticket: opt-in).  Seven steps enqueued BACK TO BACK — only
-    then do the overlaps they are about happen — must leave exactly the poses, counts and inlier totals of the plain schedule with a read
-    after every step (the one the headline-shape test compares with the oracle stream by stream)."""
+    """Round 6: three stereo sets, two copies of the key-line match indices, and the schedule built on them — the key-line stage one
+    step AHEAD (the line stream waits for the previous step's fork event and a gate behind the dispatch of the previous pose kernel: the
+    default for > 2 x CUs streams with ~100 key-lines per image).  Seven steps enqueued BACK TO BACK — only then do the overlaps it is
+    about happen — must leave exactly the poses, counts and inlier totals of the plain schedule with a read after every step (the one
+    the headline-shape test compares with the oracle stream by stream)."""
     from stvo_amd import capi
     B, S = 320, 3
     ids = np.arange(B) % synth.CONFIG5_N_SEQUENCES
@@ -479,13 +478,10 @@ def test_seq_steps_back_to_back_schedules_agree(switches):
             dev.close()
             ctx.close()
 
-    base = {"STVO_LINES_AHEAD": "0", "STVO_SEQ_PIPE": "0", "STVO_GRID_DYN": "1"}
+    base = {"STVO_LINES_AHEAD": "0"}
     ref_res, ref_counts = run(base, True)
     assert (ref_res["status"] == 0).mean() > 0.9 and ref_counts[:, 2].mean() > 500
-    for name, env in (("plain, back to back", base), ("key-line stage ahead", dict(base, STVO_LINES_AHEAD="1")),
-                      ("key-line stage ahead, gate in front of the cells kernel", dict(base, STVO_LINES_AHEAD="2")),
-                      ("pipelined steps", dict(base, STVO_SEQ_PIPE="1")), ("pipelined steps, static frames", dict(base, STVO_SEQ_PIPE="1", STVO_GRID_DYN="0")),
-                      ("pipelined steps, no gate", dict(base, STVO_SEQ_PIPE="2"))):
+    for name, env in (("plain, back to back", base), ("key-line stage ahead", dict(base, STVO_LINES_AHEAD="1"))):
         res, counts = run(env, False)
         assert np.array_equal(counts, ref_counts), name
         assert res.tobytes() == ref_res.tobytes(), name

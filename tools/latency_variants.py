@@ -36,11 +36,9 @@ def main():
     kitti = synth.make_stereo_sequence(synth.frame_seed(77, 0), n_frames=61, n_pts=1650, n_lines=85, cam=synth.KITTI_CAM)
     euroc = synth.make_stereo_sequence(synth.frame_seed(78, 0), n_frames=61, n_pts=660, n_lines=250, cam=synth.EUROC_CAM,
                                        depth=(0.5, 8.0), octave_probs=[.5, .25, .15, .1], outlier_frac=0.4)
-    keys = ["STVO_LINE_FORK", "STVO_LINE_FUSED", "STVO_MATCH_SMALL", "STVO_GRID_TAIL"]
-    variants = [dict(), dict(STVO_LINE_FORK="early"), dict(STVO_LINE_FORK="early", STVO_LINE_FUSED="0"),
-                dict(STVO_LINE_FORK="early", STVO_MATCH_SMALL="0"), dict(STVO_LINE_FORK="early", STVO_LINE_FUSED="0", STVO_MATCH_SMALL="0"),
-                dict(STVO_LINE_FORK="early", STVO_GRID_TAIL="0"),
-                dict(STVO_LINE_FORK="early", STVO_LINE_FUSED="0", STVO_MATCH_SMALL="0", STVO_GRID_TAIL="0")]
+    keys = ["STVO_LINE_FUSED", "STVO_MATCH_SMALL", "STVO_GRID_TAIL"]
+    variants = [dict(), dict(STVO_LINE_FUSED="0"), dict(STVO_MATCH_SMALL="0"), dict(STVO_LINE_FUSED="0", STVO_MATCH_SMALL="0"),
+                dict(STVO_GRID_TAIL="0"), dict(STVO_LINE_FUSED="0", STVO_MATCH_SMALL="0", STVO_GRID_TAIL="0")]
     for v in variants:
         for k in keys:
             os.environ.pop(k, None)
