@@ -268,8 +268,8 @@ int stvo_orb_detect_levels_dev(stvo_orb* orb, const uint8_t* images, float* kp_x
  * GaussianBlur(5 x 5, sigma 1), Sobel 3 x 3, the 9-band statistics of the 63-row line support region in float and in the source's
  * order of operations, both normalisations, and the 32-byte binary form (3rdparty/line_descriptor/src/binary_descriptor_custom.cpp:
  * 350-412, 539-687, 1026-1340 — source the reference holds; semantics pinned to oracle/stvo_lbd_oracle.c, which cites it line by
- * line; parity unpinned because that file needs OpenCV to build).  The key-lines themselves come from the caller: the LSD / FLD
- * detectors are not built. */
+ * line; parity unpinned because that file needs OpenCV to build).  The key-lines themselves come from the caller, for instance
+ * stvo_lsd_detect[_dev] or stvo_fld_detect[_dev] below. */
 typedef struct stvo_lbd stvo_lbd;
 int stvo_lbd_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, stvo_lbd** out);
 int stvo_lbd_destroy(stvo_lbd* lbd);
@@ -326,6 +326,42 @@ int stvo_keylines_xy_dev(stvo_ctx* ctx, int B, int stride, const stvo_keyline* l
 /* test hook: the raw segments of the detector core (cv::LineSegmentDetector::detect), host buffers, synchronises:
  * segments [B][cap][4], n_segments [B] (all found; at most cap stored) */
 int stvo_lsd_segments(stvo_lsd* lsd, const uint8_t* images, float* segments, int cap, int32_t* n_segments);
+
+/* ---- FLD line detector (use_fld_lines = true) -------------------------------------------------------------------------- */
+
+/* Replaces  createFastLineDetector(min_line_length)->detect(fld_img, fld_lines)  + the top-N cut by length + the KeyLine fields of
+ * StereoFrame::detectLineFeatures (src/stereoFrame.cpp:244-298) for B images of cols x rows bytes: cv::ximgproc::FastLineDetector
+ * (OpenCV contrib 3.x — third-party code the reference does not hold) as restated in tests/cpp/fld_ref.c (parity unpinned, DESIGN.md
+ * §10): Canny (aperture 3, L1, th1 == th2), the edge chains, extractSegments, the length / border filters and the orientation by the
+ * brighter side.  Images up to 2^20 pixels, at least 16 x 16.  Canny, the 8-connected components of the edge map and the segment
+ * fitting are data-parallel kernels; the chain walk runs one lane per component (exact: a chain never leaves its component). */
+typedef struct stvo_fld_params {
+    int32_t length_threshold;    /* (int)(min_line_length x min(cols, rows)) (stereoFrameHandler.cpp:39, truncated), >= 1 */
+    float distance_threshold;    /* 1.414213562f */
+    double canny_th1;            /* 50 */
+    double canny_th2;            /* 50; != canny_th1 (hysteresis): STVO_ERR_UNSUPPORTED */
+    int32_t canny_aperture_size; /* 3; other apertures: STVO_ERR_UNSUPPORTED */
+    int32_t do_merge;            /* 0; 1: STVO_ERR_UNSUPPORTED */
+    int32_t nfeatures;           /* Config::lsdNFeatures()   300, 0: keep all */
+    int32_t reserved;
+} stvo_fld_params;
+typedef struct stvo_fld stvo_fld;
+int stvo_fld_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, const stvo_fld_params* prm, stvo_fld** out);
+int stvo_fld_destroy(stvo_fld* fld);
+/* Host buffers in / out, synchronises.  Output as stvo_lsd_detect's: lines [B][max_keylines] (what stvo_lbd_compute consumes: end
+ * points, angle = atan2(ey - sy, ex - sx), LineIterator count), response (may be NULL) [B][max_keylines] = lineLength / max(cols,
+ * rows), n_lines [B]; detection order, or by descending length when the top-N cut applied — also when max_keylines is what cuts
+ * (nfeatures 0 or above the capacity).  STVO_ERR_CAPACITY if an internal store filled up (never drops a point silently). */
+int stvo_fld_detect(stvo_fld* fld, const uint8_t* images, stvo_keyline* lines, float* response, int32_t* n_lines);
+/* The same with DEVICE pointers, enqueued on the context's stream (no synchronisation). */
+int stvo_fld_detect_dev(stvo_fld* fld, const uint8_t* images, stvo_keyline* lines, float* response, int32_t* n_lines);
+/* Segments the last detection found before its cuts, host array [B], synchronises (the first 8192 are ranked). */
+int stvo_fld_counts(stvo_fld* fld, int32_t* n_segments);
+/* test hooks, host buffers, synchronise: the raw segments of FastLineDetector::detect in detection order, segments [B][cap][4],
+ * n_segments [B] (all found; at most min(cap, 8192) stored); the edge map the chains are walked on (corner quirk applied),
+ * edges [B][rows][cols] = 0 / 255. */
+int stvo_fld_segments(stvo_fld* fld, const uint8_t* images, float* segments, int cap, int32_t* n_segments);
+int stvo_fld_edges(stvo_fld* fld, const uint8_t* images, uint8_t* edges);
 
 /* ---- stereo rectification (input preparation of Dataset::nextFrame, src/dataset.cpp:147-157) ---------------------------- */
 

@@ -43,6 +43,7 @@ StereoFrameHandler::~StereoFrameHandler() {
     if (seq) stvo_seq_destroy(seq);
     if (orb) stvo_orb_destroy(orb);
     if (lsd) stvo_lsd_destroy(lsd);
+    if (fld) stvo_fld_destroy(fld);
     if (lbd) stvo_lbd_destroy(lbd);
     if (ctx_lines) stvo_ctx_destroy(ctx_lines);
     stvo_ctx_destroy(ctx);
@@ -129,18 +130,21 @@ FrameFeatures StereoFrameHandler::detectStereoFeatures(const GrayImage& img_l, c
     return feat;
 }
 
-// StereoFrame::detectStereoLineSegments (src/stereoFrame.cpp:191-203) -> detectLineFeatures (:207-243) for both images of the
+// StereoFrame::detectStereoLineSegments (src/stereoFrame.cpp:191-203) -> detectLineFeatures (:207-303) for both images of the
 // pair in one batch: the LSD detector with Config's lsd_* options and min_line_length x min(cols, rows) (stvo_lsd_*, oracle/
-// stvo_lsd_oracle.c), the top-N cut by response, then the LBD descriptors (stvo_lbd_*).  The FLD branch (:245-303,
-// cv::ximgproc::FastLineDetector) is not built: use_fld_lines = true is refused.
+// stvo_lsd_oracle.c) and the top-N cut by response, or with use_fld_lines the FLD detector with length_threshold =
+// (int)(min_line_length x min(cols, rows)) and the top-N cut by length (stvo_fld_*, tests/cpp/fld_ref.c); then the LBD
+// descriptors (stvo_lbd_*).
 void StereoFrameHandler::detectStereoLines(const uint8_t* pair, int cols, int rows, FrameFeatures& feat) {
-    if (Config::useFLDLines()) throw std::runtime_error("[StVO-HIP] use_fld_lines: the FLD detector is not built (LSD only)");
     const int M = STVO_POSE_MAX_LINES;  // the pipeline's capacity per image; lsd_nfeatures (300 / 100) lies below it
-    if (lsd && (line_cols != cols || line_rows != rows)) {
-        stvo_lsd_destroy(lsd); lsd = nullptr;
+    const bool use_fld = Config::useFLDLines();
+    if ((lsd || fld) && (line_cols != cols || line_rows != rows)) {
+        if (lsd) stvo_lsd_destroy(lsd);
+        if (fld) stvo_fld_destroy(fld);
+        lsd = nullptr; fld = nullptr;
         stvo_lbd_destroy(lbd); lbd = nullptr;
     }
-    if (!lsd) {
+    if (!use_fld && !lsd) {
         stvo_lsd_params prm{};
         prm.refine = Config::lsdRefine(); prm.n_bins = Config::lsdNBins(); prm.scale = Config::lsdScale();
         prm.sigma_scale = Config::lsdSigmaScale(); prm.quant = Config::lsdQuant(); prm.ang_th = Config::lsdAngTh();
@@ -148,18 +152,34 @@ void StereoFrameHandler::detectStereoLines(const uint8_t* pair, int cols, int ro
         prm.min_length = Config::minLineLength() * std::min(cols, rows);  // llength_th (:52) for this image size
         prm.nfeatures = Config::lsdNFeatures();
         check(stvo_lsd_create(ctx, 2, cols, rows, M, &prm, &lsd), "stvo_lsd_create", ctx);
-        check(stvo_lbd_create(ctx, 2, cols, rows, M, &lbd), "stvo_lbd_create", ctx);
-        line_cols = cols;
-        line_rows = rows;
     }
+    if (use_fld && !fld) {  // createFastLineDetector(min_line_length) (:257): its int length_threshold truncates llength_th
+        stvo_fld_params prm{};
+        prm.length_threshold = (int)(Config::minLineLength() * std::min(cols, rows));
+        prm.distance_threshold = 1.414213562f; prm.canny_th1 = 50.0; prm.canny_th2 = 50.0; prm.canny_aperture_size = 3; prm.do_merge = 0;
+        prm.nfeatures = Config::lsdNFeatures();
+        check(stvo_fld_create(ctx, 2, cols, rows, M, &prm, &fld), "stvo_fld_create", ctx);
+    }
+    if (!lbd) check(stvo_lbd_create(ctx, 2, cols, rows, M, &lbd), "stvo_lbd_create", ctx);
+    line_cols = cols;
+    line_rows = rows;
     std::vector<stvo_keyline> kl((size_t)2 * M);
     std::vector<uint8_t> desc((size_t)2 * M * 32);
     int32_t n[2] = {0, 0};
-    check(stvo_lsd_detect(lsd, pair, kl.data(), nullptr, n), "stvo_lsd_detect", ctx);
-    {   // "keep all" (lsd_nfeatures = 0) or a budget above the pipeline's capacity: say so when the capacity cut the lines
+    const int want = Config::lsdNFeatures();
+    if (use_fld) {
+        check(stvo_fld_detect(fld, pair, kl.data(), nullptr, n), "stvo_fld_detect", ctx);
+        int32_t n_seg[2] = {0, 0};  // "keep all" or a budget above the pipeline's capacity: say so when the capacity cut the lines
+        check(stvo_fld_counts(fld, n_seg), "stvo_fld_counts", ctx);
+        for (int s = 0; s < 2; ++s)
+            if (n_seg[s] > 8192 || (n_seg[s] > M && (want == 0 || want > M)))
+                std::cout << "[StVO-HIP] " << (s ? "right" : "left") << " image: " << n_seg[s] << " segments; the longest " << n[s]
+                          << " are kept (capacity " << M << " key-lines, 8192 ranked segments)" << std::endl;
+    } else {
+        check(stvo_lsd_detect(lsd, pair, kl.data(), nullptr, n), "stvo_lsd_detect", ctx);
+        // "keep all" (lsd_nfeatures = 0) or a budget above the pipeline's capacity: say so when the capacity cut the lines
         int32_t n_seg[2] = {0, 0}, n_pass[2] = {0, 0};
         check(stvo_lsd_counts(lsd, n_seg, n_pass), "stvo_lsd_counts", ctx);
-        const int want = Config::lsdNFeatures();
         for (int s = 0; s < 2; ++s)
             if (n_seg[s] > 8192 || (n_pass[s] > M && (want == 0 || want > M)))
                 std::cout << "[StVO-HIP] " << (s ? "right" : "left") << " image: " << n_seg[s] << " segments, " << n_pass[s]
@@ -173,7 +193,7 @@ void StereoFrameHandler::detectStereoLines(const uint8_t* pair, int cols, int ro
         ls.reserve(n[s]);
         for (int i = 0; i < n[s]; ++i) {
             const stvo_keyline& q = kl[(size_t)s * M + i];
-            ls.push_back(KeyLine{q.sx, q.sy, q.ex, q.ey, q.angle, 0});  // one octave: octaveScale = 1 (LSDDetector_custom.cpp:257)
+            ls.push_back(KeyLine{q.sx, q.sy, q.ex, q.ey, q.angle, 0});  // one octave: octaveScale = 1 (LSDDetector_custom.cpp:257; FLD :265)
             dm.push_back_row(desc.data() + ((size_t)s * M + i) * 32);
         }
     }

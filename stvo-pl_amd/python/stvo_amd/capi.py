@@ -24,7 +24,8 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_orb_set_pattern", "stvo_orb_get_pattern", "stvo_orb_detect", "stvo_orb_detect_dev", "stvo_orb_detect_levels",
            "stvo_orb_detect_levels_dev", "stvo_orb_set_fast_threshold", "stvo_seq_upload_dev", "stvo_lbd_create", "stvo_lbd_destroy",
            "stvo_lbd_compute", "stvo_lbd_compute_dev", "stvo_debug_reparse_env", "stvo_lsd_create", "stvo_lsd_destroy", "stvo_lsd_detect",
-           "stvo_lsd_detect_dev", "stvo_lsd_segments", "stvo_lsd_counts", "stvo_keylines_xy_dev", "stvo_rectify_compute",
+           "stvo_lsd_detect_dev", "stvo_lsd_segments", "stvo_lsd_counts", "stvo_fld_create", "stvo_fld_destroy", "stvo_fld_detect",
+           "stvo_fld_detect_dev", "stvo_fld_counts", "stvo_fld_segments", "stvo_fld_edges", "stvo_keylines_xy_dev", "stvo_rectify_compute",
            "stvo_rectify_create", "stvo_rectify_create_from_maps", "stvo_rectify_destroy", "stvo_rectify_camera", "stvo_rectify_images",
            "stvo_rectify_images_dev"]
 
@@ -151,6 +152,13 @@ def load():
     L.stvo_lsd_detect_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 4
     L.stvo_lsd_segments.argtypes = [C.c_void_p, u8p, f32p, C.c_int, i32p]
     L.stvo_lsd_counts.argtypes = [C.c_void_p, i32p, i32p]
+    L.stvo_fld_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FldParams), C.POINTER(C.c_void_p)]
+    L.stvo_fld_destroy.argtypes = [C.c_void_p]
+    L.stvo_fld_detect.argtypes = [C.c_void_p, u8p, C.c_void_p, C.c_void_p, i32p]
+    L.stvo_fld_detect_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 4
+    L.stvo_fld_counts.argtypes = [C.c_void_p, i32p]
+    L.stvo_fld_segments.argtypes = [C.c_void_p, u8p, f32p, C.c_int, i32p]
+    L.stvo_fld_edges.argtypes = [C.c_void_p, u8p, u8p]
     L.stvo_keylines_xy_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.stvo_seq_destroy.argtypes = [C.c_void_p]
     L.stvo_rectify_compute.argtypes = [C.POINTER(RectCalib), C.POINTER(RectCamera), C.c_void_p, C.c_void_p]
@@ -427,6 +435,69 @@ class Lsd:
         n = np.zeros(self.B, np.int32)
         self.ctx._chk(self.ctx.lib.stvo_lsd_segments(self.h, images.reshape(-1), seg.reshape(-1), cap, n))
         return [seg[b, :min(n[b], cap)].copy() for b in range(self.B)], n
+
+
+class FldParams(C.Structure):  # stvo_fld_params
+    _fields_ = [("length_threshold", C.c_int32), ("distance_threshold", C.c_float), ("canny_th1", C.c_double), ("canny_th2", C.c_double),
+                ("canny_aperture_size", C.c_int32), ("do_merge", C.c_int32), ("nfeatures", C.c_int32), ("reserved", C.c_int32)]
+
+
+def fld_params(length_threshold, nfeatures=300, distance_threshold=1.414213562, canny_th1=50.0, canny_th2=50.0, canny_aperture_size=3,
+               do_merge=0):
+    """createFastLineDetector(length_threshold) with every other parameter at its default (stereoFrame.cpp:257);
+    length_threshold = int(min_line_length x min(cols, rows)), nfeatures = Config::lsdNFeatures()."""
+    return FldParams(int(length_threshold), distance_threshold, canny_th1, canny_th2, canny_aperture_size, do_merge, nfeatures, 0)
+
+
+class Fld:
+    """The FLD key-line detector for B images of one size (stvo_fld_*)."""
+
+    def __init__(self, ctx, B, cols, rows, prm, max_keylines=512):
+        self.ctx, self.B, self.cols, self.rows, self.M = ctx, B, cols, rows, max_keylines
+        self.h = C.c_void_p()
+        ctx._chk(ctx.lib.stvo_fld_create(ctx.h, B, cols, rows, max_keylines, C.byref(prm), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.stvo_fld_destroy(self.h)
+            self.h = None
+
+    def _images(self, images):
+        return np.ascontiguousarray(images, np.uint8).reshape(self.B, self.rows, self.cols)
+
+    def detect(self, images):
+        """images uint8 [B, rows, cols] -> list of B (key-lines as KEYLINE_DTYPE records, responses float32)."""
+        images = self._images(images)
+        rec = np.zeros((self.B, self.M), KEYLINE_DTYPE)
+        resp = np.zeros((self.B, self.M), np.float32)
+        n = np.zeros(self.B, np.int32)
+        self.ctx._chk(self.ctx.lib.stvo_fld_detect(self.h, images.reshape(-1), rec.ctypes.data_as(C.c_void_p), resp.ctypes.data_as(C.c_void_p), n))
+        return [(rec[b, :n[b]].copy(), resp[b, :n[b]].copy()) for b in range(self.B)]
+
+    def detect_dev(self, img_ptr, lines_ptr, resp_ptr, n_ptr):
+        """Device pointers (uint8 [B, rows, cols]; stvo_keyline [B, M]; float32 [B, M] or None; int32 [B]); asynchronous."""
+        self.ctx._chk(self.ctx.lib.stvo_fld_detect_dev(self.h, img_ptr, lines_ptr, resp_ptr, n_ptr))
+
+    def counts(self):
+        """Segments found per image by the last detection, before the top-N / capacity cut."""
+        ns = np.zeros(self.B, np.int32)
+        self.ctx._chk(self.ctx.lib.stvo_fld_counts(self.h, ns))
+        return ns
+
+    def segments(self, images, cap=8192):
+        """The raw segments of FastLineDetector::detect: (list of B float32 [n_b, 4] in detection order, counts [B])."""
+        images = self._images(images)
+        seg = np.zeros((self.B, cap, 4), np.float32)
+        n = np.zeros(self.B, np.int32)
+        self.ctx._chk(self.ctx.lib.stvo_fld_segments(self.h, images.reshape(-1), seg.reshape(-1), cap, n))
+        return [seg[b, :min(n[b], cap)].copy() for b in range(self.B)], n
+
+    def edges(self, images):
+        """The edge map the chains are walked on: uint8 [B, rows, cols] 0 / 255."""
+        images = self._images(images)
+        out = np.zeros((self.B, self.rows, self.cols), np.uint8)
+        self.ctx._chk(self.ctx.lib.stvo_fld_edges(self.h, images.reshape(-1), out.reshape(-1)))
+        return out
 
 
 class Lbd:

@@ -5,6 +5,7 @@ owns the device buffers, every computation is behind the C-ABI.
 Replaces, per frame and stream: StereoFrame::detectStereoPoints + matchStereoPoints (/root/reference/src/stereoFrame.cpp:88-173),
 StereoFrameHandler::f2fTracking + optimizePose (src/stereoFrameHandler.cpp:106-392); with lsd = stvo_lsd_params also
 detectStereoLineSegments + matchStereoLines (:191-243, :309-398): LSD detector, top-N cut, LBD descriptors (stvo_lsd_* / stvo_lbd_*);
+with fld = stvo_fld_params the FLD detector of use_fld_lines instead (:244-303, stvo_fld_*);
 with rectify = capi.Rectifier also the rectification of the raw pairs that Dataset::nextFrame does first (src/dataset.cpp:147-157)."""
 import ctypes as C
 
@@ -17,10 +18,11 @@ from .capi import FrameFeatures
 
 class ImagePipeline:
     def __init__(self, ctx, B, cam, mp, op, max_kp=2048, nfeatures=2000, fast_threshold=20, edge_threshold=19, device="cuda:0", nlevels=1,
-                 scale_factor=1.2, lsd=None, max_kl=128, rectify=None):
+                 scale_factor=1.2, lsd=None, max_kl=128, rectify=None, fld=None):
         """cam: one camera dict (width / height = image size) for all B streams.  nlevels / scale_factor: Config::orbNLevels /
         orbScaleFactor (the key-point octaves travel with the key-points: sigma2 = 1 / scale^(2 level)).  lsd: capi.lsd_params(...)
         for the key-line front-end (op.has_lines = 1, at most max_kl key-lines per image), None: key-points only (op.has_lines = 0).
+        fld: capi.fld_params(...) instead of lsd, the FLD detector of use_fld_lines (src/stereoFrame.cpp:244-303); not both.
         rectify: a capi.Rectifier of the same context for at least B pairs of this size: enqueue first remaps the raw images into a
         resident rectified buffer (same stream, no host synchronisation) and the detectors read that buffer; cam is then the rectified
         camera (Rectifier.camera).  None: the images are taken as rectified."""
@@ -30,12 +32,17 @@ class ImagePipeline:
         if rectify is not None and (rectify.ctx is not ctx or rectify.B < B or rectify.cols != self.cols or rectify.rows != self.rows):
             raise ValueError("ImagePipeline: the rectifier must belong to the same context, hold B pairs and match the image size")
         self.orb = capi.Orb(ctx, 2 * B, self.cols, self.rows, max_kp, nfeatures, fast_threshold, edge_threshold, nlevels, scale_factor)  # left images, then right
-        if lsd is not None and (lsd.nfeatures == 0 or lsd.nfeatures > max_kl):
+        if lsd is not None and fld is not None:
+            raise ValueError("ImagePipeline: one line detector, lsd or fld")
+        lp = lsd if lsd is not None else fld
+        if lp is not None and (lp.nfeatures == 0 or lp.nfeatures > max_kl):
             import warnings
-            warnings.warn(f"ImagePipeline: lsd nfeatures = {lsd.nfeatures} against a capacity of {max_kl} key-lines per image: the strongest {max_kl} are kept")
+            warnings.warn(f"ImagePipeline: line nfeatures = {lp.nfeatures} against a capacity of {max_kl} key-lines per image: the strongest {max_kl} are kept")
         self.lsd = capi.Lsd(ctx, 2 * B, self.cols, self.rows, lsd, max_keylines=max_kl) if lsd is not None else None
-        self.lbd = capi.Lbd(ctx, 2 * B, self.cols, self.rows, max_keylines=max_kl) if lsd is not None else None
-        self.seq = capi.Sequences(ctx, B, max_kp, max_kl if lsd is not None else 64, cam, mp, op)
+        self.fld = capi.Fld(ctx, 2 * B, self.cols, self.rows, fld, max_keylines=max_kl) if fld is not None else None
+        self.lines = self.lsd if self.lsd is not None else self.fld  # the key-line detector, or None
+        self.lbd = capi.Lbd(ctx, 2 * B, self.cols, self.rows, max_keylines=max_kl) if self.lines is not None else None
+        self.seq = capi.Sequences(ctx, B, max_kp, max_kl if self.lines is not None else 64, cam, mp, op)
         dev = torch.device(device)
         self.img = torch.zeros((2 * B, self.rows, self.cols), dtype=torch.uint8, device=dev)
         self.rect_img = torch.zeros((2 * B, self.rows, self.cols), dtype=torch.uint8, device=dev) if rectify is not None else None
@@ -54,7 +61,7 @@ class ImagePipeline:
         ff.desc_l = C.c_void_p(self.desc.data_ptr())
         ff.desc_r = C.c_void_p(self.desc.data_ptr() + 32 * B * max_kp)
         ff.oct_l = C.c_void_p(self.oct.data_ptr())
-        if self.lsd is not None:  # key-lines: records from the detector, descriptors from LBD, end points as the rows the ingest takes
+        if self.lines is not None:  # key-lines: records from the detector, descriptors from LBD, end points as the rows the ingest takes
             M = max_kl
             self.kl = torch.zeros((2 * B, M, 6), dtype=torch.float32, device=dev)   # stvo_keyline records (24 bytes)
             self.kl_xy = torch.zeros((2 * B, M, 4), dtype=torch.float32, device=dev)
@@ -67,7 +74,7 @@ class ImagePipeline:
             ff.kl_r = C.c_void_p(self.kl_xy.data_ptr() + 16 * B * M)
             ff.ldesc_l = C.c_void_p(self.ldesc.data_ptr())
             ff.ldesc_r = C.c_void_p(self.ldesc.data_ptr() + 32 * B * M)
-        self.ff = ff  # (without lsd every line pointer stays NULL: no key-lines; oct_ll NULL: one octave)
+        self.ff = ff  # (without a line detector every line pointer stays NULL: no key-lines; oct_ll NULL: one octave)
         self.slot = 0
 
     def set_images(self, left, right):
@@ -87,8 +94,8 @@ class ImagePipeline:
             ip = rp
         self.orb.detect_dev(ip, self.kp.data_ptr(), self.resp.data_ptr(), self.ang.data_ptr(), self.desc.data_ptr(),
                             self.n.data_ptr(), octave=self.oct.data_ptr())
-        if self.lsd is not None:
-            self.lsd.detect_dev(ip, self.kl.data_ptr(), None, self.nl.data_ptr())
+        if self.lines is not None:
+            self.lines.detect_dev(ip, self.kl.data_ptr(), None, self.nl.data_ptr())
             self.lbd.compute_dev(ip, self.kl.data_ptr(), self.nl.data_ptr(), self.ldesc.data_ptr())
             self.ctx._chk(self.ctx.lib.stvo_keylines_xy_dev(self.ctx.h, 2 * self.B, self.M, self.kl.data_ptr(), self.nl.data_ptr(), self.kl_xy.data_ptr()))
         self.seq.upload_dev(self.slot, self.ff)
@@ -105,6 +112,6 @@ class ImagePipeline:
     def close(self):
         self.seq.close()
         self.orb.close()
-        if self.lsd is not None:
-            self.lsd.close()
+        if self.lines is not None:
+            self.lines.close()
             self.lbd.close()
