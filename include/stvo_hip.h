@@ -245,9 +245,15 @@ int stvo_orb_set_pattern(stvo_orb* orb, const int8_t* pattern /*[1024]*/);
 /* The FAST threshold of the following calls: StereoFrameHandler::updateFrame adapts orb_fast_th frame by frame
  * (src/stereoFrameHandler.cpp:66-86) and passes it to detectStereoFeatures (:56 -> src/stereoFrame.cpp:59,104-118). */
 int stvo_orb_set_fast_threshold(stvo_orb* orb, int fast_threshold /* 1 .. 254 */);
+/* The ranking of the following calls, cv::ORB::create's scoreType = Config::orbScore() (src/stereoFrame.cpp:112-114), with OpenCV's
+ * values: STVO_ORB_SCORE_FAST (1, the default) as described above; STVO_ORB_SCORE_HARRIS (0): per level retainBest(2 x the level's
+ * share) on the FAST response, HarrisResponses (7 x 7 block, k 0.04) of the survivors on the level image, retainBest(the level's
+ * share) on that response — ties kept at both cuts, row-major order as above — and `response` is the Harris response.  n_total then
+ * counts the key-points that pass the second cut.  Any other value: STVO_ERR_INVALID_ARG.  Applies to all four detect entry points. */
+int stvo_orb_set_score_type(stvo_orb* orb, int score_type);
 int stvo_orb_get_pattern(const stvo_orb* orb, int8_t* pattern /*[1024]*/);
 /* Host buffers in / out, synchronises.  images [B][rows][cols]; kp_xy [B][max_keypoints][2] = cv::KeyPoint::pt; response =
- * cv::KeyPoint::response (FAST score); angle in degrees = cv::KeyPoint::angle; desc [B][max_keypoints][32]; n_kp [B]. */
+ * cv::KeyPoint::response (FAST score, or the Harris response under STVO_ORB_SCORE_HARRIS); angle in degrees = cv::KeyPoint::angle; desc [B][max_keypoints][32]; n_kp [B]. */
 int stvo_orb_detect(stvo_orb* orb, const uint8_t* images, float* kp_xy, float* response, float* angle, uint8_t* desc,
                     int32_t* n_kp);
 /* The same with DEVICE pointers, enqueued on the context's stream (no synchronisation). */

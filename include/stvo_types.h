@@ -148,8 +148,11 @@ typedef struct stvo_frame_features {
 } stvo_frame_features;
 
 /* Parameters of the ORB point front-end = the cv::ORB::create arguments the reference passes (src/stereoFrame.cpp:112-114)
- * that vary between its configurations; fixed here: WTA_K 2, FAST_SCORE ranking (orb_score 1), patch size 31. */
+ * that vary between its configurations; fixed here: WTA_K 2 and patch size 31 (other values of orb_wta_k / orb_patch_size need
+ * OpenCV's RNG-derived test pattern: not built).  The ranking, orb_score, is chosen with stvo_orb_set_score_type (default FAST_SCORE). */
 #define STVO_ORB_MAX_LEVELS 8
+#define STVO_ORB_SCORE_HARRIS 0 /* cv::ORB::HARRIS_SCORE */
+#define STVO_ORB_SCORE_FAST 1   /* cv::ORB::FAST_SCORE   */
 typedef struct stvo_orb_params {
     int32_t nfeatures;       /* Config::orbNFeatures()  (2000 in config_kitti.yaml)                     */
     int32_t fast_threshold;  /* Config::orbFastTh() or the handler's adaptive orb_fast_th (1 .. 254)     */

@@ -1,11 +1,14 @@
 // orb_kernels.hip — the ORB point front-end on gfx950: what the reference obtains from
 //     cv::ORB::create(...)->detectAndCompute(img, Mat(), points, pdesc, false)     (/root/reference/src/stereoFrame.cpp:104-118)
 // for orb_nlevels pyramid levels (config_kitti.yaml: 1; config_euroc.yaml / src/config.cpp:96-97: 4 at scale 1.2), FAST_SCORE
-// ranking (orb_score 1), WTA_K 2, patch 31.  Per level:
+// ranking (orb_score 1, the default) or HARRIS_SCORE ranking (orb_score 0: stvo_orb_set_score_type), WTA_K 2, patch 31 (other
+// values of orb_wta_k / orb_patch_size need OpenCV's RNG-derived test pattern and are not built).  Per level:
 //   orb_fast_nms_kernel  FAST-9/16 score (cornerScore<16>) + 3x3 non-maximum suppression + border filter per 64 x 64 tile, all in
 //                        LDS: compass-point rejection, candidates compacted so that the full score runs on dense lanes;
 //                        survivors go to a per-image list + response histogram (no score map in global memory)
 //   orb_order_kernel     KeyPointsFilter::retainBest as a histogram cut (ties kept) + row-major ordering (bitonic sort in LDS)
+//   orb_harris_kernel    (orb_score 0 only) HarrisResponses of the 2 n FAST-best key-points, 8 lanes per key-point; the ordering
+//                        kernel then cuts at the exact n-th largest response (radix select on the float keys, ties kept)
 //   orb_blur_kernel      GaussianBlur 7x7, sigma 2, 8-bit fixed point, BORDER_REFLECT_101
 //   orb_describe_kernel  intensity-centroid angle (ICAngles, fastAtan2) + rotated BRIEF, one wave per key-point
 // around them (more than one level): orb_resize_kernel (level l from level l - 1, OpenCV's 8-bit bilinear resize in 11-bit fixed
@@ -37,6 +40,8 @@ struct OrbDev {
     int32_t* hist;        // [B][256] responses of the key-points that survive NMS + border
     uint32_t* cand;       // [B][cand_cap] the survivors, unordered: (y << 20 | x << 8 | response)
     int32_t* n_cand;      // [B]
+    int score_harris;     // orb_score 0: rank the 2 * nfeatures FAST-best key-points by Harris response, keep nfeatures of them
+    uint32_t* hkey;       // [B][cand_cap] Harris responses as order-preserving words, parallel to cand (0: not among the 2 * nfeatures)
     float* kp;            // [B][K][2]
     float* resp;          // [B][K]
     float* angle;         // [B][K]
@@ -328,12 +333,80 @@ __device__ __forceinline__ void order_block_scan(int* bins /* [4096], in place -
     bins[4 * tid] = base + v0; bins[4 * tid + 1] = base + v1; bins[4 * tid + 2] = base + v2; bins[4 * tid + 3] = base + v3;
     __syncthreads();
 }
+// the largest s in 1 .. 255 such that at least `need` entries of the 256-bin histogram lie in bins >= s (1 when there is none): the
+// cut of retainBest on 8-bit keys.  Called by the whole workgroup (>= 256 threads); bins[] becomes its own suffix sums.
+__device__ __forceinline__ void suffix_sums_256(int* bins) {
+    const int tid = threadIdx.x;
+    for (int off = 1; off < 256; off <<= 1) {
+        const int add = tid + off < 256 ? bins[tid + off] : 0;
+        __syncthreads();
+        if (tid < 256) bins[tid] += add;
+        __syncthreads();
+    }
+}
+
+// A float as a word whose unsigned order is the float order (never 0 for a finite value), and back
+__device__ __forceinline__ uint32_t float_to_key(float v) {
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_to_float(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+
+// HARRIS = false: the FAST_SCORE ranking described above.  HARRIS = true (orb_score 0): the candidates carry a second key, the Harris
+// response of orb_harris_kernel as an order-preserving word (0 = not among the 2 n FAST-best).  retainBest(n) on it is the EXACT n-th
+// largest key, found by an 8-bit radix select over the candidate list in global memory (four histogram passes; the list may hold
+// any number of entries — 2 n plus the FAST ties — so it is never clamped before the cut), ties at the cut kept; the survivors are
+// ordered and, beyond ORD_CAP, truncated to the first K of the row-major order exactly as in FAST mode.  `response` out is the float.
+template <bool HARRIS>
 __global__ __launch_bounds__(1024) void orb_order_kernel(OrbDev o) {
     __shared__ uint32_t s_key[ORD_CAP];
+    __shared__ uint32_t s_val[HARRIS ? ORD_CAP : 1];  // the response words travel with the keys through the sort
     __shared__ int s_part[1024];
     __shared__ int s_cut, s_n, s_acc, s_ystar, s_xstar;
     const int b = blockIdx.x, tid = threadIdx.x;
-    if (tid == 0) {
+    const uint32_t* hk = HARRIS ? o.hkey + (size_t)b * o.cand_cap : nullptr;
+    uint32_t kcut = 1u;  // HARRIS: keep the candidates whose response word is >= kcut
+    if constexpr (HARRIS) {
+        const int nc0 = min(o.n_cand[b], o.cand_cap);
+        uint32_t prefix = 0u, mask = 0u;
+        int need = o.nfeatures, above = 0;  // the need-th largest among the keys that match the prefix; `above` keys are larger than all of those
+        if (tid == 0) s_n = 0;
+        for (int pass = 0; pass < 4; ++pass) {
+            const int shift = 24 - 8 * pass;
+            if (tid < 256) s_part[tid] = 0;
+            __syncthreads();
+            for (int i = tid; i < nc0; i += 1024) {
+                const uint32_t k = hk[i];
+                if (k != 0u && (k & mask) == prefix) atomicAdd(&s_part[(k >> shift) & 255u], 1);
+            }
+            __syncthreads();
+            suffix_sums_256(s_part);
+            if (pass == 0 && s_part[0] < need) {  // fewer ranked key-points than the budget: all of them stay (block-uniform)
+                above = s_part[0];
+                prefix = 1u;
+                need = 0;
+                break;
+            }
+            if (tid < 256) {
+                const int ge = s_part[tid], gt = tid < 255 ? s_part[tid + 1] : 0;
+                if (ge >= need && gt < need) {
+                    s_cut = tid;
+                    s_acc = gt;
+                    s_ystar = ge - gt;
+                }
+            }
+            __syncthreads();
+            prefix |= (uint32_t)s_cut << shift;
+            mask |= 255u << shift;
+            above += s_acc;
+            need -= s_acc;
+            if (pass == 3) above += s_ystar;  // the keys equal to the cut: the ties
+            __syncthreads();
+        }
+        kcut = prefix;
+        __syncthreads();
+        if (tid == 0) s_acc = above;
+    } else if (tid == 0) {
         int cut = 1, acc = 0;
         for (int s = 255; s >= 1; --s) {
             acc += o.hist[(size_t)b * 256 + s];
@@ -349,6 +422,10 @@ __global__ __launch_bounds__(1024) void orb_order_kernel(OrbDev o) {
     __syncthreads();
     const int nc = min(o.n_cand[b], o.cand_cap), cut = s_cut, n_acc = s_acc;
     const uint32_t* cand = o.cand + (size_t)b * o.cand_cap;
+    auto keep = [&](int i, uint32_t c) {
+        if constexpr (HARRIS) return hk[i] >= kcut;
+        else return (int)(c & 255u) >= cut;
+    };
     uint32_t bound = 0xFFFFFFFFu;  // accept keys (y << 12 | x) <= bound
     if (n_acc > ORD_CAP) {  // block-uniform, rare: select the first K of the row-major order exactly
         const int want = min(o.K, ORD_CAP);
@@ -357,7 +434,7 @@ __global__ __launch_bounds__(1024) void orb_order_kernel(OrbDev o) {
         __syncthreads();
         for (int i = tid; i < nc; i += 1024) {
             const uint32_t c = cand[i];
-            if ((int)(c & 255u) >= cut) atomicAdd(&bins[c >> 20], 1);
+            if (keep(i, c)) atomicAdd(&bins[c >> 20], 1);
         }
         __syncthreads();
         order_block_scan(bins, s_part);
@@ -371,7 +448,7 @@ __global__ __launch_bounds__(1024) void orb_order_kernel(OrbDev o) {
         __syncthreads();
         for (int i = tid; i < nc; i += 1024) {
             const uint32_t c = cand[i];
-            if ((int)(c & 255u) >= cut && (int)(c >> 20) == ystar) atomicAdd(&bins[(c >> 8) & 0xFFFu], 1);
+            if (keep(i, c) && (int)(c >> 20) == ystar) atomicAdd(&bins[(c >> 8) & 0xFFFu], 1);
         }
         __syncthreads();
         order_block_scan(bins, s_part);
@@ -386,9 +463,12 @@ __global__ __launch_bounds__(1024) void orb_order_kernel(OrbDev o) {
     __syncthreads();
     for (int i = tid; i < nc; i += 1024) {
         const uint32_t c = cand[i];
-        if ((int)(c & 255u) >= cut && (c >> 8) <= bound) {
+        if (keep(i, c) && (c >> 8) <= bound) {
             const int slot = atomicAdd(&s_n, 1);
-            if (slot < ORD_CAP) s_key[slot] = c;
+            if (slot < ORD_CAP) {
+                s_key[slot] = c;
+                if constexpr (HARRIS) s_val[slot] = hk[i];
+            }
         }
     }
     __syncthreads();
@@ -405,6 +485,11 @@ __global__ __launch_bounds__(1024) void orb_order_kernel(OrbDev o) {
                     if ((a > c) == up) {
                         s_key[i] = c;
                         s_key[l] = a;
+                        if constexpr (HARRIS) {
+                            const uint32_t va = s_val[i];
+                            s_val[i] = s_val[l];
+                            s_val[l] = va;
+                        }
                     }
                 }
             }
@@ -416,7 +501,8 @@ __global__ __launch_bounds__(1024) void orb_order_kernel(OrbDev o) {
         const size_t k = (size_t)b * o.K + i;
         o.kp[2 * k] = (float)((c >> 8) & 0xFFFu);
         o.kp[2 * k + 1] = (float)(c >> 20);
-        o.resp[k] = (float)(c & 255u);
+        if constexpr (HARRIS) o.resp[k] = key_to_float(s_val[i]);
+        else o.resp[k] = (float)(c & 255u);
     }
     __syncthreads();
     if (tid < 256) o.hist[(size_t)b * 256 + tid] = 0;  // ready for the next frame
@@ -424,6 +510,104 @@ __global__ __launch_bounds__(1024) void orb_order_kernel(OrbDev o) {
         o.n_kp[b] = n_out;
         if (o.n_total) o.n_total[b] = n_acc;
         o.n_cand[b] = 0;
+    }
+}
+
+// HarrisResponses (features2d/src/orb.cpp; blockSize 7, harris_k 0.04) of the key-points that survive retainBest(2 n) by FAST score —
+// the same histogram cut as orb_order_kernel's, with twice the budget, ties kept — on the LEVEL image.  8 lanes per key-point (8
+// key-points per wave, 32 per workgroup): the 9 x 9 byte patch around the key-point is staged in LDS once, as 9 rows of 3 unaligned
+// words = 27 words, four loads per lane all in flight together; lane j < 7 then owns row j of the 7 x 7 block (lane 7 only loads):
+// it reads the three patch rows j .. j + 2 as 9 words, forms per column the vertical smoothing r0 + 2 r1 + r2 and difference r2 - r0
+// once (the Sobel sums of the row's 7 positions share them: Ix = H[c + 1] - H[c - 1], Iy = V[c - 1] + 2 V[c] + V[c + 1], all exact in
+// integers), and three shuffle steps add the a = sum Ix^2, b = sum Iy^2, c = sum Ix Iy of the rows.  One lane per key-point would leave 7 of
+// 8 lanes of the few thousand key-points' waves idle through 27 dependent loads; 64 lanes would spend their time in the reduction.
+// The response is formed in FP32 operation by operation as OpenCV writes it (no contraction: see the pragma above) and stored as an
+// order-preserving word beside the candidate (0 for the candidates below the FAST cut).
+constexpr int HR_LANES = 8, HR_KP_PER_WG = 256 / HR_LANES, HR_BLOCKS = 32;  // a grid-stride loop of HR_BLOCKS workgroups per image
+constexpr int HR_PW = 3;                                                    // patch: 9 rows of 3 words = bytes x - 4 .. x + 7
+__global__ __launch_bounds__(256) void orb_harris_kernel(OrbDev o) {
+    __shared__ uint32_t s_patch[HR_KP_PER_WG][HR_LANES * 4];  // 27 words used; every lane stores every word it loaded
+    __shared__ int s_bins[256];
+    __shared__ int s_cut;
+    const int b = blockIdx.y, tid = threadIdx.x, g = tid / HR_LANES, l = tid % HR_LANES;
+    const int nc = min(o.n_cand[b], o.cand_cap);
+    if (nc == 0) return;
+    s_bins[tid] = tid ? o.hist[(size_t)b * 256 + tid] : 0;
+    if (tid == 0) s_cut = 1;
+    __syncthreads();
+    suffix_sums_256(s_bins);
+    {
+        const int need = 2 * min(o.nfeatures, 1 << 29);
+        if (tid >= 1 && s_bins[tid] >= need && (tid == 255 || s_bins[tid + 1] < need)) s_cut = tid;
+    }
+    __syncthreads();
+    const int cut = s_cut;
+    const uint32_t* cand = o.cand + (size_t)b * o.cand_cap;
+    uint32_t* hkey = o.hkey + (size_t)b * o.cand_cap;
+    const uint8_t* img = o.img + (size_t)b * o.rows * o.cols;
+    const int off_hi = o.rows * o.cols - 4;
+    uint32_t* patch = s_patch[g];
+    for (int base = blockIdx.x * HR_KP_PER_WG; base < nc; base += gridDim.x * HR_KP_PER_WG) {  // (block-uniform trip count)
+        const int i = base + g;
+        const bool valid = i < nc;
+        const uint32_t c = cand[valid ? i : nc - 1];
+        const bool ranked = valid && (int)(c & 255u) >= cut;
+        if (!__any(ranked)) {  // wave-uniform
+            if (valid && l == 0) hkey[i] = 0u;
+            continue;
+        }
+        const int x = (int)((c >> 8) & 0xFFFu), y = (int)(c >> 20);
+        // the patch lies inside the image (edge threshold >= 19); the words beyond the 27 are clamped into the buffer and never read
+        const int org = (y - 4) * o.cols + (x - 4);
+        uint32_t w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = l + HR_LANES * j, r = k / HR_PW, q = k - r * HR_PW;
+            w[j] = *reinterpret_cast<const u32_unaligned*>(img + min(max(org + r * o.cols + 4 * q, 0), off_hi));
+        }
+        // (the previous round's reads of this patch are complete: its shuffles below synchronise the group)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) patch[l + HR_LANES * j] = w[j];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        int a = 0, bb = 0, cc = 0;
+        {
+            const uint32_t* rw = patch + (l < 7 ? l : 0) * HR_PW;
+            uint32_t R[3][3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) R[r][q] = rw[r * HR_PW + q];
+            int H[9], V[9];
+#pragma unroll
+            for (int n = 0; n < 9; ++n) {
+                const int p0 = (int)((R[0][n >> 2] >> (8 * (n & 3))) & 255u), p1 = (int)((R[1][n >> 2] >> (8 * (n & 3))) & 255u),
+                          p2 = (int)((R[2][n >> 2] >> (8 * (n & 3))) & 255u);
+                H[n] = p0 + 2 * p1 + p2;
+                V[n] = p2 - p0;
+            }
+#pragma unroll
+            for (int n = 1; n < 8; ++n) {  // block column n - 1 = patch column n
+                const int ix = H[n + 1] - H[n - 1], iy = V[n - 1] + 2 * V[n] + V[n + 1];
+                a += ix * ix;
+                bb += iy * iy;
+                cc += ix * iy;
+            }
+            if (l == 7) a = bb = cc = 0;
+        }
+#pragma unroll
+        for (int off = HR_LANES / 2; off > 0; off >>= 1) {
+            a += __shfl_xor(a, off, 64);
+            bb += __shfl_xor(bb, off, 64);
+            cc += __shfl_xor(cc, off, 64);
+        }
+        constexpr float scale = 1.f / (4 * 7 * 255.f), scale4 = scale * scale * scale * scale, harris_k = 0.04f;
+        const float fa = (float)a, fb = (float)bb, fc = (float)cc;
+        const float resp = (fa * fb - fc * fc - harris_k * (fa + fb) * (fa + fb)) * scale4 + 0.f;  // (+ 0: one zero, the positive one)
+        if (valid && l == 0) hkey[i] = ranked ? float_to_key(resp) : 0u;
     }
 }
 
@@ -809,6 +993,7 @@ void launch_resize_linear_u8(hipStream_t s, int B, int scols, int srows, int dco
 struct stvo_orb {
     stvo_ctx* ctx = nullptr;
     int B = 0, K = 0, nlevels = 1;
+    int score_type = STVO_ORB_SCORE_FAST;
     stvo_orb_params prm{};
     struct Level {
         stvo::OrbDev d{};      // geometry, budget and scratch of the level (img / outputs are set per call)
@@ -886,7 +1071,7 @@ int stvo_orb_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keypoints,
     }
     auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
     size_t total = 1024;  // the pattern
-    size_t off_blur[STVO_ORB_MAX_LEVELS], off_hist[STVO_ORB_MAX_LEVELS], off_cand[STVO_ORB_MAX_LEVELS], off_nc[STVO_ORB_MAX_LEVELS],
+    size_t off_blur[STVO_ORB_MAX_LEVELS], off_hist[STVO_ORB_MAX_LEVELS], off_cand[STVO_ORB_MAX_LEVELS], off_hkey[STVO_ORB_MAX_LEVELS], off_nc[STVO_ORB_MAX_LEVELS],
         off_img[STVO_ORB_MAX_LEVELS], off_out[STVO_ORB_MAX_LEVELS];
     for (int l = 0; l < nlevels; ++l) {
         stvo_orb::Level& L = o->lev[l];
@@ -902,6 +1087,7 @@ int stvo_orb_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keypoints,
         off_blur[l] = total; total += al(px);
         off_hist[l] = total; total += al((size_t)B * 256 * 4);
         off_cand[l] = total; total += al((size_t)B * d.cand_cap * 4);
+        off_hkey[l] = total; total += al((size_t)B * d.cand_cap * 4);  // (either score type may be chosen later: stvo_orb_set_score_type)
         off_nc[l] = total; total += al((size_t)B * 4);
         off_img[l] = total; if (l) total += al(px);
         off_out[l] = total; if (nlevels > 1) total += al(nk * 8) + 2 * al(nk * 4) + al(nk * 32) + 2 * al((size_t)B * 4);
@@ -918,6 +1104,7 @@ int stvo_orb_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keypoints,
         const size_t nk = (size_t)B * max_keypoints;
         d.blur = (uint8_t*)(o->dev + off_blur[l]);
         d.hist = (int32_t*)(o->dev + off_hist[l]); d.cand = (uint32_t*)(o->dev + off_cand[l]); d.n_cand = (int32_t*)(o->dev + off_nc[l]);
+        d.hkey = (uint32_t*)(o->dev + off_hkey[l]);
         d.pattern = o->d_pattern;
         if (l) L.img = (uint8_t*)(o->dev + off_img[l]);
         if (nlevels > 1) {
@@ -985,6 +1172,13 @@ int stvo_orb_set_fast_threshold(stvo_orb* o, int fast_threshold) {
     return STVO_OK;
 }
 
+int stvo_orb_set_score_type(stvo_orb* o, int score_type) {
+    if (!o || (score_type != STVO_ORB_SCORE_HARRIS && score_type != STVO_ORB_SCORE_FAST)) return STVO_ERR_INVALID_ARG;
+    o->score_type = score_type;
+    for (int l = 0; l < o->nlevels; ++l) o->lev[l].d.score_harris = score_type == STVO_ORB_SCORE_HARRIS;  // kernel argument of the next launches
+    return STVO_OK;
+}
+
 int stvo_orb_get_pattern(const stvo_orb* o, int8_t* pattern) {
     if (!o || !pattern) return STVO_ERR_INVALID_ARG;
     std::memcpy(pattern, o->pattern, 1024);
@@ -1025,7 +1219,12 @@ int stvo_orb_detect_levels_dev(stvo_orb* o, const uint8_t* images, float* kp_xy,
         hipLaunchKernelGGL(stvo::orb_fast_nms_kernel, dim3((d.cols + stvo::FT_W - 1) / stvo::FT_W, (d.rows + stvo::FT_H - 1) / stvo::FT_H, d.B),
                            dim3(256), 0, s, d);
         hipLaunchKernelGGL(stvo::orb_blur_kernel, tiles, tb, 0, s, d, o->blur_k);
-        hipLaunchKernelGGL(stvo::orb_order_kernel, dim3(d.B), dim3(1024), 0, s, d);
+        if (d.score_harris) {
+            hipLaunchKernelGGL(stvo::orb_harris_kernel, dim3(stvo::HR_BLOCKS, d.B), dim3(256), 0, s, d);
+            hipLaunchKernelGGL(stvo::orb_order_kernel<true>, dim3(d.B), dim3(1024), 0, s, d);
+        } else {
+            hipLaunchKernelGGL(stvo::orb_order_kernel<false>, dim3(d.B), dim3(1024), 0, s, d);
+        }
         hipLaunchKernelGGL(stvo::orb_describe_kernel, dim3((unsigned)(((d.K + stvo::DESC_KP_PER_WG - 1) / stvo::DESC_KP_PER_WG) * ((d.B + 7) / 8) * 8)), dim3(256),
                            0, s, d, o->umax);
     }

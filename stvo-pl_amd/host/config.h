@@ -34,6 +34,7 @@ public:
     STVO_CFG(int, matchingF2FWs, matching_f2f_ws)
     STVO_CFG(int, orbNFeatures, orb_nfeatures) STVO_CFG(double, orbScaleFactor, orb_scale_factor)
     STVO_CFG(int, orbNLevels, orb_nlevels) STVO_CFG(int, orbFastTh, orb_fast_th) STVO_CFG(int, orbEdgeTh, orb_edge_th)
+    STVO_CFG(int, orbScore, orb_score)
     STVO_CFG(int, lsdNFeatures, lsd_nfeatures) STVO_CFG(double, lsdScale, lsd_scale)
     STVO_CFG(int, lsdRefine, lsd_refine) STVO_CFG(double, lsdSigmaScale, lsd_sigma_scale) STVO_CFG(double, lsdQuant, lsd_quant)
     STVO_CFG(double, lsdAngTh, lsd_ang_th) STVO_CFG(double, lsdLogEps, lsd_log_eps) STVO_CFG(double, lsdDensityTh, lsd_density_th)
@@ -55,6 +56,7 @@ public:
     int orb_nfeatures;
     double orb_scale_factor;
     int orb_nlevels, orb_fast_th, orb_edge_th;
+    int orb_score;  // 0 - HARRIS | 1 - FAST (cv::ORB's scoreType)
     int lsd_nfeatures;
     double lsd_scale;
     int lsd_refine, lsd_n_bins;  // src/config.cpp:105-112

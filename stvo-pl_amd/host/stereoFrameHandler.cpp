@@ -109,6 +109,7 @@ FrameFeatures StereoFrameHandler::detectStereoFeatures(const GrayImage& img_l, c
         orb_rows = img_l.rows;
     }
     check(stvo_orb_set_fast_threshold(orb, fast_th), "stvo_orb_set_fast_threshold", ctx);
+    check(stvo_orb_set_score_type(orb, Config::orbScore()), "stvo_orb_set_score_type", ctx);  // src/stereoFrame.cpp:112-114
     std::vector<float> kp((size_t)2 * K * 2), resp((size_t)2 * K), ang((size_t)2 * K);
     std::vector<int32_t> oct((size_t)2 * K);
     std::vector<uint8_t> desc((size_t)2 * K * 32);

@@ -22,7 +22,7 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_seq_push", "stvo_seq_upload", "stvo_seq_step_dev", "stvo_seq_read", "stvo_seq_create_multi", "stvo_seq_set_slots",
            "stvo_seq_set_stage_timing", "stvo_seq_get_stage_timing", "stvo_seq_set_motion_model", "stvo_seq_debug_grid", "stvo_orb_create", "stvo_orb_destroy",
            "stvo_orb_set_pattern", "stvo_orb_get_pattern", "stvo_orb_detect", "stvo_orb_detect_dev", "stvo_orb_detect_levels",
-           "stvo_orb_detect_levels_dev", "stvo_orb_set_fast_threshold", "stvo_seq_upload_dev", "stvo_lbd_create", "stvo_lbd_destroy",
+           "stvo_orb_detect_levels_dev", "stvo_orb_set_fast_threshold", "stvo_orb_set_score_type", "stvo_seq_upload_dev", "stvo_lbd_create", "stvo_lbd_destroy",
            "stvo_lbd_compute", "stvo_lbd_compute_dev", "stvo_debug_reparse_env", "stvo_lsd_create", "stvo_lsd_destroy", "stvo_lsd_detect",
            "stvo_lsd_detect_dev", "stvo_lsd_segments", "stvo_lsd_counts", "stvo_fld_create", "stvo_fld_destroy", "stvo_fld_detect",
            "stvo_fld_detect_dev", "stvo_fld_counts", "stvo_fld_segments", "stvo_fld_edges", "stvo_keylines_xy_dev", "stvo_rectify_compute",
@@ -140,6 +140,7 @@ def load():
     L.stvo_orb_detect.argtypes = [C.c_void_p, u8p, f32p, f32p, f32p, u8p, i32p]
     L.stvo_orb_detect_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 6
     L.stvo_orb_set_fast_threshold.argtypes = [C.c_void_p, C.c_int]
+    L.stvo_orb_set_score_type.argtypes = [C.c_void_p, C.c_int]
     L.stvo_orb_detect_levels.argtypes = [C.c_void_p, u8p, f32p, f32p, f32p, i32p, u8p, i32p, i32p]
     L.stvo_orb_detect_levels_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 8
     L.stvo_lbd_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -344,11 +345,18 @@ class Orb:
     """The ORB point front-end for B images of one size (stvo_orb_*)."""
 
     def __init__(self, ctx, B, cols, rows, max_keypoints=2048, nfeatures=2000, fast_threshold=20, edge_threshold=19, nlevels=1,
-                 scale_factor=1.2):
+                 scale_factor=1.2, score=1):
+        """score: Config::orbScore() with OpenCV's values — 1 FAST_SCORE (the default), 0 HARRIS_SCORE."""
         self.ctx, self.B, self.cols, self.rows, self.K = ctx, B, cols, rows, max_keypoints
         self.h = C.c_void_p()
         prm = OrbParams(nfeatures, fast_threshold, edge_threshold, nlevels, scale_factor)
         ctx._chk(ctx.lib.stvo_orb_create(ctx.h, B, cols, rows, max_keypoints, C.byref(prm), C.byref(self.h)))
+        if score != 1:
+            try:
+                self.set_score_type(score)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if self.h:
@@ -365,6 +373,9 @@ class Orb:
 
     def set_fast_threshold(self, th):
         self.ctx._chk(self.ctx.lib.stvo_orb_set_fast_threshold(self.h, th))
+
+    def set_score_type(self, score):
+        self.ctx._chk(self.ctx.lib.stvo_orb_set_score_type(self.h, score))
 
     def detect(self, images):
         """images: uint8 [B, rows, cols] -> list of B dicts(kp [n,2] float32, response, angle, desc [n,32])."""
