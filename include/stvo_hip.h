@@ -215,6 +215,25 @@ int stvo_seq_strides(const stvo_seq* seq, int32_t* stride_pts, int32_t* stride_l
 int stvo_seq_set_stage_timing(stvo_seq* seq, int enable);
 int stvo_seq_get_stage_timing(stvo_seq* seq, float avg_ms[STVO_SEQ_NSTAGE], int32_t* n_steps);
 
+/* TEST HOOK: the schedule the LAST ENQUEUED step (stvo_seq_step_dev / stvo_seq_push) chose on the host, so that a test of one route
+ * can assert that the step took it.  Pure bookkeeping: nothing is launched, awaited or decided by this call.  out[STVO_SCHED_*]:
+ * POSE_KERNEL = 0 no pose kernel (first frame), STVO_SCHED_POSE_LATENCY (pose_kernel.hip) or STVO_SCHED_POSE_BATCH (pose_kernel2p.hip);
+ * POSE_WAVES = waves per frame pair of the batch kernel (2 or 4; 0 otherwise); the others are 0 / 1: FUSED_CELLS = the grid of a frame
+ * is the point matcher's first phase; CELLS_AHEAD = it was built on the key-line stream ahead of the step; LINES_AHEAD = the key-line
+ * stage waited for the PREVIOUS step's fork event; GATE = the stream gate was launched in front of it; MID_FORK = the key-line stream
+ * forks behind the cells kernel; LINE_FUSED = the key-line association ran as one workgroup per frame.  All 0 before the first step. */
+#define STVO_SCHED_POSE_KERNEL 0
+#define STVO_SCHED_POSE_WAVES 1
+#define STVO_SCHED_FUSED_CELLS 2
+#define STVO_SCHED_CELLS_AHEAD 3
+#define STVO_SCHED_LINES_AHEAD 4
+#define STVO_SCHED_GATE 5
+#define STVO_SCHED_MID_FORK 6
+#define STVO_SCHED_LINE_FUSED 7
+#define STVO_SCHED_POSE_LATENCY 1
+#define STVO_SCHED_POSE_BATCH 2
+int stvo_seq_last_schedule(const stvo_seq* seq, int32_t out[8]);
+
 /* TEST HOOK: the grid structures the last step built ON THE DEVICE for sequence b (lines = 0: key-points, 1: key-lines):
  * cell_start[3073] / cell_items (cell c = y * 64 + x owns cell_items[cell_start[c] .. cell_start[c+1]); the order inside a
  * cell is unspecified) = GridStructure after src/stereoFrame.cpp:135-139 / :325-338 (lines: every LineIterator cell);

@@ -192,7 +192,8 @@ struct PoseArgs {
 };
 // the batch kernel honours PoseArgs::start_flag for this launch (same selection as launch_pose)
 bool pose_start_flag_ok(const PoseArgs& a);
-// one thread that leaves when *flag has reached value, or after ~0.5 ms (a scheduling hint, never a dependence)
+// one thread that leaves when *flag has reached value, or after 3000 polls ~0.45 us apart, ~1.3-1.5 ms (a scheduling hint, never a
+// dependence)
 void launch_stream_gate(hipStream_t s, const unsigned* flag, unsigned value);
 constexpr int STVO_POSE_QTAB = 16;
 // internal flag in stvo_pose_result::path (never leaves the library): the eigenvalues of `cov` are still to be computed by the reader
@@ -204,6 +205,10 @@ void launch_stream_signal(hipStream_t s, unsigned* flag, unsigned value);
 // dispatch: pose_kernel.hip's latency variant up to 256 frame pairs (and for single evaluations), pose_kernel2p.hip beyond
 int launch_pose(hipStream_t s, const PoseArgs& a);
 int launch_pose2p(hipStream_t s, const PoseArgs& a);  // pose_kernel2p.hip: thread-private records, four frame pairs per CU
+// the two selections above as launch_pose / launch_pose2p make them, for callers that record the route a launch takes
+// (stvo_seq_last_schedule): does launch_pose hand this launch to launch_pose2p, and with how many waves per frame pair (2 or 4)?
+bool pose_batch_kernel_selected(const PoseArgs& a);
+int pose2p_waves_per_pair(int B);
 // the per-(device, stream) record arena of the batch kernel: every context that holds a stream retains it, the last release frees
 // it (the releasing caller has synchronised the stream and made its device current)
 void pose2p_retain_stream(hipStream_t s);

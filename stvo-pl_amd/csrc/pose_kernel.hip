@@ -642,7 +642,7 @@ namespace {
 __global__ void stream_signal_kernel(unsigned* flag, unsigned value) {
     __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
-// one thread: leaves when *flag has reached `value` (wrap-safe) or after ~0.5 ms — a scheduling hint (kernels.h: launch_stream_gate)
+// one thread: leaves when *flag has reached `value` (wrap-safe) or after ~1.3-1.5 ms (3000 polls) — a scheduling hint (kernels.h: launch_stream_gate)
 __global__ void stream_gate_kernel(const unsigned* flag, unsigned value) {
     // (the wave holds a VGPR granule of its SIMD while it waits: one wave of the 256-register pose kernel does not fit beside it, so it
     //  must leave quickly once that kernel has begun — polls ~0.4 us apart)
@@ -658,9 +658,12 @@ void launch_stream_signal(hipStream_t s, unsigned* flag, unsigned value) {
 void launch_stream_gate(hipStream_t s, const unsigned* flag, unsigned value) {
     hipLaunchKernelGGL(stream_gate_kernel, dim3(1), dim3(1), 0, s, flag, value);
 }
-bool pose_start_flag_ok(const PoseArgs& a) {  // launch_pose below takes the batch kernel on compact records (pose2c_kernel)
+bool pose_batch_kernel_selected(const PoseArgs& a) {  // launch_pose below hands the launch to launch_pose2p
     const int which = dbg().pose_kernel;
-    return a.B > 0 && !a.eval_only && a.prev_rc != nullptr && (which == 4 || (which != 1 && a.B > POSE_LATENCY_MAX_B));
+    return !a.eval_only && (which == 4 || (which != 1 && a.B > POSE_LATENCY_MAX_B));
+}
+bool pose_start_flag_ok(const PoseArgs& a) {  // launch_pose below takes the batch kernel on compact records (pose2c_kernel)
+    return a.B > 0 && a.prev_rc != nullptr && pose_batch_kernel_selected(a);
 }
 bool pose_inline_sync_ok(int B) { return B >= 1 && B <= 16 && dbg().pose_kernel != 4; }
 
@@ -673,8 +676,7 @@ int launch_pose(hipStream_t s, const PoseArgs& a) {
     //     seven worker waves + a solver wave, every record resident in LDS (121 us for one pair);
     //   * larger batches: pose_kernel2p.hip — thread-private records, two waves per pair at 256 VGPRs, four pairs per CU.
     // STVO_POSE_KERNEL = 1 / 4 (debug_switches.h) force either for every batch size: the parity tests run both everywhere.
-    const int which = dbg().pose_kernel;
-    if (!a.eval_only && (which == 4 || (which != 1 && a.B > POSE_LATENCY_MAX_B))) return launch_pose2p(s, a);
+    if (pose_batch_kernel_selected(a)) return launch_pose2p(s, a);
     if (a.max_pts > STVO_POSE_MAX_POINTS || a.max_lines > STVO_POSE_MAX_LINES) return STVO_ERR_CAPACITY;
     const size_t rec_bytes = ((size_t)a.max_pts * 6 + (size_t)a.max_lines * 14) * sizeof(double);
     // throughput variant: two workgroups per CU, each with half of the CU's LDS as record cache — most records are then read

@@ -1218,16 +1218,21 @@ void pose2p_release_stream(hipStream_t s) {
     g_arenas.erase(it);
 }
 
+// waves per frame pair: two (four pairs per CU) once the batch holds more than two pairs per CU, four (two pairs per CU,
+// half as many records per thread) below that — with 512 pairs on 256 CUs the two-wave variant leaves half of every CU's
+// wave slots empty (configs[3] leg, 512 streams: 701 k vs 774 k frame pairs/s).  STVO_POSE2P_NW overrides (developer).
+int pose2p_waves_per_pair(int B) {
+    const int nw = dbg().pose2p_nw != DBG_UNSET && dbg().pose2p_nw > 0 ? dbg().pose2p_nw : (B > 2 * device_cu_count() ? 2 : 4);
+    return nw >= 4 ? 4 : 2;
+}
+
 int launch_pose2p(hipStream_t s, const PoseArgs& a) {
     if (a.B <= 0) return STVO_OK;
     if (a.max_pts > STVO_POSE_MAX_POINTS || a.max_lines > STVO_POSE_MAX_LINES || a.eval_only) return STVO_ERR_CAPACITY;
     if (a.prev_rc && (!a.curr_rc || !a.q_tab)) return STVO_ERR_INVALID_ARG;
-    // waves per frame pair: two (four pairs per CU) once the batch holds more than two pairs per CU, four (two pairs per CU,
-    // half as many records per thread) below that — with 512 pairs on 256 CUs the two-wave variant leaves half of every CU's
-    // wave slots empty (configs[3] leg, 512 streams: 701 k vs 774 k frame pairs/s).  STVO_POSE2P_NW overrides (developer).
-    const int nw = dbg().pose2p_nw != DBG_UNSET && dbg().pose2p_nw > 0 ? dbg().pose2p_nw : (a.B > 2 * device_cu_count() ? 2 : 4);
-    if (a.prev_rc) return nw >= 4 ? launch_pose2c_variant<4>(s, a, 2) : launch_pose2c_variant<2>(s, a, 4);
-    return nw >= 4 ? launch_pose2p_variant<4>(s, a, 2) : launch_pose2p_variant<2>(s, a, 4);
+    const int nw = pose2p_waves_per_pair(a.B);
+    if (a.prev_rc) return nw == 4 ? launch_pose2c_variant<4>(s, a, 2) : launch_pose2c_variant<2>(s, a, 4);
+    return nw == 4 ? launch_pose2p_variant<4>(s, a, 2) : launch_pose2p_variant<2>(s, a, 4);
 }
 
 }  // namespace stvo

@@ -691,6 +691,7 @@ struct stvo_seq {
     stvo::GridBatch last_point_grid{};   // arguments of the last point grid match (test hook)
     stvo::GridBatch last_line_grid{};    // the general matcher's arguments for the key-lines of the last step (test hook)
     bool last_line_fused = false;        // the last step ran line_stereo_fused_kernel: the hook rebuilds the grid arrays
+    int32_t last_schedule[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // what the last enqueued step decided (stvo_seq_last_schedule)
     size_t off_kp_l, off_oct_l, off_desc_l, off_nkl, off_kp_r, off_desc_r, off_nkr, off_kl_l, off_oct_ll, off_ldesc_l,
         off_nll, off_kl_r, off_ldesc_r, off_nlr;
 };
@@ -1149,6 +1150,8 @@ struct StepPub {
     bool line_forked = false;    // the line stream waited for an event of the point stream (stvo_seq::sl_forked_frame)
     bool fetch_by_pose = false;  // the pose kernel hands the match indices to the host and then publishes fetch_value (stvo_seq::fetch_by_pose)
     unsigned fetch_value = 0;
+    // the record of the step's host-side decisions (stvo_seq_last_schedule, include/stvo_hip.h: STVO_SCHED_*): bookkeeping only
+    int32_t schedule[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 // Enqueues the kernel chain of one step on the context's stream and the line stream, and returns in `pub` what the step publishes.
@@ -1214,6 +1217,7 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, StepPub& pub) {
     const bool mid_fork = par && B >= 64;
     const bool fork_free = par && s->raw_split[slot] && !s->st_dirty;  // see stvo_seq::st_dirty
     pub.line_forked = par && (mid_fork || !fork_free);
+    pub.schedule[STVO_SCHED_MID_FORK] = mid_fork ? 1 : 0;
     if (par && !mid_fork && !fork_free) {
         HIP_TRY(ctx, hipEventRecord(s->ev_fork, st));
         HIP_TRY(ctx, hipStreamWaitEvent(sl, s->ev_fork, 0));
@@ -1265,6 +1269,9 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, StepPub& pub) {
                                  std::max(s->raw_max_lines[slot], s->set_lines_cap[s->prev_set()]) <= 128;
             const bool lines_ahead = cells_ahead && alt_ok && s->fork_rec_frame == (long long)s->frame_idx - 1 && la_sw != 0 &&
                                      (la_sw == 1 || la_pays);
+            pub.schedule[STVO_SCHED_FUSED_CELLS] = g.fused_cells ? 1 : 0;
+            pub.schedule[STVO_SCHED_CELLS_AHEAD] = cells_ahead ? 1 : 0;
+            pub.schedule[STVO_SCHED_LINES_AHEAD] = lines_ahead ? 1 : 0;
             if (lines_ahead) HIP_TRY(ctx, hipStreamWaitEvent(sl, s->ev_fork, 0));
             if (g.fused_cells)
                 g.cells = stvo::point_cells_args(d);
@@ -1286,8 +1293,10 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, StepPub& pub) {
                 pub.fork_recorded = true;
                 if (!lines_ahead)
                     HIP_TRY(ctx, hipStreamWaitEvent(sl, s->ev_fork, 0));
-                else if (s->pose_flag_frame == (long long)s->frame_idx - 1)  // the key-line kernels behind the dispatch of optimizePose(k - 1)
+                else if (s->pose_flag_frame == (long long)s->frame_idx - 1) {  // the key-line kernels behind the dispatch of optimizePose(k - 1)
                     stvo::launch_stream_gate(sl, s->d_pose_flag, s->pose_flag_value);
+                    pub.schedule[STVO_SCHED_GATE] = 1;
+                }
             }
             s->last_point_grid = g;
             stvo::launch_grid_batch(st, g, false, tev ? (light ? gev_light : tev + 2) : nullptr);
@@ -1321,6 +1330,7 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, StepPub& pub) {
             // 300 key-lines, one stream 0.310 vs 0.360 ms per frame; 102 key-lines 0.257 vs 0.252)
             s->last_line_fused = M <= stvo::LSF_MAX_LINES && (ef != stvo::DBG_UNSET ? ef != 0 : (B >= 16 || Mk <= 128)) &&
                                  (lds <= (48u << 10) || stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::line_stereo_fused_kernel<256>), (int)lds));
+            pub.schedule[STVO_SCHED_LINE_FUSED] = s->last_line_fused ? 1 : 0;
             if (s->last_line_fused) {
                 // (one wave per frame, <64>: 185 instead of 150 us beside the key-point scan, which it stretched by 15 us more)
                 hipLaunchKernelGGL(stvo::line_stereo_fused_kernel<256>, dim3(B), dim3(256), lds, sl, d, Mk, (int)s->mp.best_lr_matches, s->ratio_grid);
@@ -1434,6 +1444,8 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, StepPub& pub) {
             a.start_value = pub.pose_flag_value = ++s->pose_epoch;
             pub.pose_flagged = true;
         }
+        pub.schedule[STVO_SCHED_POSE_KERNEL] = stvo::pose_batch_kernel_selected(a) ? STVO_SCHED_POSE_BATCH : STVO_SCHED_POSE_LATENCY;
+        pub.schedule[STVO_SCHED_POSE_WAVES] = stvo::pose_batch_kernel_selected(a) ? stvo::pose2p_waves_per_pair(a.B) : 0;
         mark(8, st);
         TRY(stvo::launch_pose(st, a));
         mark(9, st);
@@ -1481,6 +1493,7 @@ int stvo_seq_step_dev(stvo_seq* s, int slot) {
     if (pub.line_forked) s->sl_forked_frame = s->frame_idx;
     s->fetch_by_pose = pub.fetch_by_pose;
     s->fetch_value = pub.fetch_value;
+    std::memcpy(s->last_schedule, pub.schedule, sizeof(s->last_schedule));
     s->st_dirty = true;
     s->set_lines[s->cur] = fl.lines_now;
     s->last_lines = fl.lines_now;
@@ -1542,6 +1555,13 @@ int stvo_seq_read(stvo_seq* s, stvo_pose_result* results, int32_t* counts) {
             counts[4 * b + 3] = track ? hr[b].n_matched_ls : 0;
         }
     }
+    return STVO_OK;
+}
+
+// What the last enqueued step decided on the host (STVO_SCHED_*): read from the bookkeeping, nothing is launched or awaited.
+int stvo_seq_last_schedule(const stvo_seq* s, int32_t out[8]) {
+    if (!s || !out) return STVO_ERR_INVALID_ARG;
+    std::memcpy(out, s->last_schedule, sizeof(s->last_schedule));
     return STVO_OK;
 }
 

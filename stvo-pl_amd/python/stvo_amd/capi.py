@@ -20,7 +20,7 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_track_batched_dev", "stvo_match_nnr_mutual_batched_dev", "stvo_optimize_pose_batched_dev",
            "stvo_time_stage_dev", "stvo_valu_peak_probe", "stvo_last_reverse_counts", "stvo_last_reverse_plan", "stvo_ctx_set_kernel_timing", "stvo_ctx_get_kernel_timing", "stvo_seq_create", "stvo_seq_destroy", "stvo_seq_enable_fetch", "stvo_seq_fetch_matches", "stvo_seq_fetch_inliers", "stvo_seq_strides",
            "stvo_seq_push", "stvo_seq_upload", "stvo_seq_step_dev", "stvo_seq_read", "stvo_seq_create_multi", "stvo_seq_set_slots",
-           "stvo_seq_set_stage_timing", "stvo_seq_get_stage_timing", "stvo_seq_set_motion_model", "stvo_seq_debug_grid", "stvo_orb_create", "stvo_orb_destroy",
+           "stvo_seq_set_stage_timing", "stvo_seq_get_stage_timing", "stvo_seq_last_schedule", "stvo_seq_set_motion_model", "stvo_seq_debug_grid", "stvo_orb_create", "stvo_orb_destroy",
            "stvo_orb_set_pattern", "stvo_orb_get_pattern", "stvo_orb_detect", "stvo_orb_detect_dev", "stvo_orb_detect_levels",
            "stvo_orb_detect_levels_dev", "stvo_orb_set_fast_threshold", "stvo_orb_set_score_type", "stvo_seq_upload_dev", "stvo_lbd_create", "stvo_lbd_destroy",
            "stvo_lbd_compute", "stvo_lbd_compute_dev", "stvo_debug_reparse_env", "stvo_lsd_create", "stvo_lsd_destroy", "stvo_lsd_detect",
@@ -31,6 +31,9 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
 
 SEQ_NSTAGE = 5  # include/stvo_hip.h: STVO_SEQ_NSTAGE
 SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_check", "pose")
+# include/stvo_hip.h: STVO_SCHED_* (pose_kernel: 0 none, 1 latency, 2 batch; pose_waves: 2 / 4 for the batch kernel; the rest 0 / 1)
+SEQ_SCHEDULE_FIELDS = ("pose_kernel", "pose_waves", "fused_cells", "cells_ahead", "lines_ahead", "gate", "mid_fork", "line_fused")
+SCHED_POSE_LATENCY, SCHED_POSE_BATCH = 1, 2
 
 u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
@@ -179,6 +182,7 @@ def load():
     L.stvo_seq_fetch_matches.argtypes = [C.c_void_p, pp32, pp32, pp32, pp32]
     L.stvo_seq_fetch_inliers.argtypes = [C.c_void_p, pp32, pp32]
     L.stvo_seq_strides.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.stvo_seq_last_schedule.argtypes = [C.c_void_p, i32p]
     L.stvo_last_reverse_counts.argtypes = [C.c_void_p, C.c_int, i32p]
     L.stvo_last_reverse_plan.argtypes = [C.c_void_p, C.c_int, i32p]
     L.stvo_ctx_set_kernel_timing.argtypes = [C.c_void_p, C.c_int]
@@ -653,6 +657,12 @@ class Sequences:
         counts = np.zeros(self.B * 4, np.int32)
         self.ctx._chk(self.ctx.lib.stvo_seq_read(self.h, res.ctypes.data_as(C.c_void_p), counts))
         return res, counts.reshape(self.B, 4)
+
+    def last_schedule(self):
+        """{field of SEQ_SCHEDULE_FIELDS: value}: what the last enqueued step decided on the host (no launch, no synchronisation)."""
+        out = np.zeros(8, np.int32)
+        self.ctx._chk(self.ctx.lib.stvo_seq_last_schedule(self.h, out))
+        return {k: int(out[i]) for i, k in enumerate(SEQ_SCHEDULE_FIELDS)}
 
     def enable_fetch(self, on=True):
         self.ctx._chk(self.ctx.lib.stvo_seq_enable_fetch(self.h, 1 if on else 0))

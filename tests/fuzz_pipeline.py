@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised parity of the device-resident per-frame pipeline (stvo_seq_*: grid stereo match, tails, f2f mutual match, optimizePose)
 against the oracle-driven pipeline (tests/pipeline_ref.py), with the comparison of tests/test_gpu_seq.py::run_and_compare: random
-batch sizes (the latency pose kernel, the batch pose kernels, the many-sequences copy-back path), feature counts from empty to full,
+batch sizes (the latency pose kernel, the batch pose kernels with four and — rarely, 530 streams — two waves per pair, the many-sequences
+copy-back path), feature counts from empty to full,
 presets, optimizer modes, motion model, noise / outlier / distractor levels that reach the failure paths, clustered descriptors.
 Test infrastructure.  Run on a GPU box from the repo root:   python tests/fuzz_pipeline.py [--seconds 150] [--seed 1]"""
 import argparse, os, sys, time
@@ -141,11 +142,18 @@ def main(argv=None):
         case += 1
         rng = np.random.default_rng([args.seed, case])
         B = int(rng.choice([1, 1, 2, 3, 5, 8, 17, 40, 130]))
+        # one case in 64 (a draw of its own, so the other cases of a seed stay what they were): more than two streams per CU — the two-wave
+        # batch pose kernel and the key-line stage ahead — with small, few frames: the routes depend on the batch count alone
+        big = int(np.random.default_rng([args.seed, case, 1]).integers(0, 64)) == 0
+        if big:
+            B = 530
         preset = str(rng.choice(["kitti", "euroc"]))
         cam = synth.KITTI_CAM if preset == "kitti" else synth.EUROC_CAM
         cams = cam if rng.integers(0, 2) or preset == "euroc" else [synth.config5_cam(int(s)) for s in rng.integers(0, 8, B)]
         mode = int(rng.choice([0, 0, 1, 2])); has_lines = int(rng.integers(0, 2)); mm = bool(rng.integers(0, 2))
         nf = int(rng.integers(3, 6))
+        if big:
+            nf = 3
         kw = dict(distract=float(rng.choice([0.0, 0.2, 0.6, 1.0])), flip_p=float(rng.choice([0.0, 0.03, 0.08, 0.15])),
                   noise_px=float(rng.choice([0.1, 0.3, 1.0, 3.0])), outlier_frac=float(rng.choice([0.0, 0.05, 0.2, 0.5])))
         if rng.integers(0, 4) == 0:
@@ -153,6 +161,8 @@ def main(argv=None):
         # (distractors are extra key-points / key-lines: the totals stay within the capacities of 2048 rows and 320 key-lines)
         pts_hi = int(rng.choice([12, 100, 700, 2000])); lines_hi = int(rng.choice([0, 10, 100, 300])) if has_lines else 0
         pts_hi = min(pts_hi, int(2000 / (1.0 + kw["distract"]))); lines_hi = min(lines_hi, int(300 / (1.0 + kw["distract"])))
+        if big:
+            pts_hi = min(pts_hi, 200); lines_hi = min(lines_hi, 40)
         seqs = []
         for b in range(B):
             c = cams[b] if isinstance(cams, list) else cams

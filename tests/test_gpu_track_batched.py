@@ -153,3 +153,46 @@ def test_track_batched_ragged_sizes(hip, oracle):
             if ref["status"] == 0:
                 assert np.allclose(res["T"][b].reshape(4, 4), ref["T"], atol=1e-8)
     hip.set_stream(None)
+
+
+@pytest.mark.parametrize("preset,mode,nnr", [("kitti", 0, 0.75), ("euroc", 2, 0.9)])
+def test_track_batched_more_than_two_pairs_per_cu(oracle, preset, mode, nnr):
+    """More than two frame pairs per CU through the batched entry: the batch size at which launch_pose2p takes TWO waves per pair by
+    default — here pose2p_kernel<2>, the general-form kernel no other test reaches without a switch — and at which the forward scan
+    K1m runs with a batch that is no multiple of the eight XCDs and two query tiles per frame (its "partial tiles last" remap).
+    Every pair against the oracle: match indices of points and lines bit for bit, inlier masks, status, path, iterations, pose."""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from stvo_amd import capi
+    from stvo_amd.devbatch import TrackBatch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    B = 2 * cus + 5
+    assert B > 256 and B > 2 * cus and B % 8 != 0   # batch pose kernel, two waves per pair, a partly empty last group of eight
+    frames = [synth.make_f2f_points_lines(synth.frame_seed(11, k), n=140 + 40 * (k % 7), n_lines=10 + 6 * (k % 6), outlier_frac=0.15)
+              for k in range(B)]
+    assert max(max(len(f["prev_P"]), len(f["curr_pl"])) for f in frames) > 256   # two 256-row tiles in some frames
+    prm = opt_params(preset, mode=mode)
+    with ThreadPoolExecutor(16) as ex:   # the oracle's C functions run outside the GIL
+        refs = list(ex.map(lambda fr: oracle_track_pl(oracle, fr, prm, nnr, nnr), frames))
+    ctx = capi.Context(device_id=0, max_rows=512, max_batch=B)
+    try:
+        batch = TrackBatch(frames, max_pts=512, max_lines=64)
+        ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        ctx.track_batched(batch, CAM, prm, nnr, nnr, 1)
+        torch.cuda.synchronize()
+        res = batch.results(); mp_all = batch.m12_pts(); ml_all = batch.m12_lines(); ip_all = batch.inlier_pts(); il_all = batch.inlier_lines()
+    finally:
+        ctx.close()
+    for b, (fr, (m12, sel, m12l, sl, ref)) in enumerate(zip(frames, refs)):
+        n1, n1l = len(fr["prev_P"]), len(fr["prev_sP"])
+        assert np.array_equal(mp_all[b, :n1], m12) and np.array_equal(ml_all[b, :n1l], m12l), b
+        assert res["status"][b] == ref["status"] and res["path"][b] == ref["path"] and tuple(res["iters"][b]) == ref["iters"], b
+        assert res["n_matched_pt"][b] == len(sel) and res["n_matched_ls"][b] == len(sl), b
+        assert res["n_inliers_pt"][b] == ref["n_inliers_pt"] and res["n_inliers_ls"][b] == ref["n_inliers_ls"], b
+        e = -np.ones(n1, np.int32); e[sel] = ref["inlier_p"]
+        assert np.array_equal(ip_all[b, :n1], e), b
+        e = -np.ones(n1l, np.int32); e[sl] = ref["inlier_l"]
+        assert np.array_equal(il_all[b, :n1l], e), b
+        T = res["T"][b].reshape(4, 4)
+        assert np_model.rot_angle(T[:3, :3], ref["T"][:3, :3]) < 1e-4 and np.linalg.norm(T[:3, 3] - ref["T"][:3, 3]) < 1e-3, b
+        assert np.allclose(T, ref["T"], atol=1e-8) and np.isclose(res["err"][b], ref["err"], rtol=1e-8), b
