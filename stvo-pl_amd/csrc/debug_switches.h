@@ -1,6 +1,8 @@
 // debug_switches.h — every developer switch of the library in ONE place.  The STVO_* environment variables are parsed once, on
 // first use, into this struct; nothing else in csrc/ calls getenv.  stvo_debug_reparse_env() (C-ABI, tests and tools only) reads
 // them again, so that a parity test can drive several variants from one process.  DBG_UNSET = not set: the library's own choice.
+// Gone with their kernels, and ignored when set: STVO_POSE_KERNEL=2 / 3, STVO_POSE2_NW, STVO_POSE3_NW, STVO_POSE3_COMPACT,
+// STVO_POSE2P_KLDS, STVO_POSE_LDS_T (tools/README.md lists every retired variable).
 #pragma once
 
 #include <climits>
@@ -10,10 +12,9 @@ namespace stvo {
 constexpr int DBG_UNSET = INT_MIN;
 
 struct DebugSwitches {
-    int pose_kernel;     // STVO_POSE_KERNEL     1: pose_kernel.hip for every batch size, 4: pose_kernel2p.hip for every batch size
+    int pose_kernel;     // STVO_POSE_KERNEL     1: pose_kernel.hip for every batch size (the same kernel at every size), 4: pose_kernel2p.hip for every batch size
     int pose2p_nw;       // STVO_POSE2P_NW       waves per frame pair of the batch kernel (2 or 4)
     int pose_prof;       // STVO_POSE_PROF       in-kernel phase ticks (tools/pose_probe.py)
-    int pose_lds_t;      // STVO_POSE_LDS_T      0: pose_kernel.hip's throughput variant without its partial LDS record cache
     int pose_los;        // STVO_POSE_LOS        0: the key-lines of pose_kernel.hip always with the worker waves (never the solver wave)
     int knn_mfma;        // STVO_KNN_MFMA        0: VALU matcher (K1 + K1v), else query blocks per wave of K1m
     int knn_nseg;        // STVO_KNN_NSEG        train segments per query tile

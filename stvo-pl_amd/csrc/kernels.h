@@ -142,8 +142,6 @@ struct PoseArgs {
     double* next_T;        // [B][16] or nullptr: the next frame pair's init_T under use_motion_model (pose_block.h: t0_commit); may alias init_T
     stvo_cam cam;
     const stvo_cam* cams;  // [B] per-frame-pair calibration (device) or nullptr: `cam` for every pair
-    // set by launch_pose: prev points / lines with an index below these live in the workgroup's LDS record cache
-    int lds_cap_pts, lds_cap_lines;
     stvo_opt_params prm;
     stvo_pose_result* results;
     int32_t* inl_p_out;  // [B][max_pts] or nullptr
@@ -202,7 +200,7 @@ constexpr int PATH_EIG_PENDING = 1 << 30;
 bool pose_inline_sync_ok(int B);
 // *flag = value (release, device scope) once everything enqueued on `s` so far has completed
 void launch_stream_signal(hipStream_t s, unsigned* flag, unsigned value);
-// dispatch: pose_kernel.hip's latency variant up to 256 frame pairs (and for single evaluations), pose_kernel2p.hip beyond
+// dispatch: pose_kernel.hip (the latency kernel) up to 256 frame pairs and for single evaluations, pose_kernel2p.hip beyond
 int launch_pose(hipStream_t s, const PoseArgs& a);
 int launch_pose2p(hipStream_t s, const PoseArgs& a);  // pose_kernel2p.hip: thread-private records, four frame pairs per CU
 // the two selections above as launch_pose / launch_pose2p make them, for callers that record the route a launch takes
@@ -213,8 +211,6 @@ int pose2p_waves_per_pair(int B);
 // it (the releasing caller has synchronised the stream and made its device current)
 void pose2p_retain_stream(hipStream_t s);
 void pose2p_release_stream(hipStream_t s);
-inline void pose_retain_stream(hipStream_t s) { pose2p_retain_stream(s); }
-inline void pose_release_stream(hipStream_t s) { pose2p_release_stream(s); }
 
 // ---- 8-bit image operations of the ORB front-end that the line detector reuses (orb_kernels.hip) ----
 // cv::GaussianBlur(7 x 7) in 8-bit fixed point with the integer kernel k7 (weights x 2^8), BORDER_REFLECT_101

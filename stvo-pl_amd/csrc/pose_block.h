@@ -1,7 +1,8 @@
 // pose_block.h — building blocks shared by the two pose kernels (pose_kernel.hip: worker waves + a solver wave, the latency
 // formulation; pose_kernel2p.hip: every wave a worker, thread-private records, the batch formulation): the per-problem state
-// in LDS, the workgroup-wide reductions / selections, and the serial sections of the optimizePose state machine
-// (/root/reference/src/stereoFrameHandler.cpp:307-547).
+// in LDS, the workgroup-wide reductions / selections, the serial sections of the optimizePose state machine
+// (/root/reference/src/stereoFrameHandler.cpp:307-547), and the state machine itself (optimize_pose_flow, :332-370): the ONE
+// copy that all three kernels run, each with its own evaluation and outlier removal.
 #pragma once
 #include <type_traits>
 
@@ -757,6 +758,120 @@ __device__ __forceinline__ void t0_commit(PoseSh* sh, stvo_pose_result* out, int
     out->n_matched_ls = sh->n_m_l;
     out->n_inliers_pt = sh->n_inl_p;
     out->n_inliers_ls = sh->n_inl_l;
+}
+
+// ---------------- the optimizePose state machine (:332-370), shared by the three kernels ----------------
+// One generic iteration loop drives GN (:394-431), robust GN (:433-480) and LM (:482-547) for stage 1, the refinement and the
+// robust fallback, so that the (large) fused evaluation and the outlier removal are instantiated exactly once in the
+// instruction stream of a kernel.
+// evaluate(robust): optimizeFunctions[Robust] at sh->DT -> sh->H / g / err (store_total); remove_outliers(): :988-1067 at
+// sh->DT1.  Every decision is block-uniform (read from LDS after a barrier); `serial` marks who runs the serial sections: every
+// lane of wave 0 in the batch kernels, the solver lane in pose_kernel.hip.
+// PRIO: the serial section is one wave's dependent chain while the co-resident workgroup's waves evaluate on the same SIMD —
+// it runs at wave priority 3 and drops back to 0 (the batch kernels).  false: the kernel keeps the priority it has
+// (pose_kernel.hip runs at 3 throughout).
+struct PoseFlow {
+    int status, path, it0, it1;
+};
+// prm(): the optimizer parameters, fetched where they are used (pose2c_kernel reads them from the kernel-argument segment)
+template <bool PRIO, typename Prm, typename Eval, typename Rem, typename Tick>
+__device__ __forceinline__ PoseFlow optimize_pose_flow(PoseSh* sh, Prm&& prm, const bool serial, Eval&& evaluate,
+                                                       Rem&& remove_outliers, Tick&& tick, long long* tprof, double* ws) {
+    int status = STVO_POSE_OK, path = 0, it0 = 0, it1 = 0;
+    if (sh->n_inl_p + sh->n_inl_l >= prm().min_features) {
+        int stage = 0;        // 0 = first optimisation (:335-338), 1 = refinement (:345-350), 2 = robust fallback (:359)
+        int alg = prm().mode;   // 0 GN, 1 robust GN, 2 LM
+        int max_it = prm().max_iters;
+        for (;;) {
+            if (serial) {
+                sh->err_prev = 999999999.9;
+                sh->good = 1;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) sh->DTr[i] = sh->DT[i];  // robust GN's entry pose (:441)
+            }
+            const int n_it = (alg == 2 && max_it < 1) ? 1 : max_it;  // LM always evaluates once (:493)
+            int evals = 0, action = ACT_BREAK;
+            for (int it = 0; it < n_it; ++it) {
+                long long tq = tick();
+                evaluate(alg == 1);
+                tprof[0] += tick() - tq;
+                tq = tick();
+                ++evals;
+                if (serial) {
+                    if (PRIO) __builtin_amdgcn_s_setprio(3);
+                    if (alg == 0) t0_gn_iter(sh, prm().min_error, prm().min_error_change, it, ws);
+                    else if (alg == 1) t0_gnr_iter(sh, prm().min_error, prm().min_error_change, ws);
+                    else t0_lm_iter(sh, prm().min_error, prm().min_error_change, it == 0 ? 1 : 0, ws);
+                    if (PRIO) __builtin_amdgcn_s_setprio(0);
+                }
+                __syncthreads();
+                tprof[1] += tick() - tq;
+                action = sh->action;
+                if (action != ACT_CONTINUE) break;
+            }
+            long long tq2 = tick();
+            if (serial) {
+                if (alg == 0 && action == ACT_FAIL) {
+                    sh->err_out = -1.0;  // :408-409, covariance left untouched
+                } else if (alg == 1 && !sh->good) {  // :473-478
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) sh->DT[i] = sh->DTr[i];
+                    sh->err_out = -1.0;
+#pragma unroll
+                    for (int i = 0; i < 36; ++i) sh->cov[i] = (i % 7 == 0) ? 1.0 : 0.0;
+                } else {
+                    t0_cov_from_H(sh, ws);  // :429 / :470 / :545 — H of the last evaluation (damped for LM)
+                    sh->err_out = evals > 0 ? sh->err : 0.0;
+                }
+            }
+            __syncthreads();
+            tprof[2] += tick() - tq2;
+            if (stage != 0) {
+                it1 = evals;
+                break;
+            }
+            it0 = evals;
+            tq2 = tick();
+            if (serial) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) sh->DT1[i] = sh->DT[i];
+                t0_is_good_fast(sh, sh->DT1, sh->err_out);
+            }
+            __syncthreads();
+            tprof[2] += tick() - tq2;
+            if (sh->good) {  // :341
+                path |= STVO_PATH_STAGE1_GOOD;
+                tq2 = tick();
+                remove_outliers();
+                tprof[3] += tick() - tq2;
+                if (sh->n_inl_p + sh->n_inl_l >= prm().min_features) {  // :345 — restart from the INITIAL DT
+                    path |= STVO_PATH_REFINED;
+                    stage = 1;
+                } else {
+                    if (serial) pm::identity4(sh->DT);
+                    status = STVO_POSE_FEW_INLIERS_AFTER;
+                    __syncthreads();
+                    break;
+                }
+            } else {  // :357-362 robust GN on everything, from the initial DT
+                path |= STVO_PATH_ROBUST_FALLBACK;
+                stage = 2;
+                alg = 1;
+            }
+            max_it = prm().max_iters_ref;
+            if (serial) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) sh->DT[i] = sh->DT0[i];
+            }
+            __syncthreads();
+        }
+    } else {
+        if (serial) pm::identity4(sh->DT);
+        status = STVO_POSE_FEW_INLIERS_BEFORE;
+        __syncthreads();
+    }
+
+    return PoseFlow{status, path, it0, it1};
 }
 
 }  // namespace

@@ -1,11 +1,13 @@
 // pose_kernel.hip — K4/K5/K6: the whole of StereoFrameHandler::optimizePose
 // (/root/reference/src/stereoFrameHandler.cpp:307-392) as ONE kernel launch, one workgroup per
-// frame pair, FP64 throughout.
+// frame pair, FP64 throughout.  The latency formulation: seven worker waves + one solver wave, one
+// workgroup per CU, for up to 256 frame pairs and for single evaluations (launch_pose below).
 //
 //   * worker waves + ONE solver wave per workgroup (same source, template flag W): a worker thread owns
-//     up to PPT matched points and LPT matched lines as two bitmasks (matched / inlier); the records
-//     (52 B / 116 B of live data) are streamed from L2 at every evaluation
-//     with the next record in flight, so that several workgroups share a CU;
+//     up to PPT matched points and LPT matched lines as two bitmasks (matched / inlier); it gathers
+//     its records (48 B / 112 B) ONCE into thread-private slots of the
+//     workgroup's LDS — up to 152 KB of the CU's 160 KB — and reads them back at every evaluation
+//     (DESIGN.md §5);
 //   * optimizeFunctions / optimizeFunctionsRobust (:549-962): fused transform + project + residual
 //     + 1x6 gradient + Cauchy weight (x overlap for lines) per feature, 28 FP64 partial sums per
 //     thread (21 upper-triangular H + 6 g + 1 e); wave reduction = reduce-scatter on
@@ -16,20 +18,20 @@
 //     float truncation (src/auxiliar.cpp:387-460);
 //   * the 6x6 algebra, SE(3) updates and every data-dependent branch of the GN / robust-GN / LM
 //     loops (:394-547) run on one lane of the solver wave (pose_math.h) and are broadcast through
-//     LDS, so the control flow is block-uniform and matches the reference iteration for iteration.
-#include <algorithm>
+//     LDS, so the control flow is block-uniform and matches the reference iteration for iteration;
+//     the loops themselves are pose_block.h's optimize_pose_flow, shared with the batch kernels.
 #include <cstdlib>
 
 #include "pose_block.h"
 
 namespace stvo {
 
-// LDSREC: the matched records of the frame pair live in LDS for the whole optimisation (latency variant: one workgroup
-// per CU, up to 152 KB of its 160 KB LDS).  Each worker thread stages ITS OWN records once (gathered through m12 from
-// HBM / L2) and reads them back at every evaluation: thread-private slots, so no barrier is involved.  Measured on one
-// frame pair: with the records streamed from L2 at every evaluation the workers spend ~70 % of an evaluation waiting for
-// them (a CU's L1 moves a whole sector per gathered 16-byte observation), 102 k vs 27 k ticks per frame.
-template <int BLOCK, int PPT, int LPT, bool W, bool LDSREC>
+// The matched records of the frame pair live in LDS for the whole optimisation (s_rec: one workgroup per CU).  Each
+// worker thread stages ITS OWN records once (gathered through m12 from HBM / L2) and reads them back at every evaluation:
+// thread-private slots, so no barrier is involved.  Measured on one frame pair: with the records gathered from L2 at
+// every evaluation instead, the workers spent ~70 % of an evaluation waiting for them (a CU's L1 moves a whole sector
+// per gathered 16-byte observation), 102 k vs 27 k ticks per frame.
+template <int BLOCK, int PPT, int LPT, bool W>
 __device__ __forceinline__ void pose_body(const PoseArgs& a, int (*s_hist)[BlockOps<BLOCK / 64>::HIST_W], double (*s_red)[28],
                                           int* s_ired, PoseSh* sh, double* s_rec) {
     using Ops = BlockOps<BLOCK / 64>;
@@ -52,10 +54,7 @@ __device__ __forceinline__ void pose_body(const PoseArgs& a, int (*s_hist)[Block
     // ---------------- which records does this thread own?  (bitmasks only) ----------------
     // Thread t of the worker waves owns prev features i = t + k*BLOCK, k < PPT.  Only two bitmasks
     // (matched, inlier) live in registers for the whole optimisation; the record itself
-    // (52 B / point, 116 B / line, gathered through m12) is re-read at every evaluation.  It comes
-    // from HBM the first time and from L2 afterwards: the working set of the workgroups resident on
-    // one XCD is < 4 MiB.  Keeping the records out of the VGPR file is what lets three workgroups
-    // share a CU, so one pair's serial 6x6 algebra overlaps the parallel phases of the others.
+    // (48 B / point, 112 B / line, gathered through m12 once) is re-read from LDS at every evaluation.
     unsigned* const sel = reinterpret_cast<unsigned*>(&s_hist[0][0]);  // BlockOps::select2's scratch: zero before its first use
     int sel_rot = 0;
     if (W)
@@ -101,36 +100,12 @@ __device__ __forceinline__ void pose_body(const PoseArgs& a, int (*s_hist)[Block
     struct PointRec {
         double X, Y, Z, ox, oy, s2;
     };
-    // latency variant (few records per thread): the match indices stay in registers, so that fetching a record
-    // is one level of loads instead of two dependent ones
-    constexpr bool CACHE_J = PPT <= 6 && !LDSREC;
-    int jcache[CACHE_J ? PPT : 1];
-    if (CACHE_J) {
-#pragma unroll
-        for (int k = 0; k < PPT; ++k) {
-            const int i = tid + k * BLOCK;
-            jcache[k] = ((pmatched >> k) & 1u) ? (a.m12p ? a.m12p[pbase + i] : i) : 0;
-        }
-    }
-    // record cache: prev points with index < cap_p and prev lines with index < cap_l (everything in the latency variant; what
-    // fits half a CU's LDS in the throughput variant — the rest is gathered from L2 at every evaluation)
-    // (PARTIAL is a compile-time property of the small-workgroup variant: the latency variant holds everything and must not pay
-    // for the index tests — they cost it 87 spilled registers)
-    constexpr bool PARTIAL = LDSREC && BLOCK < 256;
-    const int cap_p = !LDSREC ? 0 : (PARTIAL ? a.lds_cap_pts : a.max_pts), cap_l = !LDSREC ? 0 : (PARTIAL ? a.lds_cap_lines : a.max_lines);
-    double* s_pts = s_rec;                                  // [cap_p][6]  X Y Z ox oy s2
-    double* s_lns = s_rec + (size_t)cap_p * 6;              // [cap_l][14] sP eP le spl epl s2
+    double* s_pts = s_rec;                                  // [max_pts][6]  X Y Z ox oy s2
+    double* s_lns = s_rec + (size_t)a.max_pts * 6;          // [max_lines][14] sP eP le spl epl s2
+    // the *_global loaders gather a record through m12: what the staging loops below call, once per record
     auto load_point_global = [&](int k) -> PointRec {
         const size_t i = pbase + (size_t)(tid + k * BLOCK);
-        size_t j;
-        if (CACHE_J) {
-            int jj = jcache[0];
-#pragma unroll
-            for (int q = 1; q < (CACHE_J ? PPT : 1); ++q) jj = (k == q) ? jcache[q] : jj;
-            j = pbase + (size_t)jj;
-        } else {
-            j = a.m12p ? pbase + (size_t)a.m12p[i] : i;
-        }
+        const size_t j = a.m12p ? pbase + (size_t)a.m12p[i] : i;
         PointRec r;
         if (a.prev_rc) {  // compact stereo points of the device-resident pipeline: one 16-byte load per side (kernels.h)
             const float4 p = a.prev_rc[i], c = a.curr_rc[j];
@@ -145,13 +120,12 @@ __device__ __forceinline__ void pose_body(const PoseArgs& a, int (*s_hist)[Block
         r.X = a.prev_P[i * 3 + 0];
         r.Y = a.prev_P[i * 3 + 1];
         r.Z = a.prev_P[i * 3 + 2];
-        r.s2 = sqrt(a.prev_s2p[i]);  // records carry sqrt(sigma2): computed once for the LDS-resident ones
+        r.s2 = sqrt(a.prev_s2p[i]);  // records carry sqrt(sigma2): computed once
         r.ox = a.curr_pl[j * 2 + 0];
         r.oy = a.curr_pl[j * 2 + 1];
         return r;
     };
     auto load_point = [&](int k) -> PointRec {
-        if (!LDSREC || (PARTIAL && tid + k * BLOCK >= cap_p)) return load_point_global(k);
         const double2* q = reinterpret_cast<const double2*>(s_pts + (size_t)(tid + k * BLOCK) * 6);
         const double2 v0 = q[0], v1 = q[1], v2 = q[2];
         PointRec r;
@@ -177,7 +151,6 @@ __device__ __forceinline__ void pose_body(const PoseArgs& a, int (*s_hist)[Block
         return L;
     };
     auto load_line = [&](int k) -> pm::LineRec {
-        if (!LDSREC || (PARTIAL && ltid + k * lstride >= cap_l)) return load_line_global(k);
         const double2* q = reinterpret_cast<const double2*>(s_lns + (size_t)(ltid + k * lstride) * 14);
         pm::LineRec L;
         const double2 v0 = q[0], v1 = q[1], v2 = q[2], v3 = q[3], v4 = q[4], v5 = q[5], v6 = q[6];
@@ -186,10 +159,10 @@ __device__ __forceinline__ void pose_body(const PoseArgs& a, int (*s_hist)[Block
         L.sigma2 = v6.y;
         return L;
     };
-    if (LDSREC && W) {  // stage this thread's own records (thread-private slots: no barrier needed)
+    if (W) {  // stage this thread's own records (thread-private slots: no barrier needed)
 #pragma unroll
         for (int k = 0; k < PPT; ++k)
-            if (((pmatched >> k) & 1u) && (!PARTIAL || tid + k * BLOCK < cap_p)) {
+            if ((pmatched >> k) & 1u) {
                 const PointRec r = load_point_global(k);
                 double2* q = reinterpret_cast<double2*>(s_pts + (size_t)(tid + k * BLOCK) * 6);
                 q[0] = make_double2(r.X, r.Y);
@@ -197,10 +170,10 @@ __device__ __forceinline__ void pose_body(const PoseArgs& a, int (*s_hist)[Block
                 q[2] = make_double2(r.oy, r.s2);
             }
     }
-    if (LDSREC && own_l) {
+    if (own_l) {
 #pragma unroll
         for (int k = 0; k < LPT; ++k)
-            if (((lmatched >> k) & 1u) && (!PARTIAL || ltid + k * lstride < cap_l)) {
+            if ((lmatched >> k) & 1u) {
                 const pm::LineRec L = load_line_global(k);
                 double2* q = reinterpret_cast<double2*>(s_lns + (size_t)(ltid + k * lstride) * 14);
                 q[0] = make_double2(L.sP[0], L.sP[1]);
@@ -241,18 +214,13 @@ __device__ __forceinline__ void pose_body(const PoseArgs& a, int (*s_hist)[Block
         __syncthreads();
     }
 
-    double fX = 1.0, fY = 1.0, fZ = 1.0, fox = 0.0, foy = 0.0, fs2 = 1.0;  // prefetched first inlier record
+    // Remnant of the removed streamed-record variants, where the first inlier record of an evaluation was requested ahead of time:
+    // nothing sets first_k any more, so the test in evaluate() below never holds.  It stays for what it does to the register
+    // allocation: without it the kernel comes out with an 8-SGPR tuple more spilled to VGPR lanes (219 VGPRs, +348 lane moves,
+    // whichever way the first trip is written) and one stream takes 0.208-0.210 instead of 0.199-0.202 ms per frame (measured,
+    // profiles/pose_refactor_bench.txt).  To go together with whatever takes the kernel off its 106-SGPR limit.
+    double fX = 1.0, fY = 1.0, fZ = 1.0, fox = 0.0, foy = 0.0, fs2 = 1.0;
     int first_k = -1;
-    auto prefetch_first = [&]() {
-        first_k = -1;
-        if (!LDSREC && W && pinl) {
-            first_k = __builtin_ctz(pinl);
-            const PointRec r = load_point(first_k);
-            fX = r.X; fY = r.Y; fZ = r.Z; fox = r.ox; foy = r.oy; fs2 = r.s2;
-        }
-    };
-    prefetch_first();
-
     // ---------------- optimizeFunctions / optimizeFunctionsRobust at sh->DT ----------------
     auto evaluate = [&](bool robust) {
         double DT[16];
@@ -289,10 +257,9 @@ __device__ __forceinline__ void pose_body(const PoseArgs& a, int (*s_hist)[Block
         {
             // this thread's inlier points, TWO per trip (pm::point_term_t<d2>: every operation on both records, adjacent in the
             // instruction stream): a term is a chain of ~60 dependent FP64 instructions and a wave retires one of those every
-            // ~8 cycles — the second record fills the gaps (latency variant: 3.3 records per thread, two waves per SIMD; the pipe
-            // was ~40 % busy with one record per trip).
-            // The records of the NEXT trip are in flight while this one is evaluated; the FIRST record of an evaluation was
-            // requested at the end of the previous one (or by prefetch_first), i.e. while the workgroup waited for the solver wave.
+            // ~8 cycles — the second record fills the gaps (3.3 records per thread, two waves per SIMD; the pipe was ~40 % busy
+            // with one record per trip).
+            // The records of the NEXT trip are read from LDS while this one is evaluated.
             // An odd count ends with the last record evaluated twice, the second time with weight 0: an exact no-op.
             unsigned todo = pinl;
             auto next_k = [&]() -> int {
@@ -342,7 +309,6 @@ __device__ __forceinline__ void pose_body(const PoseArgs& a, int (*s_hist)[Block
                 pm::line_term_q(acc, DT, cam, prm.homog_th, inv_homog, L, robust, isl);
             }
         const long long tw1 = tick();
-        prefetch_first();  // for the next evaluation; completes while this one is reduced and solved
         Ops::template sum28_fold<W>(acc, s_red, los);
         const long long tw2 = tick();
         Ops::template sum28_finish<W>(s_red, sh, los);
@@ -397,106 +363,14 @@ __device__ __forceinline__ void pose_body(const PoseArgs& a, int (*s_hist)[Block
             if (prm.has_points) sh->n_inl_p = cnt[0];
             if (prm.has_lines) sh->n_inl_l = cnt[1];
         }
-        prefetch_first();  // the inlier set changed
         __syncthreads();
     };
 
-    // ---------------- optimizePose state machine (:332-370) ----------------
-    // One generic iteration loop drives GN (:394-431), robust GN (:433-480) and LM (:482-547) for
-    // stage 1, the refinement and the robust fallback, so that the (large) fused evaluation and
-    // the outlier removal are instantiated exactly once in the instruction stream.
-    int status = STVO_POSE_OK, path = 0, it0 = 0, it1 = 0;
-    if (sh->n_inl_p + sh->n_inl_l >= prm.min_features) {
-        int stage = 0;        // 0 = first optimisation (:335-338), 1 = refinement (:345-350), 2 = robust fallback (:359)
-        int alg = prm.mode;   // 0 GN, 1 robust GN, 2 LM
-        int max_it = prm.max_iters;
-        for (;;) {
-            if (t0) {
-                sh->err_prev = 999999999.9;
-                sh->good = 1;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) sh->DTr[i] = sh->DT[i];  // robust GN's entry pose (:441)
-            }
-            const int n_it = (alg == 2 && max_it < 1) ? 1 : max_it;  // LM always evaluates once (:493)
-            int evals = 0, action = ACT_BREAK;
-            for (int it = 0; it < n_it; ++it) {
-                long long tq = tick();
-                evaluate(alg == 1);
-                tprof[0] += tick() - tq;
-                tq = tick();
-                ++evals;
-                if (t0) {
-                    if (alg == 0) t0_gn_iter(sh, prm.min_error, prm.min_error_change, it, &s_red[0][0]);
-                    else if (alg == 1) t0_gnr_iter(sh, prm.min_error, prm.min_error_change, &s_red[0][0]);
-                    else t0_lm_iter(sh, prm.min_error, prm.min_error_change, it == 0 ? 1 : 0, &s_red[0][0]);
-                }
-                __syncthreads();
-                tprof[1] += tick() - tq;
-                action = sh->action;
-                if (action != ACT_CONTINUE) break;
-            }
-            long long tq2 = tick();
-            if (t0) {
-                if (alg == 0 && action == ACT_FAIL) {
-                    sh->err_out = -1.0;  // :408-409, covariance left untouched
-                } else if (alg == 1 && !sh->good) {  // :473-478
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) sh->DT[i] = sh->DTr[i];
-                    sh->err_out = -1.0;
-#pragma unroll
-                    for (int i = 0; i < 36; ++i) sh->cov[i] = (i % 7 == 0) ? 1.0 : 0.0;
-                } else {
-                    t0_cov_from_H(sh, &s_red[0][0]);  // :429 / :470 / :545 — H of the last evaluation (damped for LM)
-                    sh->err_out = evals > 0 ? sh->err : 0.0;
-                }
-            }
-            __syncthreads();
-            tprof[2] += tick() - tq2;
-            if (stage != 0) {
-                it1 = evals;
-                break;
-            }
-            it0 = evals;
-            tq2 = tick();
-            if (t0) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) sh->DT1[i] = sh->DT[i];
-                t0_is_good_fast(sh, sh->DT1, sh->err_out);
-            }
-            __syncthreads();
-            tprof[2] += tick() - tq2;
-            if (sh->good) {  // :341
-                path |= STVO_PATH_STAGE1_GOOD;
-                tq2 = tick();
-                remove_outliers();
-                tprof[3] += tick() - tq2;
-                if (sh->n_inl_p + sh->n_inl_l >= prm.min_features) {  // :345 — restart from the INITIAL DT
-                    path |= STVO_PATH_REFINED;
-                    stage = 1;
-                } else {
-                    if (t0) pm::identity4(sh->DT);
-                    status = STVO_POSE_FEW_INLIERS_AFTER;
-                    __syncthreads();
-                    break;
-                }
-            } else {  // :357-362 robust GN on everything, from the initial DT
-                path |= STVO_PATH_ROBUST_FALLBACK;
-                stage = 2;
-                alg = 1;
-            }
-            max_it = prm.max_iters_ref;
-            if (t0) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) sh->DT[i] = sh->DT0[i];
-            }
-            __syncthreads();
-        }
-    } else {
-        if (t0) pm::identity4(sh->DT);
-        status = STVO_POSE_FEW_INLIERS_BEFORE;
-        __syncthreads();
-    }
-
+    // ---------------- optimizePose state machine (:332-370): pose_block.h, the solver lane runs the serial sections ----------------
+    // (PRIO = false: the whole kernel runs at wave priority 3, see pose_kernel)
+    auto params = [&]() -> const stvo_opt_params& { return prm; };
+    const PoseFlow fl = optimize_pose_flow<false>(sh, params, t0, evaluate, remove_outliers, tick, tprof, &s_red[0][0]);
+    const int status = fl.status, path = fl.path, it0 = fl.it0, it1 = fl.it1;
 
     {
         const long long tq3 = tick();
@@ -534,9 +408,9 @@ __device__ __forceinline__ void pose_body(const PoseArgs& a, int (*s_hist)[Block
         for (int i = 64 * LPT + tid; i < a.max_lines; i += BLOCK) a.inl_l_out[(size_t)f * a.max_lines + i] = -1;
 }
 
-template <int BLOCK, int PPT, int LPT, bool LDSREC>
-__global__ __launch_bounds__(BLOCK + 64, 2) void pose_kernel(PoseArgs a) {  // >= 2 waves/SIMD => <= 256 VGPRs, 2 workgroups per CU
-    extern __shared__ double s_rec[];  // LDSREC: [max_pts][6] + [max_lines][14] doubles (dynamic, sized at launch)
+template <int BLOCK, int PPT, int LPT>
+__global__ __launch_bounds__(BLOCK + 64, 2) void pose_kernel(PoseArgs a) {  // 2 waves/SIMD => <= 256 VGPRs
+    extern __shared__ double s_rec[];  // [max_pts][6] + [max_lines][14] doubles (dynamic, sized at launch)
     __shared__ __align__(16) int s_hist[2][BlockOps<BLOCK / 64>::HIST_W];  // BlockOps::select2
     __shared__ double s_red[BLOCK / 64 + 1][28];  // (+ 1: the solver wave's partial sums when it owns the key-lines)
     __shared__ int s_ired[BLOCK / 64 + 1];
@@ -588,55 +462,21 @@ __global__ __launch_bounds__(BLOCK + 64, 2) void pose_kernel(PoseArgs a) {  // >
         if (lane == 0) __hip_atomic_store(a.fetch_flag, a.fetch_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     if (threadIdx.x < BLOCK)
-        pose_body<BLOCK, PPT, LPT, true, LDSREC>(a, s_hist, s_red, s_ired, &s_sh, s_rec);   // worker waves
+        pose_body<BLOCK, PPT, LPT, true>(a, s_hist, s_red, s_ired, &s_sh, s_rec);   // worker waves
     else
-        pose_body<BLOCK, PPT, LPT, false, LDSREC>(a, s_hist, s_red, s_ired, &s_sh, s_rec);  // solver wave
+        pose_body<BLOCK, PPT, LPT, false>(a, s_hist, s_red, s_ired, &s_sh, s_rec);  // solver wave
 }
 
-// Two instantiations of the same kernel:
-//   throughput: 3 worker waves + 1 solver wave (256 threads, <= 256 VGPRs): two workgroups per CU and room
-//               next to the matching kernel in overlap mode; used when the batch has more workgroups than CUs;
-//   latency:    7 worker waves + 1 solver wave (512 threads): the parallel phases of ONE frame pair run ~2.3x
-//               faster; used for small batches (single-stream operation through the handler API), where every
-//               workgroup has a CU to itself anyway.
-constexpr int POSE_BLOCK_T = 192, POSE_BLOCK_L = 448;
+// 7 worker waves + 1 solver wave (512 threads): every workgroup has a CU to itself (at most 256 frame pairs unless
+// STVO_POSE_KERNEL=1 forces this kernel; beyond that the workgroups queue for the CUs, one per CU at a time)
+constexpr int POSE_BLOCK_L = 448;
+constexpr int POSE_PPT = (STVO_POSE_MAX_POINTS + POSE_BLOCK_L - 1) / POSE_BLOCK_L;
+constexpr int POSE_LPT = (STVO_POSE_MAX_LINES + POSE_BLOCK_L - 1) / POSE_BLOCK_L;
 constexpr int POSE_LATENCY_MAX_B = 256;
-// dynamic LDS available to the record cache: 160 KB per CU minus the kernel's static LDS (PoseSh, partial sums, counters)
-constexpr size_t POSE_LDSREC_MAX_BYTES = (size_t)160 * 1024 - 8 * 1024;
-constexpr size_t POSE_LDSREC_T_BYTES = (size_t)80 * 1024 - 6 * 1024;  // throughput variant: two workgroups share a CU
-
-// lds_budget: bytes of dynamic LDS the record cache may use (LDSREC only): lines first (their gather is the longer chain),
-// points with what is left
-template <int BLK, bool LDSREC>
-static void launch_pose_variant(hipStream_t s, const PoseArgs& a_in, size_t lds_budget = 0) {
-    constexpr int PPT = (STVO_POSE_MAX_POINTS + BLK - 1) / BLK;
-    constexpr int LPT = (STVO_POSE_MAX_LINES + BLK - 1) / BLK;
-    PoseArgs a = a_in;
-    a.lds_cap_pts = a.lds_cap_lines = 0;
-    a.lines_on_solver = dbg().pose_los != 0 ? 1 : 0;
-    size_t lds = 0;
-    if (LDSREC) {
-        const size_t lb = 14 * sizeof(double), pb = 6 * sizeof(double);
-        if ((size_t)a.max_lines * lb + (size_t)a.max_pts * pb <= lds_budget) {  // everything fits (latency variant)
-            a.lds_cap_lines = a.max_lines;
-            a.lds_cap_pts = a.max_pts;
-        } else {  // an eighth for the lines (86 of them in 76 KB: the KITTI configuration detects ~100 per image)
-            a.lds_cap_lines = (int)std::min<size_t>((size_t)a.max_lines, lds_budget / 8 / lb);
-            a.lds_cap_pts = (int)std::min<size_t>((size_t)a.max_pts, (lds_budget - (size_t)a.lds_cap_lines * lb) / pb);
-        }
-        lds = ((size_t)a.lds_cap_pts * 6 + (size_t)a.lds_cap_lines * 14) * sizeof(double);
-    }
-    hipLaunchKernelGGL((pose_kernel<BLK, PPT, LPT, LDSREC>), dim3(a.B), dim3(BLK + 64), lds, s, a);
-}
-
-// More than the default 64 KB of dynamic LDS needs an explicit opt-in; done once.  false: the runtime refused, callers use
-// the streamed-record variant instead.
-template <int BLK>
-static bool pose_ldsrec_available() {
-    constexpr int PPT = (STVO_POSE_MAX_POINTS + BLK - 1) / BLK;
-    constexpr int LPT = (STVO_POSE_MAX_LINES + BLK - 1) / BLK;
-    return lds_opt_in(reinterpret_cast<const void*>(&pose_kernel<BLK, PPT, LPT, true>), (int)POSE_LDSREC_MAX_BYTES);
-}
+// dynamic LDS available to the records: 160 KB per CU minus the kernel's static LDS (PoseSh, partial sums, counters)
+constexpr size_t POSE_REC_MAX_BYTES = (size_t)160 * 1024 - 8 * 1024;
+static_assert((size_t)STVO_POSE_MAX_POINTS * 48 + (size_t)STVO_POSE_MAX_LINES * 112 <= POSE_REC_MAX_BYTES,
+              "the records of every admissible problem fit the workgroup's LDS");
 
 namespace {
 __global__ void stream_signal_kernel(unsigned* flag, unsigned value) {
@@ -672,24 +512,19 @@ int launch_pose(hipStream_t s, const PoseArgs& a) {
     if ((a.wait_flag || a.fetch_dst) && !pose_inline_sync_ok(a.B)) return STVO_ERR_INVALID_ARG;
     // Two formulations (round 4: the 128-VGPR / compacted-LDS kernel of round 2 and the owner + evaluator experiment of round 3
     // are gone — both measured slower than what is here, NOTES.md):
-    //   * up to 256 frame pairs, and for single evaluations (stvo_normal_eq): this file's latency variant — one workgroup per CU,
+    //   * up to 256 frame pairs, and for single evaluations (stvo_normal_eq): this file's kernel — one workgroup per CU,
     //     seven worker waves + a solver wave, every record resident in LDS (121 us for one pair);
     //   * larger batches: pose_kernel2p.hip — thread-private records, two waves per pair at 256 VGPRs, four pairs per CU.
     // STVO_POSE_KERNEL = 1 / 4 (debug_switches.h) force either for every batch size: the parity tests run both everywhere.
     if (pose_batch_kernel_selected(a)) return launch_pose2p(s, a);
     if (a.max_pts > STVO_POSE_MAX_POINTS || a.max_lines > STVO_POSE_MAX_LINES) return STVO_ERR_CAPACITY;
+    // more than the default 64 KB of dynamic LDS needs an explicit opt-in (done once)
+    const void* kfn = reinterpret_cast<const void*>(&pose_kernel<POSE_BLOCK_L, POSE_PPT, POSE_LPT>);
+    if (!lds_opt_in(kfn, (int)POSE_REC_MAX_BYTES)) return STVO_ERR_CAPACITY;
+    PoseArgs args = a;
+    args.lines_on_solver = dbg().pose_los != 0 ? 1 : 0;
     const size_t rec_bytes = ((size_t)a.max_pts * 6 + (size_t)a.max_lines * 14) * sizeof(double);
-    // throughput variant: two workgroups per CU, each with half of the CU's LDS as record cache — most records are then read
-    // from HBM once instead of at every evaluation (the gathers of ~64 co-resident pairs overflow an XCD's 4 MB L2)
-    const bool lds_t = dbg().pose_lds_t != 0;  // (unset: on)
-    if (a.B <= POSE_LATENCY_MAX_B && rec_bytes <= POSE_LDSREC_MAX_BYTES && pose_ldsrec_available<POSE_BLOCK_L>())
-        launch_pose_variant<POSE_BLOCK_L, true>(s, a, POSE_LDSREC_MAX_BYTES);   // one workgroup per CU: records resident in LDS
-    else if (a.B <= POSE_LATENCY_MAX_B)
-        launch_pose_variant<POSE_BLOCK_L, false>(s, a);
-    else if (lds_t && pose_ldsrec_available<POSE_BLOCK_T>())
-        launch_pose_variant<POSE_BLOCK_T, true>(s, a, POSE_LDSREC_T_BYTES);
-    else
-        launch_pose_variant<POSE_BLOCK_T, false>(s, a);
+    hipLaunchKernelGGL((pose_kernel<POSE_BLOCK_L, POSE_PPT, POSE_LPT>), dim3(a.B), dim3(POSE_BLOCK_L + 64), rec_bytes, s, args);
     return STVO_OK;
 }
 

@@ -6,7 +6,7 @@
 // the CU's FP64 pipes do depends on how many independent chains it holds.  A thread owns prev points t + k BLOCK and numbers
 // its matched records 0, 1, ... in that order (the ORDINAL); record r of thread t lives in LDS planes [r][part][t] — 16-byte
 // parts of neighbouring threads are neighbours: conflict-free wide accesses, no cross-thread compaction, no barrier between
-// staging and use.  Two kernels share the state machine below:
+// staging and use.  Two kernels, both on the state machine of pose_block.h (optimize_pose_flow):
 //   * pose2c_kernel (round 4) — COMPACT records, the device-resident pipeline's format (kernels.h: PoseArgs::prev_rc): a stereo
 //     point is {u, v, disparity, level}; the LDS record is {u, v, ox, oy} as floats + b / disparity as a double = 24 bytes, P is
 //     rebuilt with 2 subtractions + 3 products per use and sqrt(sigma2) comes from a 16-entry table.  TWELVE ordinals fit the
@@ -40,115 +40,6 @@ struct PointRec2 {
 };
 
 constexpr bool POSE2P_PRIO = true;  // serial sections at wave priority 3 (measured: 239 -> 230 us per 512 pairs with four waves per pair)
-
-// ---------------- the optimizePose state machine (:332-370), shared by both kernels ----------------
-// evaluate(robust): optimizeFunctions[Robust] at sh->DT -> sh->H / g / err (store_total); remove_outliers(): :988-1067 at
-// sh->DT1.  Every decision is block-uniform (read from LDS after a barrier); wave 0 runs the serial sections.
-struct PoseFlow {
-    int status, path, it0, it1;
-};
-// prm(): the optimizer parameters, fetched where they are used (pose2c_kernel reads them from the kernel-argument segment)
-template <typename Prm, typename Eval, typename Rem, typename Tick>
-__device__ __forceinline__ PoseFlow optimize_pose_flow(PoseSh* sh, Prm&& prm, const bool w0, Eval&& evaluate,
-                                                       Rem&& remove_outliers, Tick&& tick, long long* tprof, double* ws) {
-    int status = STVO_POSE_OK, path = 0, it0 = 0, it1 = 0;
-    if (sh->n_inl_p + sh->n_inl_l >= prm().min_features) {
-        int stage = 0;        // 0 = first optimisation (:335-338), 1 = refinement (:345-350), 2 = robust fallback (:359)
-        int alg = prm().mode;   // 0 GN, 1 robust GN, 2 LM
-        int max_it = prm().max_iters;
-        for (;;) {
-            if (w0) {
-                sh->err_prev = 999999999.9;
-                sh->good = 1;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) sh->DTr[i] = sh->DT[i];  // robust GN's entry pose (:441)
-            }
-            const int n_it = (alg == 2 && max_it < 1) ? 1 : max_it;  // LM always evaluates once (:493)
-            int evals = 0, action = ACT_BREAK;
-            for (int it = 0; it < n_it; ++it) {
-                long long tq = tick();
-                evaluate(alg == 1);
-                tprof[0] += tick() - tq;
-                tq = tick();
-                ++evals;
-                if (w0) {
-                    // the serial section is one wave's dependent chain while the co-resident workgroup's waves evaluate on the
-                    // same SIMD: let it win the issue arbitration
-                    if (POSE2P_PRIO) __builtin_amdgcn_s_setprio(3);
-                    if (alg == 0) t0_gn_iter(sh, prm().min_error, prm().min_error_change, it, ws);
-                    else if (alg == 1) t0_gnr_iter(sh, prm().min_error, prm().min_error_change, ws);
-                    else t0_lm_iter(sh, prm().min_error, prm().min_error_change, it == 0 ? 1 : 0, ws);
-                    if (POSE2P_PRIO) __builtin_amdgcn_s_setprio(0);
-                }
-                __syncthreads();
-                tprof[1] += tick() - tq;
-                action = sh->action;
-                if (action != ACT_CONTINUE) break;
-            }
-            long long tq2 = tick();
-            if (w0) {
-                if (alg == 0 && action == ACT_FAIL) {
-                    sh->err_out = -1.0;  // :408-409, covariance left untouched
-                } else if (alg == 1 && !sh->good) {  // :473-478
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) sh->DT[i] = sh->DTr[i];
-                    sh->err_out = -1.0;
-#pragma unroll
-                    for (int i = 0; i < 36; ++i) sh->cov[i] = (i % 7 == 0) ? 1.0 : 0.0;
-                } else {
-                    t0_cov_from_H(sh, ws);  // :429 / :470 / :545 — H of the last evaluation (damped for LM)
-                    sh->err_out = evals > 0 ? sh->err : 0.0;
-                }
-            }
-            __syncthreads();
-            tprof[2] += tick() - tq2;
-            if (stage != 0) {
-                it1 = evals;
-                break;
-            }
-            it0 = evals;
-            tq2 = tick();
-            if (w0) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) sh->DT1[i] = sh->DT[i];
-                t0_is_good_fast(sh, sh->DT1, sh->err_out);
-            }
-            __syncthreads();
-            tprof[2] += tick() - tq2;
-            if (sh->good) {  // :341
-                path |= STVO_PATH_STAGE1_GOOD;
-                tq2 = tick();
-                remove_outliers();
-                tprof[3] += tick() - tq2;
-                if (sh->n_inl_p + sh->n_inl_l >= prm().min_features) {  // :345 — restart from the INITIAL DT
-                    path |= STVO_PATH_REFINED;
-                    stage = 1;
-                } else {
-                    if (w0) pm::identity4(sh->DT);
-                    status = STVO_POSE_FEW_INLIERS_AFTER;
-                    __syncthreads();
-                    break;
-                }
-            } else {  // :357-362 robust GN on everything, from the initial DT
-                path |= STVO_PATH_ROBUST_FALLBACK;
-                stage = 2;
-                alg = 1;
-            }
-            max_it = prm().max_iters_ref;
-            if (w0) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) sh->DT[i] = sh->DT0[i];
-            }
-            __syncthreads();
-        }
-    } else {
-        if (w0) pm::identity4(sh->DT);
-        status = STVO_POSE_FEW_INLIERS_BEFORE;
-        __syncthreads();
-    }
-
-    return PoseFlow{status, path, it0, it1};
-}
 
 // NW waves per frame pair at 256 VGPRs (two waves per SIMD); k_lds record ordinals of every thread live in LDS
 // PROF: the developer's phase-tick instrumentation (tools/pose_probe.py) as its own instantiation — as a run-time flag its ~26
@@ -460,22 +351,6 @@ __global__ __launch_bounds__(NW * 64, 2) void pose2p_kernel(PoseArgs a, const in
         wprof[2] += tick() - tw2;
     };
 
-    if (a.eval_only) {
-        evaluate(a.eval_robust != 0);
-        if (w0) {
-            if (t0) {
-                double* o = a.eval_out + (size_t)f * 44;
-#pragma unroll
-                for (int i = 0; i < 36; ++i) o[i] = sh->H[i];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) o[36 + i] = sh->g[i];
-                o[42] = sh->err;
-                o[43] = (double)(sh->n_inl_p + sh->n_inl_l);
-            }
-        }
-        return;
-    }
-
     // ---------------- removeOutliers at pose DT1 (:988-1067) ----------------
     auto remove_outliers = [&]() {
         double DT[12];
@@ -507,7 +382,8 @@ __global__ __launch_bounds__(NW * 64, 2) void pose2p_kernel(PoseArgs a, const in
         __syncthreads();
     };
 
-    const PoseFlow fl = optimize_pose_flow(sh, [&]() -> const stvo_opt_params& { return prm; }, w0, evaluate, remove_outliers, tick, tprof, &s_red[0][0]);
+    auto params = [&]() -> const stvo_opt_params& { return prm; };
+    const PoseFlow fl = optimize_pose_flow<POSE2P_PRIO>(sh, params, w0, evaluate, remove_outliers, tick, tprof, &s_red[0][0]);
     const int status = fl.status, path = fl.path, it0 = fl.it0, it1 = fl.it1;
 
     {
@@ -1084,8 +960,8 @@ __global__ __launch_bounds__(NW * 64, 2) void pose2c_kernel(PoseArgs a_by_value,
         rprof[2] += tick() - tr2;
     };
 
-    const PoseFlow fl = optimize_pose_flow(sh, [&]() -> const stvo_opt_params __attribute__((address_space(4)))& { return ka().prm; }, w0, evaluate,
-                                           remove_outliers, tick, tprof, &s_red[0][0]);
+    auto params = [&]() -> const stvo_opt_params __attribute__((address_space(4)))& { return ka().prm; };
+    const PoseFlow fl = optimize_pose_flow<POSE2P_PRIO>(sh, params, w0, evaluate, remove_outliers, tick, tprof, &s_red[0][0]);
 
     {
         const long long tq3 = tick();
@@ -1228,7 +1104,8 @@ int pose2p_waves_per_pair(int B) {
 
 int launch_pose2p(hipStream_t s, const PoseArgs& a) {
     if (a.B <= 0) return STVO_OK;
-    if (a.max_pts > STVO_POSE_MAX_POINTS || a.max_lines > STVO_POSE_MAX_LINES || a.eval_only) return STVO_ERR_CAPACITY;
+    if (a.eval_only) return STVO_ERR_INVALID_ARG;  // single evaluations belong to the latency kernel (launch_pose)
+    if (a.max_pts > STVO_POSE_MAX_POINTS || a.max_lines > STVO_POSE_MAX_LINES) return STVO_ERR_CAPACITY;
     if (a.prev_rc && (!a.curr_rc || !a.q_tab)) return STVO_ERR_INVALID_ARG;
     const int nw = pose2p_waves_per_pair(a.B);
     if (a.prev_rc) return nw == 4 ? launch_pose2c_variant<4>(s, a, 2) : launch_pose2c_variant<2>(s, a, 4);

@@ -23,7 +23,6 @@ DebugSwitches parse_switches() {
     d.pose_kernel = env_int("STVO_POSE_KERNEL");
     d.pose2p_nw = env_int("STVO_POSE2P_NW");
     d.pose_prof = env_int("STVO_POSE_PROF");
-    d.pose_lds_t = env_int("STVO_POSE_LDS_T");
     d.pose_los = env_int("STVO_POSE_LOS");
     d.knn_mfma = env_int("STVO_KNN_MFMA");
     d.knn_nseg = env_int("STVO_KNN_NSEG");
@@ -97,7 +96,7 @@ int stvo_ctx_create(int device_id, int max_rows, int max_batch, stvo_ctx** out) 
               hip_ok(ctx, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking), "hipStreamCreate");
     ctx->own_stream = ok;
     if (ok) {
-        stvo::pose_retain_stream(ctx->stream);
+        stvo::pose2p_retain_stream(ctx->stream);
         ctx->stream_retained = true;
     }
     const size_t knn_elems = (size_t)max_rows * (size_t)max_batch;
@@ -138,10 +137,10 @@ int stvo_ctx_destroy(stvo_ctx* ctx) {
     if (ctx->arena_host) (void)hipHostFree(ctx->arena_host);
     if (ctx->probe_sink) (void)hipFree(ctx->probe_sink);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
-    if (ctx->stream_retained) stvo::pose_release_stream(ctx->stream);
+    if (ctx->stream_retained) stvo::pose2p_release_stream(ctx->stream);
     if (ctx->aux_stream) {
         (void)hipStreamSynchronize(ctx->aux_stream);
-        stvo::pose_release_stream(ctx->aux_stream);
+        stvo::pose2p_release_stream(ctx->aux_stream);
         (void)hipStreamDestroy(ctx->aux_stream);
         (void)hipEventDestroy(ctx->ev_match_done);
         (void)hipEventDestroy(ctx->ev_pose_done);
@@ -155,11 +154,11 @@ int stvo_ctx_set_stream(stvo_ctx* ctx, void* hip_stream) {
     if (!ctx) return STVO_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->stream_retained) stvo::pose_release_stream(ctx->stream);
+    if (ctx->stream_retained) stvo::pose2p_release_stream(ctx->stream);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     ctx->own_stream = false;
     ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);  // may be the NULL stream
-    stvo::pose_retain_stream(ctx->stream);
+    stvo::pose2p_retain_stream(ctx->stream);
     ctx->stream_retained = true;
     return STVO_OK;
 }
@@ -188,7 +187,7 @@ int stvo_ctx_set_overlap(stvo_ctx* ctx, int enable) {
         ctx->ev_match_done = em;
         ctx->ev_pose_done = ep;
         ctx->aux_stream = as;
-        stvo::pose_retain_stream(as);
+        stvo::pose2p_retain_stream(as);
     }
     if (!enable && ctx->aux_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->aux_stream));
     ctx->overlap = enable ? 1 : 0;

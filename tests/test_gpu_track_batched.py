@@ -196,3 +196,53 @@ def test_track_batched_more_than_two_pairs_per_cu(oracle, preset, mode, nnr):
         T = res["T"][b].reshape(4, 4)
         assert np_model.rot_angle(T[:3, :3], ref["T"][:3, :3]) < 1e-4 and np.linalg.norm(T[:3, 3] - ref["T"][:3, 3]) < 1e-3, b
         assert np.allclose(T, ref["T"], atol=1e-8) and np.isclose(res["err"][b], ref["err"], rtol=1e-8), b
+
+
+@pytest.mark.parametrize("max_pts,max_lines", [(2048, 512), (64, 0)], ids=["full-lds", "64-points"])
+def test_latency_kernel_forced_past_256_pairs_equals_single_pair_runs(switches, max_pts, max_lines):
+    """STVO_POSE_KERNEL=1 at 257 frame pairs, the first batch size the latency kernel does not take by itself: pose_kernel.hip is
+    ONE kernel at every batch size — one workgroup per pair, a fixed summation order, dynamic LDS sized by the capacities alone
+    (all 152 KB of it at 2048 points / 512 lines) — so every pair of the batch must come out bit for bit as the same pair run
+    alone under the same switch.  A difference means that a launch parameter depends on the batch size."""
+    import torch
+    from stvo_amd import capi
+    from stvo_amd.devbatch import TrackBatch
+    switches({"STVO_POSE_KERNEL": "1"})
+    B = 257
+    if max_lines:   # about 300 points and 40 lines per pair
+        frames = [synth.make_f2f_points_lines(synth.frame_seed(12, k), n=300 - 7 * (k % 5), n_lines=40 - k % 4, outlier_frac=0.15)
+                  for k in range(B)]
+        prm = opt_params("kitti")
+    else:           # up to the capacity of 64 points, down to a pair below min_features
+        frames = [synth.make_f2f_points(synth.frame_seed(13, k), n=(64, 57, 40, 23, 9)[k % 5]) for k in range(B)]
+        prm = opt_params("kitti", has_lines=0)
+
+    def outputs(batch, n):
+        res = batch.results()
+        out = [res[name][:n].copy() for name in ("status", "path", "iters", "n_matched_pt", "n_matched_ls", "n_inliers_pt", "n_inliers_ls",
+                                                  "T", "cov", "err")]
+        out.append(batch.inlier_pts()[:n].copy())
+        if max_lines:
+            out.append(batch.inlier_lines()[:n].copy())
+        return out
+
+    ctx = capi.Context(device_id=0, max_rows=2048, max_batch=B)
+    try:
+        ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        batch = TrackBatch(frames, max_pts=max_pts, max_lines=max_lines)
+        ctx.track_batched(batch, CAM, prm, 0.75, 0.75, 1)
+        torch.cuda.synchronize()
+        together = outputs(batch, B)
+        alone = []
+        for fr in frames:
+            one = TrackBatch([fr], max_pts=max_pts, max_lines=max_lines)
+            ctx.track_batched(one, CAM, prm, 0.75, 0.75, 1)
+            torch.cuda.synchronize()
+            alone.append(outputs(one, 1))
+    finally:
+        ctx.close()
+    print("status counts", np.bincount(together[0], minlength=4), "paths", sorted(set(together[1].tolist())))
+    assert (together[0] == 0).any()   # the comparison is not one of empty results
+    for b in range(B):
+        for x, y in zip(together, alone[b]):
+            assert x[b].tobytes() == y[0].tobytes(), b
