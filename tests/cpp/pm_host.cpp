@@ -80,4 +80,32 @@ void pmh_normal_eq(const double* DT, const stvo_cam* cam, double homog_th, const
             pm::line_term(acc28, DT, c, homog_th, L, robust != 0, s_l);
         }
 }
+// the same evaluation with the terms the kernels run (pm::point_term_q / pm::line_term_q), called as pose_kernel.hip and
+// pose_kernel2p.hip call them: sqrt(sigma2) in the record, 1 / homog_th, the reciprocals of the robust scales
+void pmh_normal_eq_q(const double* DT, const stvo_cam* cam, double homog_th, const stvo_matched* m, int robust, double s_p,
+                     double s_l, double* acc28) {
+    pm::Cam5 c{cam->fx, cam->fy, cam->cx, cam->cy};
+    const double inv_homog = 1.0 / homog_th;
+    const double isp = 1.0 / s_p, isl = 1.0 / s_l;
+    for (int i = 0; i < 28; ++i) acc28[i] = 0.0;
+    for (int i = 0; i < m->np; ++i)
+        if (m->inlier_p[i])
+            pm::point_term_q(acc28, DT, c, homog_th, inv_homog, m->P[3 * i], m->P[3 * i + 1], m->P[3 * i + 2], m->pl_obs[2 * i],
+                             m->pl_obs[2 * i + 1], sqrt(m->sigma2p[i]), robust != 0, isp);
+    for (int i = 0; i < m->nl; ++i)
+        if (m->inlier_l[i]) {
+            pm::LineRec L;
+            for (int k = 0; k < 3; ++k) {
+                L.sP[k] = m->sP[3 * i + k];
+                L.eP[k] = m->eP[3 * i + k];
+                L.le[k] = m->le_obs[3 * i + k];
+            }
+            for (int k = 0; k < 2; ++k) {
+                L.spl[k] = m->spl[2 * i + k];
+                L.epl[k] = m->epl[2 * i + k];
+            }
+            L.sigma2 = sqrt(m->sigma2l[i]);  // the record carries sqrt(sigma2), see pm::line_term_q
+            pm::line_term_q(acc28, DT, c, homog_th, inv_homog, L, robust != 0, isl);
+        }
+}
 }

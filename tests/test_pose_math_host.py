@@ -1,40 +1,22 @@
 """The product's FP64 building blocks (stvo-pl_amd/csrc/pose_math.h — the code the HIP pose kernel
 is assembled from) compiled for the HOST and checked against the oracle.  Runs without a GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import np_model
 import oracle_lib
+import pm_host_lib
 from stvo_amd import synth
 from stvo_amd.ctypes_types import Cam, opt_params
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 
 
 @pytest.fixture(scope="module")
 def pmh():
-    src = os.path.join(HERE, "cpp", "pm_host.cpp")
-    so = os.path.join(HERE, "cpp", "libpm_host.so")
-    hdr = os.path.join(HERE, "..", "stvo-pl_amd", "csrc", "pose_math.h")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-    lib = C.CDLL(so)
-    for n in ("pmh_expmap", "pmh_logmap", "pmh_inverse_se3", "pmh_adjoint", "pmh_inverse6", "pmh_inverse6_mem", "pmh_eig6", "pmh_step_pose",
-              "pmh_eig6_ql"):
-        getattr(lib, n).argtypes = [f64p, f64p]; getattr(lib, n).restype = None
-    lib.pmh_unccomp.argtypes = [f64p] * 4
-    lib.pmh_solve6.argtypes = [f64p, f64p, f64p, C.POINTER(C.c_double)]; lib.pmh_solve6.restype = C.c_int
-    lib.pmh_solve6_spd.argtypes = [f64p, f64p, f64p, C.POINTER(C.c_double)]; lib.pmh_solve6_spd.restype = C.c_int
-    lib.pmh_solve6_mem.argtypes = [f64p, f64p, f64p, C.POINTER(C.c_double)]; lib.pmh_solve6_mem.restype = C.c_int
-    lib.pmh_inverse6_spd.argtypes = [f64p, f64p]; lib.pmh_inverse6_spd.restype = C.c_int
-    lib.pmh_line_overlap.argtypes = [f64p] * 4; lib.pmh_line_overlap.restype = C.c_double
-    lib.pmh_normal_eq.argtypes = [f64p, C.POINTER(Cam), C.c_double, C.c_void_p, C.c_int, C.c_double, C.c_double, f64p]
-    return lib
+    return pm_host_lib.load()
 
 
 def call(lib, name, x, nout):
