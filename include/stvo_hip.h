@@ -147,8 +147,8 @@ int stvo_optimize_pose_batched_dev(stvo_ctx* ctx, const stvo_track_batch_dev* ba
  * previous frame, grids, matches) lives in HBM.  Replaces, per pushed frame and per sequence,
  * StereoFrameHandler::initialize / insertStereoPair + optimizePose + updateFrame minus feature detection
  * (src/stereoFrameHandler.cpp:35-60, 307-392, 89-100): stereo association on the 64x48 grid
- * (src/stereoFrame.cpp:120-173, 309-415), f2f tracking, pose optimisation.  The Tfw composition (:377-378) and the
- * adaptive FAST threshold (:66-86, a front-end knob) stay with the caller.  init_T is the identity
+ * (src/stereoFrame.cpp:120-173, 309-415), f2f tracking, pose optimisation.  The Tfw composition (:377-378) stays
+ * with the caller; the adaptive FAST threshold (:66-86, a front-end knob) is stvo_seq_adapt_fast_dev below.  init_T is the identity
  * (use_motion_model = false, as in every shipped configuration) unless stvo_seq_set_motion_model turns the motion model on. */
 typedef struct stvo_seq stvo_seq;
 int stvo_seq_create(stvo_ctx* ctx, int B, int max_keypoints, int max_keylines, int img_cols, int img_rows,
@@ -264,6 +264,16 @@ int stvo_orb_set_pattern(stvo_orb* orb, const int8_t* pattern /*[1024]*/);
 /* The FAST threshold of the following calls: StereoFrameHandler::updateFrame adapts orb_fast_th frame by frame
  * (src/stereoFrameHandler.cpp:66-86) and passes it to detectStereoFeatures (:56 -> src/stereoFrame.cpp:59,104-118). */
 int stvo_orb_set_fast_threshold(stvo_orb* orb, int fast_threshold /* 1 .. 254 */);
+/* One FAST threshold PER IMAGE for the following calls, at every pyramid level and under either ranking: image i of the B images takes
+ * th_dev[i % n_th].  n_th must divide B (else STVO_ERR_INVALID_ARG); n_th = B / 2 is how a stereo detector (B / 2 left images, then
+ * B / 2 right ones) shares one threshold between the two images of a pair.  th_dev is a DEVICE array that stays the caller's: the
+ * detection kernels read it when they run, in stream order, so a kernel enqueued earlier on the context's stream (stvo_fast_adapt_dev,
+ * stvo_seq_adapt_fast_dev) may write it — no host round trip.  What is read is clamped to 1 .. 254 on the device.  th_dev == NULL
+ * returns to the scalar of stvo_orb_set_fast_threshold, which keeps its meaning while an array is set but is not read. */
+int stvo_orb_set_fast_thresholds_dev(stvo_orb* orb, const int32_t* th_dev, int n_th);
+/* The same from a HOST array (every entry 1 .. 254): the detector keeps a device copy of its own, uploaded on the context's stream;
+ * synchronises.  th_host == NULL returns to the scalar. */
+int stvo_orb_set_fast_thresholds(stvo_orb* orb, const int32_t* th_host, int n_th);
 /* The ranking of the following calls, cv::ORB::create's scoreType = Config::orbScore() (src/stereoFrame.cpp:112-114), with OpenCV's
  * values: STVO_ORB_SCORE_FAST (1, the default) as described above; STVO_ORB_SCORE_HARRIS (0): per level retainBest(2 x the level's
  * share) on the FAST response, HarrisResponses (7 x 7 block, k 0.04) of the survivors on the level image, retainBest(the level's
@@ -285,6 +295,20 @@ int stvo_orb_detect_levels(stvo_orb* orb, const uint8_t* images, float* kp_xy, f
                            uint8_t* desc, int32_t* n_kp, int32_t* n_total);
 int stvo_orb_detect_levels_dev(stvo_orb* orb, const uint8_t* images, float* kp_xy, float* response, float* angle, int32_t* octave,
                                uint8_t* desc, int32_t* n_kp, int32_t* n_total);
+
+/* Replaces the adaptive FAST threshold of  StereoFrameHandler::updateFrame  (src/stereoFrameHandler.cpp:66-86, adaptative_fast: true in
+ * five of the six shipped configurations) for B streams at once, on the device: th_dev[b] (in / out) moves by what results_dev[b] says.
+ *   lost = T == Matrix4d::Identity() (every element compares equal) || err > (double)err_th       -> 2 steps of inc_th down
+ *   else the first row that applies of  n_inliers_pt < feat_th: 2 down; < 2 feat_th: 1 down; > 3 feat_th: 1 up; > 4 feat_th: 2 up
+ *   (the last row can never apply, upstream as here); a move down stops at min_th, a move up at max_th, and only on that side.
+ * A rejected pose carries T = I and err = -1.  results_dev: device memory or pinned host memory.  Enqueued on the context's stream. */
+int stvo_fast_adapt_dev(stvo_ctx* ctx, int B, const stvo_pose_result* results_dev, const stvo_fast_adapt* prm, int32_t* th_dev /* [B] */);
+/* The same behind the LAST ENQUEUED step of the pipeline (stvo_seq_step_dev / stvo_seq_push), reading that step's results where the
+ * step wrote them, on the stream its pose kernel ran on; th_dev [B] device.  With stvo_orb_set_fast_thresholds_dev(orb, th_dev, B) on a
+ * detector of 2 B images of the same context, the next frame's detection takes the adapted thresholds without the host seeing them.
+ * The first frame of a sequence has no pose (initialize() calls no updateFrame(), app/imagesStVO.cpp:90-124): nothing is launched for
+ * it and th_dev stays.  STVO_ERR_INVALID_ARG before the first step. */
+int stvo_seq_adapt_fast_dev(stvo_seq* seq, const stvo_fast_adapt* prm, int32_t* th_dev);
 
 /* ---- LBD line descriptor (first half) ------------------------------------------------------- */
 

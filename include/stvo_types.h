@@ -162,6 +162,14 @@ typedef struct stvo_orb_params {
     double scale_factor;     /* Config::orbScaleFactor()  (1.2; > 1; ignored for one level) */
 } stvo_orb_params;
 
+/* The adaptive FAST threshold rule of StereoFrameHandler::updateFrame (src/stereoFrameHandler.cpp:66-86) = Config::fastMinTh /
+ * fastMaxTh / fastIncTh / fastFeatTh / fastErrTh (config_kitti.yaml: 7, 30, 5, 50, 0.5; the other shipped files: 5, 50, 5, 50, 0.5).
+ * err_th is a float as in the reference (:72): err_norm is compared with its value widened to double. */
+typedef struct stvo_fast_adapt {
+    int32_t min_th, max_th, inc_th, feat_th;
+    float err_th;
+} stvo_fast_adapt;
+
 /* A key-line as the LBD descriptor consumes it: the line_descriptor::KeyLine fields BinaryDescriptor::computeImpl copies into its
  * OctaveSingleLine (3rdparty/line_descriptor/src/binary_descriptor_custom.cpp:592-609), octave 0. */
 typedef struct stvo_keyline {

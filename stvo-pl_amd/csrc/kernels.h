@@ -303,4 +303,8 @@ void launch_grid_batch(hipStream_t s, const GridBatch& g, bool lines, hipEvent_t
 bool grid_points_fused_ok(const GridBatch& g);
 void launch_grid_range_debug(hipStream_t s, const GridBatch& g);  // test hook, see stvo_seq_debug_grid
 
+// StereoFrameHandler::updateFrame's adaptive FAST rule for B streams, one lane per stream (fast_adapt_kernel.hip): th[b] moves by what
+// results[b] says.  `results` may be device memory or the pinned block a zero-copy step writes its results to.
+void launch_fast_adapt(hipStream_t s, int B, const stvo_pose_result* results, const stvo_fast_adapt& prm, int32_t* th);
+
 }  // namespace stvo

@@ -33,6 +33,8 @@ constexpr int ORB_HP = 15;  // half patch
 
 struct OrbDev {
     int B, cols, rows, K, nfeatures, fast_th, edge_th;
+    const int32_t* th;    // [n_th] or nullptr: FAST threshold of image i = th[i % n_th] (stvo_orb_set_fast_thresholds[_dev]); nullptr: fast_th
+    int n_th;
     int cand_cap;         // rows * cols / 4 + 64: a 3x3 strict maximum every 2 x 2 pixels at most, so the list cannot overflow
     int32_t* n_total;     // [B] or nullptr: key-points that qualified before the cap K
     const uint8_t* img;   // [B][rows][cols]
@@ -161,6 +163,10 @@ __global__ __launch_bounds__(256) void orb_fast_nms_kernel(OrbDev o) {
     const uint8_t* img = o.img + (size_t)b * o.rows * o.cols;
     const uint8_t* tile8 = reinterpret_cast<const uint8_t*>(&tile[0][0]);
     uint8_t* sc = reinterpret_cast<uint8_t*>(&sc_w[0][0]);
+    // one threshold per image: blockIdx.z is uniform, so this is one scalar load and one select per workgroup (the value stays in a
+    // scalar register, as the kernel argument does).  The array is written by another kernel (stvo_fast_adapt_dev): what is read is
+    // clamped to the range the scalar is validated to on the host
+    const int t = o.th ? __builtin_amdgcn_readfirstlane(min(max(o.th[b % o.n_th], 1), 254)) : o.fast_th;
     {
         // every word of the tile is requested before the first is used (as a loop of load -> wait -> LDS store the workgroup began
         // its life with six memory round trips one after the other).  Words that cross the image border are re-read byte by byte
@@ -198,7 +204,6 @@ __global__ __launch_bounds__(256) void orb_fast_nms_kernel(OrbDev o) {
         s_nkp = 0;
     }
     __syncthreads();
-    const int t = o.fast_th;
     // (all lanes of a wave run the same number of trips: the ballots of append4 need the whole wave)
     constexpr int GROUPS = (SC_W + 3) / 4;  // 17 groups of four score positions per row
     const uint32_t sad_min = 2u * (uint32_t)(t + 1);
@@ -1010,6 +1015,7 @@ struct stvo_orb {
     size_t io_bytes = 0;
     int8_t pattern[1024];
     int8_t* d_pattern = nullptr;
+    int32_t* d_th_own = nullptr;  // [B] device copy behind stvo_orb_set_fast_thresholds (carved from dev)
     stvo::BlurK blur_k{};
     stvo::Umax umax{};
 };
@@ -1071,6 +1077,7 @@ int stvo_orb_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keypoints,
     }
     auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
     size_t total = 1024;  // the pattern
+    const size_t off_th = total; total += al((size_t)B * 4);
     size_t off_blur[STVO_ORB_MAX_LEVELS], off_hist[STVO_ORB_MAX_LEVELS], off_cand[STVO_ORB_MAX_LEVELS], off_hkey[STVO_ORB_MAX_LEVELS], off_nc[STVO_ORB_MAX_LEVELS],
         off_img[STVO_ORB_MAX_LEVELS], off_out[STVO_ORB_MAX_LEVELS];
     for (int l = 0; l < nlevels; ++l) {
@@ -1098,6 +1105,7 @@ int stvo_orb_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keypoints,
         return STVO_ERR_HIP;
     }
     o->d_pattern = (int8_t*)o->dev;
+    o->d_th_own = (int32_t*)(o->dev + off_th);
     for (int l = 0; l < nlevels; ++l) {
         stvo_orb::Level& L = o->lev[l];
         stvo::OrbDev& d = L.d;
@@ -1170,6 +1178,29 @@ int stvo_orb_set_fast_threshold(stvo_orb* o, int fast_threshold) {
     o->prm.fast_threshold = fast_threshold;
     for (int l = 0; l < o->nlevels; ++l) o->lev[l].d.fast_th = fast_threshold;  // kernel argument of the next launches
     return STVO_OK;
+}
+
+int stvo_orb_set_fast_thresholds_dev(stvo_orb* o, const int32_t* th_dev, int n_th) {
+    if (!o) return STVO_ERR_INVALID_ARG;
+    if (th_dev && (n_th <= 0 || n_th > o->B || o->B % n_th != 0)) return STVO_ERR_INVALID_ARG;
+    for (int l = 0; l < o->nlevels; ++l) {  // kernel arguments of the next launches; the array itself is read by those launches
+        o->lev[l].d.th = th_dev;
+        o->lev[l].d.n_th = th_dev ? n_th : 0;
+    }
+    return STVO_OK;
+}
+
+int stvo_orb_set_fast_thresholds(stvo_orb* o, const int32_t* th_host, int n_th) {
+    if (!o) return STVO_ERR_INVALID_ARG;
+    if (!th_host) return stvo_orb_set_fast_thresholds_dev(o, nullptr, 0);
+    if (n_th <= 0 || n_th > o->B || o->B % n_th != 0) return STVO_ERR_INVALID_ARG;
+    for (int i = 0; i < n_th; ++i)
+        if (th_host[i] < 1 || th_host[i] > 254) return STVO_ERR_INVALID_ARG;
+    HIP_TRY(o->ctx, hipSetDevice(o->ctx->device));
+    // (ordered behind the detections already enqueued, which may still read the previous contents)
+    HIP_TRY(o->ctx, hipMemcpyAsync(o->d_th_own, th_host, (size_t)n_th * 4, hipMemcpyHostToDevice, o->ctx->stream));
+    HIP_TRY(o->ctx, hipStreamSynchronize(o->ctx->stream));
+    return stvo_orb_set_fast_thresholds_dev(o, o->d_th_own, n_th);
 }
 
 int stvo_orb_set_score_type(stvo_orb* o, int score_type) {

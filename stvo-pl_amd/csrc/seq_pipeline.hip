@@ -1503,6 +1503,19 @@ int stvo_seq_step_dev(stvo_seq* s, int slot) {
     return STVO_OK;
 }
 
+// updateFrame's adaptive FAST rule (:66-86) behind the last enqueued step, on the stream its pose kernel ran on.  That step tracked iff it
+// was not the first of the sequence (StepFlags::track = frame_idx > 0, and frame_idx has moved on since): initialize() has no updateFrame().
+int stvo_seq_adapt_fast_dev(stvo_seq* s, const stvo_fast_adapt* prm, int32_t* th_dev) {
+    if (!s || !prm || !th_dev || prm->min_th > prm->max_th || s->frame_idx < 1) return STVO_ERR_INVALID_ARG;
+    if (s->frame_idx == 1) return STVO_OK;
+    stvo_ctx* ctx = s->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // where seq_enqueue_step pointed PoseArgs::results
+    const stvo_pose_result* res = s->zero_copy ? reinterpret_cast<const stvo_pose_result*>(s->out_host) : s->results;
+    stvo::launch_fast_adapt(ctx->stream, s->B, res, *prm, th_dev);
+    return check_launch(ctx);
+}
+
 // Results of the LAST step (synchronises).  counts (optional, [B][4]): stereo points, stereo lines, matched
 // points, matched lines of that frame; results are zeroed after the first frame (nothing to track against yet).
 int stvo_seq_read(stvo_seq* s, stvo_pose_result* results, int32_t* counts) {

@@ -27,7 +27,8 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_lsd_detect_dev", "stvo_lsd_segments", "stvo_lsd_counts", "stvo_fld_create", "stvo_fld_destroy", "stvo_fld_detect",
            "stvo_fld_detect_dev", "stvo_fld_counts", "stvo_fld_segments", "stvo_fld_edges", "stvo_keylines_xy_dev", "stvo_rectify_compute",
            "stvo_rectify_create", "stvo_rectify_create_from_maps", "stvo_rectify_destroy", "stvo_rectify_camera", "stvo_rectify_images",
-           "stvo_rectify_images_dev"]
+           "stvo_rectify_images_dev", "stvo_orb_set_fast_thresholds", "stvo_orb_set_fast_thresholds_dev", "stvo_fast_adapt_dev",
+           "stvo_seq_adapt_fast_dev"]
 
 SEQ_NSTAGE = 5  # include/stvo_hip.h: STVO_SEQ_NSTAGE
 SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_check", "pose")
@@ -64,6 +65,32 @@ class FrameFeatures(C.Structure):
 
 class StvoError(RuntimeError):
     pass
+
+
+class FastAdapt(C.Structure):  # stvo_fast_adapt
+    _fields_ = [("min_th", C.c_int32), ("max_th", C.c_int32), ("inc_th", C.c_int32), ("feat_th", C.c_int32), ("err_th", C.c_float)]
+
+
+def fast_adapt_params(preset="kitti", **overrides):
+    """Config::fastMinTh / fastMaxTh / fastIncTh / fastFeatTh / fastErrTh as the reference's YAML files ship them: "kitti" =
+    config_kitti.yaml (7, 30, 5, 50, 0.5), "euroc" = every other file (5, 50, 5, 50, 0.5).  overrides: min_th, max_th, inc_th, feat_th, err_th."""
+    base = {"kitti": dict(min_th=7, max_th=30), "euroc": dict(min_th=5, max_th=50)}[preset]
+    base.update(inc_th=5, feat_th=50, err_th=0.5)
+    unknown = set(overrides) - set(base)
+    if unknown:
+        raise TypeError(f"fast_adapt_params: unknown field(s) {sorted(unknown)}")
+    base.update(overrides)
+    return FastAdapt(**base)
+
+
+def fast_adapt_dev(ctx, results, prm, th):
+    """updateFrame's adaptive FAST rule for len(th) streams, on the context's stream (stvo_fast_adapt_dev): results = a torch uint8
+    device tensor holding that many stvo_pose_result records (POSE_RESULT_DTYPE), th = a torch int32 device tensor, moved in place."""
+    B = th.numel()
+    if str(th.dtype) != "torch.int32" or not th.is_cuda or not th.is_contiguous() or not results.is_contiguous() or \
+            results.numel() * results.element_size() < B * POSE_RESULT_DTYPE.itemsize:
+        raise ValueError("fast_adapt_dev: th must be a contiguous int32 tensor and results hold one record per threshold")
+    ctx._chk(ctx.lib.stvo_fast_adapt_dev(ctx.h, B, results.data_ptr(), C.byref(prm), th.data_ptr()))
 
 
 def build(force=False):
@@ -144,6 +171,10 @@ def load():
     L.stvo_orb_detect_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 6
     L.stvo_orb_set_fast_threshold.argtypes = [C.c_void_p, C.c_int]
     L.stvo_orb_set_score_type.argtypes = [C.c_void_p, C.c_int]
+    L.stvo_orb_set_fast_thresholds.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.stvo_orb_set_fast_thresholds_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.stvo_fast_adapt_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(FastAdapt), C.c_void_p]
+    L.stvo_seq_adapt_fast_dev.argtypes = [C.c_void_p, C.POINTER(FastAdapt), C.c_void_p]
     L.stvo_orb_detect_levels.argtypes = [C.c_void_p, u8p, f32p, f32p, f32p, i32p, u8p, i32p, i32p]
     L.stvo_orb_detect_levels_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 8
     L.stvo_lbd_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -377,6 +408,24 @@ class Orb:
 
     def set_fast_threshold(self, th):
         self.ctx._chk(self.ctx.lib.stvo_orb_set_fast_threshold(self.h, th))
+
+    def set_fast_thresholds(self, th):
+        """One FAST threshold per image, image i takes th[i % len(th)] (len(th) divides B).  A numpy array / sequence: host form, the
+        detector keeps its own device copy (stvo_orb_set_fast_thresholds).  A torch int32 device tensor: device form, the tensor is
+        read by every later detection when it runs and must outlive them (stvo_orb_set_fast_thresholds_dev).  None: back to the scalar."""
+        lib = self.ctx.lib
+        if th is None:
+            self.ctx._chk(lib.stvo_orb_set_fast_thresholds_dev(self.h, None, 0))
+            self._th_keep = None
+        elif hasattr(th, "data_ptr"):
+            if str(th.dtype) != "torch.int32" or not th.is_cuda or not th.is_contiguous():
+                raise ValueError("Orb.set_fast_thresholds: the device form takes a contiguous int32 device tensor")
+            self.ctx._chk(lib.stvo_orb_set_fast_thresholds_dev(self.h, th.data_ptr(), th.numel()))
+            self._th_keep = th
+        else:
+            a = np.ascontiguousarray(th, np.int32).reshape(-1)
+            self.ctx._chk(lib.stvo_orb_set_fast_thresholds(self.h, _ptr(a), a.size))
+            self._th_keep = None
 
     def set_score_type(self, score):
         self.ctx._chk(self.ctx.lib.stvo_orb_set_score_type(self.h, score))
@@ -651,6 +700,13 @@ class Sequences:
 
     def step_dev(self, slot):
         self.ctx._chk(self.ctx.lib.stvo_seq_step_dev(self.h, slot))
+
+    def adapt_fast_dev(self, prm, th):
+        """updateFrame's adaptive FAST rule behind the last enqueued step (stvo_seq_adapt_fast_dev): th = torch int32 [B] device tensor,
+        moved in place by that step's results; asynchronous.  A sequence's first frame leaves it alone."""
+        if str(th.dtype) != "torch.int32" or not th.is_cuda or not th.is_contiguous() or th.numel() != self.B:
+            raise ValueError("Sequences.adapt_fast_dev: th must be a contiguous int32 device tensor of B entries")
+        self.ctx._chk(self.ctx.lib.stvo_seq_adapt_fast_dev(self.h, C.byref(prm), th.data_ptr()))
 
     def read(self):
         res = np.zeros(self.B, dtype=POSE_RESULT_DTYPE)

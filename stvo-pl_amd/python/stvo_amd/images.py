@@ -18,7 +18,7 @@ from .capi import FrameFeatures
 
 class ImagePipeline:
     def __init__(self, ctx, B, cam, mp, op, max_kp=2048, nfeatures=2000, fast_threshold=20, edge_threshold=19, device="cuda:0", nlevels=1,
-                 scale_factor=1.2, lsd=None, max_kl=128, rectify=None, fld=None, orb_score=1):
+                 scale_factor=1.2, lsd=None, max_kl=128, rectify=None, fld=None, orb_score=1, adaptive_fast=None):
         """cam: one camera dict (width / height = image size) for all B streams.  nlevels / scale_factor: Config::orbNLevels /
         orbScaleFactor (the key-point octaves travel with the key-points: sigma2 = 1 / scale^(2 level)).  orb_score: Config::orbScore
         (1 FAST_SCORE, 0 HARRIS_SCORE ranking of the key-points).  lsd: capi.lsd_params(...)
@@ -26,7 +26,11 @@ class ImagePipeline:
         fld: capi.fld_params(...) instead of lsd, the FLD detector of use_fld_lines (src/stereoFrame.cpp:244-303); not both.
         rectify: a capi.Rectifier of the same context for at least B pairs of this size: enqueue first remaps the raw images into a
         resident rectified buffer (same stream, no host synchronisation) and the detectors read that buffer; cam is then the rectified
-        camera (Rectifier.camera).  None: the images are taken as rectified."""
+        camera (Rectifier.camera).  None: the images are taken as rectified.
+        adaptive_fast: capi.fast_adapt_params(...) turns on the reference's adaptative_fast (StereoFrameHandler::updateFrame,
+        src/stereoFrameHandler.cpp:66-86) per stream: self.fast_th (int32 [B] on the device, fast_threshold at first) is what the
+        detector reads for the two images of stream b, and every enqueue ends with the rule moving it by that step's pose results —
+        on the device, in stream order, the host never sees it.  None: one fixed threshold, no kernel added."""
         self.ctx, self.B, self.K, self.M = ctx, B, max_kp, max_kl
         self.cols, self.rows = cam["width"], cam["height"]
         self.rectify = rectify
@@ -76,6 +80,12 @@ class ImagePipeline:
             ff.kl_r = C.c_void_p(self.kl_xy.data_ptr() + 16 * B * M)
             ff.ldesc_l = C.c_void_p(self.ldesc.data_ptr())
             ff.ldesc_r = C.c_void_p(self.ldesc.data_ptr() + 32 * B * M)
+        self.adaptive_fast = adaptive_fast
+        self.fast_th = None
+        if adaptive_fast is not None:
+            self.fast_th = torch.full((B,), fast_threshold, dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()  # the fill ran on torch's stream, the library uses its own
+            self.orb.set_fast_thresholds(self.fast_th)  # n_th = B on 2 B images: left image b and right image B + b share entry b
         self.ff = ff  # (without a line detector every line pointer stays NULL: no key-lines; oct_ll NULL: one octave)
         self.slot = 0
 
@@ -102,6 +112,8 @@ class ImagePipeline:
             self.ctx._chk(self.ctx.lib.stvo_keylines_xy_dev(self.ctx.h, 2 * self.B, self.M, self.kl.data_ptr(), self.nl.data_ptr(), self.kl_xy.data_ptr()))
         self.seq.upload_dev(self.slot, self.ff)
         self.seq.step_dev(self.slot)
+        if self.adaptive_fast is not None:
+            self.seq.adapt_fast_dev(self.adaptive_fast, self.fast_th)
         self.slot ^= 1
 
     def push_images(self, left, right):
@@ -110,6 +122,13 @@ class ImagePipeline:
         torch.cuda.current_stream().synchronize()  # the copies above ran on torch's stream, the library uses its own
         self.enqueue()
         return self.seq.read()
+
+    def fast_thresholds(self):
+        """Host copy of the per-stream FAST thresholds the NEXT detection will read (synchronises); tests and tools."""
+        if self.fast_th is None:
+            raise ValueError("ImagePipeline.fast_thresholds: built without adaptive_fast")
+        self.ctx.synchronize()
+        return self.fast_th.cpu().numpy().copy()
 
     def close(self):
         self.seq.close()

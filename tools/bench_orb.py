@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Throughput of the ORB point front-end (stvo_orb_detect_dev) on B KITTI-sized images resident in HBM, next to the oracle
-(oracle/stvo_orb_oracle.c, one host core).  python tools/bench_orb.py [--batch 256] [--iters 10]"""
+(oracle/stvo_orb_oracle.c, one host core).  python tools/bench_orb.py [--batch 256] [--iters 10] [--thresholds TH]
+--thresholds TH: the per-image threshold array (stvo_orb_set_fast_thresholds_dev) set to TH for every image instead of the scalar —
+with TH 20, the default scalar, the same work through the array path."""
 import argparse
 import json
 import os
@@ -14,6 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "stvo-pl_amd", "python")); sys.path.insert
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--iters", type=int, default=10)
+ap.add_argument("--thresholds", type=int, default=None)
 a = ap.parse_args()
 import torch  # noqa: E402
 from stvo_amd import capi, synth  # noqa: E402
@@ -28,6 +31,9 @@ orb = capi.Orb(ctx, B, 1241, 376, max_keypoints=K)
 d = dict(img=torch.from_numpy(imgs).cuda(), kp=torch.zeros(B, K, 2, device="cuda"), resp=torch.zeros(B, K, device="cuda"),
          ang=torch.zeros(B, K, device="cuda"), desc=torch.zeros(B, K, 32, dtype=torch.uint8, device="cuda"),
          n=torch.zeros(B, dtype=torch.int32, device="cuda"))
+if a.thresholds is not None:
+    d["th"] = torch.full((B,), a.thresholds, dtype=torch.int32, device="cuda")
+    orb.set_fast_thresholds(d["th"])
 
 
 def run():
@@ -49,6 +55,6 @@ for b in range(8):
     orc.orb_detect(imgs[b], cap=K)
 dtc = (time.perf_counter() - t1) / 8
 px = B * 1241 * 376
-print(json.dumps({"images_per_launch": B, "ms_per_launch": dt * 1e3, "images_per_s": B / dt, "mean_keypoints": float(d["n"].float().mean()),
+print(json.dumps({"images_per_launch": B, "threshold_array": a.thresholds, "ms_per_launch": dt * 1e3, "images_per_s": B / dt, "mean_keypoints": float(d["n"].float().mean()),
                   "image_bytes_GBps": px / dt / 1e9, "oracle_ms_per_image_1_core": dtc * 1e3, "speedup_vs_1_core": dtc / (dt / B)}))
 orb.close(); ctx.close()
