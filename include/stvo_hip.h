@@ -243,6 +243,17 @@ int stvo_seq_last_schedule(const stvo_seq* seq, int32_t out[8]);
 int stvo_seq_debug_grid(stvo_seq* seq, int b, int lines, int32_t* cell_start, int32_t* cell_items, int32_t cap_items,
                         int32_t* cells_left, int32_t* cand_off, int32_t* cand, int32_t cap_cand, int32_t* n_left);
 
+/* TEST HOOK: the stereo sets the last step built from its frame for sequence b, i.e. what the tails of the stereo association
+ * (src/stereoFrame.cpp:152-172, :351-395) wrote: n_pts stereo points as rc [n_pts][4] = {u, v, disparity, level} (floats) with the kept
+ * left descriptor rows desc [n_pts][32]; n_lines stereo lines as spl, epl [n_lines][2], sP, eP, le [n_lines][3], s2l (sigma2 of the
+ * LineFeature constructor), s2lm (after LineFeature::safeCopy's re-scaling) [n_lines] and ldesc [n_lines][32].  Synchronises the
+ * context's stream and the key-line stream, copies, launches nothing and changes no state.  cap_pts / cap_lines: rows the caller's
+ * arrays hold; too few: STVO_ERR_CAPACITY with the counts filled in.  A step of any schedule writes the set it then makes the
+ * previous one, so the last step's set is always known; before the first step there is none: STVO_ERR_INVALID_ARG. */
+int stvo_seq_debug_stereo(stvo_seq* seq, int b, int32_t cap_pts, int32_t* n_pts, float* rc, uint8_t* desc, int32_t cap_lines,
+                          int32_t* n_lines, double* spl, double* epl, double* sP, double* eP, double* le, double* s2l, double* s2lm,
+                          uint8_t* ldesc);
+
 /* ---- ORB point front-end ------------------------------------------------------------------ */
 
 /* Replaces  cv::ORB::create(nfeatures, scaleFactor, nlevels, ...)->detectAndCompute(img, Mat(), points, pdesc, false)  as

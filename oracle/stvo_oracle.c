@@ -369,19 +369,24 @@ int orc_stereo_points(const float* kp_l, const int32_t* oct_l, const uint8_t* de
     return k;
 }
 
+/* std::min / std::max as the reference calls them (src/stereoFrame.cpp:410, :480-493): (b < a) ? b : a and (a < b) ? b : a.  fmin /
+ * fmax return the other argument where one is NaN — a horizontal right line makes NaN disparities (0 / 0 at :366). */
+static double std_min(double a, double b) { return b < a ? b : a; }
+static double std_max(double a, double b) { return a < b ? b : a; }
+
 /* StereoFrame::lineSegmentOverlapStereo, src/stereoFrame.cpp:473-508 (note length = eln - spn). */
 double orc_line_overlap_stereo(double spl_obs, double epl_obs, double spl_proj, double epl_proj, double line_horiz_th) {
     double overlap = 1.0;
     if (fabs(epl_obs - spl_obs) > line_horiz_th) {
-        double sln = fmin(spl_obs, epl_obs), eln = fmax(spl_obs, epl_obs);
-        double spn = fmin(spl_proj, epl_proj), epn = fmax(spl_proj, epl_proj);
+        double sln = std_min(spl_obs, epl_obs), eln = std_max(spl_obs, epl_obs);
+        double spn = std_min(spl_proj, epl_proj), epn = std_max(spl_proj, epl_proj);
         double length = eln - spn;
         if (epn < sln || spn > eln)
             overlap = 0.0;
         else if (epn > eln && spn < sln)
             overlap = eln - sln;
         else
-            overlap = fmin(eln, epn) - fmax(sln, spn);
+            overlap = std_min(eln, epn) - std_max(sln, spn);
         if (length > (double)0.01f)
             overlap = overlap / length;
         else
@@ -464,7 +469,7 @@ int orc_stereo_lines(const float* kl_l, const float* angle_l, const int32_t* oct
         ep_r[0] = epx;
         ep_r[1] = ep_l[1];
         double disp_s = sp_l[0] - sp_r[0], disp_e = ep_l[0] - ep_r[0]; /* :407-408 */
-        if (fmin(disp_s, disp_e) / fmax(disp_s, disp_e) < mp->ls_min_disp_ratio) {
+        if (std_min(disp_s, disp_e) / std_max(disp_s, disp_e) < mp->ls_min_disp_ratio) {
             disp_s = -1.0;
             disp_e = -1.0;
         }

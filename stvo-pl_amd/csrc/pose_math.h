@@ -1022,21 +1022,27 @@ PM_HD double line_overlap(double sox, double soy, double eox, double eoy, double
     return overlap_from_lambdas((fsx - sox) / lx, (fex - sox) / lx);
 }
 
+// std::min / std::max to the letter — (b < a) ? b : a and (a < b) ? b : a — for the two functions below, which restate calls of them
+// (src/stereoFrame.cpp:410, :480-493): dmax above returns its SECOND argument where the two compare equal (+0 / -0) or the first is
+// NaN, std::max its first (tests/test_stereo_tail_host.py sweeps NaN / inf / equal arguments against a plain statement).
+PM_HD double smin(double a, double b) { return b < a ? b : a; }
+PM_HD double smax(double a, double b) { return a < b ? b : a; }
+
 // Stereo association of a line pair, shared by line_tail_kernel (seq_pipeline.hip) and the host mirror (host/stereoFrame.cpp).
 // Fraction of the left segment's row span [min(y_s, y_e), max(y_s, y_e)] that the right segment's rows cover
 // (StereoFrame::lineSegmentOverlapStereo, src/stereoFrame.cpp:473-508): 1 for a left segment flatter than horiz_th, and the
 // reference normalises by  max(left rows) - min(right rows)  (not by the left span) and clips at 1.
 PM_HD double stereo_row_overlap(double yl_s, double yl_e, double yr_s, double yr_e, double horiz_th) {
     if (!(fabs(yl_e - yl_s) > horiz_th)) return 1.0;
-    const double l_top = dmin(yl_s, yl_e), l_bot = dmax(yl_s, yl_e);
-    const double r_top = dmin(yr_s, yr_e), r_bot = dmax(yr_s, yr_e);
+    const double l_top = smin(yl_s, yl_e), l_bot = smax(yl_s, yl_e);
+    const double r_top = smin(yr_s, yr_e), r_bot = smax(yr_s, yr_e);
     double cover;
     if (r_bot < l_top || r_top > l_bot)
         cover = 0.0;                                   // disjoint row ranges
     else if (r_bot > l_bot && r_top < l_top)
         cover = l_bot - l_top;                         // the right segment spans the whole left one
     else
-        cover = dmin(l_bot, r_bot) - dmax(l_top, r_top);
+        cover = smin(l_bot, r_bot) - smax(l_top, r_top);
     const double denom = l_bot - r_top;
     cover = denom > (double)0.01f ? cover / denom : 0.0;
     return cover > 1.0 ? 1.0 : cover;
@@ -1046,7 +1052,7 @@ PM_HD double stereo_row_overlap(double yl_s, double yl_e, double yr_s, double yr
 PM_HD void stereo_line_disparities(double xl_s, double xl_e, double xr_s, double xr_e, double min_ratio, double* disp_s,
                                    double* disp_e) {
     const double ds = xl_s - xr_s, de = xl_e - xr_e;
-    const bool consistent = !(dmin(ds, de) / dmax(ds, de) < min_ratio);
+    const bool consistent = !(smin(ds, de) / smax(ds, de) < min_ratio);
     *disp_s = consistent ? ds : -1.0;
     *disp_e = consistent ? de : -1.0;
 }

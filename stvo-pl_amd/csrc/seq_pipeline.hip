@@ -1772,6 +1772,49 @@ int stvo_seq_debug_grid(stvo_seq* s, int b, int lines, int32_t* cell_start, int3
     return tot > cap_cand ? STVO_ERR_CAPACITY : STVO_OK;
 }
 
+// TEST HOOK.  The stereo sets the LAST step built from its frame for sequence b, as the tails of the association left them
+// (point_tail.h / fused_tail; line_tail_frame): tests/test_gpu_stereo_tail.py compares them record by record with the oracle and
+// with tests/np_stereo_tail.py.  Copies only: nothing is launched, no state of `s` changes.
+// Which of the three sets: every step — whatever its schedule, the key-line stage ahead included, which only moves the key-line
+// kernels of a step behind an earlier event — writes set[cur] and then advances cur, so the last step's set is set[prev_set()] (what
+// stvo_seq_read reads its counts from).  Before the first step no set belongs to a frame: STVO_ERR_INVALID_ARG.
+int stvo_seq_debug_stereo(stvo_seq* s, int b, int32_t cap_pts, int32_t* n_pts, float* rc, uint8_t* desc, int32_t cap_lines,
+                          int32_t* n_lines, double* spl, double* epl, double* sP, double* eP, double* le, double* s2l, double* s2lm,
+                          uint8_t* ldesc) {
+    if (!s || b < 0 || b >= s->B || cap_pts < 0 || cap_lines < 0 || !n_pts || !n_lines || s->frame_idx == 0) return STVO_ERR_INVALID_ARG;
+    if ((cap_pts > 0 && (!rc || !desc)) || (cap_lines > 0 && (!spl || !epl || !sP || !eP || !le || !s2l || !s2lm || !ldesc)))
+        return STVO_ERR_INVALID_ARG;
+    stvo_ctx* ctx = s->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(s->line_stream));
+    const stvo_seq::Set& ls = s->set[s->prev_set()];
+    const size_t K = (size_t)s->K, M = (size_t)s->M;
+    int32_t n = 0, nl = 0;
+    if (s->op.has_points) HIP_TRY(ctx, hipMemcpy(&n, ls.n + b, 4, hipMemcpyDeviceToHost));
+    if (s->last_lines) HIP_TRY(ctx, hipMemcpy(&nl, ls.nl + b, 4, hipMemcpyDeviceToHost));
+    if (n < 0 || (size_t)n > K || nl < 0 || (size_t)nl > M) return STVO_ERR_HIP;
+    *n_pts = n;
+    *n_lines = nl;
+    if (n > cap_pts || nl > cap_lines) return STVO_ERR_CAPACITY;
+    if (n) {
+        HIP_TRY(ctx, hipMemcpy(rc, ls.rc + b * K, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(desc, ls.desc + b * K * STVO_DESC_BYTES, (size_t)n * STVO_DESC_BYTES, hipMemcpyDeviceToHost));
+    }
+    if (nl) {
+        const size_t r = (size_t)nl * sizeof(double);
+        HIP_TRY(ctx, hipMemcpy(spl, ls.spl + b * M * 2, 2 * r, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(epl, ls.epl + b * M * 2, 2 * r, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(sP, ls.sP + b * M * 3, 3 * r, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(eP, ls.eP + b * M * 3, 3 * r, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(le, ls.le + b * M * 3, 3 * r, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(s2l, ls.s2l + b * M, r, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(s2lm, ls.s2lm + b * M, r, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ldesc, ls.ldesc + b * M * STVO_DESC_BYTES, (size_t)nl * STVO_DESC_BYTES, hipMemcpyDeviceToHost));
+    }
+    return STVO_OK;
+}
+
 int stvo_seq_push(stvo_seq* s, const stvo_frame_features* f, stvo_pose_result* results, int32_t* counts) {
     if (!s || !f) return STVO_ERR_INVALID_ARG;
     const int slot = s->frame_idx & 1;  // (slots beyond the first two belong to callers of upload / step_dev)

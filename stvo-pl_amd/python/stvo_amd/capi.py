@@ -20,7 +20,7 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_track_batched_dev", "stvo_match_nnr_mutual_batched_dev", "stvo_optimize_pose_batched_dev",
            "stvo_time_stage_dev", "stvo_valu_peak_probe", "stvo_last_reverse_counts", "stvo_last_reverse_plan", "stvo_ctx_set_kernel_timing", "stvo_ctx_get_kernel_timing", "stvo_seq_create", "stvo_seq_destroy", "stvo_seq_enable_fetch", "stvo_seq_fetch_matches", "stvo_seq_fetch_inliers", "stvo_seq_strides",
            "stvo_seq_push", "stvo_seq_upload", "stvo_seq_step_dev", "stvo_seq_read", "stvo_seq_create_multi", "stvo_seq_set_slots",
-           "stvo_seq_set_stage_timing", "stvo_seq_get_stage_timing", "stvo_seq_last_schedule", "stvo_seq_set_motion_model", "stvo_seq_debug_grid", "stvo_orb_create", "stvo_orb_destroy",
+           "stvo_seq_set_stage_timing", "stvo_seq_get_stage_timing", "stvo_seq_last_schedule", "stvo_seq_set_motion_model", "stvo_seq_debug_grid", "stvo_seq_debug_stereo", "stvo_orb_create", "stvo_orb_destroy",
            "stvo_orb_set_pattern", "stvo_orb_get_pattern", "stvo_orb_detect", "stvo_orb_detect_dev", "stvo_orb_detect_levels",
            "stvo_orb_detect_levels_dev", "stvo_orb_set_fast_threshold", "stvo_orb_set_score_type", "stvo_seq_upload_dev", "stvo_lbd_create", "stvo_lbd_destroy",
            "stvo_lbd_compute", "stvo_lbd_compute_dev", "stvo_debug_reparse_env", "stvo_lsd_create", "stvo_lsd_destroy", "stvo_lsd_detect",
@@ -165,6 +165,8 @@ def load():
     L.stvo_orb_destroy.argtypes = [C.c_void_p]
     i8p = np.ctypeslib.ndpointer(np.int8, flags="C_CONTIGUOUS")
     f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
+    L.stvo_seq_debug_stereo.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.POINTER(C.c_int32), f32p, u8p, C.c_int32, C.POINTER(C.c_int32),
+                                        f64p, f64p, f64p, f64p, f64p, f64p, f64p, u8p]
     L.stvo_orb_set_pattern.argtypes = [C.c_void_p, i8p]
     L.stvo_orb_get_pattern.argtypes = [C.c_void_p, i8p]
     L.stvo_orb_detect.argtypes = [C.c_void_p, u8p, f32p, f32p, f32p, u8p, i32p]
@@ -653,6 +655,22 @@ class Sequences:
         nl = n.value
         return (start, items[:start[-1]].copy(), cells[:nl * (4 if lines else 2)].reshape(nl, -1).copy(), off[:nl + 1].copy(),
                 cand[:off[nl]].copy())
+
+    def debug_stereo(self, b):
+        """The stereo sets the last step built from its frame for sequence b (stvo_seq_debug_stereo): dict of n, rc [n, 4] float32
+        {u, v, disparity, level}, desc [n, 32]; nl, spl, epl [nl, 2], sP, eP, le [nl, 3], s2l, s2lm [nl], ldesc [nl, 32]."""
+        K, M = self.strides()
+        rc = np.empty((K, 4), np.float32); desc = np.empty((K, 32), np.uint8); ldesc = np.empty((M, 32), np.uint8)
+        spl, epl = np.empty((M, 2)), np.empty((M, 2))
+        sP, eP, le = np.empty((M, 3)), np.empty((M, 3)), np.empty((M, 3))
+        s2l, s2lm = np.empty(M), np.empty(M)
+        n, nl = C.c_int32(), C.c_int32()
+        self.ctx._chk(self.ctx.lib.stvo_seq_debug_stereo(self.h, b, K, C.byref(n), rc.reshape(-1), desc.reshape(-1), M, C.byref(nl),
+                                                        spl.reshape(-1), epl.reshape(-1), sP.reshape(-1), eP.reshape(-1), le.reshape(-1),
+                                                        s2l, s2lm, ldesc.reshape(-1)))
+        n, nl = n.value, nl.value
+        return dict(n=n, rc=rc[:n].copy(), desc=desc[:n].copy(), nl=nl, spl=spl[:nl].copy(), epl=epl[:nl].copy(), sP=sP[:nl].copy(),
+                    eP=eP[:nl].copy(), le=le[:nl].copy(), s2l=s2l[:nl].copy(), s2lm=s2lm[:nl].copy(), ldesc=ldesc[:nl].copy())
 
     def close(self):
         if self.h:

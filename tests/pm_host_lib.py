@@ -31,6 +31,8 @@ def load():
     lib.pmh_solve6_mem.argtypes = [f64p, f64p, f64p, C.POINTER(C.c_double)]; lib.pmh_solve6_mem.restype = C.c_int
     lib.pmh_inverse6_spd.argtypes = [f64p, f64p]; lib.pmh_inverse6_spd.restype = C.c_int
     lib.pmh_line_overlap.argtypes = [f64p] * 4; lib.pmh_line_overlap.restype = C.c_double
+    lib.pmh_stereo_row_overlap.argtypes = [C.c_double] * 5; lib.pmh_stereo_row_overlap.restype = C.c_double
+    lib.pmh_stereo_line_disparities.argtypes = [C.c_double] * 5 + [f64p]; lib.pmh_stereo_line_disparities.restype = None
     for n in ("pmh_normal_eq", "pmh_normal_eq_q"):
         getattr(lib, n).argtypes = [f64p, C.POINTER(Cam), C.c_double, C.c_void_p, C.c_int, C.c_double, C.c_double, f64p]
         getattr(lib, n).restype = None
