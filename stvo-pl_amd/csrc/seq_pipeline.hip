@@ -27,6 +27,7 @@
 #include "ctx_internal.h"
 #include "point_cells.h"
 #include "pose_math.h"
+#include "step_plan.h"
 
 // The geometry filters of the tail kernels decide on thresholds (min_disp, ls_min_disp_ratio, stereo_overlap_th): no
 // fused multiply-adds, so that they round exactly like the reference's separate operations (and like the host mirror,
@@ -397,7 +398,7 @@ __global__ __launch_bounds__(256) void line_tail_kernel(SeqDev s) {
 // asks for, i.e. how many of its workgroups a CU holds, weighs more than its instruction count.)
 constexpr uint32_t LSF_ROW_EMPTY = 0xFFFFu;      // cmin = 255 > cmax = 0
 constexpr uint32_t LSF_NO_WINDOW = 0x0000FFFFu;  // hi = -1: below every cmin
-constexpr int LSF_MAX_LINES = 512, LSF_BYTES_PER_LINE = 32 + 16 + 16 + 4 + 2 * STVO_GRID_ROWS + 2 + 2 + 1;
+// (LSF_MAX_LINES and LSF_BYTES_PER_LINE, what a launch is sized with: step_plan.h)
 // Mk (<= s.M): lines per image the LDS arrays are sized for — the host knows that no image of the batch holds more.
 // T: threads per frame (256; a single wave per frame was tried to hold fewer wave slots, and was slower).
 template <int T>
@@ -646,9 +647,8 @@ struct stvo_seq {
     int32_t* m12l_alt = nullptr;  // batches only
     unsigned* d_pose_flag = nullptr;
     unsigned pose_epoch = 0;         // the last start value handed to a pose kernel
-    long long fork_rec_frame = -2;   // the last step that recorded ev_fork on the point stream
-    long long pose_flag_frame = -2;  // the last step whose pose kernel publishes its start (d_pose_flag reaches pose_flag_value)
-    unsigned pose_flag_value = 0;
+    stvo::StepHistory hist;          // which step last recorded ev_fork / published its pose kernel's start / forked the line stream (step_plan.h)
+    unsigned pose_flag_value = 0;    // what d_pose_flag reaches when the pose kernel of step hist.pose_flag_frame starts
     stvo_pose_result* results;
     char* out_host = nullptr;  // pinned: results + counts
     // second stream: the line stage (stereo association + f2f of the key-lines) is independent of the point stage
@@ -657,12 +657,11 @@ struct stvo_seq {
     hipStream_t line_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // Batches: the grid of frame k + 1 (point_cells_kernel) is enqueued on the LINE stream, which is idle from ~0.2 ms into step k on, and
-    // the point stream only waits for it in front of its matcher — 38 us less in the chain of a step (see seq_enqueue_step).  The kernel's
+    // the point stream only waits for it in front of its matcher — 38 us less in the chain of a step (step_plan.h: cells_ahead).  The kernel's
     // outputs are double-buffered by the parity of the step (cells_buf[cur]): the grid of frame k + 1 may be built while the matcher
     // of frame k still reads its own.
     hipEvent_t ev_cells = nullptr, ev_upload = nullptr;
     unsigned long long upload_seq = 0, upload_seen = 0;  // uploads enqueued on the point stream / the last one the line stream has been made to wait for
-    long long sl_forked_frame = -2;                      // the last step in which the line stream waited for an event of the point stream
     struct CellsBuf {
         int32_t *pstart, *pperm, *pcell, *plperm;
         uint32_t* plstart;
@@ -1134,35 +1133,253 @@ int stvo_seq_upload_dev(stvo_seq* s, int slot, const stvo_frame_features* f) {
     return check_launch(ctx);
 }
 
-// Runs the whole per-frame pipeline on the features resident in `slot` (asynchronous; no host transfer).
+// One step of the pipeline on the features resident in a slot: gather the facts, plan (step_plan.h), enqueue.
 namespace {
 
 struct StepFlags {
     bool lines_now, lines_prev, track;
 };
 
-// What a step has published for the steps after it.  stvo_seq_step_dev commits it to `s` only when the whole step has been enqueued,
-// so that no later step waits on an event or a flag that a failed step never recorded.
+// The values a step drew from the epoch counters for the flags it publishes; stvo_seq_step_dev commits them, with the plan, only when
+// the whole step has been enqueued.
 struct StepPub {
-    bool fork_recorded = false;  // ev_fork was recorded on the point stream (stvo_seq::fork_rec_frame)
-    bool pose_flagged = false;   // the pose kernel publishes its start: d_pose_flag reaches pose_flag_value (stvo_seq::pose_flag_frame)
-    unsigned pose_flag_value = 0;
-    bool line_forked = false;    // the line stream waited for an event of the point stream (stvo_seq::sl_forked_frame)
-    bool fetch_by_pose = false;  // the pose kernel hands the match indices to the host and then publishes fetch_value (stvo_seq::fetch_by_pose)
-    unsigned fetch_value = 0;
-    // the record of the step's host-side decisions (stvo_seq_last_schedule, include/stvo_hip.h: STVO_SCHED_*): bookkeeping only
-    int32_t schedule[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned pose_flag_value = 0;  // StepPlan::pose_flagged: d_pose_flag reaches it when the pose kernel starts
+    unsigned fetch_value = 0;      // StepPlan::fetch_by_pose: the pose kernel publishes it behind the match indices
 };
 
-// Enqueues the kernel chain of one step on the context's stream and the line stream, and returns in `pub` what the step publishes.
-// Of the state of `s` it changes only: the counters the three flags' values are drawn from (pose_epoch, join_epoch, fetch_epoch) — a
-// value handed to a launch may reach the device even when a later launch of the step fails, so it is never handed out twice; later
-// steps wait only for the values committed from `pub` —, the key-line capacity of the set it builds (set_lines_cap[cur]), the
-// stage-timing events it takes, and the test hooks (last_*_grid, last_line_fused).
-int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, StepPub& pub) {
+// What the stages of one step share: the plan they carry out and where they enqueue.
+struct StepEnq {
+    stvo_seq* s;
+    stvo_ctx* ctx;
+    const stvo::StepPlan& p;
+    hipEvent_t* tev;     // live stage timing: STVO_SEQ_NSTAGE event pairs of this step (see stvo_seq_get_stage_timing), or nullptr
+    hipStream_t st, sl;  // the point stream, and the stream of the line stage
+    const stvo::SeqDev& d;
+    stvo_seq::Set &cs, &ps;  // the stereo sets the step builds / tracks against
+    int32_t* m12l_use;       // the copy of the key-line match indices of this step
+    void mark(int k, hipStream_t q) const {
+        if (tev && !(p.light && k < 2)) (void)hipEventRecord(tev[k], q);
+    }
+    int point_stage(stvo::GridBatch& g) const;
+    int line_stage() const;
+    int f2f_and_join() const;
+    int pose(StepPub& pub) const;
+};
+
+// The arguments of the stereo point matcher, up to what the plan decides (lean_cells, has_tail, fused_cells).
+stvo::GridBatch point_grid_args(const stvo_seq* s, const stvo::SeqDev& d) {
+    const int K = s->K;
+    stvo::GridBatch g;
+    std::memset(&g, 0, sizeof(g));
+    g.B = s->B; g.stride1 = K; g.stride2 = K; g.xy_width = 2; g.items_stride = K; g.words64 = K / 64; g.n1p = K;
+    g.cell_xy1 = d.pxy_l; g.d1 = d.desc_l; g.n1 = d.n_kp_l; g.cell_start = d.pstart; g.cell_items = d.pitems;
+    g.d2 = d.desc_r; g.n2 = d.n_kp_r; g.dir2 = nullptr;
+    g.w = stvo_grid_window{s->mp.matching_s_ws, 0, 0, 0};  // stereoFrame.cpp:141-143
+    g.ratio = s->ratio_grid; g.line_sim_th = 0.0; g.mutual = s->mp.best_lr_matches;
+    g.cover = s->cover; g.rank = d.prank; g.perm = d.pperm; g.top2 = s->top2; g.owner2 = s->owner2; g.m12 = s->m12s_p;
+    if (g.mutual) { g.elig = s->elig; g.elig_cnt = s->elig_cnt; g.ovf = s->govf; }
+    g.misfit = s->govf + s->B;
+    g.range_points = 1;  // device CSR: right key-points are numbered in cell order, one grid row per window
+    g.range1 = d.prange;
+    g.cell2 = d.pcell;
+    g.lstart = d.plstart; g.lperm = d.plperm;
+    return g;
+}
+
+// Everything plan_step reads.  The launch helpers are asked what they were asked before, each only where it was asked before.
+void gather_step_facts(const stvo_seq* s, int slot, const StepFlags& fl, bool timing_events, const stvo::GridBatch& g, stvo::StepFacts& f) {
+    f.B = s->B; f.K = s->K; f.M = s->M; f.cus = stvo::device_cu_count();
+    f.has_points = s->op.has_points; f.has_lines = s->op.has_lines; f.best_lr_matches = s->mp.best_lr_matches;
+    f.lines_now = fl.lines_now; f.lines_prev = fl.lines_prev; f.track = fl.track;
+    f.frame_idx = s->frame_idx;
+    f.raw_split = s->raw_split[slot]; f.raw_max_lines = s->raw_max_lines[slot];
+    f.set_lines_cap_prev = s->set_lines_cap[s->prev_set()]; f.set_lines_cap_cur = s->set_lines_cap[s->cur];
+    f.st_dirty = s->st_dirty; f.fetch = s->fetch; f.zero_copy = s->zero_copy;
+    f.timing = s->timing; f.timing_events = timing_events;
+    f.has_alt_m12l = s->m12l_alt != nullptr;
+    f.cells_differ = s->cells_buf[0].pstart != s->cells_buf[1].pstart;
+    f.grid_points_fused_ok = f.has_points && stvo::grid_points_fused_ok(g);
+    if (f.track) {
+        f.match_small_ok_K = stvo::match_small_ok(f.K); f.match_small_ok_M = stvo::match_small_ok(f.M);
+        f.pose_inline_sync_ok = stvo::pose_inline_sync_ok(f.B);
+        stvo::PoseArgs a{};  // what the two questions about the pose launch read of its arguments
+        std::memset(&a, 0, sizeof(a));
+        a.B = f.B; a.prev_rc = s->set[s->prev_set()].rc;
+        f.pose_batch_kernel_selected = stvo::pose_batch_kernel_selected(a);
+        f.pose_start_flag_ok = stvo::pose_start_flag_ok(a);
+        f.pose2p_waves_per_pair = f.pose_batch_kernel_selected ? stvo::pose2p_waves_per_pair(f.B) : 0;
+    }
+    f.sw = stvo::dbg();
+}
+
+// ---- stereo association of the key-points into set[cur]
+int StepEnq::point_stage(stvo::GridBatch& g) const {
+    const int B = s->B;
+    if (!p.point_stage) {
+        HIP_TRY(ctx, hipMemsetAsync(cs.n, 0, (size_t)B * 4, st));
+        return STVO_OK;
+    }
+    mark(0, st);
+    g.lean_cells = p.lean_cells;
+    g.has_tail = p.has_tail;
+    if (p.has_tail) g.tail = stvo::point_tail_args(d);
+    g.fused_cells = p.fused_cells;
+    if (p.lines_ahead) HIP_TRY(ctx, hipStreamWaitEvent(sl, s->ev_fork, 0));  // the PREVIOUS step's fork event
+    if (p.fused_cells)
+        g.cells = stvo::point_cells_args(d);
+    else if (p.lean_cells)
+        hipLaunchKernelGGL(stvo::point_cells_kernel<true>, dim3(B), dim3(256), 0, p.cells_ahead ? sl : st, d);
+    else
+        hipLaunchKernelGGL(stvo::point_cells_kernel<false>, dim3(B), dim3(256), 0, st, d);
+    if (p.cells_ahead) {
+        HIP_TRY(ctx, hipEventRecord(s->ev_cells, sl));
+        HIP_TRY(ctx, hipStreamWaitEvent(st, s->ev_cells, 0));
+    }
+    // light timing: the matcher's start stamp in FRONT of the fork — a barrier packet between the fork and the matcher would give the
+    // key-line kernels a head start on the CUs, which the untimed step does not give them (first GPU call of round 6: 0.226 ms
+    // instead of the timed region's 0.139)
+    hipEvent_t gev_light[2] = {nullptr, tev ? tev[3] : nullptr};
+    if (p.light) (void)hipEventRecord(tev[2], st);
+    if (p.mid_fork) {
+        HIP_TRY(ctx, hipEventRecord(s->ev_fork, st));
+        if (!p.lines_ahead) HIP_TRY(ctx, hipStreamWaitEvent(sl, s->ev_fork, 0));
+        if (p.gate) stvo::launch_stream_gate(sl, s->d_pose_flag, s->pose_flag_value);
+    }
+    s->last_point_grid = g;
+    stvo::launch_grid_batch(st, g, false, tev ? (p.light ? gev_light : tev + 2) : nullptr);
+    if (!p.has_tail) hipLaunchKernelGGL(stvo::point_tail_kernel, dim3(B), dim3(stvo::TAIL_BLOCK), 0, st, d);
+    mark(1, st);
+    return STVO_OK;
+}
+
+// ---- stereo association of the key-lines into set[cur]
+int StepEnq::line_stage() const {
+    const int B = s->B, M = s->M;
+    if (p.line_stage) {
+        stvo::GridBatch g;
+        std::memset(&g, 0, sizeof(g));
+        g.B = B; g.stride1 = M; g.stride2 = M; g.xy_width = 4; g.items_stride = M * stvo::LENT; g.words64 = M / 64; g.n1p = M;
+        g.cell_xy1 = d.lxy_l; g.d1 = d.ldesc_l; g.n1 = d.n_kl_l; g.cell_start = d.lstart; g.cell_items = d.litems;
+        g.d2 = d.ldesc_r; g.n2 = d.n_kl_r; g.dir2 = d.ldir;
+        g.w = stvo_grid_window{s->mp.matching_s_ws, 0, 0, 0};  // :340-342
+        g.ratio = s->ratio_grid /* sic, minRatio12P: matching.cpp:241 */; g.line_sim_th = s->mp.line_sim_th;
+        g.mutual = s->mp.best_lr_matches;
+        g.cover = s->cover_l; g.rank = d.lrank; g.perm = d.lperm; g.top2 = s->top2_l; g.owner2 = s->owner2_l; g.m12 = s->m12s_l;
+        if (g.mutual) { g.elig = s->elig_l; g.elig_cnt = s->elig_cnt_l; g.ovf = s->govf_l; }
+        s->last_line_grid = g;
+        s->set_lines_cap[s->cur] = p.Mk;
+        s->last_line_fused = p.line_fused;
+        if (p.line_fused) {
+            // (one wave per frame, <64>: 185 instead of 150 us beside the key-point scan, which it stretched by 15 us more)
+            hipLaunchKernelGGL(stvo::line_stereo_fused_kernel<256>, dim3(B), dim3(256), p.line_lds, sl, d, p.Mk, (int)s->mp.best_lr_matches, s->ratio_grid);
+        } else {
+            hipLaunchKernelGGL(stvo::line_cells_kernel, dim3(B), dim3(256), 0, sl, d);
+            stvo::launch_grid_batch(sl, g, true);
+            hipLaunchKernelGGL(stvo::line_tail_kernel, dim3(B), dim3(256), 0, sl, d);
+        }
+    } else if (p.clear_nl) {
+        HIP_TRY(ctx, hipMemsetAsync(cs.nl, 0, (size_t)B * 4, st));
+    }
+    return STVO_OK;
+}
+
+// ---- f2fTracking: prev stereo sets vs curr stereo sets, then the line stream joins (or signals) and the match indices leave for the host
+int StepEnq::f2f_and_join() const {
+    const int B = s->B;
+    auto match_set = [&](const stvo::MatchPlan& m, hipStream_t q, const stvo::LazyScratch& ws, int stride, const uint8_t* da, const int32_t* na,
+                         const uint8_t* db, const int32_t* nb, float nnr, int32_t* m12, hipEvent_t* mev) {
+        if (m.route == stvo::MatchRoute::SMALL) {
+            stvo::launch_match_small(q, B, stride, da, na, db, nb, nnr, s->mp.best_lr_matches, m12, m.small_cap);
+        } else if (m.route == stvo::MatchRoute::BOTH_DIRS) {
+            const int nseg = std::min(m.nseg_cap, stvo::knn_pick_nseg(B, stride, ws.knn_capacity));
+            stvo::launch_hamming_knn2(q, B, stride, stride, da, na, db, nb, ws.knn12, ws.knn21, 1, 0, 0, nullptr, nullptr, nseg);
+            stvo::launch_nnr_mutual(q, B, stride, ws.knn12, ws.knn21, na, nb, nnr, 1, m12, nseg);
+        } else if (m.route == stvo::MatchRoute::LAZY) {
+            stvo::launch_match_mutual_lazy(q, B, stride, da, na, db, nb, nnr, ws, m12, 0, nullptr, mev);
+        } else {
+            const int nseg = stvo::knn_pick_nseg(B, stride, ws.knn_capacity);
+            stvo::launch_hamming_knn2(q, B, stride, stride, da, na, db, nb, ws.knn12, ws.knn21, 0, 0, 0, nullptr, nullptr, nseg);
+            stvo::launch_nnr_mutual(q, B, stride, ws.knn12, ws.knn21, na, nb, nnr, 0, m12, nseg);
+        }
+    };
+    if (p.track) {
+        const stvo::LazyScratch w{ctx->knn12, ctx->knn21, ctx->cand, ctx->need, ctx->qsel, ctx->nsel, ctx->knn_capacity};
+        hipEvent_t mev_light[4] = {tev ? tev[4] : nullptr, tev ? tev[5] : nullptr, nullptr, nullptr};  // (light: no pair around plan + reverse scans)
+        if (p.point_stage)
+            match_set(p.match_points, st, w, s->K, ps.desc, ps.n, cs.desc, cs.n, s->mp.min_ratio_12_p, s->m12p, tev ? (p.light ? mev_light : tev + 4) : nullptr);
+        if (p.match_lines_run)
+            match_set(p.match_lines, sl, s->lazy_l, s->M, ps.ldesc, ps.nl, cs.ldesc, cs.nl, s->mp.min_ratio_12_l, m12l_use, nullptr);
+        if (p.clear_m12l) HIP_TRY(ctx, hipMemsetAsync(m12l_use, 0xFF, (size_t)B * s->M * sizeof(int32_t), st));
+    }
+    if (p.join_signal) {
+        stvo::launch_stream_signal(sl, s->d_join_flag, ++s->join_epoch);
+    } else if (p.par) {  // join before optimizePose; first frame: nothing to track, but the main stream must still see the line stage's results
+        HIP_TRY(ctx, hipEventRecord(s->ev_join, sl));
+        HIP_TRY(ctx, hipStreamWaitEvent(st, s->ev_join, 0));
+    }
+    if (p.fetch_copy) {
+        stvo::launch_copy16(st, s->m12s_p, s->fetch_host, s->m12_span);
+        HIP_TRY(ctx, hipEventRecord(s->ev_fetch, st));
+    }
+    return STVO_OK;
+}
+
+// ---- optimizePose
+int StepEnq::pose(StepPub& pub) const {
+    const int B = s->B;
+    stvo::PoseArgs a{};
+    std::memset(&a, 0, sizeof(a));
+    a.B = B; a.max_pts = s->K; a.max_lines = s->M;
+    a.n_prev_pts = s->op.has_points ? ps.n : nullptr;
+    a.prev_rc = ps.rc; a.curr_rc = cs.rc; a.q_tab = s->d_qtab; a.level_scale = s->mp.orb_scale_factor; a.m12p = s->m12p;
+    a.n_prev_lines = s->op.has_lines ? ps.nl : nullptr;
+    a.prev_sP = ps.sP; a.prev_eP = ps.eP; a.prev_spl = ps.spl; a.prev_epl = ps.epl; a.prev_s2l = ps.s2lm;
+    a.curr_le = cs.le; a.m12l = m12l_use;
+    a.cams = s->d_cams; a.prm = s->op;
+    a.init_T = s->d_motion_T; a.next_T = s->d_motion_T;  // (nullptr: DT = I, use_motion_model = false)
+    a.results = s->zero_copy ? reinterpret_cast<stvo_pose_result*>(s->out_host) : s->results;
+    a.inl_p_out = s->inlp; a.inl_l_out = s->inll;
+    if (p.inl_zero_copy) {
+        a.inl_p_out = reinterpret_cast<int32_t*>(s->fetch_host + s->m12_span);
+        a.inl_l_out = reinterpret_cast<int32_t*>(s->fetch_host + s->m12_span + (reinterpret_cast<const char*>(s->inll) - reinterpret_cast<const char*>(s->inlp)));
+    }
+    if (stvo::dbg().pose_prof != stvo::DBG_UNSET) {  // (a developer's buffer, not a schedule)
+        if (!s->d_prof) HIP_TRY(ctx, hipMalloc((void**)&s->d_prof, (size_t)B * 16 * sizeof(long long)));
+        a.prof_out = s->d_prof;
+    }
+    if (p.join_signal) {
+        a.wait_flag = s->d_join_flag;
+        a.wait_value = s->join_epoch;
+    }
+    a.lazy_eig = p.lazy_eig ? 1 : 0;
+    if (p.fetch_by_pose) {
+        a.fetch_src = reinterpret_cast<const uint4*>(s->m12s_p);
+        a.fetch_dst = reinterpret_cast<uint4*>(s->fetch_host);
+        a.fetch_n16 = (unsigned)(s->m12_span / 16);
+        a.fetch_flag = reinterpret_cast<unsigned*>(s->fetch_host + s->m12_span + s->inl_span);
+        a.fetch_value = pub.fetch_value = ++s->fetch_epoch;
+    }
+    if (p.pose_flagged) {
+        a.start_flag = s->d_pose_flag;
+        a.start_value = pub.pose_flag_value = ++s->pose_epoch;
+    }
+    mark(8, st);
+    TRY(stvo::launch_pose(st, a));
+    mark(9, st);
+    if (p.inl_copy) stvo::launch_copy16(st, s->inlp, s->fetch_host + s->m12_span, s->inl_span);
+    return STVO_OK;
+}
+
+// Enqueues the kernel chain of one step on the context's stream and the line stream; returns the step's plan and, in `pub`, the flag
+// values it handed out.  Of the state of `s` it changes only: the counters the three flags' values are drawn from (pose_epoch, join_epoch,
+// fetch_epoch) — a value handed to a launch may reach the device even when a later launch of the step fails, so it is never handed out
+// twice (which is why the planner draws none); later steps wait only for what stvo_seq_step_dev commits —, the key-line capacity of the
+// set it builds (set_lines_cap[cur]), the stage-timing events it takes, and the test hooks (last_*_grid, last_line_fused).
+// The stream operations are those of the step before the planner existed, in the same order.  The queries that enqueue nothing — the
+// LDS opt-ins behind grid_points_fused_ok and plan_step's lds_fits (hipGetDevice, and hipFuncSetAttribute the first time), the CU
+// count — are the same ones, made under the same conditions, but all in front of the first stream operation instead of between them.
+int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, stvo::StepPlan& plan, StepPub& pub) {
     stvo_ctx* ctx = s->ctx;
-    const int B = s->B, K = s->K, M = s->M;
-    hipStream_t st = ctx->stream;
     // live stage timing: STVO_SEQ_NSTAGE event pairs per step (see stvo_seq_get_stage_timing)
     hipEvent_t* tev = nullptr;
     if (s->timing) {
@@ -1176,290 +1393,37 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, StepPub& pub) {
             s->tev_used += 2 * STVO_SEQ_NSTAGE;
         }
     }
-    // light timing (stvo_seq_set_stage_timing(.., 2)): event pairs around the grid matcher, the forward scan and the pose kernel only, on
-    // the point stream; the key-line stream runs unmarked and the next frame's grid is still built ahead on it, so the three kernels
-    // keep the neighbours they have in an untimed step (bench.py: `roofline` must come from the region that produced `value`)
-    const bool light = tev && s->timing == 2;
-    auto mark = [&](int k, hipStream_t q) {
-        if (tev && !(light && k < 2)) (void)hipEventRecord(tev[k], q);
-    };
     pub = StepPub{};
-    // two copies of the key-line match indices, by the parity of the step (batches without the by-product fetch, whose copies read the
-    // first): with the key-line stage ahead, the matches of step k + 1 may be written while optimizePose(k) reads those of step k
-    const bool alt_ok = s->m12l_alt != nullptr && !s->fetch;
-    int32_t* const m12l_use = (alt_ok && (s->frame_idx & 1)) ? s->m12l_alt : s->m12l;
-    // ---- stereo association of the new frame into set[cur]
+    // ---- gather: the step's arrays, then the facts
     stvo_seq::Set& cs = s->set[s->cur];
-    stvo_seq::Set& ps = s->set[s->prev_set()];
     stvo::SeqDev d = s->d;
     bind_raw(s, d, slot);
     d.rc = cs.rc; d.desc = cs.desc; d.n = cs.n;
     d.spl = cs.spl; d.epl = cs.epl; d.sP = cs.sP; d.eP = cs.eP; d.le = cs.le; d.s2l = cs.s2l; d.s2lm = cs.s2lm;
     d.ldesc = cs.ldesc; d.nl = cs.nl;
-    const size_t res_bytes = (size_t)B * sizeof(stvo_pose_result);
+    const size_t res_bytes = (size_t)s->B * sizeof(stvo_pose_result);
     d.host_n = s->zero_copy ? reinterpret_cast<int32_t*>(s->out_host + res_bytes) : nullptr;
-    d.host_nl = s->zero_copy ? reinterpret_cast<int32_t*>(s->out_host + res_bytes + (size_t)B * 4) : nullptr;
-    // a frame without key-lines skips the whole line stage (7 launches) and, below, the f2f line matching (6)
-    const bool lines_now = fl.lines_now, lines_prev = fl.lines_prev;
-    // fork: everything enqueued so far (ingest, the previous step) happens-before the line stream's work
-    const bool par = lines_now && s->op.has_points;
-    hipStream_t sl = par ? s->line_stream : st;
-    // Where the line stream forks off.  Every big kernel of the point stream fills the register file of the CUs it runs on, so work
-    // of the line stream never runs BESIDE it, only instead of it.  Forked at the start of the step (small batches) the line kernels
-    // share the GPU with point_cells_kernel and delay the start of some of the persistent point matcher's workgroups (0.158 -> 0.198 ms
-    // per 1024 frames) but leave the key-point scan alone (0.467 ms); forked after the point stage (measured, then removed) they
-    // stretched the scan instead (0.510 ms): 1024 KITTI-shaped streams 929 k (start) vs 935 k (after) frame pairs/s, 512 EuRoC-shaped
-    // streams 857 k vs 777 k, one stream 0.252 vs 0.280 ms per frame.
-    // Round 5: behind the cells kernel (mid), the default for batches: the line kernels then become ready together with the
-    // persistent point matcher, whose workgroups (already queued) take their CUs first, instead of finding four line workgroups per CU
-    // in their way.  1024 KITTI-shaped streams 0.872 -> 0.853 ms per step, 512 EuRoC-shaped 1.036 -> 1.105 M frame pairs/s; one
-    // stream is SLOWER that way (0.205 -> 0.211 ms: its line kernels lose their head start), so small batches keep the fork at the start.
-    const bool mid_fork = par && B >= 64;
-    const bool fork_free = par && s->raw_split[slot] && !s->st_dirty;  // see stvo_seq::st_dirty
-    pub.line_forked = par && (mid_fork || !fork_free);
-    pub.schedule[STVO_SCHED_MID_FORK] = mid_fork ? 1 : 0;
-    if (par && !mid_fork && !fork_free) {
-        HIP_TRY(ctx, hipEventRecord(s->ev_fork, st));
-        HIP_TRY(ctx, hipStreamWaitEvent(sl, s->ev_fork, 0));
+    d.host_nl = s->zero_copy ? reinterpret_cast<int32_t*>(s->out_host + res_bytes + (size_t)s->B * 4) : nullptr;
+    stvo::GridBatch g;
+    if (s->op.has_points) g = point_grid_args(s, d);
+    stvo::StepFacts facts;
+    gather_step_facts(s, slot, fl, tev != nullptr, g, facts);
+    // ---- plan
+    plan = stvo::plan_step(facts, s->hist, [](int lds) {
+        return stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::line_stereo_fused_kernel<256>), lds);
+    });
+    const stvo::StepPlan& p = plan;
+    // ---- enqueue
+    d.zero_nl = p.zero_nl ? 1 : 0;
+    const StepEnq e{s, ctx, p, tev, ctx->stream, p.par ? s->line_stream : ctx->stream, d, cs, s->set[s->prev_set()], p.use_alt_m12l ? s->m12l_alt : s->m12l};
+    if (p.fork_at_start) {
+        HIP_TRY(ctx, hipEventRecord(s->ev_fork, e.st));
+        HIP_TRY(ctx, hipStreamWaitEvent(e.sl, s->ev_fork, 0));
     }
-    d.zero_nl = (!lines_now && s->op.has_points) ? 1 : 0;
-    auto point_stage = [&]() -> int {
-        if (s->op.has_points) {
-            mark(0, st);
-            stvo::GridBatch g;
-            std::memset(&g, 0, sizeof(g));
-            g.B = B; g.stride1 = K; g.stride2 = K; g.xy_width = 2; g.items_stride = K; g.words64 = K / 64; g.n1p = K;
-            g.cell_xy1 = d.pxy_l; g.d1 = d.desc_l; g.n1 = d.n_kp_l; g.cell_start = d.pstart; g.cell_items = d.pitems;
-            g.d2 = d.desc_r; g.n2 = d.n_kp_r; g.dir2 = nullptr;
-            g.w = stvo_grid_window{s->mp.matching_s_ws, 0, 0, 0};  // stereoFrame.cpp:141-143
-            g.ratio = s->ratio_grid; g.line_sim_th = 0.0; g.mutual = s->mp.best_lr_matches;
-            g.cover = s->cover; g.rank = d.prank; g.perm = d.pperm; g.top2 = s->top2; g.owner2 = s->owner2; g.m12 = s->m12s_p;
-            if (g.mutual) { g.elig = s->elig; g.elig_cnt = s->elig_cnt; g.ovf = s->govf; }
-            g.misfit = s->govf + s->B;
-            g.range_points = 1;  // device CSR: right key-points are numbered in cell order, one grid row per window
-            g.range1 = d.prange;
-            g.cell2 = d.pcell;
-            g.lstart = d.plstart; g.lperm = d.plperm;
-            // the one-workgroup matcher: lean cells kernel in front, the tail of the association as its last phase
-            g.lean_cells = stvo::grid_points_fused_ok(g) ? 1 : 0;
-            g.has_tail = g.lean_cells;
-            if (stvo::dbg().grid_tail == 0) g.has_tail = 0;  // developer: point_tail_kernel as its own launch
-            if (g.has_tail) g.tail = stvo::point_tail_args(d);
-            // one frame per workgroup of the matcher (single-stream operation, small batches): the grid of the frame is the matcher's
-            // first phase — one dependent launch less in the chain of a frame
-            g.fused_cells = g.lean_cells && B <= stvo::device_cu_count() && stvo::dbg().grid_cells != 0;
-            // Batches: the grid of this frame on the LINE stream, which has been idle since ~0.2 ms into the previous step — the kernel (38 us
-            // per 1024 frames; few instructions, mostly waiting) then runs beside the previous step's forward scan or pose kernel and
-            // the point stream meets it with one awaited event in front of the matcher.  Safe because (a) its outputs are double-buffered
-            // by the parity of the step (the matcher of the previous frame may still read the other copy; the copy written here was
-            // last read two steps ago, and the line stream's work of the previous step waited for an event the point stream recorded
-            // after that: sl_forked_frame), (b) the line stream has been made to wait for every upload enqueued on the point stream
-            // (stvo_seq_step_dev), (c) everything else the kernel reads is the resident slot.  STVO_CELLS_AHEAD=0: in the point stream.
-            const bool cells_ahead = mid_fork && g.lean_cells && !g.fused_cells && (!tev || light) &&
-                                     s->cells_buf[0].pstart != s->cells_buf[1].pstart && s->sl_forked_frame == (long long)s->frame_idx - 1 &&
-                                     stvo::dbg().cells_ahead != 0;
-            // key-line stage ahead (stvo_seq: fork_rec_frame): the line stream waits for the PREVIOUS step's fork event — in front of the
-            // cells kernel, whose output copy the matcher of two steps ago read — and not for this step's
-            // Only where it was measured to pay: ~100 key-lines per image (their kernels are a few per cent of the step) behind a pose kernel
-            // that publishes its start, i.e. the two-waves-per-pair batch kernel.  With hundreds of key-lines per image the line kernels are
-            // long enough to hold the pose kernel's freed slots against the next matcher: 512 EuRoC-shaped streams 0.442 -> 0.520 ms per step
-            // (round 6), so those keep the fork of their own step.  STVO_LINES_AHEAD=1 forces it wherever it is safe.
-            const int la_sw = stvo::dbg().lines_ahead;
-            const bool la_pays = s->pose_flag_frame == (long long)s->frame_idx - 1 && B > 2 * stvo::device_cu_count() &&
-                                 std::max(s->raw_max_lines[slot], s->set_lines_cap[s->prev_set()]) <= 128;
-            const bool lines_ahead = cells_ahead && alt_ok && s->fork_rec_frame == (long long)s->frame_idx - 1 && la_sw != 0 &&
-                                     (la_sw == 1 || la_pays);
-            pub.schedule[STVO_SCHED_FUSED_CELLS] = g.fused_cells ? 1 : 0;
-            pub.schedule[STVO_SCHED_CELLS_AHEAD] = cells_ahead ? 1 : 0;
-            pub.schedule[STVO_SCHED_LINES_AHEAD] = lines_ahead ? 1 : 0;
-            if (lines_ahead) HIP_TRY(ctx, hipStreamWaitEvent(sl, s->ev_fork, 0));
-            if (g.fused_cells)
-                g.cells = stvo::point_cells_args(d);
-            else if (g.lean_cells)
-                hipLaunchKernelGGL(stvo::point_cells_kernel<true>, dim3(B), dim3(256), 0, cells_ahead ? sl : st, d);
-            else
-                hipLaunchKernelGGL(stvo::point_cells_kernel<false>, dim3(B), dim3(256), 0, st, d);
-            if (cells_ahead) {
-                HIP_TRY(ctx, hipEventRecord(s->ev_cells, sl));
-                HIP_TRY(ctx, hipStreamWaitEvent(st, s->ev_cells, 0));
-            }
-            // light timing: the matcher's start stamp in FRONT of the fork — a barrier packet between the fork and the matcher would give the
-            // key-line kernels a head start on the CUs, which the untimed step does not give them (first GPU call of round 6: 0.226 ms
-            // instead of the timed region's 0.139)
-            hipEvent_t gev_light[2] = {nullptr, tev ? tev[3] : nullptr};
-            if (light) (void)hipEventRecord(tev[2], st);
-            if (mid_fork) {
-                HIP_TRY(ctx, hipEventRecord(s->ev_fork, st));
-                pub.fork_recorded = true;
-                if (!lines_ahead)
-                    HIP_TRY(ctx, hipStreamWaitEvent(sl, s->ev_fork, 0));
-                else if (s->pose_flag_frame == (long long)s->frame_idx - 1) {  // the key-line kernels behind the dispatch of optimizePose(k - 1)
-                    stvo::launch_stream_gate(sl, s->d_pose_flag, s->pose_flag_value);
-                    pub.schedule[STVO_SCHED_GATE] = 1;
-                }
-            }
-            s->last_point_grid = g;
-            stvo::launch_grid_batch(st, g, false, tev ? (light ? gev_light : tev + 2) : nullptr);
-            if (!g.has_tail) hipLaunchKernelGGL(stvo::point_tail_kernel, dim3(B), dim3(stvo::TAIL_BLOCK), 0, st, d);
-            mark(1, st);
-        } else {
-            HIP_TRY(ctx, hipMemsetAsync(cs.n, 0, (size_t)B * 4, st));
-        }
-        return STVO_OK;
-    };
-    auto line_stage = [&]() -> int {
-        if (lines_now) {
-            stvo::GridBatch g;
-            std::memset(&g, 0, sizeof(g));
-            g.B = B; g.stride1 = M; g.stride2 = M; g.xy_width = 4; g.items_stride = M * stvo::LENT; g.words64 = M / 64; g.n1p = M;
-            g.cell_xy1 = d.lxy_l; g.d1 = d.ldesc_l; g.n1 = d.n_kl_l; g.cell_start = d.lstart; g.cell_items = d.litems;
-            g.d2 = d.ldesc_r; g.n2 = d.n_kl_r; g.dir2 = d.ldir;
-            g.w = stvo_grid_window{s->mp.matching_s_ws, 0, 0, 0};  // :340-342
-            g.ratio = s->ratio_grid /* sic, minRatio12P: matching.cpp:241 */; g.line_sim_th = s->mp.line_sim_th;
-            g.mutual = s->mp.best_lr_matches;
-            g.cover = s->cover_l; g.rank = d.lrank; g.perm = d.lperm; g.top2 = s->top2_l; g.owner2 = s->owner2_l; g.m12 = s->m12s_l;
-            if (g.mutual) { g.elig = s->elig_l; g.elig_cnt = s->elig_cnt_l; g.ovf = s->govf_l; }
-            s->last_line_grid = g;
-            // few key-lines per frame: the whole association in one workgroup per frame (STVO_LINE_FUSED=0: the general grid matcher)
-            // LDS for the lines the slot holds, not for the capacity
-            const int Mk = std::min(M, std::max(64, (s->raw_max_lines[slot] + 63) & ~63));
-            s->set_lines_cap[s->cur] = Mk;
-            const size_t lds = (size_t)Mk * stvo::LSF_BYTES_PER_LINE + 4 + (size_t)Mk * (Mk / 32) * 4;
-            const int ef = stvo::dbg().line_fused;
-            // (a single stream with hundreds of key-lines is better off with the general matcher's many small workgroups: EuRoC-shaped,
-            // 300 key-lines, one stream 0.310 vs 0.360 ms per frame; 102 key-lines 0.257 vs 0.252)
-            s->last_line_fused = M <= stvo::LSF_MAX_LINES && (ef != stvo::DBG_UNSET ? ef != 0 : (B >= 16 || Mk <= 128)) &&
-                                 (lds <= (48u << 10) || stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::line_stereo_fused_kernel<256>), (int)lds));
-            pub.schedule[STVO_SCHED_LINE_FUSED] = s->last_line_fused ? 1 : 0;
-            if (s->last_line_fused) {
-                // (one wave per frame, <64>: 185 instead of 150 us beside the key-point scan, which it stretched by 15 us more)
-                hipLaunchKernelGGL(stvo::line_stereo_fused_kernel<256>, dim3(B), dim3(256), lds, sl, d, Mk, (int)s->mp.best_lr_matches, s->ratio_grid);
-            } else {
-                hipLaunchKernelGGL(stvo::line_cells_kernel, dim3(B), dim3(256), 0, sl, d);
-                stvo::launch_grid_batch(sl, g, true);
-                hipLaunchKernelGGL(stvo::line_tail_kernel, dim3(B), dim3(256), 0, sl, d);
-            }
-        } else if (!d.zero_nl) {
-            HIP_TRY(ctx, hipMemsetAsync(cs.nl, 0, (size_t)B * 4, st));
-        }
-        return STVO_OK;
-    };
-    TRY(point_stage());
-    TRY(line_stage());
-    const bool track = fl.track;
-    if (track) {
-        // ---- f2fTracking: prev stereo sets vs curr stereo sets
-        const stvo::LazyScratch w{ctx->knn12, ctx->knn21, ctx->cand, ctx->need, ctx->qsel, ctx->nsel, ctx->knn_capacity};
-        const int esm = stvo::dbg().match_small;  // developer: 0 = the general machinery for the key-line sets too
-        const int lines_cap = std::max(s->set_lines_cap[s->cur], s->set_lines_cap[s->prev_set()]);
-        // one workgroup per frame pair (match_small_kernel) up to 128 key-lines per image; beyond that its row-by-row scan is the
-        // longest thing on the key-line stream and the general machinery (K1m + planned reverse check, five launches) wins for every
-        // batch size: 512 EuRoC-shaped streams with ~250 key-lines 844 k -> 913 k frame pairs/s (both directions in one K1m launch +
-        // one ratio / mutual kernel: 895 k), one such stream 0.360 -> 0.310 ms (round 3)
-        const bool small_sets = esm != stvo::DBG_UNSET ? esm != 0 : lines_cap <= 128;
-        const bool elz = stvo::dbg().match_lazy == 1;  // developer: the lazy formulation for small batches too
-        int small_cap = 0;  // rows per set the small-set kernel sizes its LDS for (0: the stride)
-        auto match_set = [&](hipStream_t q, const stvo::LazyScratch& ws, int stride, const uint8_t* da, const int32_t* na,
-                             const uint8_t* db, const int32_t* nb, float nnr, int32_t* m12, hipEvent_t* mev) {
-            if (stvo::match_small_ok(stride) && small_sets && !mev) {  // (mev: the stage timers want the general launches)
-                stvo::launch_match_small(q, B, stride, da, na, db, nb, nnr, s->mp.best_lr_matches, m12, small_cap);
-            } else if (s->mp.best_lr_matches && B <= 4 && !mev && !elz) {
-                // a few frame pairs leave most of the GPU idle: the reverse direction as a full scan in the SAME launch and one
-                // ratio / mutual kernel, instead of the plan + two selective reverse scans + final check of the lazy formulation
-                // (five dependent launches: 42 -> ~18 us of a single stream's 230 us)
-                // (four train segments, not the 16 a single direction gets: both directions already double the workgroups, and the
-                // ratio / mutual kernel merges 2 x nseg partial keys per row — one stream 0.2465 -> 0.2357 ms)
-                const int nseg = std::min(4, stvo::knn_pick_nseg(B, stride, ws.knn_capacity));
-                stvo::launch_hamming_knn2(q, B, stride, stride, da, na, db, nb, ws.knn12, ws.knn21, 1, 0, 0, nullptr, nullptr, nseg);
-                stvo::launch_nnr_mutual(q, B, stride, ws.knn12, ws.knn21, na, nb, nnr, 1, m12, nseg);
-            } else if (s->mp.best_lr_matches) {
-                stvo::launch_match_mutual_lazy(q, B, stride, da, na, db, nb, nnr, ws, m12, 0, nullptr, mev);
-            } else {
-                const int nseg = stvo::knn_pick_nseg(B, stride, ws.knn_capacity);
-                stvo::launch_hamming_knn2(q, B, stride, stride, da, na, db, nb, ws.knn12, ws.knn21, 0, 0, 0, nullptr, nullptr, nseg);
-                stvo::launch_nnr_mutual(q, B, stride, ws.knn12, ws.knn21, na, nb, nnr, 0, m12, nseg);
-            }
-        };
-        hipEvent_t mev_light[4] = {tev ? tev[4] : nullptr, tev ? tev[5] : nullptr, nullptr, nullptr};  // (light: no pair around plan + reverse scans)
-        if (s->op.has_points) match_set(st, w, K, ps.desc, ps.n, cs.desc, cs.n, s->mp.min_ratio_12_p, s->m12p, tev ? (light ? mev_light : tev + 4) : nullptr);
-        small_cap = lines_cap;
-        if (lines_prev && lines_now)
-            match_set(sl, s->lazy_l, M, ps.ldesc, ps.nl, cs.ldesc, cs.nl, s->mp.min_ratio_12_l, m12l_use, nullptr);
-        else if (lines_prev)  // nothing to match against: every prev line is unmatched
-            HIP_TRY(ctx, hipMemsetAsync(m12l_use, 0xFF, (size_t)B * M * sizeof(int32_t), st));
-        // Small batches (single-stream operation): the pose kernel itself waits for the line stream and hands the match indices to
-        // the host — an event awaited or recorded in front of it delays its start by ~6 us each on this runtime.
-        const bool inline_sync = stvo::pose_inline_sync_ok(B) && stvo::dbg().seq_inline != 0 && !tev && (!s->fetch || (B == 1 && s->zero_copy));
-        if (par && inline_sync) {
-            stvo::launch_stream_signal(sl, s->d_join_flag, ++s->join_epoch);
-        } else if (par) {  // join before optimizePose
-            HIP_TRY(ctx, hipEventRecord(s->ev_join, sl));
-            HIP_TRY(ctx, hipStreamWaitEvent(st, s->ev_join, 0));
-        }
-        pub.fetch_by_pose = s->fetch && inline_sync;
-        if (s->fetch && !inline_sync) {
-            stvo::launch_copy16(st, s->m12s_p, s->fetch_host, s->m12_span);
-            HIP_TRY(ctx, hipEventRecord(s->ev_fetch, st));
-        }
-        // ---- optimizePose
-        stvo::PoseArgs a{};
-        std::memset(&a, 0, sizeof(a));
-        a.B = B; a.max_pts = K; a.max_lines = M;
-        a.n_prev_pts = s->op.has_points ? ps.n : nullptr;
-        a.prev_rc = ps.rc; a.curr_rc = cs.rc; a.q_tab = s->d_qtab; a.level_scale = s->mp.orb_scale_factor; a.m12p = s->m12p;
-        a.n_prev_lines = s->op.has_lines ? ps.nl : nullptr;
-        a.prev_sP = ps.sP; a.prev_eP = ps.eP; a.prev_spl = ps.spl; a.prev_epl = ps.epl; a.prev_s2l = ps.s2lm;
-        a.curr_le = cs.le; a.m12l = m12l_use;
-        a.cams = s->d_cams; a.prm = s->op;
-        a.init_T = s->d_motion_T; a.next_T = s->d_motion_T;  // (nullptr: DT = I, use_motion_model = false)
-        a.results = s->zero_copy ? reinterpret_cast<stvo_pose_result*>(s->out_host) : s->results;
-        a.inl_p_out = s->inlp; a.inl_l_out = s->inll;
-        // small batches with the by-product fetch on (the StereoFrameHandler mirror): the pose kernel writes the inlier masks straight
-        // into the pinned block — like its result — instead of a copy kernel behind it (one launch less on the single-stream chain)
-        const bool inl_zero_copy = s->fetch && s->zero_copy;
-        if (inl_zero_copy) {
-            a.inl_p_out = reinterpret_cast<int32_t*>(s->fetch_host + s->m12_span);
-            a.inl_l_out = reinterpret_cast<int32_t*>(s->fetch_host + s->m12_span + (reinterpret_cast<const char*>(s->inll) - reinterpret_cast<const char*>(s->inlp)));
-        }
-        if (stvo::dbg().pose_prof != stvo::DBG_UNSET) {
-            if (!s->d_prof) HIP_TRY(ctx, hipMalloc((void**)&s->d_prof, (size_t)B * 16 * sizeof(long long)));
-            a.prof_out = s->d_prof;
-        }
-        if (par && inline_sync) {
-            a.wait_flag = s->d_join_flag;
-            a.wait_value = s->join_epoch;
-        }
-        // single-stream operation: the eigenvalues of the committed covariance (an output only) are computed by stvo_seq_read
-        a.lazy_eig = (inline_sync && s->zero_copy && stvo::dbg().pose_kernel != 4) ? 1 : 0;
-        if (pub.fetch_by_pose) {
-            a.fetch_src = reinterpret_cast<const uint4*>(s->m12s_p);
-            a.fetch_dst = reinterpret_cast<uint4*>(s->fetch_host);
-            a.fetch_n16 = (unsigned)(s->m12_span / 16);
-            a.fetch_flag = reinterpret_cast<unsigned*>(s->fetch_host + s->m12_span + s->inl_span);
-            a.fetch_value = pub.fetch_value = ++s->fetch_epoch;
-        }
-        // batches on the batch kernel: the key-line stage of the next step may wait for this launch to begin
-        if (s->m12l_alt != nullptr && stvo::pose_start_flag_ok(a)) {
-            a.start_flag = s->d_pose_flag;
-            a.start_value = pub.pose_flag_value = ++s->pose_epoch;
-            pub.pose_flagged = true;
-        }
-        pub.schedule[STVO_SCHED_POSE_KERNEL] = stvo::pose_batch_kernel_selected(a) ? STVO_SCHED_POSE_BATCH : STVO_SCHED_POSE_LATENCY;
-        pub.schedule[STVO_SCHED_POSE_WAVES] = stvo::pose_batch_kernel_selected(a) ? stvo::pose2p_waves_per_pair(a.B) : 0;
-        mark(8, st);
-        TRY(stvo::launch_pose(st, a));
-        mark(9, st);
-        if (s->fetch && !inl_zero_copy) stvo::launch_copy16(st, s->inlp, s->fetch_host + s->m12_span, s->inl_span);
-    } else {
-        if (par) {  // first frame: nothing to track, but the main stream must still see the line stage's results
-            HIP_TRY(ctx, hipEventRecord(s->ev_join, sl));
-            HIP_TRY(ctx, hipStreamWaitEvent(st, s->ev_join, 0));
-        }
-        if (s->fetch) {
-            stvo::launch_copy16(st, s->m12s_p, s->fetch_host, s->m12_span);
-            HIP_TRY(ctx, hipEventRecord(s->ev_fetch, st));
-        }
-    }
+    TRY(e.point_stage(g));
+    TRY(e.line_stage());
+    TRY(e.f2f_and_join());
+    if (p.track) TRY(e.pose(pub));
     return check_launch(ctx);
 }
 
@@ -1482,18 +1446,15 @@ int stvo_seq_step_dev(stvo_seq* s, int slot) {
             s->upload_seen = s->upload_seq;
         }
     }
+    stvo::StepPlan plan;
     StepPub pub;
-    TRY(seq_enqueue_step(s, slot, fl, pub));
+    TRY(seq_enqueue_step(s, slot, fl, plan, pub));
     // the whole step is enqueued: what it published
-    if (pub.fork_recorded) s->fork_rec_frame = s->frame_idx;
-    if (pub.pose_flagged) {
-        s->pose_flag_frame = s->frame_idx;
-        s->pose_flag_value = pub.pose_flag_value;
-    }
-    if (pub.line_forked) s->sl_forked_frame = s->frame_idx;
-    s->fetch_by_pose = pub.fetch_by_pose;
+    stvo::commit(s->hist, plan, s->frame_idx);
+    if (plan.pose_flagged) s->pose_flag_value = pub.pose_flag_value;
+    s->fetch_by_pose = plan.fetch_by_pose;
     s->fetch_value = pub.fetch_value;
-    std::memcpy(s->last_schedule, pub.schedule, sizeof(s->last_schedule));
+    std::memcpy(s->last_schedule, plan.schedule, sizeof(s->last_schedule));
     s->st_dirty = true;
     s->set_lines[s->cur] = fl.lines_now;
     s->last_lines = fl.lines_now;

@@ -485,3 +485,82 @@ def test_seq_steps_back_to_back_schedules_agree(switches):
         res, counts = run(env, False)
         assert np.array_equal(counts, ref_counts), name
         assert res.tobytes() == ref_res.tobytes(), name
+
+
+_SMALL_BATCH = dict(streams=[], cams=[], pushed={})   # streams b = 0, 1, ... and B -> (results, counts) of the last frame pushed
+
+
+def _small_batch_streams(B):
+    from concurrent.futures import ThreadPoolExecutor
+    n0 = len(_SMALL_BATCH["streams"])
+    if B > n0:
+        with ThreadPoolExecutor(16) as ex:   # numpy's generators run outside the GIL
+            _SMALL_BATCH["streams"] += list(ex.map(
+                lambda b: synth.make_config5_sequence(b % 8, n_frames=4, n_pts=300, n_lines=40, replica=3000 + b // 8), range(n0, B)))
+        _SMALL_BATCH["cams"] += [synth.config5_cam(b % 8) for b in range(n0, B)]
+    return _SMALL_BATCH["streams"][:B], _SMALL_BATCH["cams"][:B]
+
+
+@pytest.mark.parametrize("size,timing", [("1", 0), ("17", 0), ("64", 0), ("CUs+1", 0), ("CUs+1", 1)],
+                         ids=["B1", "B17", "B64", "CUs+1", "CUs+1-stage-timing"])
+def test_seq_small_batch_schedule_record(size, timing):
+    """The schedule record (Sequences.last_schedule) of every step at the batch sizes below two streams per CU, on default switches,
+    against values written down from the rules of csrc/step_plan.h: 512 key-point and 64 key-line capacities, ~300 key-points and ~40
+    key-lines per image, four steps enqueued back to back.  The rules:
+      * the key-line stream forks behind the cells kernel from 64 streams on;
+      * the grid is the point matcher's first phase up to one frame per CU; beyond that it is its own launch, and from the second
+        step on (the first one that follows a step in which the line stream was forked) it is built ahead on the key-line stream —
+        unless every stage is timed;
+      * the key-line stage never runs ahead (needs more than two streams per CU), so no gate either;
+      * at most 64 key-lines per image: the one-workgroup stereo line matcher at every batch size;
+      * no pose kernel in the first step; then the latency kernel up to 256 frame pairs, the batch kernel beyond, on four waves per pair
+        (two only beyond two pairs per CU).
+    The last step's results and counts equal, bit for bit, those of the same frames pushed one at a time."""
+    import torch
+    from stvo_amd import capi
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    B = cus + 1 if size == "CUs+1" else int(size)
+    streams, cams = _small_batch_streams(B)
+    mp = match_params("kitti"); op = opt_params("kitti")
+    ctx = capi.Context(device_id=0, max_rows=512, max_batch=B)
+    try:
+        if B not in _SMALL_BATCH["pushed"]:
+            ref = capi.Sequences(ctx, B, 512, 64, cams, mp, op)
+            try:
+                for k in range(4):
+                    out = ref.push([st[k] for st in streams])
+            finally:
+                ref.close()
+            _SMALL_BATCH["pushed"][B] = (out[0].copy(), out[1].copy())
+        dev = capi.Sequences(ctx, B, 512, 64, cams, mp, op)
+        try:
+            dev.set_slots(4)
+            if timing:
+                dev.set_stage_timing(timing)
+            for k in range(4):
+                dev.upload(k, [st[k] for st in streams])
+            got = []
+            for k in range(4):
+                dev.step_dev(k)
+                got.append(dev.last_schedule())
+            res, counts = dev.read()
+        finally:
+            dev.close()
+    finally:
+        ctx.close()
+    # 256 = POSE_LATENCY_MAX_B (csrc/pose_kernel.hip), a constant of the library and not the CU count: on a 256-CU device the CUs + 1 case
+    # crosses the fused_cells threshold and this one together
+    batch_pose = B > 256
+    for k, sch in enumerate(got):
+        exp = dict(mid_fork=1 if B >= 64 else 0,
+                   fused_cells=1 if B <= cus else 0,
+                   cells_ahead=1 if (B >= 64 and B > cus and k >= 1 and timing != 1) else 0,
+                   lines_ahead=0, gate=0, line_fused=1,
+                   pose_kernel=0 if k == 0 else (capi.SCHED_POSE_BATCH if batch_pose else capi.SCHED_POSE_LATENCY),
+                   pose_waves=0 if (k == 0 or not batch_pose) else (2 if B > 2 * cus else 4))
+        print(f"[small batch] B {B} timing {timing} step {k}: {sch}")
+        assert sch == exp, (B, timing, k, sch, exp)
+    ref_res, ref_counts = _SMALL_BATCH["pushed"][B]
+    assert counts[:, 0].min() > 100 and counts[:, 1].max() > 0 and res["n_matched_ls"].max() > 0   # points and key-lines take part
+    assert np.array_equal(counts, ref_counts)
+    assert res.tobytes() == ref_res.tobytes()
