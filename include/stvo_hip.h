@@ -321,6 +321,36 @@ int stvo_fast_adapt_dev(stvo_ctx* ctx, int B, const stvo_pose_result* results_de
  * it and th_dev stays.  STVO_ERR_INVALID_ARG before the first step. */
 int stvo_seq_adapt_fast_dev(stvo_seq* seq, const stvo_fast_adapt* prm, int32_t* th_dev);
 
+/* ---- trajectory and key-frame decision per stream ------------------------------------------------------------------------ */
+
+/* Replaces, for B streams at once and on the device, what StereoFrameHandler does with a pose result after optimizePose: the "set
+ * estimated pose" block (src/stereoFrameHandler.cpp:372-391)
+ *   status == STVO_POSE_OK:  Tfw <- expmap_se3(logmap_se3(Tfw * T)),  Tfw_cov <- unccomp_se3(Tfw_old, Tfw_cov_old, cov)
+ *   otherwise:               both carried over; the frame counts as DT = I, DT_cov = 0
+ * and, with prm->keyframes, needNewKF (:1136-1188) followed by currFrameIsKF (:1190-1218) when it says so: Tfw = I, Tfw_cov = I,
+ * T_prevKF = I, cov_prevKF_currF = 0, prev_f_iskf = 1, N_prevKF_currF = 0, n_keyframes + 1.  The record (records_dev [B], may be NULL)
+ * holds the pose BEFORE that reset, entropy_ratio / t / r as compared (0 with keyframes off), new_kf and the frame number.
+ * state_dev [B] is in / out; stvo_traj_init_dev fills the state `initialize` leaves.  results_dev: device memory or pinned host
+ * memory; T, cov and status are read.  Both are enqueued on the context's stream. */
+int stvo_traj_init_dev(stvo_ctx* ctx, int B, stvo_traj_state* state_dev /* [B] */);
+int stvo_traj_update_dev(stvo_ctx* ctx, int B, const stvo_pose_result* results_dev, const stvo_traj_params* prm,
+                         stvo_traj_state* state_dev /* [B] */, stvo_traj_record* records_dev /* [B] or NULL */);
+/* The same inside the pipeline.  prm != NULL: the sequence object owns the state [B] and a ring of log_steps (>= 1) x B records, and
+ * every step that tracks (every step but a sequence's first) enqueues the update right behind its pose kernel, on the same stream,
+ * writing ring row (tracked step) % log_steps.  prm == NULL: off (the default): nothing is allocated, nothing launched.  Only before
+ * the first step; a ring above 1 GiB (448 bytes per record) is refused.  STVO_ERR_INVALID_ARG otherwise, and nothing changes.
+ * The update is the last launch of stvo_seq_step_dev, behind the step's own bookkeeping: should that launch fail, the call returns
+ * the error but the step counts as taken (the frame index has moved on, its results are readable), and so does its ring row. */
+int stvo_seq_set_trajectory(stvo_seq* seq, const stvo_traj_params* prm, int log_steps);
+/* The records of the last min(n_last, log_steps, tracked steps) steps, oldest first, into records [n_last][B] (host); *n_got = how
+ * many steps.  Synchronises the context's stream (after stvo_seq_push / stvo_seq_read it is idle already).  STVO_ERR_INVALID_ARG
+ * when the trajectory is off. */
+int stvo_seq_read_trajectory(stvo_seq* seq, int n_last, stvo_traj_record* records, int32_t* n_got);
+/* The device state [B], for callers that chain their own kernels on the context's stream. */
+int stvo_seq_trajectory_state_dev(stvo_seq* seq, stvo_traj_state** state_dev);
+/* A host copy of the state [B] behind everything enqueued so far (copied on the context's stream; synchronises). */
+int stvo_seq_read_trajectory_state(stvo_seq* seq, stvo_traj_state* state /* [B] host */);
+
 /* ---- LBD line descriptor (first half) ------------------------------------------------------- */
 
 /* Replaces  BinaryDescriptor::createBinaryDescriptor()->compute(img, lines, ldesc)  as called by StereoFrame::detectLineFeatures

@@ -170,6 +170,41 @@ typedef struct stvo_fast_adapt {
     float err_th;
 } stvo_fast_adapt;
 
+/* Trajectory and key-frame decision per stream (StereoFrameHandler's public state the odometry leaves behind: curr_frame->Tfw /
+ * Tfw_cov of optimizePose's "set estimated pose" block, src/stereoFrameHandler.cpp:372-391, and the "slam functions" needNewKF /
+ * currFrameIsKF, :1136-1218).  The thresholds are Config::minEntropyRatio / maxKFTDist / maxKFRDist (0.85, 5.0, 15.0 in every
+ * shipped configuration).  keyframes = 0: the pose is composed and never reset. */
+typedef struct stvo_traj_params {
+    int32_t keyframes;
+    int32_t reserved;
+    double min_entropy_ratio, max_kf_t_dist, max_kf_r_dist;
+} stvo_traj_params;
+
+/* One stream's state: the pose of the last frame in the map frame, and the five members the key-frame decision keeps
+ * (include/stereoFrameHandler.h:81-85).  Initial (stvo_traj_init_dev; src/stereoFrameHandler.cpp:35-51): Tfw = I, Tfw_cov = I,
+ * prev_f_iskf = 1, entropy_first_prevKF = 0, T_prevKF = I, cov_prevKF_currF = 0, counters 0. */
+typedef struct stvo_traj_state {
+    double Tfw[16];
+    double Tfw_cov[36];
+    double entropy_first_prevKF;
+    double T_prevKF[16];
+    double cov_prevKF_currF[36];
+    int32_t prev_f_iskf;
+    int32_t N_prevKF_currF;
+    int32_t n_frames;    /* pose results taken in */
+    int32_t n_keyframes; /* resets among them */
+} stvo_traj_state;
+
+/* What one update leaves for the caller (448 bytes): the frame's pose BEFORE a key-frame reset, the three quantities the decision
+ * compared (0 with keyframes off), the decision, and the number of the frame in its stream (the first tracked frame is 1). */
+typedef struct stvo_traj_record {
+    double Tfw[16];
+    double Tfw_cov[36];
+    double entropy_ratio, t, r;
+    int32_t new_kf;
+    int32_t frame;
+} stvo_traj_record;
+
 /* A key-line as the LBD descriptor consumes it: the line_descriptor::KeyLine fields BinaryDescriptor::computeImpl copies into its
  * OctaveSingleLine (3rdparty/line_descriptor/src/binary_descriptor_custom.cpp:592-609), octave 0. */
 typedef struct stvo_keyline {

@@ -7,7 +7,8 @@
 //   imagesStVO_synth <sequence.bin> <results.bin> [--preset kitti|euroc|default] [-c config.yaml] [--mode 0|1|2]
 //                    [-o offset] [-n N] [-s step]   (the reference's options, app/imagesStVO.cpp:138-171)
 //                    [--keyframes]   (needNewKF / currFrameIsKF after every optimizePose, as PL-SLAM drives them)
-//                    [--device-pipeline]   (stvo_seq_*: one upload + one synchronisation per frame, state in HBM)
+//                    [--device-pipeline]   (stvo_seq_*: one upload + one synchronisation per frame, state in HBM; Tfw / Tfw_cov and,
+//                                           with --keyframes, the key-frame decision come from the device: stvo_seq_set_trajectory)
 //                    [--no-lines]    (Config::hasLines() = false)
 //                    [--dataset-params FILE]   (image files: the camera comes from the dataset parameter file and every raw pair is
 //                                               rectified before initialize / insertStereoPair, as Dataset::nextFrame does,
@@ -133,7 +134,7 @@ int main(int argc, char** argv) {
     }
 
     if (device_pipeline) {
-        // ---- the same loop on the device-resident pipeline: pose + counters per frame, Tfw composed here
+        // ---- the same loop on the device-resident pipeline: pose + counters per frame, Tfw / Tfw_cov / new_kf from the device
         stvo_ctx* ctx = nullptr;
         if (stvo_ctx_create(0, 2048, 1, &ctx) != STVO_OK) {
             std::cerr << "[StVO-HIP] no MI355X available" << std::endl;
@@ -147,8 +148,8 @@ int main(int argc, char** argv) {
         mp.ls_min_disp_ratio = Config::lsMinDispRatio(); mp.orb_scale_factor = Config::orbScaleFactor();
         mp.lsd_scale = Config::lsdScale();
         mp.min_ratio_12_p_d = Config::minRatio12P();
-        if (frame_offset != 0 || frame_step != 1 || keyframes) {
-            std::cerr << "--device-pipeline takes the sequence as it is: -o / -s / --keyframes belong to the handler path" << std::endl;
+        if (frame_offset != 0 || frame_step != 1) {
+            std::cerr << "--device-pipeline takes the sequence as it is: -o / -s belong to the handler path" << std::endl;
             return -1;
         }
         stvo_opt_params op{};
@@ -160,6 +161,14 @@ int main(int argc, char** argv) {
         stvo_seq* seq = nullptr;
         if (stvo_seq_create(ctx, 1, 2048, 512, cols, rows, &cam, &mp, &op, &seq) != STVO_OK) {
             std::cerr << "stvo_seq_create failed" << std::endl;
+            return -2;
+        }
+        // the trajectory of the stream, and the key-frame decision PL-SLAM drives on top of it, behind every pose kernel
+        stvo_traj_params tp{};
+        tp.keyframes = keyframes ? 1 : 0;
+        tp.min_entropy_ratio = Config::minEntropyRatio(); tp.max_kf_t_dist = Config::maxKFTDist(); tp.max_kf_r_dist = Config::maxKFRDist();
+        if (stvo_seq_set_trajectory(seq, &tp, 1) != STVO_OK) {
+            std::cerr << "stvo_seq_set_trajectory failed: " << stvo_ctx_last_error(ctx) << std::endl;
             return -2;
         }
         double t_sum = 0.0;
@@ -194,6 +203,12 @@ int main(int argc, char** argv) {
             }
             const double t1 = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
             if (k == 0) continue;
+            stvo_traj_record tr{};
+            int32_t n_tr = 0;
+            if (stvo_seq_read_trajectory(seq, 1, &tr, &n_tr) != STVO_OK || n_tr != 1) {  // (the stream is idle after the push: no second wait)
+                std::cerr << "stvo_seq_read_trajectory failed: " << stvo_ctx_last_error(ctx) << std::endl;
+                return -3;
+            }
             t_sum += t1;
             t_all.push_back(t1);
             std::printf("Frame: %d\tRes.: %.8f \t Proc. time: %.3f ms\t \t Points: %d (%d) \t Lines:  %d (%d) \n", k, r.err, t1,
@@ -205,9 +220,9 @@ int main(int argc, char** argv) {
             wr(out, r.cov, 36);
             wr(out, r.cov_eig, 6);
             wr(out, &r.err, 1);
-            const double zeros[52] = {0};
-            wr(out, zeros, 52);  // Tfw / Tfw_cov are composed by the caller in this mode
-            const int32_t z2[2] = {0, 0};
+            wr(out, tr.Tfw, 16);  // the pose of the frame, before a key-frame restarts the map frame
+            wr(out, tr.Tfw_cov, 36);
+            const int32_t z2[2] = {0, tr.new_kf};  // (no adaptive FAST threshold on feature files; the spare word as on the handler path)
             wr(out, z2, 2);
         }
         if (n_frames > 1) {

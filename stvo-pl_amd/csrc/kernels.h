@@ -307,4 +307,10 @@ void launch_grid_range_debug(hipStream_t s, const GridBatch& g);  // test hook, 
 // results[b] says.  `results` may be device memory or the pinned block a zero-copy step writes its results to.
 void launch_fast_adapt(hipStream_t s, int B, const stvo_pose_result* results, const stvo_fast_adapt& prm, int32_t* th);
 
+// Trajectory and key-frame decision for B streams, one lane per stream (traj_kernel.hip): state[b] advances by results[b] (T, cov, status),
+// records (may be null) [B] takes what the update leaves for the caller.  `results` as for launch_fast_adapt.
+void launch_traj_init(hipStream_t s, int B, stvo_traj_state* state);
+void launch_traj_update(hipStream_t s, int B, const stvo_pose_result* results, const stvo_traj_params& prm, stvo_traj_state* state,
+                        stvo_traj_record* records);
+
 }  // namespace stvo

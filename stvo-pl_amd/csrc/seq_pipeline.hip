@@ -588,6 +588,12 @@ struct stvo_seq {
     double* d_inv_wh = nullptr;    // [B][2] per-sequence grid scale (device)
     double* d_qtab = nullptr;      // [STVO_POSE_QTAB] sqrt(sigma2) of pyramid level l (kernels.h: PoseArgs::q_tab)
     double* d_motion_T = nullptr;  // [B][16] use_motion_model: the next step's initial DT per sequence, written by the pose kernel's commit (stvo_seq_set_motion_model)
+    // trajectory and key-frame decision per stream (stvo_seq_set_trajectory): null = off
+    stvo_traj_state* d_traj_state = nullptr;   // [B]
+    stvo_traj_record* d_traj_ring = nullptr;   // [traj_log_steps][B]: tracked step k writes row k % traj_log_steps
+    stvo_traj_params traj_prm{};
+    int traj_log_steps = 0;
+    unsigned long long traj_steps = 0;         // tracked steps enqueued so far
     long long* d_prof = nullptr;   // STVO_POSE_PROF (developer aid): [B][16] phase ticks of the last pose launch, printed by stvo_seq_read
     char* dev = nullptr;     // one allocation, carved below
     size_t dev_bytes = 0;
@@ -977,6 +983,8 @@ int stvo_seq_destroy(stvo_seq* s) {
     (void)hipStreamSynchronize(s->ctx->stream);
     if (s->d_prof) (void)hipFree(s->d_prof);
     if (s->d_motion_T) (void)hipFree(s->d_motion_T);
+    if (s->d_traj_state) (void)hipFree(s->d_traj_state);
+    if (s->d_traj_ring) (void)hipFree(s->d_traj_ring);
     if (s->line_stream) {
         (void)hipStreamSynchronize(s->line_stream);
         (void)hipStreamDestroy(s->line_stream);
@@ -1461,6 +1469,91 @@ int stvo_seq_step_dev(stvo_seq* s, int slot) {
     s->last_slot = slot;
     s->cur = (s->cur + 1) % 3;  // updateFrame: curr becomes prev
     s->frame_idx++;
+    if (s->d_traj_state && fl.track) {  // the trajectory behind the pose kernel, reading the results where PoseArgs::results pointed
+        // (the step above is committed: a launch that fails here returns its error from a step that counts as taken, ring row included)
+        const stvo_pose_result* res = s->zero_copy ? reinterpret_cast<const stvo_pose_result*>(s->out_host) : s->results;
+        stvo::launch_traj_update(ctx->stream, s->B, res, s->traj_prm, s->d_traj_state,
+                                 s->d_traj_ring + (size_t)(s->traj_steps % (unsigned long long)s->traj_log_steps) * s->B);
+        s->traj_steps++;
+        return check_launch(ctx);
+    }
+    return STVO_OK;
+}
+
+// Trajectory per stream inside the pipeline (stvo_hip.h).  The state and the ring are new device memory: filled on the context's own stream.
+int stvo_seq_set_trajectory(stvo_seq* s, const stvo_traj_params* prm, int log_steps) {
+    if (!s || s->frame_idx != 0) return STVO_ERR_INVALID_ARG;
+    stvo_ctx* ctx = s->ctx;
+    if (!prm) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (s->d_traj_state) {
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (its fill may still run)
+            (void)hipFree(s->d_traj_state);
+            (void)hipFree(s->d_traj_ring);
+        }
+        s->d_traj_state = nullptr; s->d_traj_ring = nullptr; s->traj_log_steps = 0;
+        return STVO_OK;
+    }
+    if (log_steps < 1) return STVO_ERR_INVALID_ARG;
+    const unsigned long long ring_bytes = (unsigned long long)log_steps * (unsigned long long)s->B * sizeof(stvo_traj_record);
+    if (ring_bytes > (1ull << 30)) return STVO_ERR_INVALID_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (s->d_traj_state) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        (void)hipFree(s->d_traj_state);
+        (void)hipFree(s->d_traj_ring);
+        s->d_traj_state = nullptr; s->d_traj_ring = nullptr; s->traj_log_steps = 0;
+    }
+    stvo_traj_state* st = nullptr;
+    stvo_traj_record* ring = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&st, (size_t)s->B * sizeof(stvo_traj_state)));
+    if (hipMalloc((void**)&ring, (size_t)ring_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(st);
+        std::snprintf(ctx->last_error, sizeof(ctx->last_error), "%s", "hipMalloc of the trajectory ring failed");
+        return STVO_ERR_HIP;
+    }
+    stvo::launch_traj_init(ctx->stream, s->B, st);
+    if (hipMemsetAsync(ring, 0, (size_t)ring_bytes, ctx->stream) != hipSuccess || check_launch(ctx) != STVO_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(st);
+        (void)hipFree(ring);
+        return STVO_ERR_HIP;
+    }
+    s->d_traj_state = st; s->d_traj_ring = ring; s->traj_prm = *prm; s->traj_log_steps = log_steps; s->traj_steps = 0;
+    return STVO_OK;
+}
+
+int stvo_seq_read_trajectory(stvo_seq* s, int n_last, stvo_traj_record* records, int32_t* n_got) {
+    if (!s || !s->d_traj_state || n_last < 1 || !records || !n_got) return STVO_ERR_INVALID_ARG;
+    stvo_ctx* ctx = s->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    unsigned long long n = (unsigned long long)n_last;
+    if (n > (unsigned long long)s->traj_log_steps) n = (unsigned long long)s->traj_log_steps;
+    if (n > s->traj_steps) n = s->traj_steps;
+    const size_t row = (size_t)s->B * sizeof(stvo_traj_record);
+    for (unsigned long long i = 0; i < n; ++i) {  // oldest first
+        const size_t r = (size_t)((s->traj_steps - n + i) % (unsigned long long)s->traj_log_steps);
+        HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<char*>(records) + i * row, reinterpret_cast<const char*>(s->d_traj_ring) + r * row, row,
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *n_got = (int32_t)n;
+    return STVO_OK;
+}
+
+int stvo_seq_read_trajectory_state(stvo_seq* s, stvo_traj_state* state) {
+    if (!s || !s->d_traj_state || !state) return STVO_ERR_INVALID_ARG;
+    stvo_ctx* ctx = s->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(state, s->d_traj_state, (size_t)s->B * sizeof(stvo_traj_state), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return STVO_OK;
+}
+
+int stvo_seq_trajectory_state_dev(stvo_seq* s, stvo_traj_state** state_dev) {
+    if (!s || !s->d_traj_state || !state_dev) return STVO_ERR_INVALID_ARG;
+    *state_dev = s->d_traj_state;
     return STVO_OK;
 }
 

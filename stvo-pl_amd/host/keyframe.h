@@ -8,7 +8,7 @@
 #include <cmath>
 #include <iostream>
 
-#include "../csrc/pose_math.h"
+#include "../csrc/traj_update.h"
 #include "stvo_compat.h"
 
 namespace StVO {
@@ -23,64 +23,31 @@ struct KeyFrameState {
 
 // needNewKF (:1136-1188).  Tfw, DT, DT_cov are curr_frame's fields.  Returns true when a new key-frame is needed;
 // otherwise counts the frame (N_prevKF_currF++).  The accumulated covariance is updated in both cases, like the original.
+// The rule itself is pm::kf_decide (csrc/traj_update.h), the text the device runs per stream.
 inline bool kf_need_new(KeyFrameState& k, const Matrix4d& Tfw, const Matrix4d& DT, const Matrix6d& DT_cov,
                         double min_entropy_ratio, double max_kf_t_dist, double max_kf_r_dist, bool verbose = true) {
-    const double kPi = 3.1415926535897932384626433832795;  // CV_PI
-    const double two_pi_term = 3.0 * (1.0 + std::log(2.0 * std::acos(-1.0)));
-    if (k.prev_f_iskf) {  // :1140-1153 — first frame after a key-frame fixes the reference entropy
-        const double det = pm::det6(DT_cov.m);
-        k.entropy_first_prevKF = (det != 0.0) ? two_pi_term + 0.5 * std::log(det) : -999999999.99;
-        k.prev_f_iskf = false;
+    int32_t iskf = k.prev_f_iskf ? 1 : 0, N = k.N_prevKF_currF;
+    pm::KfTerms o;
+    const bool need = pm::kf_decide(iskf, k.entropy_first_prevKF, k.T_prevKF.m, k.cov_prevKF_currF.m, N, Tfw.m, DT.m, DT_cov.m,
+                                    min_entropy_ratio, max_kf_t_dist, max_kf_r_dist, o);
+    k.prev_f_iskf = iskf != 0;
+    if (verbose) {
+        if (need)
+            std::cout << std::endl << "Entropy ratio: " << o.entropy_ratio << "\t" << o.t << " " << o.r << " " << k.N_prevKF_currF << std::endl;
+        else
+            std::cout << std::endl << "No new KF needed: " << o.entropy_ratio << "\t" << o.entropy_curr << " " << k.entropy_first_prevKF << " "
+                      << o.det_acc << "\t" << o.t << " " << o.r << " " << k.N_prevKF_currF << std::endl << std::endl;
     }
-    // geometric distance from the previous key-frame (:1156-1159)
-    double Ti[16], D[16], dX[6];
-    pm::inverse_se3(Tfw.m, Ti);
-    pm::mat4_mul(Ti, k.T_prevKF.m, D);
-    pm::logmap_se3(D, dX);
-    const double t = std::sqrt(dX[0] * dX[0] + dX[1] * dX[1] + dX[2] * dX[2]);
-    const double r = std::sqrt(dX[3] * dX[3] + dX[4] * dX[4] + dX[5] * dX[5]) * 180.f / kPi;
-    // accumulated covariance from the previous key-frame (:1162-1166)
-    double A[36], cinv[36], tmp[36];
-    pm::adjoint_se3(k.T_prevKF.m, A);
-    pm::uncTinv_se3(DT.m, DT_cov.m, cinv);
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) {
-            double s = 0.0;
-            for (int q = 0; q < 6; ++q) s += A[i * 6 + q] * cinv[q * 6 + j];
-            tmp[i * 6 + j] = s;
-        }
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) {
-            double s = 0.0;
-            for (int q = 0; q < 6; ++q) s += tmp[i * 6 + q] * A[j * 6 + q];
-            k.cov_prevKF_currF.m[i * 6 + j] += s;
-        }
-    const double det_acc = pm::det6(k.cov_prevKF_currF.m);
-    const double entropy_curr = two_pi_term + 0.5 * std::log(det_acc);
-    const double entropy_ratio = entropy_curr / k.entropy_first_prevKF;
-    bool zero_cov = true, ident = true;
-    for (int i = 0; i < 36; ++i) zero_cov = zero_cov && DT_cov.m[i] == 0.0;
-    for (int i = 0; i < 16; ++i) ident = ident && DT.m[i] == ((i % 5 == 0) ? 1.0 : 0.0);
-    // :1173-1175
-    if (entropy_ratio < min_entropy_ratio || std::isnan(entropy_ratio) || std::isinf(entropy_ratio) || (zero_cov && ident) ||
-        t > max_kf_t_dist || r > max_kf_r_dist || k.N_prevKF_currF > 10) {
-        if (verbose)
-            std::cout << std::endl << "Entropy ratio: " << entropy_ratio << "\t" << t << " " << r << " " << k.N_prevKF_currF << std::endl;
-        return true;
-    }
-    if (verbose)
-        std::cout << std::endl << "No new KF needed: " << entropy_ratio << "\t" << entropy_curr << " " << k.entropy_first_prevKF << " "
-                  << det_acc << "\t" << t << " " << r << " " << k.N_prevKF_currF << std::endl << std::endl;
-    k.N_prevKF_currF++;
-    return false;
+    k.N_prevKF_currF = N;
+    return need;
 }
 
 // the state part of currFrameIsKF (:1209-1216); the caller resets the feature indices and the frame pose
 inline void kf_reset(KeyFrameState& k, const Matrix4d& Tfw_of_new_kf) {
-    k.T_prevKF = Tfw_of_new_kf;
-    k.cov_prevKF_currF = Matrix6d::Zero();
-    k.prev_f_iskf = true;
-    k.N_prevKF_currF = 0;
+    int32_t iskf, N;
+    pm::kf_restart(iskf, k.T_prevKF.m, k.cov_prevKF_currF.m, N, Tfw_of_new_kf.m);
+    k.prev_f_iskf = iskf != 0;
+    k.N_prevKF_currF = N;
 }
 
 }  // namespace StVO

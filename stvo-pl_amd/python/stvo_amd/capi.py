@@ -9,7 +9,8 @@ import subprocess
 
 import numpy as np
 
-from .ctypes_types import Cam, GridWindow, MatchParams, OptParams, PoseResult, POSE_RESULT_DTYPE, RectCalib, RectCamera
+from .ctypes_types import Cam, GridWindow, MatchParams, OptParams, PoseResult, POSE_RESULT_DTYPE, RectCalib, RectCamera, TrajParams, \
+    TRAJ_RECORD_DTYPE, TRAJ_STATE_DTYPE
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # stvo-pl_amd/
 LIB_PATH = os.environ.get("STVO_LIB") or os.path.join(PKG_DIR, "libstvo_hip.so")   # STVO_LIB: A/B runs of two builds (developer)
@@ -28,7 +29,8 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_fld_detect_dev", "stvo_fld_counts", "stvo_fld_segments", "stvo_fld_edges", "stvo_keylines_xy_dev", "stvo_rectify_compute",
            "stvo_rectify_create", "stvo_rectify_create_from_maps", "stvo_rectify_destroy", "stvo_rectify_camera", "stvo_rectify_images",
            "stvo_rectify_images_dev", "stvo_orb_set_fast_thresholds", "stvo_orb_set_fast_thresholds_dev", "stvo_fast_adapt_dev",
-           "stvo_seq_adapt_fast_dev"]
+           "stvo_seq_adapt_fast_dev", "stvo_traj_init_dev", "stvo_traj_update_dev", "stvo_seq_set_trajectory", "stvo_seq_read_trajectory",
+           "stvo_seq_trajectory_state_dev", "stvo_seq_read_trajectory_state"]
 
 SEQ_NSTAGE = 5  # include/stvo_hip.h: STVO_SEQ_NSTAGE
 SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_check", "pose")
@@ -91,6 +93,45 @@ def fast_adapt_dev(ctx, results, prm, th):
             results.numel() * results.element_size() < B * POSE_RESULT_DTYPE.itemsize:
         raise ValueError("fast_adapt_dev: th must be a contiguous int32 tensor and results hold one record per threshold")
     ctx._chk(ctx.lib.stvo_fast_adapt_dev(ctx.h, B, results.data_ptr(), C.byref(prm), th.data_ptr()))
+
+
+def traj_params(preset="kitti", keyframes=True, **overrides):
+    """Config::minEntropyRatio / maxKFTDist / maxKFRDist as the reference ships them (config_euroc.yaml: 0.85, 5.0, 15.0; the files that
+    do not name them take the same values from src/config.cpp, so every preset agrees).  keyframes=False: the pose is composed and never
+    reset.  overrides: min_entropy_ratio, max_kf_t_dist, max_kf_r_dist."""
+    if preset not in ("kitti", "euroc", "default"):
+        raise KeyError(preset)
+    base = dict(min_entropy_ratio=0.85, max_kf_t_dist=5.0, max_kf_r_dist=15.0)
+    unknown = set(overrides) - set(base)
+    if unknown:
+        raise TypeError(f"traj_params: unknown field(s) {sorted(unknown)}")
+    base.update(overrides)
+    return TrajParams(keyframes=1 if keyframes else 0, reserved=0, **base)
+
+
+def _dev_bytes(t, n, itemsize, what):
+    if not t.is_cuda or not t.is_contiguous() or t.numel() * t.element_size() < n * itemsize:
+        raise ValueError(f"{what}: a contiguous device tensor of at least {n} records of {itemsize} bytes is needed")
+
+
+def traj_init_dev(ctx, state):
+    """The state `initialize` leaves, for every record of `state` (a torch uint8 device tensor of B * TRAJ_STATE_DTYPE.itemsize bytes),
+    on the context's stream (stvo_traj_init_dev)."""
+    B = state.numel() * state.element_size() // TRAJ_STATE_DTYPE.itemsize
+    _dev_bytes(state, max(B, 1), TRAJ_STATE_DTYPE.itemsize, "traj_init_dev")
+    ctx._chk(ctx.lib.stvo_traj_init_dev(ctx.h, B, state.data_ptr()))
+
+
+def traj_update_dev(ctx, results, prm, state, records=None):
+    """One trajectory / key-frame update for B streams on the context's stream (stvo_traj_update_dev): results = torch uint8 device
+    tensor of B stvo_pose_result records, state = B TRAJ_STATE_DTYPE records (in / out), records = None or B TRAJ_RECORD_DTYPE records."""
+    B = state.numel() * state.element_size() // TRAJ_STATE_DTYPE.itemsize
+    _dev_bytes(state, max(B, 1), TRAJ_STATE_DTYPE.itemsize, "traj_update_dev: state")
+    _dev_bytes(results, B, POSE_RESULT_DTYPE.itemsize, "traj_update_dev: results")
+    if records is not None:
+        _dev_bytes(records, B, TRAJ_RECORD_DTYPE.itemsize, "traj_update_dev: records")
+    ctx._chk(ctx.lib.stvo_traj_update_dev(ctx.h, B, results.data_ptr(), C.byref(prm), state.data_ptr(),
+                                          records.data_ptr() if records is not None else None))
 
 
 def build(force=False):
@@ -177,6 +218,12 @@ def load():
     L.stvo_orb_set_fast_thresholds_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.stvo_fast_adapt_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(FastAdapt), C.c_void_p]
     L.stvo_seq_adapt_fast_dev.argtypes = [C.c_void_p, C.POINTER(FastAdapt), C.c_void_p]
+    L.stvo_traj_init_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.stvo_traj_update_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TrajParams), C.c_void_p, C.c_void_p]
+    L.stvo_seq_set_trajectory.argtypes = [C.c_void_p, C.POINTER(TrajParams), C.c_int]
+    L.stvo_seq_read_trajectory.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
+    L.stvo_seq_trajectory_state_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.stvo_seq_read_trajectory_state.argtypes = [C.c_void_p, C.c_void_p]
     L.stvo_orb_detect_levels.argtypes = [C.c_void_p, u8p, f32p, f32p, f32p, i32p, u8p, i32p, i32p]
     L.stvo_orb_detect_levels_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 8
     L.stvo_lbd_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -725,6 +772,26 @@ class Sequences:
         if str(th.dtype) != "torch.int32" or not th.is_cuda or not th.is_contiguous() or th.numel() != self.B:
             raise ValueError("Sequences.adapt_fast_dev: th must be a contiguous int32 device tensor of B entries")
         self.ctx._chk(self.ctx.lib.stvo_seq_adapt_fast_dev(self.h, C.byref(prm), th.data_ptr()))
+
+    def set_trajectory(self, prm, log_steps=1):
+        """Trajectory and key-frame decision per stream behind every tracked step (stvo_seq_set_trajectory): prm = traj_params(...) or
+        None (off); the last log_steps steps' records stay readable.  Only before the first step."""
+        self.ctx._chk(self.ctx.lib.stvo_seq_set_trajectory(self.h, C.byref(prm) if prm is not None else None, log_steps))
+        self._traj_log_steps = log_steps if prm is not None else 0
+
+    def read_trajectory(self, n_last=1):
+        """TRAJ_RECORD_DTYPE array [n, B]: the last n = min(n_last, log_steps, tracked steps) steps, oldest first; synchronises."""
+        rows = max(1, min(n_last, getattr(self, "_traj_log_steps", 0)))   # the library returns no more than the ring holds
+        rec = np.zeros((rows, self.B), dtype=TRAJ_RECORD_DTYPE)
+        n = C.c_int32()
+        self.ctx._chk(self.ctx.lib.stvo_seq_read_trajectory(self.h, n_last, rec.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return rec[:n.value].copy()
+
+    def trajectory_state(self):
+        """Host copy of the B stream states (TRAJ_STATE_DTYPE) after everything enqueued so far; synchronises."""
+        out = np.zeros(self.B, dtype=TRAJ_STATE_DTYPE)
+        self.ctx._chk(self.ctx.lib.stvo_seq_read_trajectory_state(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def read(self):
         res = np.zeros(self.B, dtype=POSE_RESULT_DTYPE)

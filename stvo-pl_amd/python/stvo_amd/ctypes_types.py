@@ -51,6 +51,20 @@ POSE_RESULT_DTYPE = np.dtype([("T", "<f8", (16,)), ("cov", "<f8", (36,)), ("cov_
                               ("n_inliers_pt", "<i4"), ("n_inliers_ls", "<i4")])
 assert POSE_RESULT_DTYPE.itemsize == C.sizeof(PoseResult), (POSE_RESULT_DTYPE.itemsize, C.sizeof(PoseResult))
 
+
+class TrajParams(C.Structure):  # stvo_traj_params
+    _fields_ = [("keyframes", C.c_int32), ("reserved", C.c_int32), ("min_entropy_ratio", C.c_double), ("max_kf_t_dist", C.c_double),
+                ("max_kf_r_dist", C.c_double)]
+
+
+# stvo_traj_state / stvo_traj_record (include/stvo_types.h)
+TRAJ_STATE_DTYPE = np.dtype([("Tfw", "<f8", (16,)), ("Tfw_cov", "<f8", (36,)), ("entropy_first_prevKF", "<f8"), ("T_prevKF", "<f8", (16,)),
+                             ("cov_prevKF_currF", "<f8", (36,)), ("prev_f_iskf", "<i4"), ("N_prevKF_currF", "<i4"), ("n_frames", "<i4"),
+                             ("n_keyframes", "<i4")])
+TRAJ_RECORD_DTYPE = np.dtype([("Tfw", "<f8", (16,)), ("Tfw_cov", "<f8", (36,)), ("entropy_ratio", "<f8"), ("t", "<f8"), ("r", "<f8"),
+                              ("new_kf", "<i4"), ("frame", "<i4")])
+assert TRAJ_STATE_DTYPE.itemsize == 856 and TRAJ_RECORD_DTYPE.itemsize == 448 and C.sizeof(TrajParams) == 32
+
 STATUS_OK, STATUS_FEW_BEFORE, STATUS_FEW_AFTER, STATUS_REJECTED = 0, 1, 2, 3
 PATH_STAGE1_GOOD, PATH_ROBUST_FALLBACK, PATH_REFINED = 1, 2, 4
 

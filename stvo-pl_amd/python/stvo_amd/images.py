@@ -18,7 +18,8 @@ from .capi import FrameFeatures
 
 class ImagePipeline:
     def __init__(self, ctx, B, cam, mp, op, max_kp=2048, nfeatures=2000, fast_threshold=20, edge_threshold=19, device="cuda:0", nlevels=1,
-                 scale_factor=1.2, lsd=None, max_kl=128, rectify=None, fld=None, orb_score=1, adaptive_fast=None):
+                 scale_factor=1.2, lsd=None, max_kl=128, rectify=None, fld=None, orb_score=1, adaptive_fast=None,
+                 trajectory=None, trajectory_log=1):
         """cam: one camera dict (width / height = image size) for all B streams.  nlevels / scale_factor: Config::orbNLevels /
         orbScaleFactor (the key-point octaves travel with the key-points: sigma2 = 1 / scale^(2 level)).  orb_score: Config::orbScore
         (1 FAST_SCORE, 0 HARRIS_SCORE ranking of the key-points).  lsd: capi.lsd_params(...)
@@ -30,7 +31,11 @@ class ImagePipeline:
         adaptive_fast: capi.fast_adapt_params(...) turns on the reference's adaptative_fast (StereoFrameHandler::updateFrame,
         src/stereoFrameHandler.cpp:66-86) per stream: self.fast_th (int32 [B] on the device, fast_threshold at first) is what the
         detector reads for the two images of stream b, and every enqueue ends with the rule moving it by that step's pose results —
-        on the device, in stream order, the host never sees it.  None: one fixed threshold, no kernel added."""
+        on the device, in stream order, the host never sees it.  None: one fixed threshold, no kernel added.
+        trajectory: capi.traj_params(...) turns on the pose in the map frame and the key-frame decision per stream (the rest of
+        optimizePose's "set estimated pose" block, :372-391, and needNewKF / currFrameIsKF, :1136-1218): every tracked step is followed
+        by the update on the device, read_trajectory() returns the records of the last trajectory_log steps.  None: images -> poses as
+        before, no launch and no allocation added."""
         self.ctx, self.B, self.K, self.M = ctx, B, max_kp, max_kl
         self.cols, self.rows = cam["width"], cam["height"]
         self.rectify = rectify
@@ -49,6 +54,9 @@ class ImagePipeline:
         self.lines = self.lsd if self.lsd is not None else self.fld  # the key-line detector, or None
         self.lbd = capi.Lbd(ctx, 2 * B, self.cols, self.rows, max_keylines=max_kl) if self.lines is not None else None
         self.seq = capi.Sequences(ctx, B, max_kp, max_kl if self.lines is not None else 64, cam, mp, op)
+        self.trajectory = trajectory
+        if trajectory is not None:
+            self.seq.set_trajectory(trajectory, trajectory_log)
         dev = torch.device(device)
         self.img = torch.zeros((2 * B, self.rows, self.cols), dtype=torch.uint8, device=dev)
         self.rect_img = torch.zeros((2 * B, self.rows, self.cols), dtype=torch.uint8, device=dev) if rectify is not None else None
@@ -122,6 +130,13 @@ class ImagePipeline:
         torch.cuda.current_stream().synchronize()  # the copies above ran on torch's stream, the library uses its own
         self.enqueue()
         return self.seq.read()
+
+    def read_trajectory(self, n_last=1):
+        """TRAJ_RECORD_DTYPE [n, B]: Tfw / Tfw_cov (before a key-frame reset), entropy_ratio, t, r, new_kf, frame of the last
+        n <= trajectory_log tracked steps, oldest first (Sequences.read_trajectory; synchronises)."""
+        if self.trajectory is None:
+            raise ValueError("ImagePipeline.read_trajectory: built without trajectory")
+        return self.seq.read_trajectory(n_last)
 
     def fast_thresholds(self):
         """Host copy of the per-stream FAST thresholds the NEXT detection will read (synchronises); tests and tools."""
