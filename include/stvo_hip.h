@@ -351,6 +351,36 @@ int stvo_seq_trajectory_state_dev(stvo_seq* seq, stvo_traj_state** state_dev);
 /* A host copy of the state [B] behind everything enqueued so far (copied on the context's stream; synchronises). */
 int stvo_seq_read_trajectory_state(stvo_seq* seq, stvo_traj_state* state /* [B] host */);
 
+/* ---- restart and park single streams between steps ---------------------------------------------------------------------- */
+
+/* One control word per stream for the NEXT step of the pipeline (stvo_seq_step_dev / stvo_seq_push), then all-RUN again:
+ *   RUN      as without a control;
+ *   RESTART  the frame in the slot is the first frame of a new sequence — StereoFrameHandler::initialize
+ *            (src/stereoFrameHandler.cpp:35-52; the app calls no optimizePose / updateFrame for it): its stereo association runs and
+ *            counts[b][0..1] report it; the stream's pose result reads as all-zero bytes (as stvo_seq_read reports a pipeline's very
+ *            first frame) and counts[b][2..3] are 0; nothing of the previous sequence reaches a later result; the motion-model seed of
+ *            the next step is the identity (:45); with the trajectory on, the stream's state becomes what stvo_traj_init_dev writes
+ *            and its ring record of this step is all-zero (frame == 0: no pose in this step), so the next tracked frame is frame 1;
+ *            with fetch enabled its f2f match rows and inlier rows are -1, its stereo match rows those of the new frame;
+ *   PARK     the stream has no sequence at the moment: the step still builds the stereo set of whatever the slot holds (a following
+ *            RUN tracks against it, a following RESTART ignores it); result all-zero, counts[b][2..3] 0, ring record all-zero, seed
+ *            identity; trajectory state and key-frame members stay bit for bit (the final pose of a finished sequence stays readable).
+ * In the pipeline's own first step nothing is tracked anyway: a control staged for it is consumed without effect.
+ * ctl_host [B] is read during the call.  Values outside 0 .. 2: STVO_ERR_INVALID_ARG and nothing changes.  All zero: accepted, nothing
+ * is staged (a control staged earlier for the same step is withdrawn).  Otherwise the words travel to the device NOW, on the context's
+ * stream, through pinned staging that is not reused before its copy has completed — so that kernels enqueued before the step
+ * (stvo_seq_restart_fast_dev) read them.  No synchronisation.  A step that carries a control gives up the key-line stage ahead and the
+ * event-free fork of single-stream operation, and adds two small launches; every other step is enqueued exactly as before. */
+#define STVO_STREAM_RUN 0
+#define STVO_STREAM_RESTART 1
+#define STVO_STREAM_PARK 2
+int stvo_seq_control_next_step(stvo_seq* seq, const int32_t* ctl_host /* [B] */);
+/* th_dev[b] = th0 (1 .. 254) for the streams the STAGED control marks RESTART, enqueued on the context's stream: the FAST threshold is
+ * orb_fast_th again before the restart frame is detected (:38 precedes :41-42), so call it before that detection.  Nothing is
+ * launched when nothing is staged.  stvo_seq_adapt_fast_dev behind a step that carried a control leaves the thresholds of its RESTART
+ * and PARK streams alone (initialize has no updateFrame). */
+int stvo_seq_restart_fast_dev(stvo_seq* seq, int32_t* th_dev /* [B] */, int th0);
+
 /* ---- LBD line descriptor (first half) ------------------------------------------------------- */
 
 /* Replaces  BinaryDescriptor::createBinaryDescriptor()->compute(img, lines, ldesc)  as called by StereoFrame::detectLineFeatures

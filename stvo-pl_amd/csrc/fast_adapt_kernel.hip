@@ -6,10 +6,7 @@
 namespace stvo {
 namespace {
 
-__global__ __launch_bounds__(64) void fast_adapt_kernel(int B, const stvo_pose_result* __restrict__ results, stvo_fast_adapt p, int32_t* __restrict__ th) {
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= B) return;
-    const stvo_pose_result& r = results[b];
+__device__ __forceinline__ void fast_adapt_stream(const stvo_pose_result& r, const stvo_fast_adapt& p, int32_t* __restrict__ th, int b) {
     // :75 — curr_frame->DT == Matrix4d::Identity(): every element compares equal (a rejected pose is exactly I, :385)
     bool ident = true;
     for (int i = 0; i < 16; ++i) ident = ident && r.T[i] == ((i % 5 == 0) ? 1.0 : 0.0);
@@ -25,10 +22,27 @@ __global__ __launch_bounds__(64) void fast_adapt_kernel(int B, const stvo_pose_r
     else if (steps > 0) th[b] = min(p.max_th, moved);
 }
 
+__global__ __launch_bounds__(64) void fast_adapt_kernel(int B, const stvo_pose_result* __restrict__ results, stvo_fast_adapt p, int32_t* __restrict__ th) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    fast_adapt_stream(results[b], p, th, b);
+}
+
+// behind a step that carried a control (stvo_seq_control_next_step): initialize() has no updateFrame(), and a parked stream has no frame
+__global__ __launch_bounds__(64) void fast_adapt_ctl_kernel(int B, const stvo_pose_result* __restrict__ results, stvo_fast_adapt p, int32_t* __restrict__ th,
+                                                            const int32_t* __restrict__ ctl) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B || ctl[b] != STVO_STREAM_RUN) return;
+    fast_adapt_stream(results[b], p, th, b);
+}
+
 }  // namespace
 
-void launch_fast_adapt(hipStream_t s, int B, const stvo_pose_result* results, const stvo_fast_adapt& prm, int32_t* th) {
-    hipLaunchKernelGGL(fast_adapt_kernel, dim3((B + 63) / 64), dim3(64), 0, s, B, results, prm, th);
+void launch_fast_adapt(hipStream_t s, int B, const stvo_pose_result* results, const stvo_fast_adapt& prm, int32_t* th, const int32_t* ctl) {
+    if (ctl)
+        hipLaunchKernelGGL(fast_adapt_ctl_kernel, dim3((B + 63) / 64), dim3(64), 0, s, B, results, prm, th, ctl);
+    else
+        hipLaunchKernelGGL(fast_adapt_kernel, dim3((B + 63) / 64), dim3(64), 0, s, B, results, prm, th);
 }
 
 }  // namespace stvo

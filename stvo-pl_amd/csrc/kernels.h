@@ -305,12 +305,27 @@ void launch_grid_range_debug(hipStream_t s, const GridBatch& g);  // test hook, 
 
 // StereoFrameHandler::updateFrame's adaptive FAST rule for B streams, one lane per stream (fast_adapt_kernel.hip): th[b] moves by what
 // results[b] says.  `results` may be device memory or the pinned block a zero-copy step writes its results to.
-void launch_fast_adapt(hipStream_t s, int B, const stvo_pose_result* results, const stvo_fast_adapt& prm, int32_t* th);
+// ctl ([B] device, or nullptr = exactly the launch above all): the control words of the step the results come from (stvo_seq_control_next_step);
+// the thresholds of the streams that did not RUN stay.
+void launch_fast_adapt(hipStream_t s, int B, const stvo_pose_result* results, const stvo_fast_adapt& prm, int32_t* th, const int32_t* ctl = nullptr);
 
 // Trajectory and key-frame decision for B streams, one lane per stream (traj_kernel.hip): state[b] advances by results[b] (T, cov, status),
 // records (may be null) [B] takes what the update leaves for the caller.  `results` as for launch_fast_adapt.
 void launch_traj_init(hipStream_t s, int B, stvo_traj_state* state);
+// ctl ([B] device, or nullptr = the update for every stream, by the kernel that has always run it): the control words of the step the
+// results come from.  RESTART: state[b] becomes what launch_traj_init writes, PARK: state[b] stays, bit for bit; the record of either is
+// all-zero (frame == 0: no pose in this step).
 void launch_traj_update(hipStream_t s, int B, const stvo_pose_result* results, const stvo_traj_params& prm, stvo_traj_state* state,
-                        stvo_traj_record* records);
+                        stvo_traj_record* records, const int32_t* ctl = nullptr);
+
+// The per-stream control word of the device-resident pipeline (stream_control.hip).  ctl: [B] device, STVO_STREAM_*.
+// pre: in front of the f2f stage — the streams that do not RUN present an empty previous stereo set (counts 0, their f2f match rows -1).
+void launch_stream_ctl_pre(hipStream_t s, int B, const int32_t* ctl, int32_t* n_prev, int32_t* nl_prev, int32_t* m12p, int K, int32_t* m12l, int M);
+// post: behind the pose kernel — their result record all-zero, their motion-model seed (motion_T, may be null) the identity, their
+// inlier rows (inl_p / inl_l, may be null) -1.  results / inl_*: device memory or the pinned blocks the pose kernel wrote.
+void launch_stream_ctl_post(hipStream_t s, int B, const int32_t* ctl, stvo_pose_result* results, double* motion_T, int32_t* inl_p, int K,
+                            int32_t* inl_l, int M);
+// th[b] = th0 for the RESTART streams
+void launch_fast_restart(hipStream_t s, int B, const int32_t* ctl, int32_t* th, int th0);
 
 }  // namespace stvo

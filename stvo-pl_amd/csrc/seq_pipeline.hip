@@ -594,6 +594,17 @@ struct stvo_seq {
     stvo_traj_params traj_prm{};
     int traj_log_steps = 0;
     unsigned long long traj_steps = 0;         // tracked steps enqueued so far
+    // per-stream control of the NEXT step (stvo_seq_control_next_step; stream_control.hip): nothing of it exists until a control with a
+    // word other than RUN is staged.  Two device copies: the one being staged for the next step, and the one the last step consumed, which
+    // stvo_seq_adapt_fast_dev behind that step still reads while a caller may already stage the next.  Every reader and the copy that fills
+    // them run on the context's stream.  Two pinned staging blocks used alternately, each with an event behind the copy that read it.
+    int32_t* d_ctl[2] = {nullptr, nullptr};
+    int32_t* ctl_stage[2] = {nullptr, nullptr};
+    hipEvent_t ev_ctl[2] = {nullptr, nullptr};
+    bool ctl_stage_busy[2] = {false, false};
+    int ctl_stage_next = 0, ctl_next = 0;   // the staging block / device copy the next stvo_seq_control_next_step fills
+    bool ctl_staged = false;                // d_ctl[ctl_next] holds a control for the next step
+    const int32_t* last_ctl = nullptr;      // the control the last enqueued step carried out (device), or nullptr
     long long* d_prof = nullptr;   // STVO_POSE_PROF (developer aid): [B][16] phase ticks of the last pose launch, printed by stvo_seq_read
     char* dev = nullptr;     // one allocation, carved below
     size_t dev_bytes = 0;
@@ -985,6 +996,10 @@ int stvo_seq_destroy(stvo_seq* s) {
     if (s->d_motion_T) (void)hipFree(s->d_motion_T);
     if (s->d_traj_state) (void)hipFree(s->d_traj_state);
     if (s->d_traj_ring) (void)hipFree(s->d_traj_ring);
+    if (s->d_ctl[0]) (void)hipFree(s->d_ctl[0]);   // (one allocation for both copies, likewise the staging blocks)
+    if (s->ctl_stage[0]) (void)hipHostFree(s->ctl_stage[0]);
+    for (auto e : s->ev_ctl)
+        if (e) (void)hipEventDestroy(e);
     if (s->line_stream) {
         (void)hipStreamSynchronize(s->line_stream);
         (void)hipStreamDestroy(s->line_stream);
@@ -1146,6 +1161,7 @@ namespace {
 
 struct StepFlags {
     bool lines_now, lines_prev, track;
+    const int32_t* ctl;  // [B] device: the control words this step carries out (only a step that tracks does), or nullptr
 };
 
 // The values a step drew from the epoch counters for the flags it publishes; stvo_seq_step_dev commits them, with the plan, only when
@@ -1165,6 +1181,7 @@ struct StepEnq {
     const stvo::SeqDev& d;
     stvo_seq::Set &cs, &ps;  // the stereo sets the step builds / tracks against
     int32_t* m12l_use;       // the copy of the key-line match indices of this step
+    const int32_t* ctl;      // StepFlags::ctl
     void mark(int k, hipStream_t q) const {
         if (tev && !(p.light && k < 2)) (void)hipEventRecord(tev[k], q);
     }
@@ -1200,6 +1217,7 @@ void gather_step_facts(const stvo_seq* s, int slot, const StepFlags& fl, bool ti
     f.has_points = s->op.has_points; f.has_lines = s->op.has_lines; f.best_lr_matches = s->mp.best_lr_matches;
     f.lines_now = fl.lines_now; f.lines_prev = fl.lines_prev; f.track = fl.track;
     f.frame_idx = s->frame_idx;
+    f.has_control = fl.ctl != nullptr;
     f.raw_split = s->raw_split[slot]; f.raw_max_lines = s->raw_max_lines[slot];
     f.set_lines_cap_prev = s->set_lines_cap[s->prev_set()]; f.set_lines_cap_cur = s->set_lines_cap[s->cur];
     f.st_dirty = s->st_dirty; f.fetch = s->fetch; f.zero_copy = s->zero_copy;
@@ -1374,6 +1392,9 @@ int StepEnq::pose(StepPub& pub) const {
     mark(8, st);
     TRY(stvo::launch_pose(st, a));
     mark(9, st);
+    // the one place the results are written: behind it, the streams that restart or are parked read as "no pose in this step"
+    if (ctl)
+        stvo::launch_stream_ctl_post(st, B, ctl, a.results, s->d_motion_T, s->fetch ? a.inl_p_out : nullptr, s->K, s->fetch ? a.inl_l_out : nullptr, s->M);
     if (p.inl_copy) stvo::launch_copy16(st, s->inlp, s->fetch_host + s->m12_span, s->inl_span);
     return STVO_OK;
 }
@@ -1423,7 +1444,10 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, stvo::StepPlan&
     const stvo::StepPlan& p = plan;
     // ---- enqueue
     d.zero_nl = p.zero_nl ? 1 : 0;
-    const StepEnq e{s, ctx, p, tev, ctx->stream, p.par ? s->line_stream : ctx->stream, d, cs, s->set[s->prev_set()], p.use_alt_m12l ? s->m12l_alt : s->m12l};
+    const StepEnq e{s, ctx, p, tev, ctx->stream, p.par ? s->line_stream : ctx->stream, d, cs, s->set[s->prev_set()], p.use_alt_m12l ? s->m12l_alt : s->m12l, fl.ctl};
+    // a control: the streams that restart or are parked present no previous features.  First on the point stream — behind the previous
+    // step's pose kernel, the last reader of these counts, and in front of every event the line stream waits for in this step (step_plan.h)
+    if (fl.ctl) stvo::launch_stream_ctl_pre(e.st, s->B, fl.ctl, e.ps.n, e.ps.nl, s->m12p, s->K, e.m12l_use, s->M);
     if (p.fork_at_start) {
         HIP_TRY(ctx, hipEventRecord(s->ev_fork, e.st));
         HIP_TRY(ctx, hipStreamWaitEvent(e.sl, s->ev_fork, 0));
@@ -1446,6 +1470,8 @@ int stvo_seq_step_dev(stvo_seq* s, int slot) {
     fl.lines_now = s->op.has_lines && s->raw_lines[slot];
     fl.lines_prev = s->op.has_lines && s->set_lines[s->prev_set()];
     fl.track = s->frame_idx > 0;
+    // (the pipeline's own first step tracks nothing and stvo_seq_read zeroes its results: a control staged for it is consumed without effect)
+    fl.ctl = (s->ctl_staged && fl.track) ? s->d_ctl[s->ctl_next] : nullptr;
     {   // the grid buffers of this step (stvo_seq::cells_buf), and the line stream behind every upload the point stream holds
         const stvo_seq::CellsBuf& cb = s->cells_buf[s->frame_idx & 1];
         s->d.pstart = cb.pstart; s->d.pperm = cb.pperm; s->d.pcell = cb.pcell; s->d.plperm = cb.plperm; s->d.plstart = cb.plstart;
@@ -1469,11 +1495,16 @@ int stvo_seq_step_dev(stvo_seq* s, int slot) {
     s->last_slot = slot;
     s->cur = (s->cur + 1) % 3;  // updateFrame: curr becomes prev
     s->frame_idx++;
+    s->last_ctl = fl.ctl;
+    if (s->ctl_staged) {  // one-shot: the next step is all-RUN again, the next control goes to the other device copy
+        s->ctl_staged = false;
+        s->ctl_next ^= 1;
+    }
     if (s->d_traj_state && fl.track) {  // the trajectory behind the pose kernel, reading the results where PoseArgs::results pointed
         // (the step above is committed: a launch that fails here returns its error from a step that counts as taken, ring row included)
         const stvo_pose_result* res = s->zero_copy ? reinterpret_cast<const stvo_pose_result*>(s->out_host) : s->results;
         stvo::launch_traj_update(ctx->stream, s->B, res, s->traj_prm, s->d_traj_state,
-                                 s->d_traj_ring + (size_t)(s->traj_steps % (unsigned long long)s->traj_log_steps) * s->B);
+                                 s->d_traj_ring + (size_t)(s->traj_steps % (unsigned long long)s->traj_log_steps) * s->B, fl.ctl);
         s->traj_steps++;
         return check_launch(ctx);
     }
@@ -1566,7 +1597,56 @@ int stvo_seq_adapt_fast_dev(stvo_seq* s, const stvo_fast_adapt* prm, int32_t* th
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // where seq_enqueue_step pointed PoseArgs::results
     const stvo_pose_result* res = s->zero_copy ? reinterpret_cast<const stvo_pose_result*>(s->out_host) : s->results;
-    stvo::launch_fast_adapt(ctx->stream, s->B, res, *prm, th_dev);
+    stvo::launch_fast_adapt(ctx->stream, s->B, res, *prm, th_dev, s->last_ctl);
+    return check_launch(ctx);
+}
+
+// Per-stream control of the next step (stvo_hip.h).  Validated before anything changes; the words reach the device now, in stream order.
+int stvo_seq_control_next_step(stvo_seq* s, const int32_t* ctl_host) {
+    if (!s || !ctl_host) return STVO_ERR_INVALID_ARG;
+    bool any = false;
+    for (int b = 0; b < s->B; ++b) {
+        if (ctl_host[b] < STVO_STREAM_RUN || ctl_host[b] > STVO_STREAM_PARK) return STVO_ERR_INVALID_ARG;
+        any = any || ctl_host[b] != STVO_STREAM_RUN;
+    }
+    if (!any) {  // all-RUN: nothing to stage, and nothing staged stays
+        s->ctl_staged = false;
+        return STVO_OK;
+    }
+    stvo_ctx* ctx = s->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)s->B * sizeof(int32_t), span = (bytes + 255) & ~size_t(255);
+    if (!s->d_ctl[0]) {  // first use
+        HIP_TRY(ctx, hipMalloc((void**)&s->d_ctl[0], 2 * span));
+        s->d_ctl[1] = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(s->d_ctl[0]) + span);
+    }
+    if (!s->ctl_stage[0]) {
+        HIP_TRY(ctx, hipHostMalloc((void**)&s->ctl_stage[0], 2 * span, hipHostMallocDefault));
+        s->ctl_stage[1] = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(s->ctl_stage[0]) + span);
+    }
+    for (auto& e : s->ev_ctl)
+        if (!e) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    const int hb = s->ctl_stage_next;
+    if (s->ctl_stage_busy[hb]) {  // the copy that last read this block (two calls ago): done long since, unless nothing has synchronised
+        HIP_TRY(ctx, hipEventSynchronize(s->ev_ctl[hb]));
+        s->ctl_stage_busy[hb] = false;
+    }
+    std::memcpy(s->ctl_stage[hb], ctl_host, bytes);
+    HIP_TRY(ctx, hipMemcpyAsync(s->d_ctl[s->ctl_next], s->ctl_stage[hb], bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev_ctl[hb], ctx->stream));
+    s->ctl_stage_busy[hb] = true;
+    s->ctl_stage_next = hb ^ 1;
+    s->ctl_staged = true;
+    return STVO_OK;
+}
+
+// initialize()'s orb_fast_th (:38) for the streams the staged control restarts, in front of the detection of their first frame.
+int stvo_seq_restart_fast_dev(stvo_seq* s, int32_t* th_dev, int th0) {
+    if (!s || !th_dev || th0 < 1 || th0 > 254) return STVO_ERR_INVALID_ARG;
+    if (!s->ctl_staged) return STVO_OK;
+    stvo_ctx* ctx = s->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    stvo::launch_fast_restart(ctx->stream, s->B, s->d_ctl[s->ctl_next], th_dev, th0);
     return check_launch(ctx);
 }
 

@@ -44,6 +44,9 @@ struct StepFacts {
     bool grid_points_fused_ok = false, match_small_ok_K = false, match_small_ok_M = false, pose_inline_sync_ok = false,
          pose_batch_kernel_selected = false, pose_start_flag_ok = false;
     int pose2p_waves_per_pair = 0;
+    // the step tracks AND carries a per-stream control (stvo_seq_control_next_step): a kernel at the very start of the step, on the point
+    // stream, empties the previous stereo set of the streams that restart or are parked.  false (every other step): every plan as before.
+    bool has_control = false;
     DebugSwitches sw = switches_unset();
 };
 
@@ -123,7 +126,9 @@ inline StepPlan plan_step(const StepFacts& f, const StepHistory& h, LdsFits&& ld
     p.mid_fork = p.par && B >= 64;
     // single-stream operation: the upload copied the key-line arrays ON the line stream and nothing the line stream would have to wait
     // for has been enqueued on the point stream since the last synchronisation — the step forks without an event
-    const bool fork_free = p.par && f.raw_split && !f.st_dirty;
+    // (a step with a control forks WITH an event: the line stream's f2f match reads the key-line count the control kernel cleared on the
+    // point stream)
+    const bool fork_free = p.par && f.raw_split && !f.st_dirty && !f.has_control;
     p.fork_at_start = p.par && !p.mid_fork && !fork_free;
     p.line_forked = p.par && (p.mid_fork || !fork_free);
     p.zero_nl = !f.lines_now && f.has_points;
@@ -147,8 +152,13 @@ inline StepPlan plan_step(const StepFacts& f, const StepHistory& h, LdsFits&& ld
         // last read two steps ago, and the line stream's work of the previous step waited for an event the point stream recorded
         // after that: sl_forked_frame), (b) the line stream has been made to wait for every upload enqueued on the point stream
         // (stvo_seq_step_dev), (c) everything else the kernel reads is the resident slot.  STVO_CELLS_AHEAD=0: in the point stream.
+        // Never in a step with a control, and with it (below) never the key-line stage ahead: the key-line f2f match of such a step must see
+        // the previous set's key-line counts as the control kernel left them, and that kernel runs on the point stream behind
+        // optimizePose(k - 1), which still reads the set before.  So the line stream does nothing in such a step before it has waited for the
+        // step's OWN fork event, recorded behind the control kernel.  The next step may run ahead again: the event it waits for is this
+        // step's, and nothing its key-line kernels touch is written by the control kernels.
         p.cells_ahead = p.mid_fork && p.lean_cells && !p.fused_cells && (!tev || p.light) && f.cells_differ && h.sl_forked_frame == last &&
-                        f.sw.cells_ahead != 0;
+                        f.sw.cells_ahead != 0 && !f.has_control;
         // key-line stage ahead (stvo_seq::m12l_alt has the whole argument): the line stream waits for the PREVIOUS step's fork event — in
         // front of the cells kernel, whose output copy the matcher of two steps ago read — and not for this step's.  Safe only while the
         // second copy of the key-line match indices is in use (alt_ok) and after a step that recorded the fork event (fork_rec_frame).

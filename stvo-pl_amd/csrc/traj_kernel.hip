@@ -14,12 +14,33 @@ __global__ __launch_bounds__(64) void traj_init_kernel(int B, stvo_traj_state* _
     pm::traj_init(state[b]);
 }
 
+static_assert(sizeof(stvo_traj_record) % sizeof(unsigned long long) == 0, "a record is zeroed in 8-byte words");
+
 __global__ __launch_bounds__(64) void traj_update_kernel(int B, const stvo_pose_result* __restrict__ results, stvo_traj_params prm,
                                                          stvo_traj_state* __restrict__ state, stvo_traj_record* __restrict__ records) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
     const stvo_pose_result& r = results[b];
     pm::traj_update(state[b], r.T, r.cov, r.status, prm, records ? records + b : nullptr);
+}
+
+// behind a step that carried a control (stvo_seq_control_next_step): `initialize` for the RESTART streams, nothing for the parked ones
+__global__ __launch_bounds__(64) void traj_update_ctl_kernel(int B, const stvo_pose_result* __restrict__ results, stvo_traj_params prm,
+                                                             stvo_traj_state* __restrict__ state, stvo_traj_record* __restrict__ records,
+                                                             const int32_t* __restrict__ ctl) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const int c = ctl[b];
+    if (c == STVO_STREAM_RUN) {
+        const stvo_pose_result& r = results[b];
+        pm::traj_update(state[b], r.T, r.cov, r.status, prm, records ? records + b : nullptr);
+        return;
+    }
+    if (c == STVO_STREAM_RESTART) pm::traj_init(state[b]);
+    if (records) {  // frame == 0: no pose in this step
+        unsigned long long* w = reinterpret_cast<unsigned long long*>(records + b);
+        for (int i = 0; i < (int)(sizeof(stvo_traj_record) / sizeof(unsigned long long)); ++i) w[i] = 0ull;
+    }
 }
 
 }  // namespace
@@ -29,8 +50,11 @@ void launch_traj_init(hipStream_t s, int B, stvo_traj_state* state) {
 }
 
 void launch_traj_update(hipStream_t s, int B, const stvo_pose_result* results, const stvo_traj_params& prm, stvo_traj_state* state,
-                        stvo_traj_record* records) {
-    hipLaunchKernelGGL(traj_update_kernel, dim3((B + 63) / 64), dim3(64), 0, s, B, results, prm, state, records);
+                        stvo_traj_record* records, const int32_t* ctl) {
+    if (ctl)
+        hipLaunchKernelGGL(traj_update_ctl_kernel, dim3((B + 63) / 64), dim3(64), 0, s, B, results, prm, state, records, ctl);
+    else
+        hipLaunchKernelGGL(traj_update_kernel, dim3((B + 63) / 64), dim3(64), 0, s, B, results, prm, state, records);
 }
 
 }  // namespace stvo

@@ -30,13 +30,14 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_rectify_create", "stvo_rectify_create_from_maps", "stvo_rectify_destroy", "stvo_rectify_camera", "stvo_rectify_images",
            "stvo_rectify_images_dev", "stvo_orb_set_fast_thresholds", "stvo_orb_set_fast_thresholds_dev", "stvo_fast_adapt_dev",
            "stvo_seq_adapt_fast_dev", "stvo_traj_init_dev", "stvo_traj_update_dev", "stvo_seq_set_trajectory", "stvo_seq_read_trajectory",
-           "stvo_seq_trajectory_state_dev", "stvo_seq_read_trajectory_state"]
+           "stvo_seq_trajectory_state_dev", "stvo_seq_read_trajectory_state", "stvo_seq_control_next_step", "stvo_seq_restart_fast_dev"]
 
 SEQ_NSTAGE = 5  # include/stvo_hip.h: STVO_SEQ_NSTAGE
 SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_check", "pose")
 # include/stvo_hip.h: STVO_SCHED_* (pose_kernel: 0 none, 1 latency, 2 batch; pose_waves: 2 / 4 for the batch kernel; the rest 0 / 1)
 SEQ_SCHEDULE_FIELDS = ("pose_kernel", "pose_waves", "fused_cells", "cells_ahead", "lines_ahead", "gate", "mid_fork", "line_fused")
 SCHED_POSE_LATENCY, SCHED_POSE_BATCH = 1, 2
+STREAM_RUN, STREAM_RESTART, STREAM_PARK = 0, 1, 2  # include/stvo_hip.h: STVO_STREAM_* (Sequences.control_next_step)
 
 u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
@@ -224,6 +225,8 @@ def load():
     L.stvo_seq_read_trajectory.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
     L.stvo_seq_trajectory_state_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.stvo_seq_read_trajectory_state.argtypes = [C.c_void_p, C.c_void_p]
+    L.stvo_seq_control_next_step.argtypes = [C.c_void_p, C.c_void_p]
+    L.stvo_seq_restart_fast_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.stvo_orb_detect_levels.argtypes = [C.c_void_p, u8p, f32p, f32p, f32p, i32p, u8p, i32p, i32p]
     L.stvo_orb_detect_levels_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 8
     L.stvo_lbd_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -772,6 +775,22 @@ class Sequences:
         if str(th.dtype) != "torch.int32" or not th.is_cuda or not th.is_contiguous() or th.numel() != self.B:
             raise ValueError("Sequences.adapt_fast_dev: th must be a contiguous int32 device tensor of B entries")
         self.ctx._chk(self.ctx.lib.stvo_seq_adapt_fast_dev(self.h, C.byref(prm), th.data_ptr()))
+
+    def control_next_step(self, ctl):
+        """One control word per stream for the NEXT step only (stvo_seq_control_next_step): STREAM_RUN, STREAM_RESTART (the frame in
+        the slot starts a new sequence: StereoFrameHandler::initialize) or STREAM_PARK (no sequence at the moment: nothing of the
+        stream is reported or advanced).  ctl: B integers; staged on the context's stream at once, no synchronisation."""
+        ctl = np.ascontiguousarray(np.asarray(ctl).reshape(-1), dtype=np.int32)
+        if ctl.size != self.B:
+            raise ValueError("Sequences.control_next_step: one control word per stream")
+        self.ctx._chk(self.ctx.lib.stvo_seq_control_next_step(self.h, _ptr(ctl)))
+
+    def restart_fast_dev(self, th, th0):
+        """th[b] = th0 for the streams the staged control restarts (stvo_seq_restart_fast_dev), before their first frame is detected;
+        th = torch int32 [B] device tensor.  Nothing is launched when no control is staged."""
+        if str(th.dtype) != "torch.int32" or not th.is_cuda or not th.is_contiguous() or th.numel() != self.B:
+            raise ValueError("Sequences.restart_fast_dev: th must be a contiguous int32 device tensor of B entries")
+        self.ctx._chk(self.ctx.lib.stvo_seq_restart_fast_dev(self.h, th.data_ptr(), int(th0)))
 
     def set_trajectory(self, prm, log_steps=1):
         """Trajectory and key-frame decision per stream behind every tracked step (stvo_seq_set_trajectory): prm = traj_params(...) or

@@ -94,6 +94,7 @@ class ImagePipeline:
             self.fast_th = torch.full((B,), fast_threshold, dtype=torch.int32, device=dev)
             torch.cuda.current_stream(dev).synchronize()  # the fill ran on torch's stream, the library uses its own
             self.orb.set_fast_thresholds(self.fast_th)  # n_th = B on 2 B images: left image b and right image B + b share entry b
+        self.fast_threshold = fast_threshold
         self.ff = ff  # (without a line detector every line pointer stays NULL: no key-lines; oct_ll NULL: one octave)
         self.slot = 0
 
@@ -103,9 +104,16 @@ class ImagePipeline:
         self.img[:B].copy_(torch.as_tensor(left).reshape(B, self.rows, self.cols), non_blocking=True)
         self.img[B:].copy_(torch.as_tensor(right).reshape(B, self.rows, self.cols), non_blocking=True)
 
-    def enqueue(self, img_ptr=None):
+    def enqueue(self, img_ptr=None, control=None):
         """Detection + description of the 2 B resident images (or of the uint8 [2 B, rows, cols] device buffer at img_ptr: B left,
-        then B right), ingestion, one pipeline step — all asynchronous.  With a rectifier the images are raw and are rectified first."""
+        then B right), ingestion, one pipeline step — all asynchronous.  With a rectifier the images are raw and are rectified first.
+        control: None, or B words capi.STREAM_RUN / STREAM_RESTART / STREAM_PARK for this step (Sequences.control_next_step): staged
+        first, so that with adaptive_fast the restarted streams are detected at fast_threshold again (initialize sets orb_fast_th
+        before it detects); the rule at the end of the step leaves the thresholds of restarted and parked streams alone."""
+        if control is not None:
+            self.seq.control_next_step(control)
+            if self.adaptive_fast is not None:
+                self.seq.restart_fast_dev(self.fast_th, self.fast_threshold)
         ip = img_ptr if img_ptr is not None else self.img.data_ptr()
         if self.rectify is not None:
             side = self.B * self.rows * self.cols
@@ -124,11 +132,11 @@ class ImagePipeline:
             self.seq.adapt_fast_dev(self.adaptive_fast, self.fast_th)
         self.slot ^= 1
 
-    def push_images(self, left, right):
-        """One frame of every stream: (pose results [B], counts [B, 4]) like Sequences.push."""
+    def push_images(self, left, right, control=None):
+        """One frame of every stream: (pose results [B], counts [B, 4]) like Sequences.push.  control: as for enqueue."""
         self.set_images(left, right)
         torch.cuda.current_stream().synchronize()  # the copies above ran on torch's stream, the library uses its own
-        self.enqueue()
+        self.enqueue(control=control)
         return self.seq.read()
 
     def read_trajectory(self, n_last=1):
