@@ -381,6 +381,43 @@ int stvo_seq_control_next_step(stvo_seq* seq, const int32_t* ctl_host /* [B] */)
  * and PARK streams alone (initialize has no updateFrame). */
 int stvo_seq_restart_fast_dev(stvo_seq* seq, int32_t* th_dev /* [B] */, int th0);
 
+/* ---- feature tracks and key-frame sets per stream ------------------------------------------------------------------------- */
+
+/* What a consumer of new_kf needs beside the pose: the identity of every feature of a stream's current stereo set (stvo_track:
+ * which feature of the last key-frame it observes, since how many frames, whether the pose kernel kept it) and the stereo set of the
+ * stream's last key-frame itself, which the pipeline overwrites three steps later.  Off by default: nothing is allocated, nothing
+ * launched.  On: every step (the first included) ends with ONE launch on the context's stream, behind the pose kernel, the control
+ * kernel and the trajectory update.  Per stream, for key-points and key-lines alike, with i1 over the previous stereo set and
+ * i2 = m12[i1] its f2f match (what stvo_seq_fetch_matches reports):
+ *   matched i2     idx, kf of i1's record; age + 1 (saturating at 65535); inlier = the pose kernel's flag of i1 (what
+ *                  stvo_seq_fetch_inliers reports).  Several i1 naming one i2 (best_lr_matches off): the largest i1 wins;
+ *   unmatched i2   idx = i2, age 0, kf 0, inlier -1;
+ *   first step of the pipeline and RESTART (StereoFrameHandler::initialize):  idx = i2, age 0, kf 1, inlier -1;
+ *   PARK           idx = i2, age 0, kf 0, inlier -1 (the frame belongs to no sequence);
+ *   key-frame      the first step, RESTART, and a step whose trajectory record has new_kf = 1 (trajectory on with keyframes): the
+ *                  record keeps the values above, the state the NEXT step propagates from becomes idx = i2, age 0, kf 1 — and, with
+ *                  keyframe_sets, rows [0, n) of every array of the stream's current stereo set are copied byte for byte into the
+ *                  stream's key-frame set, then its header {n_pts, n_lines, frame = the pipeline step (0 = first), serial = the
+ *                  key-frame's number in its sequence, 1 for a sequence's first frame}.
+ * Without the trajectory there is no key-frame after a sequence's first frame.  Rows at or beyond a stream's count are never written.
+ * Memory: (2 + log_steps) x B x (K + M) records of 8 bytes (K, M = stvo_seq_strides; 20 KB per stream and row at 2048 / 512) plus,
+ * with keyframe_sets, B x (48 K + 152 M) bytes (about 176 KB per stream at 2048 / 512), zeroed on the context's stream.
+ * Only before the first step.  log_steps >= 1: on, the records of the last log_steps steps stay readable; log_steps == 0 (with
+ * keyframe_sets 0): off again.  A failed allocation returns STVO_ERR_HIP and leaves the feature off. */
+int stvo_seq_set_tracks(stvo_seq* seq, int keyframe_sets /* 0 | 1 */, int log_steps);
+/* The records of the last min(n_last, log_steps, steps) steps, oldest first: pts [n_last][B][K], lines [n_last][B][M],
+ * counts [n_last][B][2] = {stereo points, stereo lines} (host; each may be NULL); *n_got = how many steps.  Rows [0, count) of a
+ * stream are meaningful.  Synchronises the context's stream.  STVO_ERR_INVALID_ARG when the tracks are off. */
+int stvo_seq_read_tracks(stvo_seq* seq, int n_last, stvo_track* pts, stvo_track* lines, int32_t* counts, int32_t* n_got);
+/* Device pointers of the last step's row ([B][K], [B][M], [B][2]; each may be NULL), for kernels chained on the context's stream. */
+int stvo_seq_tracks_dev(stvo_seq* seq, const stvo_track** pts_dev, const stvo_track** lines_dev, const int32_t** counts_dev);
+/* The B key-frame headers, and one stream's key-frame set: the arrays and the capacity rule of stvo_seq_debug_stereo (hdr is written
+ * even when the set does not fit: STVO_ERR_CAPACITY).  Both synchronise the context's stream.  STVO_ERR_INVALID_ARG unless
+ * stvo_seq_set_tracks was called with keyframe_sets = 1. */
+int stvo_seq_keyframe_headers(stvo_seq* seq, stvo_kf_header* hdr /* [B] host */);
+int stvo_seq_read_keyframe(stvo_seq* seq, int b, stvo_kf_header* hdr, int32_t cap_pts, float* rc, uint8_t* desc, int32_t cap_lines,
+                           double* spl, double* epl, double* sP, double* eP, double* le, double* s2l, double* s2lm, uint8_t* ldesc);
+
 /* ---- LBD line descriptor (first half) ------------------------------------------------------- */
 
 /* Replaces  BinaryDescriptor::createBinaryDescriptor()->compute(img, lines, ldesc)  as called by StereoFrame::detectLineFeatures

@@ -205,6 +205,26 @@ typedef struct stvo_traj_record {
     int32_t frame;
 } stvo_traj_record;
 
+/* One feature of a stream's current stereo set as the handler's lists know it (stvo_seq_set_tracks), 8 bytes:
+ *   idx     PointFeature::idx / LineFeature::idx: handed from the previous frame's feature by the f2f match
+ *           (src/stereoFrameHandler.cpp:151,178), the feature's own position when nothing matched it (src/stereoFrame.cpp:151,165,350,384),
+ *           and the position again behind a key-frame (currFrameIsKF, :1190-1218);
+ *   age     f2f matches in a row that led to this feature since it was last numbered by position (saturates at 65535);
+ *   kf      1: idx names a feature of the stream's last key-frame (an observation of it), 0: a feature first seen after it;
+ *   inlier  the pose kernel's flag of the match that led here (1 / 0), -1 for a feature nothing matched. */
+typedef struct stvo_track {
+    int32_t idx;
+    uint16_t age;
+    uint8_t kf;
+    int8_t inlier;
+} stvo_track;
+
+/* What goes with a stream's key-frame set: the rows of the set that are valid, the pipeline step (0 = the first) whose stereo set
+ * it is, and the number of the key-frame in its sequence (the first frame is 1).  serial == 0: no key-frame set yet. */
+typedef struct stvo_kf_header {
+    int32_t n_pts, n_lines, frame, serial;
+} stvo_kf_header;
+
 /* A key-line as the LBD descriptor consumes it: the line_descriptor::KeyLine fields BinaryDescriptor::computeImpl copies into its
  * OctaveSingleLine (3rdparty/line_descriptor/src/binary_descriptor_custom.cpp:592-609), octave 0. */
 typedef struct stvo_keyline {

@@ -60,18 +60,54 @@ bool read_lines(std::ifstream& f, int n, std::vector<KeyLine>& kl, DescMat& d) {
     d.data.resize((size_t)n * 32);
     return n == 0 || rd(f, d.data.data(), (size_t)n * 32);
 }
+// --tracks: what a frame's current features say about the last key-frame — how many observe one of its features (kf = 1), how many of
+// those the pose kept as inliers, and the sum of the key-frame indices they name.  The same line on both routes.
+struct TrackLine {
+    int n_kf = 0, n_inl = 0;
+    long long idx_sum = 0;
+    void add(bool kf, bool inlier, int idx) {
+        if (!kf) return;
+        ++n_kf;
+        if (inlier) ++n_inl;
+        idx_sum += idx;
+    }
+};
+void print_tracks(int frame, const TrackLine& p, const TrackLine& l) {
+    std::printf("Tracks: %d\t points kf %d inliers %d idx %lld \t lines kf %d inliers %d idx %lld\n", frame, p.n_kf, p.n_inl, p.idx_sum, l.n_kf,
+                l.n_inl, l.idx_sum);
+}
+// The handler route: the mirror's lists carry idx; kf travels in a side array of the app, per stereo feature of the previous frame.
+template <class Features, class Matched>
+TrackLine follow_tracks(const std::vector<int32_t>& m12, const Features& curr, const Matched& matched, std::vector<uint8_t>& kf_prev) {
+    std::vector<uint8_t> kf_cur(curr.size(), 0);
+    std::vector<int8_t> inl_cur(curr.size(), -1);
+    auto it = matched.begin();
+    for (size_t i1 = 0; i1 < m12.size(); ++i1) {  // ascending: the last one that names a feature wins, as for idx
+        const int i2 = m12[i1];
+        if (i2 < 0) continue;
+        const bool inl = it != matched.end() ? (*it)->inlier : false;
+        if (it != matched.end()) ++it;
+        if ((size_t)i2 >= curr.size()) continue;
+        kf_cur[(size_t)i2] = i1 < kf_prev.size() ? kf_prev[i1] : 0;
+        inl_cur[(size_t)i2] = inl ? 1 : 0;
+    }
+    TrackLine t;
+    for (size_t i = 0; i < curr.size(); ++i) t.add(kf_cur[i] != 0, inl_cur[i] == 1, curr[i]->idx);
+    kf_prev.swap(kf_cur);
+    return t;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::cerr << "usage: imagesStVO_synth <sequence.bin> <results.bin> [--preset kitti|euroc|default] [-c cfg] "
-                     "[--mode m] [-n frames]\n";
+                     "[--mode m] [-n frames] [--device-pipeline] [--keyframes] [--tracks]\n";
         return -1;
     }
     std::string preset = "kitti", cfg, dataset_params;
     int mode = 0, max_frames = 0, frame_offset = 0, frame_step = 1;
     bool keyframes = false;
-    bool device_pipeline = false, no_lines = false;
+    bool device_pipeline = false, no_lines = false, tracks = false;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--preset") && i + 1 < argc) preset = argv[++i];
         else if (!std::strcmp(argv[i], "-c") && i + 1 < argc) cfg = argv[++i];
@@ -80,6 +116,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--device-pipeline")) device_pipeline = true;
         else if (!std::strcmp(argv[i], "--keyframes")) keyframes = true;
         else if (!std::strcmp(argv[i], "--no-lines")) no_lines = true;
+        else if (!std::strcmp(argv[i], "--tracks")) tracks = true;
         else if (!std::strcmp(argv[i], "--dataset-params") && i + 1 < argc) dataset_params = argv[++i];
         else if (!std::strcmp(argv[i], "-o") && i + 1 < argc) frame_offset = std::atoi(argv[++i]);  // imagesStVO.cpp:158-159
         else if (!std::strcmp(argv[i], "-s") && i + 1 < argc) frame_step = std::atoi(argv[++i]);    // imagesStVO.cpp:162-163
@@ -171,6 +208,17 @@ int main(int argc, char** argv) {
             std::cerr << "stvo_seq_set_trajectory failed: " << stvo_ctx_last_error(ctx) << std::endl;
             return -2;
         }
+        // --tracks: the feature identities of every frame from the device (stvo_seq_set_tracks), one row of records
+        int32_t trK = 0, trM = 0;
+        std::vector<stvo_track> tr_pts, tr_lines;
+        if (tracks) {
+            if (stvo_seq_set_tracks(seq, 0, 1) != STVO_OK || stvo_seq_strides(seq, &trK, &trM) != STVO_OK) {
+                std::cerr << "stvo_seq_set_tracks failed: " << stvo_ctx_last_error(ctx) << std::endl;
+                return -2;
+            }
+            tr_pts.resize((size_t)trK);
+            tr_lines.resize((size_t)trM);
+        }
         double t_sum = 0.0;
         std::vector<double> t_all;
         for (int k = 0; k < n_frames; ++k) {
@@ -224,6 +272,17 @@ int main(int argc, char** argv) {
             wr(out, tr.Tfw_cov, 36);
             const int32_t z2[2] = {0, tr.new_kf};  // (no adaptive FAST threshold on feature files; the spare word as on the handler path)
             wr(out, z2, 2);
+            if (tracks) {
+                int32_t tc[2] = {0, 0}, n_rows = 0;
+                if (stvo_seq_read_tracks(seq, 1, tr_pts.data(), tr_lines.data(), tc, &n_rows) != STVO_OK || n_rows != 1) {
+                    std::cerr << "stvo_seq_read_tracks failed: " << stvo_ctx_last_error(ctx) << std::endl;
+                    return -3;
+                }
+                TrackLine lp, ll;
+                for (int i = 0; i < tc[0]; ++i) lp.add(tr_pts[i].kf != 0, tr_pts[i].inlier == 1, tr_pts[i].idx);
+                for (int i = 0; i < tc[1]; ++i) ll.add(tr_lines[i].kf != 0, tr_lines[i].inlier == 1, tr_lines[i].idx);
+                print_tracks(k, lp, ll);
+            }
         }
         if (n_frames > 1) {
             // the median is the steady-state figure: the first frames of a process pay for code-object loading and allocations
@@ -250,6 +309,7 @@ int main(int argc, char** argv) {
     // -o / -s / -n as the reference's Dataset applies them (src/dataset.cpp: skip `offset` frames, then take every `step`-th
     // frame, at most `n` of them): frames that are not selected are read and dropped
     int frame_counter = -1, n_done = 0;
+    std::vector<uint8_t> kf_pt, kf_ls;  // --tracks: kf of the stereo features of prev_frame
     for (int file_idx = 0; file_idx < n_file_frames; ++file_idx) {
         FrameFeatures feat;
         feat.img_cols = cols;
@@ -289,6 +349,8 @@ int main(int argc, char** argv) {
         if (frame_counter == 0) {
             if (image_file) StVO->initialize(gl, gr, 0);  // initialize(img_l, img_r, 0), imagesStVO.cpp:90
             else StVO->initialize(feat, 0);
+            kf_pt.assign(StVO->prev_frame->stereo_pt.size(), 1);  // initialize: the first frame is a key-frame
+            kf_ls.assign(StVO->prev_frame->stereo_ls.size(), 1);
             continue;
         }
         const auto t0 = std::chrono::high_resolution_clock::now();  // timer.start()  (imagesStVO.cpp:95)
@@ -325,10 +387,18 @@ int main(int argc, char** argv) {
         wr(out, StVO->curr_frame->Tfw_cov.m, 36);
         // the key-frame decision PL-SLAM drives on top of the odometry (src/stereoFrameHandler.cpp:1136-1218): the pose of the
         // frame has been written above; a new key-frame restarts the map frame (Tfw = I) for the frames that follow
+        TrackLine lp, ll;
+        if (tracks) {  // before currFrameIsKF renumbers: the frame's record keeps the values from before the reset
+            lp = follow_tracks(StVO->f2f_m12_pt, StVO->curr_frame->stereo_pt, StVO->matched_pt, kf_pt);
+            ll = follow_tracks(StVO->f2f_m12_ls, StVO->curr_frame->stereo_ls, StVO->matched_ls, kf_ls);
+        }
         if (keyframes && StVO->needNewKF()) {
             StVO->currFrameIsKF();
             new_kf = 1;
+            std::fill(kf_pt.begin(), kf_pt.end(), 1);
+            std::fill(kf_ls.begin(), kf_ls.end(), 1);
         }
+        if (tracks) print_tracks(frame_counter, lp, ll);
         StVO->updateFrame();
         const int32_t fast = StVO->orb_fast_th;
         wr(out, &fast, 1);

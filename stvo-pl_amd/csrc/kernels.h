@@ -328,4 +328,34 @@ void launch_stream_ctl_post(hipStream_t s, int B, const int32_t* ctl, stvo_pose_
 // th[b] = th0 for the RESTART streams
 void launch_fast_restart(hipStream_t s, int B, const int32_t* ctl, int32_t* th, int th0);
 
+// Feature tracks and key-frame sets per stream (track_kernel.hip around track_update.h), one workgroup per stream, one launch per step.
+// The arrays of one stereo set of the pipeline, [B][K] / [B][M] rows each (seq_pipeline.hip: stvo_seq::Set).
+struct StereoSetPtrs {
+    float4* rc;
+    uint8_t* desc;
+    int32_t* n;
+    double *spl, *epl, *sP, *eP, *le, *s2l, *s2lm;
+    uint8_t* ldesc;
+    int32_t* nl;
+};
+struct TrackArgs {
+    int B, K, M;         // K <= STVO_POSE_MAX_POINTS, M <= STVO_POSE_MAX_LINES: the winners of a stream fit the kernel's LDS
+    int first;           // the pipeline's first step: every stream starts a sequence; nothing below up to `ctl` is read
+    const int32_t *n_prev, *nl_prev;  // [B] counts of the previous stereo set, as the f2f stage saw them (0 for a stream under a control)
+    const int32_t *m12p, *m12l;       // [B][K] / [B][M] f2f match of previous feature i1, or -1
+    const int32_t *inlp, *inll;       // [B][K] / [B][M] the pose kernel's flag of previous feature i1 (device memory or the pinned block)
+    const int32_t* ctl;               // [B] STVO_STREAM_* of this step, or nullptr = all RUN
+    const stvo_traj_record* traj;     // [B] the trajectory records of this step (new_kf is read), or nullptr = no trajectory
+    const int32_t *n_cur, *nl_cur;    // [B] counts of the current stereo set
+    const stvo_track *prev_p, *prev_l;  // state the step propagates from ...
+    stvo_track *next_p, *next_l;        // ... and leaves (another copy)
+    stvo_track *rec_p, *rec_l;          // the step's ring row
+    int32_t* rec_counts;                // [B][2] the counts that go with it
+    // key-frame sets (kf_hdr == nullptr: off): at a key-frame the stream's rows [0, n) of `cur` are copied to `kf`
+    StereoSetPtrs cur, kf;
+    stvo_kf_header* kf_hdr;             // [B]
+    int frame;                          // the pipeline step
+};
+void launch_track_update(hipStream_t s, const TrackArgs& a);
+
 }  // namespace stvo

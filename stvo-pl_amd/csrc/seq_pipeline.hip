@@ -605,6 +605,22 @@ struct stvo_seq {
     int ctl_stage_next = 0, ctl_next = 0;   // the staging block / device copy the next stvo_seq_control_next_step fills
     bool ctl_staged = false;                // d_ctl[ctl_next] holds a control for the next step
     const int32_t* last_ctl = nullptr;      // the control the last enqueued step carried out (device), or nullptr
+    // feature tracks and key-frame sets per stream (stvo_seq_set_tracks; track_kernel.hip): null = off.  d_tracks is one allocation of
+    // 2 + track_log_steps rows of [B][K] point records followed by [B][M] key-line records — rows 0 / 1 the state (step k reads copy
+    // (k + 1) & 1 and writes copy k & 1), row 2 + k % track_log_steps the record of step k — and behind them the ring's counts
+    // [track_log_steps][B][2].  d_kf is one allocation of B key-frame sets (the arrays of a Set without the counts) and their headers.
+    char* d_tracks = nullptr;
+    char* d_kf = nullptr;
+    int track_log_steps = 0;
+    unsigned long long track_steps = 0;     // steps enqueued with the tracks on
+    stvo::StereoSetPtrs kf_set{};
+    stvo_kf_header* d_kf_hdr = nullptr;
+    size_t track_row_bytes() const { return (size_t)B * ((size_t)K + (size_t)M) * sizeof(stvo_track); }
+    stvo_track* track_row_p(size_t row) const { return reinterpret_cast<stvo_track*>(d_tracks + row * track_row_bytes()); }
+    stvo_track* track_row_l(size_t row) const { return track_row_p(row) + (size_t)B * K; }
+    int32_t* track_counts(size_t ring_row) const {
+        return reinterpret_cast<int32_t*>(d_tracks + (size_t)(2 + track_log_steps) * track_row_bytes()) + ring_row * (size_t)B * 2;
+    }
     long long* d_prof = nullptr;   // STVO_POSE_PROF (developer aid): [B][16] phase ticks of the last pose launch, printed by stvo_seq_read
     char* dev = nullptr;     // one allocation, carved below
     size_t dev_bytes = 0;
@@ -996,6 +1012,8 @@ int stvo_seq_destroy(stvo_seq* s) {
     if (s->d_motion_T) (void)hipFree(s->d_motion_T);
     if (s->d_traj_state) (void)hipFree(s->d_traj_state);
     if (s->d_traj_ring) (void)hipFree(s->d_traj_ring);
+    if (s->d_tracks) (void)hipFree(s->d_tracks);
+    if (s->d_kf) (void)hipFree(s->d_kf);
     if (s->d_ctl[0]) (void)hipFree(s->d_ctl[0]);   // (one allocation for both copies, likewise the staging blocks)
     if (s->ctl_stage[0]) (void)hipHostFree(s->ctl_stage[0]);
     for (auto e : s->ev_ctl)
@@ -1394,7 +1412,10 @@ int StepEnq::pose(StepPub& pub) const {
     mark(9, st);
     // the one place the results are written: behind it, the streams that restart or are parked read as "no pose in this step"
     if (ctl)
-        stvo::launch_stream_ctl_post(st, B, ctl, a.results, s->d_motion_T, s->fetch ? a.inl_p_out : nullptr, s->K, s->fetch ? a.inl_l_out : nullptr, s->M);
+    {   // (the inlier rows of such streams matter to whoever reads them behind the step: the by-product fetch, the feature tracks)
+        const bool rows = s->fetch || s->d_tracks;
+        stvo::launch_stream_ctl_post(st, B, ctl, a.results, s->d_motion_T, rows ? a.inl_p_out : nullptr, s->K, rows ? a.inl_l_out : nullptr, s->M);
+    }
     if (p.inl_copy) stvo::launch_copy16(st, s->inlp, s->fetch_host + s->m12_span, s->inl_span);
     return STVO_OK;
 }
@@ -1459,6 +1480,49 @@ int seq_enqueue_step(stvo_seq* s, int slot, const StepFlags& fl, stvo::StepPlan&
     return check_launch(ctx);
 }
 
+stvo::StereoSetPtrs set_ptrs(const stvo_seq::Set& q) {
+    return stvo::StereoSetPtrs{q.rc, q.desc, q.n, q.spl, q.epl, q.sP, q.eP, q.le, q.s2l, q.s2lm, q.ldesc, q.nl};
+}
+
+// The feature tracks of the step stvo_seq_step_dev has just committed (cur, frame_idx, traj_steps have moved on): the last launch of the
+// step on the context's stream, behind the pose kernel, stream_ctl_post_kernel and the trajectory update.  It reads the counts of the
+// previous set, every array of the set the step built, the copy of the key-line match indices the step used, the inlier rows where
+// the pose kernel wrote them and the step's trajectory records.  DESIGN.md (feature tracks) has the argument why the key-line stage
+// ahead, which recycles the set and the match copy, cannot overtake it.
+int enqueue_track_update(stvo_seq* s, const stvo::StepPlan& plan, const StepFlags& fl) {
+    stvo_ctx* ctx = s->ctx;
+    const stvo_seq::Set& cs = s->set[s->prev_set()];
+    const stvo_seq::Set& ps = s->set[(s->cur + 1) % 3];
+    stvo::TrackArgs a{};
+    std::memset(&a, 0, sizeof(a));
+    a.B = s->B; a.K = s->K; a.M = s->M;
+    a.first = fl.track ? 0 : 1;
+    a.frame = s->frame_idx - 1;
+    if (fl.track) {
+        a.n_prev = ps.n; a.nl_prev = ps.nl;
+        a.m12p = s->m12p; a.m12l = plan.use_alt_m12l ? s->m12l_alt : s->m12l;
+        a.inlp = s->inlp; a.inll = s->inll;
+        if (plan.inl_zero_copy) {  // StepEnq::pose: the pose kernel wrote the masks straight into the pinned block
+            a.inlp = reinterpret_cast<const int32_t*>(s->fetch_host + s->m12_span);
+            a.inll = reinterpret_cast<const int32_t*>(s->fetch_host + s->m12_span + (reinterpret_cast<const char*>(s->inll) - reinterpret_cast<const char*>(s->inlp)));
+        }
+        a.ctl = fl.ctl;
+        if (s->d_traj_state) a.traj = s->d_traj_ring + (size_t)((s->traj_steps - 1) % (unsigned long long)s->traj_log_steps) * s->B;
+    }
+    a.n_cur = cs.n; a.nl_cur = cs.nl;
+    const size_t k = (size_t)(s->track_steps & 1ull), ring = (size_t)(s->track_steps % (unsigned long long)s->track_log_steps);
+    a.prev_p = s->track_row_p(k ^ 1); a.prev_l = s->track_row_l(k ^ 1);
+    a.next_p = s->track_row_p(k); a.next_l = s->track_row_l(k);
+    a.rec_p = s->track_row_p(2 + ring); a.rec_l = s->track_row_l(2 + ring);
+    a.rec_counts = s->track_counts(ring);
+    a.cur = set_ptrs(cs);
+    a.kf = s->kf_set;
+    a.kf_hdr = s->d_kf_hdr;
+    stvo::launch_track_update(ctx->stream, a);
+    s->track_steps++;
+    return check_launch(ctx);
+}
+
 }  // namespace
 
 // Runs the whole per-frame pipeline on the features resident in `slot` (asynchronous; no host transfer).
@@ -1506,8 +1570,9 @@ int stvo_seq_step_dev(stvo_seq* s, int slot) {
         stvo::launch_traj_update(ctx->stream, s->B, res, s->traj_prm, s->d_traj_state,
                                  s->d_traj_ring + (size_t)(s->traj_steps % (unsigned long long)s->traj_log_steps) * s->B, fl.ctl);
         s->traj_steps++;
-        return check_launch(ctx);
+        if (!s->d_tracks) return check_launch(ctx);
     }
+    if (s->d_tracks) return enqueue_track_update(s, plan, fl);
     return STVO_OK;
 }
 
@@ -1570,6 +1635,124 @@ int stvo_seq_read_trajectory(stvo_seq* s, int n_last, stvo_traj_record* records,
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *n_got = (int32_t)n;
+    return STVO_OK;
+}
+
+// Feature tracks and key-frame sets per stream inside the pipeline (stvo_hip.h).  New device memory, zeroed on the context's own stream.
+int stvo_seq_set_tracks(stvo_seq* s, int keyframe_sets, int log_steps) {
+    if (!s || s->frame_idx != 0 || log_steps < 0 || (keyframe_sets != 0 && keyframe_sets != 1)) return STVO_ERR_INVALID_ARG;
+    if (log_steps == 0 && keyframe_sets) return STVO_ERR_INVALID_ARG;
+    stvo_ctx* ctx = s->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (s->d_tracks || s->d_kf) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the fill may still run)
+        if (s->d_tracks) (void)hipFree(s->d_tracks);
+        if (s->d_kf) (void)hipFree(s->d_kf);
+    }
+    s->d_tracks = nullptr; s->d_kf = nullptr; s->d_kf_hdr = nullptr; s->track_log_steps = 0; s->track_steps = 0;
+    s->kf_set = stvo::StereoSetPtrs{};
+    if (log_steps == 0) return STVO_OK;
+    if ((unsigned long long)log_steps * s->track_row_bytes() > (1ull << 34)) return STVO_ERR_INVALID_ARG;
+    const size_t nb = (size_t)s->B, K = (size_t)s->K, M = (size_t)s->M;
+    const size_t track_bytes = (size_t)(2 + log_steps) * s->track_row_bytes() + (size_t)log_steps * nb * 2 * sizeof(int32_t);
+    Carver c;
+    const size_t o_rc = c.take(nb * K * 16), o_desc = c.take(nb * K * 32), o_spl = c.take(nb * M * 16), o_epl = c.take(nb * M * 16),
+                 o_sP = c.take(nb * M * 24), o_eP = c.take(nb * M * 24), o_le = c.take(nb * M * 24), o_s2l = c.take(nb * M * 8),
+                 o_s2lm = c.take(nb * M * 8), o_ldesc = c.take(nb * M * 32), o_hdr = c.take(nb * sizeof(stvo_kf_header));
+    char *tr = nullptr, *kf = nullptr;
+    bool ok = hipMalloc((void**)&tr, track_bytes) == hipSuccess;
+    if (ok && keyframe_sets) ok = hipMalloc((void**)&kf, c.off) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        if (tr) (void)hipFree(tr);
+        std::snprintf(ctx->last_error, sizeof(ctx->last_error), "%s", "hipMalloc of the feature tracks or the key-frame sets failed");
+        return STVO_ERR_HIP;
+    }
+    if (hipMemsetAsync(tr, 0, track_bytes, ctx->stream) != hipSuccess || (kf && hipMemsetAsync(kf, 0, c.off, ctx->stream) != hipSuccess)) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(tr);
+        if (kf) (void)hipFree(kf);
+        return STVO_ERR_HIP;
+    }
+    s->d_tracks = tr; s->track_log_steps = log_steps;
+    if (kf) {
+        s->d_kf = kf;
+        s->kf_set = stvo::StereoSetPtrs{(float4*)(kf + o_rc), (uint8_t*)(kf + o_desc), nullptr, (double*)(kf + o_spl), (double*)(kf + o_epl),
+                                        (double*)(kf + o_sP), (double*)(kf + o_eP), (double*)(kf + o_le), (double*)(kf + o_s2l),
+                                        (double*)(kf + o_s2lm), (uint8_t*)(kf + o_ldesc), nullptr};
+        s->d_kf_hdr = (stvo_kf_header*)(kf + o_hdr);
+    }
+    return STVO_OK;
+}
+
+int stvo_seq_read_tracks(stvo_seq* s, int n_last, stvo_track* pts, stvo_track* lines, int32_t* counts, int32_t* n_got) {
+    if (!s || !s->d_tracks || n_last < 1 || !n_got) return STVO_ERR_INVALID_ARG;
+    stvo_ctx* ctx = s->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    unsigned long long n = (unsigned long long)n_last;
+    if (n > (unsigned long long)s->track_log_steps) n = (unsigned long long)s->track_log_steps;
+    if (n > s->track_steps) n = s->track_steps;
+    const size_t bp = (size_t)s->B * s->K * sizeof(stvo_track), bl = (size_t)s->B * s->M * sizeof(stvo_track), bc = (size_t)s->B * 2 * sizeof(int32_t);
+    for (unsigned long long i = 0; i < n; ++i) {  // oldest first
+        const size_t r = (size_t)((s->track_steps - n + i) % (unsigned long long)s->track_log_steps);
+        if (pts) HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<char*>(pts) + i * bp, s->track_row_p(2 + r), bp, hipMemcpyDeviceToHost, ctx->stream));
+        if (lines) HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<char*>(lines) + i * bl, s->track_row_l(2 + r), bl, hipMemcpyDeviceToHost, ctx->stream));
+        if (counts) HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<char*>(counts) + i * bc, s->track_counts(r), bc, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *n_got = (int32_t)n;
+    return STVO_OK;
+}
+
+int stvo_seq_tracks_dev(stvo_seq* s, const stvo_track** pts_dev, const stvo_track** lines_dev, const int32_t** counts_dev) {
+    if (!s || !s->d_tracks || s->track_steps == 0) return STVO_ERR_INVALID_ARG;
+    const size_t r = (size_t)((s->track_steps - 1) % (unsigned long long)s->track_log_steps);
+    if (pts_dev) *pts_dev = s->track_row_p(2 + r);
+    if (lines_dev) *lines_dev = s->track_row_l(2 + r);
+    if (counts_dev) *counts_dev = s->track_counts(r);
+    return STVO_OK;
+}
+
+int stvo_seq_keyframe_headers(stvo_seq* s, stvo_kf_header* hdr) {
+    if (!s || !s->d_kf_hdr || !hdr) return STVO_ERR_INVALID_ARG;
+    stvo_ctx* ctx = s->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(hdr, s->d_kf_hdr, (size_t)s->B * sizeof(stvo_kf_header), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return STVO_OK;
+}
+
+int stvo_seq_read_keyframe(stvo_seq* s, int b, stvo_kf_header* hdr, int32_t cap_pts, float* rc, uint8_t* desc, int32_t cap_lines, double* spl,
+                           double* epl, double* sP, double* eP, double* le, double* s2l, double* s2lm, uint8_t* ldesc) {
+    if (!s || !s->d_kf_hdr || b < 0 || b >= s->B || !hdr || cap_pts < 0 || cap_lines < 0) return STVO_ERR_INVALID_ARG;
+    if ((cap_pts > 0 && (!rc || !desc)) || (cap_lines > 0 && (!spl || !epl || !sP || !eP || !le || !s2l || !s2lm || !ldesc)))
+        return STVO_ERR_INVALID_ARG;
+    stvo_ctx* ctx = s->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    stvo_kf_header h{};
+    HIP_TRY(ctx, hipMemcpy(&h, s->d_kf_hdr + b, sizeof(h), hipMemcpyDeviceToHost));
+    const size_t K = (size_t)s->K, M = (size_t)s->M;
+    if (h.n_pts < 0 || (size_t)h.n_pts > K || h.n_lines < 0 || (size_t)h.n_lines > M) return STVO_ERR_HIP;
+    *hdr = h;
+    if (h.n_pts > cap_pts || h.n_lines > cap_lines) return STVO_ERR_CAPACITY;
+    const stvo::StereoSetPtrs& q = s->kf_set;
+    if (h.n_pts) {
+        HIP_TRY(ctx, hipMemcpy(rc, q.rc + b * K, (size_t)h.n_pts * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(desc, q.desc + b * K * STVO_DESC_BYTES, (size_t)h.n_pts * STVO_DESC_BYTES, hipMemcpyDeviceToHost));
+    }
+    if (h.n_lines) {
+        const size_t r = (size_t)h.n_lines * sizeof(double);
+        HIP_TRY(ctx, hipMemcpy(spl, q.spl + b * M * 2, 2 * r, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(epl, q.epl + b * M * 2, 2 * r, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(sP, q.sP + b * M * 3, 3 * r, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(eP, q.eP + b * M * 3, 3 * r, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(le, q.le + b * M * 3, 3 * r, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(s2l, q.s2l + b * M, r, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(s2lm, q.s2lm + b * M, r, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ldesc, q.ldesc + b * M * STVO_DESC_BYTES, (size_t)h.n_lines * STVO_DESC_BYTES, hipMemcpyDeviceToHost));
+    }
     return STVO_OK;
 }
 

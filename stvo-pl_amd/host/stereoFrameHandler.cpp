@@ -297,6 +297,7 @@ void StereoFrameHandler::f2fTracking() {
 // :131-153
 void StereoFrameHandler::matchF2FPoints() {
     matched_pt.clear();
+    f2f_m12_pt.clear();
     if (!Config::hasPoints() || curr_frame->stereo_pt.empty() || prev_frame->stereo_pt.empty()) return;
     std::vector<int32_t> matches_12(prev_frame->pdesc_l.rows);
     check(stvo_match_nnr_mutual(ctx, prev_frame->pdesc_l.ptr(), prev_frame->pdesc_l.rows, curr_frame->pdesc_l.ptr(),
@@ -308,6 +309,7 @@ void StereoFrameHandler::matchF2FPoints() {
 
 // :144-152
 void StereoFrameHandler::buildMatchedPoints(const int32_t* matches_12, size_t n) {
+    f2f_m12_pt.assign(matches_12, matches_12 + n);
     for (size_t i1 = 0; i1 < n; ++i1) {
         const int i2 = matches_12[i1];
         if (i2 < 0) continue;
@@ -321,6 +323,7 @@ void StereoFrameHandler::buildMatchedPoints(const int32_t* matches_12, size_t n)
 // :155-180
 void StereoFrameHandler::matchF2FLines() {
     matched_ls.clear();
+    f2f_m12_ls.clear();
     if (!Config::hasLines() || curr_frame->stereo_ls.empty() || prev_frame->stereo_ls.empty()) return;
     std::vector<int32_t> matches_12(prev_frame->ldesc_l.rows);
     stvo_ctx* cl = ctx_lines ? ctx_lines : ctx;
@@ -333,6 +336,7 @@ void StereoFrameHandler::matchF2FLines() {
 
 // :167-179
 void StereoFrameHandler::buildMatchedLines(const int32_t* matches_12, size_t n) {
+    f2f_m12_ls.assign(matches_12, matches_12 + n);
     for (size_t i1 = 0; i1 < n; ++i1) {
         const int i2 = matches_12[i1];
         if (i2 < 0) continue;
@@ -562,6 +566,8 @@ void StereoFrameHandler::pipelineCollect(StereoFrame* frame) {
     for (auto ls : matched_ls) delete ls;
     matched_pt.clear();
     matched_ls.clear();
+    f2f_m12_pt.clear();
+    f2f_m12_ls.clear();
     if (Config::hasPoints() && !curr_frame->stereo_pt.empty() && !prev_frame->stereo_pt.empty())
         buildMatchedPoints(m_p, prev_frame->stereo_pt.size());
     if (Config::hasLines() && !curr_frame->stereo_ls.empty() && !prev_frame->stereo_ls.empty())

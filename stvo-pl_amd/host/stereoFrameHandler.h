@@ -51,6 +51,10 @@ public:
 
     std::list<PointFeature*> matched_pt;
     std::list<LineFeature*> matched_ls;
+    // the f2f match of every stereo feature of prev_frame into curr_frame (-1: none) as the last insertStereoPair built matched_pt /
+    // matched_ls from it (entry k of a list = the k-th matched index); empty when there was nothing to match.  For callers that follow
+    // feature identities beyond idx (the app's --tracks).
+    std::vector<int32_t> f2f_m12_pt, f2f_m12_ls;
 
     StereoFrame* prev_frame;
     StereoFrame* curr_frame;

@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 
 from .ctypes_types import Cam, GridWindow, MatchParams, OptParams, PoseResult, POSE_RESULT_DTYPE, RectCalib, RectCamera, TrajParams, \
-    TRAJ_RECORD_DTYPE, TRAJ_STATE_DTYPE
+    TRAJ_RECORD_DTYPE, TRAJ_STATE_DTYPE, TRACK_DTYPE, KF_HEADER_DTYPE
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # stvo-pl_amd/
 LIB_PATH = os.environ.get("STVO_LIB") or os.path.join(PKG_DIR, "libstvo_hip.so")   # STVO_LIB: A/B runs of two builds (developer)
@@ -30,7 +30,8 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_rectify_create", "stvo_rectify_create_from_maps", "stvo_rectify_destroy", "stvo_rectify_camera", "stvo_rectify_images",
            "stvo_rectify_images_dev", "stvo_orb_set_fast_thresholds", "stvo_orb_set_fast_thresholds_dev", "stvo_fast_adapt_dev",
            "stvo_seq_adapt_fast_dev", "stvo_traj_init_dev", "stvo_traj_update_dev", "stvo_seq_set_trajectory", "stvo_seq_read_trajectory",
-           "stvo_seq_trajectory_state_dev", "stvo_seq_read_trajectory_state", "stvo_seq_control_next_step", "stvo_seq_restart_fast_dev"]
+           "stvo_seq_trajectory_state_dev", "stvo_seq_read_trajectory_state", "stvo_seq_control_next_step", "stvo_seq_restart_fast_dev",
+           "stvo_seq_set_tracks", "stvo_seq_read_tracks", "stvo_seq_tracks_dev", "stvo_seq_keyframe_headers", "stvo_seq_read_keyframe"]
 
 SEQ_NSTAGE = 5  # include/stvo_hip.h: STVO_SEQ_NSTAGE
 SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_check", "pose")
@@ -226,6 +227,12 @@ def load():
     L.stvo_seq_trajectory_state_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.stvo_seq_read_trajectory_state.argtypes = [C.c_void_p, C.c_void_p]
     L.stvo_seq_control_next_step.argtypes = [C.c_void_p, C.c_void_p]
+    L.stvo_seq_set_tracks.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.stvo_seq_read_tracks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+    L.stvo_seq_tracks_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.stvo_seq_keyframe_headers.argtypes = [C.c_void_p, C.c_void_p]
+    L.stvo_seq_read_keyframe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int32, f32p, u8p, C.c_int32, f64p, f64p, f64p, f64p, f64p,
+                                         f64p, f64p, u8p]
     L.stvo_seq_restart_fast_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.stvo_orb_detect_levels.argtypes = [C.c_void_p, u8p, f32p, f32p, f32p, i32p, u8p, i32p, i32p]
     L.stvo_orb_detect_levels_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 8
@@ -811,6 +818,53 @@ class Sequences:
         out = np.zeros(self.B, dtype=TRAJ_STATE_DTYPE)
         self.ctx._chk(self.ctx.lib.stvo_seq_read_trajectory_state(self.h, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def set_tracks(self, log_steps=1, keyframe_sets=False):
+        """Feature tracks per stream behind every step (stvo_seq_set_tracks): the TRACK_DTYPE records of the last log_steps steps stay
+        readable; keyframe_sets: every stream also keeps the stereo set of its last key-frame.  log_steps = 0: off.  Only before the
+        first step."""
+        self.ctx._chk(self.ctx.lib.stvo_seq_set_tracks(self.h, 1 if keyframe_sets else 0, int(log_steps)))
+        self._track_log_steps = int(log_steps)
+
+    def read_tracks(self, n_last=1):
+        """(pts [n, B, K], lines [n, B, M] as TRACK_DTYPE, counts [n, B, 2]) of the last n = min(n_last, log_steps, steps) steps, oldest
+        first; rows [0, count) of a stream are meaningful.  Synchronises."""
+        K, M = self.strides()
+        rows = max(1, min(n_last, getattr(self, "_track_log_steps", 0)))
+        pts, lines = np.zeros((rows, self.B, K), TRACK_DTYPE), np.zeros((rows, self.B, M), TRACK_DTYPE)
+        counts = np.zeros((rows, self.B, 2), np.int32)
+        n = C.c_int32()
+        self.ctx._chk(self.ctx.lib.stvo_seq_read_tracks(self.h, n_last, pts.ctypes.data_as(C.c_void_p), lines.ctypes.data_as(C.c_void_p),
+                                                       counts.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return pts[:n.value].copy(), lines[:n.value].copy(), counts[:n.value].copy()
+
+    def tracks_dev(self):
+        """Device addresses (points, lines, counts) of the last step's records (stvo_seq_tracks_dev), for chained kernels."""
+        ps = [C.c_void_p() for _ in range(3)]
+        self.ctx._chk(self.ctx.lib.stvo_seq_tracks_dev(self.h, *[C.byref(p) for p in ps]))
+        return tuple(p.value for p in ps)
+
+    def keyframe_headers(self):
+        """KF_HEADER_DTYPE array [B] (stvo_seq_keyframe_headers); serial == 0: the stream has no key-frame set yet.  Synchronises."""
+        hdr = np.zeros(self.B, KF_HEADER_DTYPE)
+        self.ctx._chk(self.ctx.lib.stvo_seq_keyframe_headers(self.h, hdr.ctypes.data_as(C.c_void_p)))
+        return hdr
+
+    def read_keyframe(self, b):
+        """Stream b's key-frame set (stvo_seq_read_keyframe): the dict of debug_stereo plus frame and serial of the header."""
+        K, M = self.strides()
+        rc = np.empty((K, 4), np.float32); desc = np.empty((K, 32), np.uint8); ldesc = np.empty((M, 32), np.uint8)
+        spl, epl = np.empty((M, 2)), np.empty((M, 2))
+        sP, eP, le = np.empty((M, 3)), np.empty((M, 3)), np.empty((M, 3))
+        s2l, s2lm = np.empty(M), np.empty(M)
+        hdr = np.zeros(1, KF_HEADER_DTYPE)
+        self.ctx._chk(self.ctx.lib.stvo_seq_read_keyframe(self.h, b, hdr.ctypes.data_as(C.c_void_p), K, rc.reshape(-1), desc.reshape(-1), M,
+                                                         spl.reshape(-1), epl.reshape(-1), sP.reshape(-1), eP.reshape(-1), le.reshape(-1),
+                                                         s2l, s2lm, ldesc.reshape(-1)))
+        n, nl = int(hdr["n_pts"][0]), int(hdr["n_lines"][0])
+        return dict(n=n, rc=rc[:n].copy(), desc=desc[:n].copy(), nl=nl, spl=spl[:nl].copy(), epl=epl[:nl].copy(), sP=sP[:nl].copy(),
+                    eP=eP[:nl].copy(), le=le[:nl].copy(), s2l=s2l[:nl].copy(), s2lm=s2lm[:nl].copy(), ldesc=ldesc[:nl].copy(),
+                    frame=int(hdr["frame"][0]), serial=int(hdr["serial"][0]))
 
     def read(self):
         res = np.zeros(self.B, dtype=POSE_RESULT_DTYPE)

@@ -65,6 +65,19 @@ TRAJ_RECORD_DTYPE = np.dtype([("Tfw", "<f8", (16,)), ("Tfw_cov", "<f8", (36,)), 
                               ("new_kf", "<i4"), ("frame", "<i4")])
 assert TRAJ_STATE_DTYPE.itemsize == 856 and TRAJ_RECORD_DTYPE.itemsize == 448 and C.sizeof(TrajParams) == 32
 
+# stvo_track / stvo_kf_header (include/stvo_types.h): Sequences.read_tracks / keyframe_headers
+class Track(C.Structure):
+    _fields_ = [("idx", C.c_int32), ("age", C.c_uint16), ("kf", C.c_uint8), ("inlier", C.c_int8)]
+
+
+class KfHeader(C.Structure):
+    _fields_ = [("n_pts", C.c_int32), ("n_lines", C.c_int32), ("frame", C.c_int32), ("serial", C.c_int32)]
+
+
+TRACK_DTYPE = np.dtype([("idx", "<i4"), ("age", "<u2"), ("kf", "u1"), ("inlier", "i1")])
+KF_HEADER_DTYPE = np.dtype([("n_pts", "<i4"), ("n_lines", "<i4"), ("frame", "<i4"), ("serial", "<i4")])
+assert TRACK_DTYPE.itemsize == 8 == C.sizeof(Track) and KF_HEADER_DTYPE.itemsize == 16 == C.sizeof(KfHeader)
+
 STATUS_OK, STATUS_FEW_BEFORE, STATUS_FEW_AFTER, STATUS_REJECTED = 0, 1, 2, 3
 PATH_STAGE1_GOOD, PATH_ROBUST_FALLBACK, PATH_REFINED = 1, 2, 4
 

@@ -19,7 +19,7 @@ from .capi import FrameFeatures
 class ImagePipeline:
     def __init__(self, ctx, B, cam, mp, op, max_kp=2048, nfeatures=2000, fast_threshold=20, edge_threshold=19, device="cuda:0", nlevels=1,
                  scale_factor=1.2, lsd=None, max_kl=128, rectify=None, fld=None, orb_score=1, adaptive_fast=None,
-                 trajectory=None, trajectory_log=1):
+                 trajectory=None, trajectory_log=1, tracks=0, keyframe_sets=False):
         """cam: one camera dict (width / height = image size) for all B streams.  nlevels / scale_factor: Config::orbNLevels /
         orbScaleFactor (the key-point octaves travel with the key-points: sigma2 = 1 / scale^(2 level)).  orb_score: Config::orbScore
         (1 FAST_SCORE, 0 HARRIS_SCORE ranking of the key-points).  lsd: capi.lsd_params(...)
@@ -35,7 +35,10 @@ class ImagePipeline:
         trajectory: capi.traj_params(...) turns on the pose in the map frame and the key-frame decision per stream (the rest of
         optimizePose's "set estimated pose" block, :372-391, and needNewKF / currFrameIsKF, :1136-1218): every tracked step is followed
         by the update on the device, read_trajectory() returns the records of the last trajectory_log steps.  None: images -> poses as
-        before, no launch and no allocation added."""
+        before, no launch and no allocation added.
+        tracks: >= 1 turns on the feature tracks per stream (Sequences.set_tracks: which feature of the last key-frame every current
+        stereo feature observes), read_tracks() returns the records of the last `tracks` steps; keyframe_sets: every stream also keeps
+        the stereo set of its last key-frame (keyframe_headers / read_keyframe).  0: off, no launch and no allocation added."""
         self.ctx, self.B, self.K, self.M = ctx, B, max_kp, max_kl
         self.cols, self.rows = cam["width"], cam["height"]
         self.rectify = rectify
@@ -57,6 +60,9 @@ class ImagePipeline:
         self.trajectory = trajectory
         if trajectory is not None:
             self.seq.set_trajectory(trajectory, trajectory_log)
+        self.tracks, self.keyframe_sets = int(tracks), bool(keyframe_sets)
+        if self.tracks or self.keyframe_sets:
+            self.seq.set_tracks(log_steps=self.tracks, keyframe_sets=self.keyframe_sets)
         dev = torch.device(device)
         self.img = torch.zeros((2 * B, self.rows, self.cols), dtype=torch.uint8, device=dev)
         self.rect_img = torch.zeros((2 * B, self.rows, self.cols), dtype=torch.uint8, device=dev) if rectify is not None else None
@@ -145,6 +151,19 @@ class ImagePipeline:
         if self.trajectory is None:
             raise ValueError("ImagePipeline.read_trajectory: built without trajectory")
         return self.seq.read_trajectory(n_last)
+
+    def read_tracks(self, n_last=1):
+        """(points [n, B, K], lines [n, B, M] as TRACK_DTYPE, counts [n, B, 2]) of the last n <= tracks steps, oldest first
+        (Sequences.read_tracks; synchronises)."""
+        if not self.tracks:
+            raise ValueError("ImagePipeline.read_tracks: built without tracks")
+        return self.seq.read_tracks(n_last)
+
+    def keyframe_headers(self):
+        return self.seq.keyframe_headers()
+
+    def read_keyframe(self, b):
+        return self.seq.read_keyframe(b)
 
     def fast_thresholds(self):
         """Host copy of the per-stream FAST thresholds the NEXT detection will read (synchronises); tests and tools."""

@@ -48,11 +48,17 @@ def empty_frame():
     return dict(kp_l=z2, oct_l=zi, desc_l=zd, kp_r=z2, desc_r=zd, kl_l=z4, oct_ll=zi, ldesc_l=zd, kl_r=z4, ldesc_r=zd)
 
 
-def run(dev, sequences):
+def run(dev, sequences, tracks=0, keyframe_sets=False):
     """Drives dev (a fresh capi.Sequences of B streams) through plan([len(s) for s in sequences], dev.B), one push per step.
     Returns (results, counts, records): per sequence a POSE_RESULT_DTYPE array [frames] (entry 0, the sequence's first frame, all-zero),
     an int32 array [frames, 4], and — with the trajectory on (Sequences.set_trajectory), else records is None — a TRAJ_RECORD_DTYPE
-    array [frames - 1] of the tracked frames (its `frame` counts from 1 in every sequence)."""
+    array [frames - 1] of the tracked frames (its `frame` counts from 1 in every sequence).
+    tracks >= 1 (the ring's rows; keyframe_sets as for Sequences.set_tracks): the feature tracks are turned on before the first step and a
+    fourth value is returned — per sequence and frame a dict of pts / lines (TRACK_DTYPE rows [0, count)) and, with keyframe_sets,
+    kf_header (the stream's KF_HEADER_DTYPE record behind that step)."""
+    if tracks:
+        dev.set_tracks(log_steps=tracks, keyframe_sets=keyframe_sets)
+    feats = [[] for _ in sequences] if tracks else None
     steps = plan([len(s) for s in sequences], dev.B)
     traj = getattr(dev, "_traj_log_steps", 0) > 0
     results = [[] for _ in sequences]
@@ -64,6 +70,9 @@ def run(dev, sequences):
             dev.control_next_step(st.control)
         res, cnt = dev.push([sequences[c[0]][c[1]] if c is not None else idle for c in st.consume])
         rec = dev.read_trajectory(1) if traj else None
+        if tracks:
+            tp, tl, tc = dev.read_tracks(1)
+            hdr = dev.keyframe_headers() if keyframe_sets else None
         for b, c in enumerate(st.consume):
             if c is None:
                 continue
@@ -71,9 +80,16 @@ def run(dev, sequences):
             counts[c[0]].append(cnt[b].copy())
             if traj and c[1] > 0:
                 records[c[0]].append(rec[-1][b].copy())
+            if tracks:
+                f = dict(pts=tp[-1][b][:tc[-1][b][0]].copy(), lines=tl[-1][b][:tc[-1][b][1]].copy())
+                if keyframe_sets:
+                    f["kf_header"] = hdr[b].copy()
+                feats[c[0]].append(f)
     results = [np.array(r, dtype=r[0].dtype) for r in results]
     counts = [np.array(c, np.int32).reshape(-1, 4) for c in counts]
     if traj:
         from .ctypes_types import TRAJ_RECORD_DTYPE
         records = [np.array(r, dtype=TRAJ_RECORD_DTYPE) for r in records]
+    if tracks:
+        return results, counts, records, feats
     return results, counts, records
