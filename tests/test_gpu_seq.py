@@ -211,17 +211,20 @@ def test_seq_fetch_by_products(oracle):
             assert np.all(ms_p[0, n_l:] == -1) and np.all(ms_l[0, n_ll:] == -1)
             assert len(ref["P"]) == counts[0, 0] and len(ref["sP"]) == counts[0, 1]
             if k == 0:
-                prev_counts = counts.copy()
+                prev_counts, prev_ref = counts.copy(), ref
                 continue
             r = res[0]
             assert (m_p[0, :prev_counts[0, 0]] >= 0).sum() == r["n_matched_pt"]
             assert (m_l[0, :prev_counts[0, 1]] >= 0).sum() == r["n_matched_ls"]
+            # the f2f key-line matches equal StVO::match on the two kept sets, index for index
+            exp_l, _ = oracle.match(prev_ref["ldesc"], ref["ldesc"], mp.min_ratio_12_l, mp.best_lr_matches)
+            assert np.array_equal(m_l[0, :prev_counts[0, 1]], exp_l)
             assert np.all(m_p[0, :prev_counts[0, 0]] < counts[0, 0])
             ip, il = dev.fetch_inliers()
             assert (ip[0, :prev_counts[0, 0]] == 1).sum() == r["n_inliers_pt"]
             assert (il[0, :prev_counts[0, 1]] == 1).sum() == r["n_inliers_ls"]
             assert np.array_equal(ip[0, :prev_counts[0, 0]] >= 0, m_p[0, :prev_counts[0, 0]] >= 0)
-            prev_counts = counts.copy()
+            prev_counts, prev_ref = counts.copy(), ref
     finally:
         dev.close()
         ctx.close()
