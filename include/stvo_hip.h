@@ -243,6 +243,15 @@ int stvo_seq_last_schedule(const stvo_seq* seq, int32_t out[8]);
 int stvo_seq_debug_grid(stvo_seq* seq, int b, int lines, int32_t* cell_start, int32_t* cell_items, int32_t cap_items,
                         int32_t* cells_left, int32_t* cand_off, int32_t* cand, int32_t cap_cand, int32_t* n_left);
 
+/* TEST HOOK: the route the stereo point matcher of the last step took for every sequence: out [B][2] = {misfit, ovf}.  misfit = 1: the
+ * one-workgroup-per-frame kernel handed the frame to the scan formulation (more keys or wide right key-points than its LDS holds);
+ * ovf = 1: the scan formulation met a right key-point with more eligible pairs than its list holds and ran its second scan.  A word
+ * that the step's route does not write for a frame is reported as 0 (misfit on the scan route; ovf for a frame the one-workgroup
+ * kernel matched itself, and with best_lr_matches off), never as an earlier step left it.  Synchronises, copies, launches nothing
+ * and changes no state; call it before stvo_seq_debug_grid, whose own kernels clear ovf.  Before the first step:
+ * STVO_ERR_INVALID_ARG. */
+int stvo_seq_debug_point_route(stvo_seq* seq, int32_t* out);
+
 /* TEST HOOK: the stereo sets the last step built from its frame for sequence b, i.e. what the tails of the stereo association
  * (src/stereoFrame.cpp:152-172, :351-395) wrote: n_pts stereo points as rc [n_pts][4] = {u, v, disparity, level} (floats) with the kept
  * left descriptor rows desc [n_pts][32]; n_lines stereo lines as spl, epl [n_lines][2], sP, eP, le [n_lines][3], s2l (sigma2 of the

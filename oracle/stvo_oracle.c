@@ -165,9 +165,12 @@ int orc_line_coords(double x1, double y1, double x2, double y2, int32_t* out_xy,
 }
 
 /* GridStructure::get, src/gridStructure.cpp:65-76: union (std::unordered_set) of the cells of the
- * clamped window.  `seen` de-duplicates; entries touched are reset before returning. */
-int orc_grid_window_gather(const int32_t* cell_start, const int32_t* cell_items, int x, int y, const stvo_grid_window* w,
-                           int32_t* out, uint8_t* seen) {
+ * clamped window.  `seen` de-duplicates; entries touched are reset before returning.
+ * For n2 right features (`seen` has n2 entries): ids outside [0, n2) — which the set of the reference may hold and matchGrid skips
+ * one by one (src/matching.cpp:141, :218) — are left out here.  A set of such ids alone ends like an empty one: no candidate is
+ * ever eligible, best_d stays INT_MAX and the ratio test fails. */
+static int grid_window_gather_n(const int32_t* cell_start, const int32_t* cell_items, int x, int y, const stvo_grid_window* w,
+                                int32_t* out, uint8_t* seen, int n2) {
     int min_x = x - w->w_lo > 0 ? x - w->w_lo : 0;
     int max_x = x + w->w_hi + 1 < STVO_GRID_COLS ? x + w->w_hi + 1 : STVO_GRID_COLS;
     int min_y = y - w->h_lo > 0 ? y - w->h_lo : 0;
@@ -178,6 +181,7 @@ int orc_grid_window_gather(const int32_t* cell_start, const int32_t* cell_items,
             int c = y_ * STVO_GRID_COLS + x_;
             for (int k = cell_start[c]; k < cell_start[c + 1]; ++k) {
                 int id = cell_items[k];
+                if (id < 0 || id >= n2) continue;
                 if (!seen[id]) {
                     seen[id] = 1;
                     out[n++] = id;
@@ -185,6 +189,11 @@ int orc_grid_window_gather(const int32_t* cell_start, const int32_t* cell_items,
             }
         }
     return n;
+}
+
+int orc_grid_window_gather(const int32_t* cell_start, const int32_t* cell_items, int x, int y, const stvo_grid_window* w,
+                           int32_t* out, uint8_t* seen) {
+    return grid_window_gather_n(cell_start, cell_items, x, y, w, out, seen, INT_MAX);
 }
 
 /* Shared inner loop of both matchGrid overloads (src/matching.cpp:140-163, :217-244). */
@@ -235,7 +244,7 @@ int orc_match_grid_points(const int32_t* cell_xy1, const uint8_t* d1, int n1, co
     uint8_t* seen = (uint8_t*)calloc((size_t)(n2 + 1), 1);
     for (int i1 = 0; i1 < n1; ++i1) {
         m12[i1] = -1;
-        int nc = orc_grid_window_gather(cell_start, cell_items, cell_xy1[2 * i1], cell_xy1[2 * i1 + 1], w, cand, seen);
+        int nc = grid_window_gather_n(cell_start, cell_items, cell_xy1[2 * i1], cell_xy1[2 * i1 + 1], w, cand, seen, n2);
         for (int c = 0; c < nc; ++c) seen[cand[c]] = 0;
         if (nc == 0) continue; /* :139 */
         int r = grid_scan_one(d1 + (size_t)i1 * STVO_DESC_BYTES, cand, nc, d2, n2, NULL, NULL, 0.0, best_lr, distances,
@@ -281,8 +290,8 @@ int orc_match_grid_lines(const int32_t* cell_xy1, const uint8_t* d1, int n1, con
         double mag = sqrt(v[0] * v[0] + v[1] * v[1]); /* include/matching.h:48-53 */
         v[0] /= mag;
         v[1] /= mag;
-        int nc = orc_grid_window_gather(cell_start, cell_items, sx, sy, w, cand, seen);
-        nc += orc_grid_window_gather(cell_start, cell_items, ex, ey, w, cand + nc, seen);
+        int nc = grid_window_gather_n(cell_start, cell_items, sx, sy, w, cand, seen, n2);
+        nc += grid_window_gather_n(cell_start, cell_items, ex, ey, w, cand + nc, seen, n2);
         for (int c = 0; c < nc; ++c) seen[cand[c]] = 0;
         if (nc == 0) continue;
         int r = grid_scan_one(d1 + (size_t)i1 * STVO_DESC_BYTES, cand, nc, d2, n2, v, dir2, line_sim_th, best_lr,

@@ -578,9 +578,14 @@ __device__ __forceinline__ void fused_fetch2(const GridBatch& g, const int f, co
         n.q0[r] = D2[2 * i2];
         n.q1[r] = D2[2 * i2 + 1];
         // GridStructure::get seen from the right feature: left cells x .. x + w_lo of its row (the window is clamped, :67-71)
+        // A right key-point outside the grid (cell -1, the reference's out_of_bounds sink; scanned last) is nobody's candidate: it
+        // reads lstart[0] twice — la = lb = 0, an empty range.  (Unguarded, y = -1 and x = 63 addressed the words 17 and
+        // 16 - w_lo before the frame's table: the tail of the previous frame's, or memory in front of the array.)  The selects sit
+        // on the address, in front of the loads: nothing waits for a load here.
         const int y = rc >> 6, x = rc & (STVO_GRID_COLS - 1);
-        n.la[r] = (int)lstart[y * FUSED_LW + x];
-        n.lb[r] = (int)lstart[y * FUSED_LW + x + g.w.w_lo + 1];
+        const int c0 = rc >= 0 ? y * FUSED_LW + x : 0, span = rc >= 0 ? g.w.w_lo + 1 : 0;
+        n.la[r] = (int)lstart[c0];
+        n.lb[r] = (int)lstart[c0 + span];
     }
 }
 

@@ -2089,6 +2089,31 @@ int stvo_seq_debug_grid(stvo_seq* s, int b, int lines, int32_t* cell_start, int3
     return tot > cap_cand ? STVO_ERR_CAPACITY : STVO_OK;
 }
 
+// TEST HOOK.  Which way the stereo point matcher of the LAST step took each frame: out[b] = {misfit, ovf}, the two words the matcher keeps
+// side by side in govf (ovf[B] then misfit[B]).  Copies only: nothing is launched, no state of `s` changes.  A word that the route of
+// the step did not write for a frame is reported as 0, not as an earlier step left it: misfit belongs to the one-workgroup kernel
+// (lean_cells), ovf to a frame the scan formulation ran with best_lr_matches on (every frame of the scan route, the misfit frames of
+// the other).  Ask BEFORE stvo_seq_debug_grid: after a step of the one-workgroup route that hook runs the full cells kernel, which
+// clears ovf.
+int stvo_seq_debug_point_route(stvo_seq* s, int32_t* out) {
+    if (!s || !out || s->frame_idx == 0) return STVO_ERR_INVALID_ARG;
+    stvo_ctx* ctx = s->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(s->line_stream));
+    const int B = s->B;
+    std::vector<int32_t> w((size_t)2 * B, 0);
+    if (s->op.has_points) HIP_TRY(ctx, hipMemcpy(w.data(), s->govf, w.size() * 4, hipMemcpyDeviceToHost));
+    const bool fused = s->op.has_points && s->last_point_grid.lean_cells != 0, lr = s->last_point_grid.ovf != nullptr;
+    for (int b = 0; b < B; ++b) {
+        const int misfit = fused ? w[(size_t)B + b] : 0;
+        const bool scanned = s->op.has_points && (!fused || misfit != 0);
+        out[2 * b] = misfit;
+        out[2 * b + 1] = scanned && lr ? w[b] : 0;
+    }
+    return STVO_OK;
+}
+
 // TEST HOOK.  The stereo sets the LAST step built from its frame for sequence b, as the tails of the association left them
 // (point_tail.h / fused_tail; line_tail_frame): tests/test_gpu_stereo_tail.py compares them record by record with the oracle and
 // with tests/np_stereo_tail.py.  Copies only: nothing is launched, no state of `s` changes.

@@ -21,7 +21,7 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_track_batched_dev", "stvo_match_nnr_mutual_batched_dev", "stvo_optimize_pose_batched_dev",
            "stvo_time_stage_dev", "stvo_valu_peak_probe", "stvo_last_reverse_counts", "stvo_last_reverse_plan", "stvo_ctx_set_kernel_timing", "stvo_ctx_get_kernel_timing", "stvo_seq_create", "stvo_seq_destroy", "stvo_seq_enable_fetch", "stvo_seq_fetch_matches", "stvo_seq_fetch_inliers", "stvo_seq_strides",
            "stvo_seq_push", "stvo_seq_upload", "stvo_seq_step_dev", "stvo_seq_read", "stvo_seq_create_multi", "stvo_seq_set_slots",
-           "stvo_seq_set_stage_timing", "stvo_seq_get_stage_timing", "stvo_seq_last_schedule", "stvo_seq_set_motion_model", "stvo_seq_debug_grid", "stvo_seq_debug_stereo", "stvo_orb_create", "stvo_orb_destroy",
+           "stvo_seq_set_stage_timing", "stvo_seq_get_stage_timing", "stvo_seq_last_schedule", "stvo_seq_set_motion_model", "stvo_seq_debug_grid", "stvo_seq_debug_point_route", "stvo_seq_debug_stereo", "stvo_orb_create", "stvo_orb_destroy",
            "stvo_orb_set_pattern", "stvo_orb_get_pattern", "stvo_orb_detect", "stvo_orb_detect_dev", "stvo_orb_detect_levels",
            "stvo_orb_detect_levels_dev", "stvo_orb_set_fast_threshold", "stvo_orb_set_score_type", "stvo_seq_upload_dev", "stvo_lbd_create", "stvo_lbd_destroy",
            "stvo_lbd_compute", "stvo_lbd_compute_dev", "stvo_debug_reparse_env", "stvo_lsd_create", "stvo_lsd_destroy", "stvo_lsd_detect",
@@ -204,6 +204,7 @@ def load():
     L.stvo_seq_get_stage_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
     L.stvo_seq_debug_grid.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, i32p, C.c_int32, i32p, i32p, i32p, C.c_int32,
                                       C.POINTER(C.c_int32)]
+    L.stvo_seq_debug_point_route.argtypes = [C.c_void_p, i32p]
     L.stvo_orb_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(OrbParams), C.POINTER(C.c_void_p)]
     L.stvo_orb_destroy.argtypes = [C.c_void_p]
     i8p = np.ctypeslib.ndpointer(np.int8, flags="C_CONTIGUOUS")
@@ -712,6 +713,13 @@ class Sequences:
         nl = n.value
         return (start, items[:start[-1]].copy(), cells[:nl * (4 if lines else 2)].reshape(nl, -1).copy(), off[:nl + 1].copy(),
                 cand[:off[nl]].copy())
+
+    def debug_point_route(self):
+        """int32 [B, 2] = (misfit, ovf) of the stereo point matcher of the last step (stvo_seq_debug_point_route); copies only.  Call it
+        before debug_grid, whose kernels clear ovf."""
+        out = np.zeros((self.B, 2), np.int32)
+        self.ctx._chk(self.ctx.lib.stvo_seq_debug_point_route(self.h, out.reshape(-1)))
+        return out
 
     def debug_stereo(self, b):
         """The stereo sets the last step built from its frame for sequence b (stvo_seq_debug_stereo): dict of n, rc [n, 4] float32
