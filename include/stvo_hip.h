@@ -458,7 +458,15 @@ int stvo_lbd_compute_dev(stvo_lbd* lbd, const uint8_t* images, const stvo_keylin
  * off); 2 (LSD_REFINE_ADV: rect_improve + the NFA test): STVO_ERR_UNSUPPORTED.  Images up to 2^20 pixels after scaling.  Blur, resize, gradient /
  * level-line angles and the pseudo-ordering are data-parallel kernels; region growing is inherently sequential per image (a
  * pixel joins a region depending on the running region angle and on what every earlier region took) and runs as ONE wavefront
- * per image, the images of the batch side by side. */
+ * per image, the images of the batch side by side.
+ *
+ * The scaled image (scale != 1): cv::GaussianBlur with sigma = sigma_scale / scale below scale 1 and sigma_scale above it, kernel
+ * (1 + 2h) x (1 + 2h) with h = ceil(sigma sqrt(2 3 ln 10)), in OpenCV 3's 8-bit fixed point (integer weights x 2^8 per pass, one
+ * rounding shift, bytes), then cv::resize(…, Size(), scale, scale).  Every pair with h = 0 .. STVO_LSD_MAX_RADIUS is built
+ * (sigma <= 4.03: scale >= 0.25 at sigma_scale <= 1); a larger radius is STVO_ERR_UNSUPPORTED, a negative sigma_scale
+ * STVO_ERR_INVALID_ARG.  stvo_lsd_geometry tells what a pair means without a device. */
+#define STVO_LSD_MAX_RADIUS 15
+#define STVO_LSD_MAX_TAPS (1 + 2 * STVO_LSD_MAX_RADIUS)
 typedef struct stvo_lsd_params {
     int32_t refine;        /* Config::lsdRefine()      0 (or 1) */
     int32_t n_bins;        /* Config::lsdNBins()       1024 (1 .. 2048; more: STVO_ERR_UNSUPPORTED) */
@@ -473,6 +481,13 @@ typedef struct stvo_lsd_params {
     int32_t reserved;
 } stvo_lsd_params;
 typedef struct stvo_lsd stvo_lsd;
+/* HOST ONLY, no context: what stvo_lsd_create derives from the parameters and the image size, and the same verdict on them
+ * (STVO_ERR_INVALID_ARG / STVO_ERR_UNSUPPORTED / STVO_ERR_CAPACITY exactly where stvo_lsd_create returns them; it takes its own
+ * numbers from here).  Every output may be NULL: the size of the scaled image, sigma and the radius h of the blur (0, 0 at scale 1:
+ * no blur), and the 1 + 2h integer weights  lrint((float)(k_i / sum) 256)  of one pass in weights[STVO_LSD_MAX_TAPS] (the rest
+ * zeroed; h = 0: the single weight 256, the identity).  The weights need not add up to 256 (252 .. 259 occur), and one can BE 256. */
+int stvo_lsd_geometry(const stvo_lsd_params* prm, int cols, int rows, int32_t* scaled_cols, int32_t* scaled_rows, double* sigma,
+                      int32_t* radius, int32_t* weights);
 int stvo_lsd_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, const stvo_lsd_params* prm, stvo_lsd** out);
 int stvo_lsd_destroy(stvo_lsd* lsd);
 /* Host buffers in / out, synchronises.  images [B][rows][cols]; lines [B][max_keylines] (what stvo_lbd_compute consumes: in-octave
@@ -492,6 +507,9 @@ int stvo_keylines_xy_dev(stvo_ctx* ctx, int B, int stride, const stvo_keyline* l
 /* test hook: the raw segments of the detector core (cv::LineSegmentDetector::detect), host buffers, synchronises:
  * segments [B][cap][4], n_segments [B] (all found; at most cap stored) */
 int stvo_lsd_segments(stvo_lsd* lsd, const uint8_t* images, float* segments, int cap, int32_t* n_segments);
+/* test hook: the image the detector core sees — blurred and resized (the input itself at scale 1) — host buffers, synchronises:
+ * images [B][rows][cols] in, scaled [B][scaled_rows][scaled_cols] out (sizes: stvo_lsd_geometry); nothing is detected */
+int stvo_lsd_scaled_image(stvo_lsd* lsd, const uint8_t* images, uint8_t* scaled);
 
 /* ---- FLD line detector (use_fld_lines = true) -------------------------------------------------------------------------- */
 

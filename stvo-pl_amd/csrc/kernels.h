@@ -219,6 +219,16 @@ void launch_blur7_u8(hipStream_t s, int B, int cols, int rows, const uint8_t* sr
 // fx, fy > 0: resize(src, dst, Size(), fx, fy) with dsize = cvRound(ssize f) — the sample step stays 1 / f (LSD's scaled image)
 void launch_resize_linear_u8(hipStream_t s, int B, int scols, int srows, int dcols, int drows, const uint8_t* src, uint8_t* dst, double fx = 0.0,
                              double fy = 0.0);
+// ---- the same two operations fused, for every blur radius 0 .. STVO_LSD_MAX_RADIUS (lsd_scale_kernels.hip) ----
+// cv::GaussianBlur((1 + 2 radius)^2) with the integer weights (x 2^8, 32-bit: one can be 256) + cv::resize(…, Size(), scale, scale):
+// one workgroup per tile of the scaled image, the blurred bytes only in LDS.  The plan (tile, dynamic LDS) depends on the geometry
+// alone and is made once; false: no tile fits the LDS (scales far below 0.01).
+struct BlurResizePlan {
+    int tw_log, th_log, lds_bytes;
+};
+bool plan_blur_resize_u8(int scols, int srows, double scale, int radius, BlurResizePlan* p);
+void launch_blur_resize_u8(hipStream_t s, int B, int scols, int srows, int dcols, int drows, const uint8_t* src, uint8_t* dst, double scale,
+                           int radius, const int* weights, const BlurResizePlan& p);
 
 // ---- K3: grid-windowed stereo matchers, batched over frame pairs (blockIdx.y) ----------------------
 constexpr int GRID_LW = STVO_GRID_COLS + 16, GRID_LCELLS = STVO_GRID_ROWS * GRID_LW, GRID_LSTART_STRIDE = GRID_LCELLS + 4;

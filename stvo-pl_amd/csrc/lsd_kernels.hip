@@ -4,7 +4,8 @@
 // The detector core is third-party code that is not under /root/reference: the semantics are those of oracle/stvo_lsd_oracle.c
 // (restated from the published algorithm, parity unpinned), against which these kernels are bit-exact (tests/test_gpu_lsd.py).
 //
-//   blur + resize        the scaled image (cv::GaussianBlur 7 x 7 + cv::resize on 8-bit data): orb_kernels.hip's kernels
+//   blur + resize        the scaled image (cv::GaussianBlur (1 + 2h) x (1 + 2h) + cv::resize on 8-bit data): for h = 3 (every shipped
+//                        yaml) orb_kernels.hip's two kernels, for every other radius 0 .. 15 lsd_scale_kernels.hip's fused one
 //   lsd_gradient_kernel  ll_angle: 2 x 2 gradient, norm, level-line angle (fastAtan2, degrees), the float cos / sin a pixel
 //                        contributes to a region angle, the largest squared gradient of the image (integer atomic max)
 //   lsd_hist / lsd_scan / lsd_scatter_kernel   the pseudo-ordering: the defined pixels by bin of the gradient norm, highest bin first,
@@ -1946,7 +1947,9 @@ struct stvo_lsd {
     stvo_ctx* ctx = nullptr;
     stvo::LsdDev d{};
     stvo_lsd_params prm{};
-    int k7[7] = {0, 0, 0, 0, 0, 0, 0};
+    int radius = 0;                     // of the blur (stvo_lsd_geometry)
+    int kw[STVO_LSD_MAX_TAPS] = {0};    // its 1 + 2 radius integer weights
+    stvo::BlurResizePlan plan{};        // radius != 3: the tile of lsd_blur_resize_kernel
     char* dev = nullptr;
     uint8_t *img = nullptr, *blur = nullptr, *scaled = nullptr;
     stvo_keyline* lines = nullptr;  // device buffers of the host-pointer entry points
@@ -1961,14 +1964,25 @@ struct stvo_lsd {
 
 namespace {
 
+// the scaled image of a detector with scale != 1: radius 3 on the two kernels it always had, every other radius on the fused one
+void lsd_scaled_enqueue(stvo_lsd* o, const uint8_t* images) {
+    const stvo::LsdDev& d = o->d;
+    hipStream_t s = o->ctx->stream;
+    if (o->radius == 3) {
+        stvo::launch_blur7_u8(s, d.B, d.cols, d.rows, images, o->blur, o->kw);
+        stvo::launch_resize_linear_u8(s, d.B, d.cols, d.rows, d.w, d.h, o->blur, o->scaled, d.scale, d.scale);
+    } else {
+        stvo::launch_blur_resize_u8(s, d.B, d.cols, d.rows, d.w, d.h, images, o->scaled, d.scale, o->radius, o->kw, o->plan);
+    }
+}
+
 int lsd_enqueue(stvo_lsd* o, const uint8_t* images, stvo_keyline* lines, float* response, int32_t* n_lines) {
     stvo_ctx* ctx = o->ctx;
     hipStream_t s = ctx->stream;
     stvo::LsdDev d = o->d;
     const uint8_t* src = images;
     if (d.scale != 1) {
-        stvo::launch_blur7_u8(s, d.B, d.cols, d.rows, images, o->blur, o->k7);
-        stvo::launch_resize_linear_u8(s, d.B, d.cols, d.rows, d.w, d.h, o->blur, o->scaled, d.scale, d.scale);
+        lsd_scaled_enqueue(o, images);
         src = o->scaled;
     }
     d.scaled = src;
@@ -2004,8 +2018,9 @@ int lsd_enqueue(stvo_lsd* o, const uint8_t* images, stvo_keyline* lines, float* 
 
 extern "C" {
 
-int stvo_lsd_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, const stvo_lsd_params* prm, stvo_lsd** out) {
-    if (!ctx || !prm || !out || B < 1 || cols < 8 || rows < 8 || max_keylines < 1) return STVO_ERR_INVALID_ARG;
+int stvo_lsd_geometry(const stvo_lsd_params* prm, int cols, int rows, int32_t* scaled_cols, int32_t* scaled_rows, double* sigma_out,
+                      int32_t* radius, int32_t* weights) {
+    if (!prm || cols < 8 || rows < 8) return STVO_ERR_INVALID_ARG;
     if (prm->refine != 0 && prm->refine != 1) return STVO_ERR_UNSUPPORTED;  // LSD_REFINE_ADV (rect_improve + the NFA test) is not built; no shipped configuration uses it
     if (prm->refine == 1 && !(prm->density_th >= 0)) return STVO_ERR_INVALID_ARG;
     if (!(prm->scale > 0) || !(prm->ang_th > 0 && prm->ang_th < 180) || prm->n_bins < 1 || prm->n_bins > 4096 || prm->nfeatures < 0)
@@ -2013,6 +2028,49 @@ int stvo_lsd_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, 
     // sort key = (n_bins - 1 - bin) << LSD_IDX_BITS | index, LSD_NOKEY = all ones: with 4096 bins the keys of bin 0 would share their
     // top 12 bits with the undefined pixels' key and the bin-bits-only sort would interleave them
     if (prm->n_bins > stvo::LSD_MAX_BINS) return STVO_ERR_UNSUPPORTED;
+    int w = cols, h = rows, hk = 0;
+    double sigma = 0.0;
+    int32_t kw[STVO_LSD_MAX_TAPS] = {256};  // radius 0: the identity
+    if (prm->scale != 1) {
+        if (!(prm->sigma_scale >= 0)) return STVO_ERR_INVALID_ARG;  // (a negative or NaN sigma has no kernel size)
+        sigma = prm->scale < 1 ? prm->sigma_scale / prm->scale : prm->sigma_scale;
+        const double hd = std::ceil(sigma * std::sqrt(2 * 3.0 * std::log(10.0)));
+        // radii 0 .. 15 are built: radius 3 (sigma between 0.54 and 0.80: scale 1.2 / sigma_scale 0.6 and OpenCV's own 0.8 / 0.6) on the
+        // 7 x 7 kernel of the ORB front-end, the others on lsd_blur_resize_kernel
+        if (!(hd <= STVO_LSD_MAX_RADIUS)) return STVO_ERR_UNSUPPORTED;
+        hk = (int)hd;
+        if (hk > 0) {  // orc_lsd_kernel7 with 7 -> 1 + 2 hk (sigma = 0 has hk = 0 and no Gaussian to evaluate)
+            double k[STVO_LSD_MAX_TAPS], sum = 0.0;
+            for (int i = 0; i <= 2 * hk; ++i) {
+                const double x = i - hk;
+                k[i] = std::exp(-x * x / (2.0 * sigma * sigma));
+                sum += k[i];
+            }
+            for (int i = 0; i <= 2 * hk; ++i) kw[i] = (int32_t)std::lrint((float)(k[i] / sum) * 256.0);
+        }
+        const double wd = std::rint((double)cols * prm->scale), hd2 = std::rint((double)rows * prm->scale);  // resize(..., Size(), scale, scale): cvRound
+        if (!(wd >= 1 && hd2 >= 1)) return STVO_ERR_INVALID_ARG;  // nothing is left of the image
+        if (wd >= 65536 || hd2 >= 32768) return STVO_ERR_CAPACITY;
+        w = (int)wd;
+        h = (int)hd2;
+    }
+    if ((long long)w * h > (1ll << stvo::LSD_IDX_BITS) || w >= 65536 || h >= 32768) return STVO_ERR_CAPACITY;
+    if (scaled_cols) *scaled_cols = w;
+    if (scaled_rows) *scaled_rows = h;
+    if (sigma_out) *sigma_out = sigma;
+    if (radius) *radius = hk;
+    if (weights)
+        for (int i = 0; i < STVO_LSD_MAX_TAPS; ++i) weights[i] = kw[i];
+    return STVO_OK;
+}
+
+int stvo_lsd_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, const stvo_lsd_params* prm, stvo_lsd** out) {
+    if (!ctx || !out || B < 1 || max_keylines < 1) return STVO_ERR_INVALID_ARG;
+    int32_t gw = 0, gh = 0, radius = 0, kw[STVO_LSD_MAX_TAPS];
+    TRY(stvo_lsd_geometry(prm, cols, rows, &gw, &gh, nullptr, &radius, kw));
+    stvo::BlurResizePlan plan{};
+    // (a tile of the fused kernel holds the source window of one output pixel at least: scales far below 0.01 do not fit the LDS)
+    if (prm->scale != 1 && radius != 3 && !stvo::plan_blur_resize_u8(cols, rows, prm->scale, radius, &plan)) return STVO_ERR_UNSUPPORTED;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     stvo_lsd* o = new (std::nothrow) stvo_lsd();
     if (!o) return STVO_ERR_HIP;
@@ -2021,27 +2079,10 @@ int stvo_lsd_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, 
     stvo::LsdDev& d = o->d;
     d.B = B; d.cols = cols; d.rows = rows; d.w = cols; d.h = rows;
     d.scale = prm->scale;
-    if (prm->scale != 1) {
-        const double sigma = prm->scale < 1 ? prm->sigma_scale / prm->scale : prm->sigma_scale;
-        const unsigned hk = (unsigned)std::ceil(sigma * std::sqrt(2 * 3.0 * std::log(10.0)));
-        if (hk != 3) {  // only the 7 x 7 blur is built (sigma between 0.54 and 0.80: scale 1.2 / sigma_scale 0.6 and OpenCV's own 0.8 / 0.6)
-            delete o;
-            return STVO_ERR_UNSUPPORTED;
-        }
-        double k[7], sum = 0.0;  // orc_lsd_kernel7
-        for (int i = 0; i < 7; ++i) {
-            const double x = i - 3;
-            k[i] = std::exp(-x * x / (2.0 * sigma * sigma));
-            sum += k[i];
-        }
-        for (int i = 0; i < 7; ++i) o->k7[i] = (int)std::lrint((float)(k[i] / sum) * 256.0);
-        d.w = (int)std::lrint((double)cols * prm->scale);  // resize(..., Size(), scale, scale): cvRound
-        d.h = (int)std::lrint((double)rows * prm->scale);
-    }
-    if ((long long)d.w * d.h > (1ll << stvo::LSD_IDX_BITS) || d.w >= 65536 || d.h >= 32768) {
-        delete o;
-        return STVO_ERR_CAPACITY;
-    }
+    d.w = gw; d.h = gh;  // stvo_lsd_geometry: the scaled size, the blur's radius and weights
+    o->radius = radius;
+    for (int i = 0; i < STVO_LSD_MAX_TAPS; ++i) o->kw[i] = kw[i];
+    o->plan = plan;
     d.n_bins = prm->n_bins;
     d.rho = prm->quant / std::sin(stvo::LSD_PI * prm->ang_th / 180);
     d.prec = stvo::LSD_PI * prm->ang_th / 180;
@@ -2063,7 +2104,7 @@ int stvo_lsd_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, 
             return o;
         }
     } c;
-    const size_t o_blur = c.take(nb * cols * rows), o_scaled = c.take(nb * npx), o_img = c.take(nb * cols * rows), o_px = c.take(nb * npx * sizeof(stvo::LsdPx)),
+    const size_t o_blur = c.take(radius == 3 ? nb * cols * rows : 0) /* (the fused kernel keeps the blurred bytes in LDS) */, o_scaled = c.take(nb * npx), o_img = c.take(nb * cols * rows), o_px = c.take(nb * npx * sizeof(stvo::LsdPx)),
                  o_k32 = c.take(nb * npx * 4), o_cnt = c.take(nb * ((npx + stvo::LSD_UNIT - 1) / stvo::LSD_UNIT) * (size_t)d.n_bins * 4),
                  o_order = c.take(nb * npx * 4), o_reg = c.take(nb * npx * 4), o_kmax = c.take(nb * 4), o_seg = c.take(nb * d.seg_cap * 16),
                  o_nseg = c.take(nb * 4), o_lines = c.take(nb * d.K * sizeof(stvo_keyline)),
@@ -2197,6 +2238,21 @@ int stvo_lsd_segments(stvo_lsd* o, const uint8_t* images, float* segments, int c
     HIP_TRY(ctx, hipMemcpyAsync(n_segments, d.n_seg, (size_t)d.B * 4, hipMemcpyDeviceToHost, ctx->stream));
     const int take = cap < d.seg_cap ? cap : d.seg_cap;
     HIP_TRY(ctx, hipMemcpy2DAsync(segments, (size_t)cap * 16, d.seg, (size_t)d.seg_cap * 16, (size_t)take * 16, d.B, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return STVO_OK;
+}
+
+int stvo_lsd_scaled_image(stvo_lsd* o, const uint8_t* images, uint8_t* scaled) {
+    if (!o || !images || !scaled) return STVO_ERR_INVALID_ARG;
+    stvo_ctx* ctx = o->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const stvo::LsdDev& d = o->d;
+    HIP_TRY(ctx, hipMemcpyAsync(o->img, images, (size_t)d.B * d.cols * d.rows, hipMemcpyHostToDevice, ctx->stream));
+    if (d.scale != 1) {
+        lsd_scaled_enqueue(o, o->img);
+        TRY(check_launch(ctx));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(scaled, d.scale != 1 ? o->scaled : o->img, (size_t)d.B * d.w * d.h, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return STVO_OK;
 }

@@ -25,7 +25,7 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_orb_set_pattern", "stvo_orb_get_pattern", "stvo_orb_detect", "stvo_orb_detect_dev", "stvo_orb_detect_levels",
            "stvo_orb_detect_levels_dev", "stvo_orb_set_fast_threshold", "stvo_orb_set_score_type", "stvo_seq_upload_dev", "stvo_lbd_create", "stvo_lbd_destroy",
            "stvo_lbd_compute", "stvo_lbd_compute_dev", "stvo_debug_reparse_env", "stvo_lsd_create", "stvo_lsd_destroy", "stvo_lsd_detect",
-           "stvo_lsd_detect_dev", "stvo_lsd_segments", "stvo_lsd_counts", "stvo_fld_create", "stvo_fld_destroy", "stvo_fld_detect",
+           "stvo_lsd_detect_dev", "stvo_lsd_segments", "stvo_lsd_counts", "stvo_lsd_geometry", "stvo_lsd_scaled_image", "stvo_fld_create", "stvo_fld_destroy", "stvo_fld_detect",
            "stvo_fld_detect_dev", "stvo_fld_counts", "stvo_fld_segments", "stvo_fld_edges", "stvo_keylines_xy_dev", "stvo_rectify_compute",
            "stvo_rectify_create", "stvo_rectify_create_from_maps", "stvo_rectify_destroy", "stvo_rectify_camera", "stvo_rectify_images",
            "stvo_rectify_images_dev", "stvo_orb_set_fast_thresholds", "stvo_orb_set_fast_thresholds_dev", "stvo_fast_adapt_dev",
@@ -247,6 +247,9 @@ def load():
     L.stvo_lsd_detect_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 4
     L.stvo_lsd_segments.argtypes = [C.c_void_p, u8p, f32p, C.c_int, i32p]
     L.stvo_lsd_counts.argtypes = [C.c_void_p, i32p, i32p]
+    L.stvo_lsd_geometry.argtypes = [C.POINTER(LsdParams), C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_int32), i32p]
+    L.stvo_lsd_scaled_image.argtypes = [C.c_void_p, u8p, u8p]
     L.stvo_fld_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FldParams), C.POINTER(C.c_void_p)]
     L.stvo_fld_destroy.argtypes = [C.c_void_p]
     L.stvo_fld_detect.argtypes = [C.c_void_p, u8p, C.c_void_p, C.c_void_p, i32p]
@@ -520,6 +523,21 @@ def lsd_params(min_length=0.0, nfeatures=300, refine=0, scale=1.2, sigma_scale=0
     return LsdParams(refine, n_bins, scale, sigma_scale, quant, ang_th, 1.0, 0.6, min_length, nfeatures, 0)
 
 
+LSD_MAX_RADIUS = 15  # STVO_LSD_MAX_RADIUS
+
+
+def lsd_geometry(prm, cols, rows):
+    """stvo_lsd_geometry (host only, no context): what a parameter set means for cols x rows images — the scaled size, sigma and radius
+    of the blur and the 1 + 2 radius integer weights of one pass; StvoError where stvo_lsd_create would refuse."""
+    lib = load()
+    w, h, radius, sigma = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+    k = np.zeros(1 + 2 * LSD_MAX_RADIUS, np.int32)
+    rc = lib.stvo_lsd_geometry(C.byref(prm), cols, rows, C.byref(w), C.byref(h), C.byref(sigma), C.byref(radius), k)
+    if rc != 0:
+        raise StvoError(f"{lib.stvo_error_string(rc).decode()} ({rc}): stvo_lsd_geometry")
+    return dict(cols=w.value, rows=h.value, sigma=sigma.value, radius=radius.value, weights=k[:1 + 2 * radius.value].copy())
+
+
 class Lsd:
     """The LSD key-line detector for B images of one size (stvo_lsd_*)."""
 
@@ -527,6 +545,7 @@ class Lsd:
         self.ctx, self.B, self.cols, self.rows, self.M = ctx, B, cols, rows, max_keylines
         self.h = C.c_void_p()
         ctx._chk(ctx.lib.stvo_lsd_create(ctx.h, B, cols, rows, max_keylines, C.byref(prm), C.byref(self.h)))
+        self.geometry = lsd_geometry(prm, cols, rows)
 
     def close(self):
         if self.h:
@@ -559,6 +578,13 @@ class Lsd:
         n = np.zeros(self.B, np.int32)
         self.ctx._chk(self.ctx.lib.stvo_lsd_segments(self.h, images.reshape(-1), seg.reshape(-1), cap, n))
         return [seg[b, :min(n[b], cap)].copy() for b in range(self.B)], n
+
+    def scaled_image(self, images):
+        """The image the detector core sees (blurred and resized; the input itself at scale 1): uint8 [B, scaled rows, scaled cols]."""
+        images = np.ascontiguousarray(images, np.uint8).reshape(self.B, self.rows, self.cols)
+        out = np.zeros((self.B, self.geometry["rows"], self.geometry["cols"]), np.uint8)
+        self.ctx._chk(self.ctx.lib.stvo_lsd_scaled_image(self.h, images.reshape(-1), out.reshape(-1)))
+        return out
 
 
 class FldParams(C.Structure):  # stvo_fld_params

@@ -1,0 +1,88 @@
+"""LSD at any lsd_scale, the host side (no GPU): stvo_lsd_geometry — what stvo_lsd_create derives from (lsd_scale, lsd_sigma_scale)
+and the image size, callable without a context — against the numpy statement of tests/lsd_scale_statement.py, and that statement's
+own footing: composed from the oracle at scale 1 it reproduces the oracle at the scales the oracle itself accepts."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import lsd_scale_statement as st
+from stvo_amd import synth
+
+
+def scenes():
+    return [synth.make_image(900 + i, 160, 96, n_rects=30, n_discs=4) for i in range(3)]
+
+
+def test_composition_equals_the_oracle_at_scale_2(oracle):
+    """Scale 2.0 / sigma_scale 0.6 has radius 3, which the oracle accepts directly; dividing by 2 is exact: bit for bit."""
+    assert st.sigma_radius(2.0, 0.6)[1] == 3
+    for img in scenes():
+        want = oracle.lsd_segments(img, oracle.lsd_opts(scale=2.0))
+        got = st.segments(oracle, img, 2.0, 0.6)
+        assert len(want) >= 10
+        assert got.shape == want.shape and np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("scale", [0.8, 1.2])
+def test_composition_follows_the_oracle_within_the_rounding_bound(oracle, scale):
+    """float((x + 0.5) / scale) against float(float(x + 0.5) / scale): same count and order, at most 2^-23 relative apart."""
+    assert st.sigma_radius(scale, 0.6)[1] == 3
+    for img in scenes():
+        want = oracle.lsd_segments(img, oracle.lsd_opts(scale=scale))
+        got = st.segments(oracle, img, scale, 0.6)
+        assert len(want) >= 5 and got.shape == want.shape
+        assert np.all(np.abs(got.astype(np.float64) - want) <= st.REL_BOUND * np.abs(want.astype(np.float64)))
+
+
+@pytest.mark.parametrize("scale,sigma_scale,radius", st.PAIRS + [(2.0, 1.0, 4), (0.6, 0.6, 4)])
+def test_geometry_weights_against_the_statement(scale, sigma_scale, radius):
+    from stvo_amd import capi
+    g = capi.lsd_geometry(capi.lsd_params(scale=scale, sigma_scale=sigma_scale), 97, 61)
+    sigma, h, w = st.weights(scale, sigma_scale)
+    assert h == radius and g["radius"] == radius
+    assert g["sigma"] == sigma
+    assert g["weights"].dtype == np.int32 and np.array_equal(g["weights"], w)
+    assert (g["cols"], g["rows"]) == (int(np.rint(97 * scale)), int(np.rint(61 * scale)))
+
+
+def test_geometry_facts_a_kernel_must_survive():
+    from stvo_amd import capi
+
+    def w(scale, sigma_scale):
+        return capi.lsd_geometry(capi.lsd_params(scale=scale, sigma_scale=sigma_scale), 640, 480)["weights"]
+    assert list(w(1.5, 0.0)) == [256]                       # radius 0: the identity
+    assert list(w(1.5, 0.2)) == [0, 256, 0]                 # a weight of 256 does not fit a byte
+    assert list(w(0.65, 0.6)) == [0, 1, 11, 62, 111, 62, 11, 1, 0] and w(0.65, 0.6).sum() == 259
+    assert len(w(0.22, 0.8)) == 29 and w(0.22, 0.8).sum() == 252
+    g1 = capi.lsd_geometry(capi.lsd_params(scale=1.0), 640, 480)   # scale 1: no blur, no resize
+    assert (g1["cols"], g1["rows"], g1["radius"], list(g1["weights"])) == (640, 480, 0, [256])
+
+
+def test_geometry_radius_3_is_the_oracles_kernel(oracle):
+    from stvo_amd import capi
+    oracle.lib.orc_lsd_kernel7.argtypes = [C.c_double, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")]
+    oracle.lib.orc_lsd_kernel7.restype = None
+    for scale, sigma_scale in ((1.2, 0.6), (0.8, 0.6), (2.0, 0.6), (0.9, 0.55)):
+        g = capi.lsd_geometry(capi.lsd_params(scale=scale, sigma_scale=sigma_scale), 320, 200)
+        k7 = np.zeros(7, np.int32)
+        oracle.lib.orc_lsd_kernel7(g["sigma"], k7)
+        assert g["radius"] == 3 and np.array_equal(g["weights"], k7)
+
+
+def test_geometry_refuses_what_create_refuses():
+    from stvo_amd import capi
+    from stvo_amd.capi import StvoError
+    assert capi.lsd_geometry(capi.lsd_params(scale=0.25, sigma_scale=1.0), 640, 480)["radius"] == 15
+    for scale, sigma_scale in ((0.2, 0.85), (0.2, 0.9), (1.5, 4.4)):    # radius 16, 17, 17
+        assert st.sigma_radius(scale, sigma_scale)[1] >= 16
+        with pytest.raises(StvoError, match=r"\(-5\)"):                   # STVO_ERR_UNSUPPORTED
+            capi.lsd_geometry(capi.lsd_params(scale=scale, sigma_scale=sigma_scale), 640, 480)
+    with pytest.raises(StvoError, match=r"\(-5\)"):
+        capi.lsd_geometry(capi.lsd_params(refine=2), 640, 480)            # LSD_REFINE_ADV
+    with pytest.raises(StvoError, match=r"\(-4\)"):
+        capi.lsd_geometry(capi.lsd_params(), 2000, 1000)                  # more than 2^20 pixels after scaling: STVO_ERR_CAPACITY
+    with pytest.raises(StvoError, match=r"\(-1\)"):
+        capi.lsd_geometry(capi.lsd_params(scale=0.5, sigma_scale=-0.6), 640, 480)
+    with pytest.raises(StvoError, match=r"\(-1\)"):
+        capi.lsd_geometry(capi.lsd_params(scale=0.0), 640, 480)
