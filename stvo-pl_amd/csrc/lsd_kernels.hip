@@ -10,18 +10,28 @@
 //                        contributes to a region angle, the largest squared gradient of the image (integer atomic max)
 //   lsd_hist / lsd_scan / lsd_scatter_kernel   the pseudo-ordering: the defined pixels by bin of the gradient norm, highest bin first,
 //                        row-major inside a bin (oracle note (1)) — a stable counting sort written here (until round 5: rocPRIM's radix sort)
-//   lsd_grow_kernel      the search: region_grow + region2rect for every unused seed in that order.  Inherently sequential
-//                        per image — whether a pixel joins depends on the running region angle, which changes with every pixel
-//                        added, and on what all earlier regions took — so ONE wavefront walks an image and the batch supplies
-//                        the parallelism.  Inside the wave the work of one step is spread over the lanes: the 9 neighbours of
+//   the search           region_grow + region2rect for every unused seed in that order.  Inherently sequential per image — whether a
+//                        pixel joins depends on the running region angle, which changes with every pixel added, and on what all
+//                        earlier regions took.  Inside a wave the work of one step is spread over the lanes: the 9 neighbours of
 //                        7 consecutive region points are fetched by 63 lanes at once (one memory round trip per 7 points) and
-//                        then resolved in order with ballots; the sums of region2rect are accumulated strictly in region
-//                        order (lane-parallel products, serial additions through v_readlane), so every rounding is the oracle's
+//                        then resolved in the oracle's order; the sums of region2rect are accumulated strictly in region order
+//                        (lane-parallel products, serial additions), so every rounding is the oracle's.  Each job is ONE routine:
+//                          lsd_angle_dist    isAligned's distance of two angles
+//                          lsd_grow_plain    region_grow, candidates one after the other (the oracle's loop as it stands)
+//                          lsd_grow_fast     region_grow, a sub-group's candidates by guess + verification (same regions)
+//                          lsd_region2rect   the rectangle; its ordered sums through LDS chains (add_ordered) or v_readlane
+//                          lsd_segment       rectangle -> end points in the input image
+//                        and three kernels say who calls them:
+//   lsd_grow_kernel      ONE wavefront walks an image, the batch supplies the parallelism: lsd_grow_fast + LDS chains
 //   lsd_grow_xcd_kernel  the same search for batches of <= 128 images as an exact speculate / commit protocol over the CUs of one XCD per
-//                        image: a committing wave (LDS bitmap), a dispatcher, a feeder, speculating workgroups (9 ms instead of 63 per image)
-//   lsd_grow_refine_kernel  lsd_refine = 1 (LSD_REFINE_STD): the plain search with refine / reduce_region_radius — a sparse region gives its
-//                        pixels back, is grown again under a tolerance from the angles near its seed, then cut back by radius; one wave per
-//                        image for every batch size (flags that turn off break the strike-off and the speculation of the other forms)
+//                        image: a committing wave (LDS bitmap), a dispatcher, a feeder, speculating workgroups (9 ms instead of 63 per
+//                        image); the committer and the speculating waves grow with lsd_grow_fast
+//   lsd_grow_refine_kernel  one wave per image on lsd_grow_plain + v_readlane sums, for every batch size.  <REFINE = true>: lsd_refine = 1
+//                        (LSD_REFINE_STD) — a sparse region gives its pixels back, is grown again under a tolerance from the angles near
+//                        its seed, then cut back by radius (flags that turn off break the strike-off and the speculation of the other
+//                        forms).  <REFINE = false>: STVO_LSD_GROW=0, the in-library cross-check of the fast routines
+//                        The three take a bool PROF: the <PROF = true> instances carry the developer's cycle counters and debug rows
+//                        (LsdProbe) and run only while stvo_lsd_debug has them switched on; the shipped instances hold none of it
 //   lsd_keylines_kernel  the wrapper: checkLineExtremes, length, min_length, KeyLine fields (numOfPixels = the CLIPPED cv::LineIterator
 //                        count), top-N by response (stable)
 // Byte / integer work except where the source computes in floating point; no fused multiply-adds outside the two of the sine /
@@ -78,7 +88,7 @@ struct LsdDev {
     float4* seg;               // [B][seg_cap] (x1, y1, x2, y2) in detection order
     int32_t* n_seg;            // [B]
     int32_t* n_pass;           // [B] segments longer than min_length, before the top-N / capacity cut (stvo_lsd_counts)
-    double* dbg;               // developer aid (stvo_lsd_debug): [B][seg_cap][8] cx, cy, Ixx, Iyy, Ixy, theta, l_min, l_max, or nullptr
+    double* dbg;               // developer aid (stvo_lsd_debug), touched by the PROF instances of the search kernels only: [B][seg_cap][8] cx, cy, Ixx, Iyy, Ixy, theta, l_min, l_max, or nullptr
     // outputs of the wrapper
     stvo_keyline* lines;       // [B][K]
     float* response;           // [B][K] or nullptr
@@ -248,6 +258,7 @@ __global__ __launch_bounds__(256) void lsd_scatter_kernel(LsdDev d) {
 }
 
 constexpr int LSD_RING = 1024;  // the most recent region points, in LDS (4 KB: the LDS must not limit the images in flight per CU)
+constexpr int LSD_WRING = 256;  // the same per wave of lsd_grow_xcd_kernel
 constexpr int LSD_GR = 2;       // sub-groups of 7 region points (63 lanes) fetched per round of the region growing
 
 // The flags / the region list are written by lane 0 and read by all lanes of the SAME wave later: workgroup-scope ordering is
@@ -268,16 +279,499 @@ __device__ __forceinline__ void wave_publish() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
+// LDS of this wave: the writes so far before the reads that follow
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// the committer of lsd_grow_xcd_kernel keeps the flags it decides on as a bitmap in LDS
+__device__ __forceinline__ unsigned bit_ld(const unsigned* bits, int q) { return (__hip_atomic_load(bits + (q >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> (q & 31)) & 1u; }
+__device__ __forceinline__ void bit_set(unsigned* bits, int q) { (void)__hip_atomic_fetch_or(bits + (q >> 5), 1u << (q & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
-// FAST (the default; STVO_LSD_GROW=0 selects the plain form, debug_switches.h): a sub-group's candidates are resolved by guess +
-// verification instead of one after the other, region2rect's ordered sums read their terms from LDS instead of through v_readlane,
-// the loads of all sub-groups of a round are issued before the first is used.  Same results: the plain form is the direct statement
-// of the oracle's loops and stays as the in-library cross-check (tests/test_gpu_lsd.py runs both).  Round 4, one KITTI-size image:
-// 233 M cycles plain, 155 M fast (NOTES.md has the table of the steps in between).
-template <bool FAST>
+// The developer's cycle counters and event counts (stvo_lsd_debug, tools/lsd_probe.py).  Only the PROF instances of the search
+// kernels, which lsd_enqueue launches while stvo_lsd_debug has them enabled, hold any of it: for the shipped instances the type is
+// empty and every call on it compiles to nothing.
+template <bool PROF>
+struct LsdProbe {
+    long long v[16] = {};
+    bool on;  // this wave measures
+    __device__ explicit LsdProbe(bool on_) : on(on_) {}
+    __device__ long long now() const { return on ? (long long)__builtin_readcyclecounter() : 0ll; }
+    __device__ void add(int i, long long x) { v[i] += x; }
+    __device__ void settle() const {  // everything in flight has arrived: what follows is timed alone (this changes what it measures)
+        if (on) __builtin_amdgcn_s_waitcnt(0);
+    }
+};
+template <>
+struct LsdProbe<false> {
+    __device__ explicit LsdProbe(bool) {}
+    __device__ long long now() const { return 0ll; }
+    __device__ void add(int, long long) {}
+    __device__ void settle() const {}
+};
+// what a one-wave kernel counts, in the order of its two counter rows (behind the total)
+enum { OW_GROW, OW_RES, OW_RECT, OW_ROUNDS, OW_ADD, OW_REGIONS, OW_BATCHES, OW_PUB, OW_ISSUE, OW_WAIT, OW_SEED, OW_N };
+
+// isAligned: the distance of two level-line angles, folded at 3 pi / 2
+__device__ __forceinline__ double lsd_angle_dist(double theta, double a) {
+    double n_theta = theta - a;
+    if (n_theta < 0) n_theta = -n_theta;
+    if (n_theta > LSD_3_2_PI) {
+        n_theta -= LSD_2_PI;
+        if (n_theta < 0) n_theta = -n_theta;
+    }
+    return n_theta;
+}
+
+// The batch of 64 seeds a one-wave kernel is working through: lane l holds the seed of rank o0 + l.  A seed of the batch that a region
+// grown from an earlier seed of the batch takes is struck off as it is taken (one compare + ballot per pixel added) — re-reading the
+// flags after every region cost a memory round trip per region
+struct LsdSeeds {
+    int q_l;                  // the seed's pixel
+    bool key_ok;              // (the last batch of an image is not full)
+    unsigned long long todo;  // the seeds still to be looked at, a lane mask
+};
+
+// One round of the region growing: the next (up to) 7 LSD_GR region points — sub-group r holds points i + 7 r .. i + 7 r + 6, lane =
+// 9 x point + neighbour — fetched together, then resolved sub-group after sub-group, lane after lane: the oracle's order.
+//
+// PLAIN region_grow from `seed` (angle ang_deg) under the tolerance tol — the direct statement of the oracle's loop: the candidates of
+// a sub-group are taken one after the other.  The list goes to reg (and the ring), the size is returned.  STVO_LSD_GROW=0 and
+// lsd_refine = 1 run it; the former as the in-library cross-check of the fast form below (tests/test_gpu_lsd.py runs both).
+template <bool PROF>
+__device__ __forceinline__ int lsd_grow_plain(LsdPx* px, int32_t* reg, int* ring, int seed, float ang_deg, int w, int h, double tol, LsdSeeds& sd,
+                                              double& reg_angle, LsdProbe<PROF>& pr) {
+    const int lane = threadIdx.x & 63, npx = w * h;
+    const long long tg0 = pr.now();
+    pr.add(OW_REGIONS, 1);
+    const int sx0 = seed % w, sy0 = seed / w;
+    reg_angle = (double)ang_deg * LSD_DEG2RAD;
+    double sn0, cs0;
+    sincos_det(reg_angle, sn0, cs0);
+    float sumdx = (float)cs0, sumdy = (float)sn0;
+    int n_reg = 1;
+    if (lane == 0) {
+        st_coherent(&px[seed].used, 1);
+        st_coherent(reg, sx0 | (sy0 << 16));
+        ring[0] = sx0 | (sy0 << 16);
+    }
+    pr.add(OW_SEED, pr.now() - tg0);
+    for (int i = 0; i < n_reg;) {
+        const long long tp0 = pr.now();
+        wave_publish();  // lane 0's stores of the earlier rounds before the flag / list loads below
+        pr.settle();
+        const long long tp1 = pr.now();
+        pr.add(OW_PUB, tp1 - tp0);
+        const int cnt = n_reg - i < 7 * LSD_GR ? n_reg - i : 7 * LSD_GR;  // uniform
+        const int slot0 = lane / 9, nb = lane - slot0 * 9;
+        int qq[LSD_GR], xy[LSD_GR];
+        float2 cs[LSD_GR];
+        double ad[LSD_GR];
+        bool cand[LSD_GR];
+#pragma unroll
+        for (int r = 0; r < LSD_GR; ++r) {
+            const int slot = 7 * r + slot0;
+            bool valid = lane < 63 && slot < cnt && nb != 4;  // (the centre is the region point itself)
+            int pxy = 0;
+            if (valid) pxy = (n_reg - (i + slot) <= LSD_RING) ? ring[(i + slot) & (LSD_RING - 1)] : ld_coherent(reg + i + slot);
+            const int xx = (pxy & 0xFFFF) + (nb % 3) - 1, yy = (pxy >> 16) + nb / 3 - 1;  // neighbours row by row
+            valid = valid && xx >= 0 && xx < w && yy >= 0 && yy < h;
+            qq[r] = valid ? yy * w + xx : 0;
+            xy[r] = xx | (yy << 16);
+            int u = 1;
+            float a = -1.f;
+            cs[r] = make_float2(0.f, 0.f);
+            if (valid) {
+                const LsdPx t = px_ld(px + qq[r]);
+                u = t.used;
+                a = t.ang;
+                cs[r] = make_float2(t.c, t.s);
+            }
+            cand[r] = valid && u == 0 && a >= 0.f;
+            ad[r] = (double)a * LSD_DEG2RAD;
+        }
+        const long long ti1 = pr.now();  // the loads are issued ...
+        pr.settle();
+        const long long tr0 = pr.now();  // ... and have arrived
+        pr.add(OW_ISSUE, ti1 - tp1);
+        pr.add(OW_WAIT, tr0 - ti1);
+        pr.add(OW_ROUNDS, 1);
+#pragma unroll
+        for (int r = 0; r < LSD_GR; ++r) {
+            if (7 * r >= cnt) break;  // uniform
+            int next = 0;  // lanes below `next` have had their turn
+            for (;;) {
+                const unsigned long long m = __ballot(cand[r] && lane >= next && lsd_angle_dist(reg_angle, ad[r]) <= tol);
+                if (!m || n_reg >= npx) break;  // (the bound can only bind if a flag were lost: never write past the list)
+                const int L = __builtin_ctzll(m);
+                const int qL = __builtin_amdgcn_readlane(qq[r], L), xyL = __builtin_amdgcn_readlane(xy[r], L);
+                const float cL = readlane_f32(cs[r].x, L), sL = readlane_f32(cs[r].y, L);
+                if (lane == 0) {
+                    st_coherent(&px[qL].used, 1);
+                    st_coherent(reg + n_reg, xyL);
+                    ring[n_reg & (LSD_RING - 1)] = xyL;
+                }
+                ++n_reg;
+#pragma unroll
+                for (int r2 = 0; r2 < LSD_GR; ++r2) cand[r2] = cand[r2] && qq[r2] != qL;  // the same pixel seen from another point of the round
+                sd.todo &= ~__ballot(sd.key_ok && sd.q_l == qL);
+                sumdx += cL;
+                sumdy += sL;
+                reg_angle = (double)fast_atan2_deg(sumdy, sumdx) * LSD_DEG2RAD;
+                next = L + 1;
+            }
+        }
+        pr.add(OW_RES, pr.now() - tr0);
+        i += cnt;
+        wave_lds_sync();  // the ring: lane 0's writes before the next round's reads
+    }
+    pr.add(OW_GROW, pr.now() - tg0);
+    pr.add(OW_ADD, n_reg);
+    return n_reg;
+}
+
+// FAST region_grow from `seed` (the default of every route without refinement): a sub-group's candidates are resolved by guess +
+// verification instead of one after the other, and the loads of all sub-groups of a round are issued before the first is used.  Same
+// results as the plain form.  Round 4, one KITTI-size image: 233 M cycles plain, 155 M fast (NOTES.md has the table of the steps in
+// between).
+//   MARK     (a one-wave kernel, the committer): a pixel is taken by setting its flag.  !MARK (a speculating wave): the flags are only
+//            read; the wave's own pixels carry `id` in `stamp`.
+//   FAR      the flag in a pixel's record is stored by ANOTHER CU: the load bypasses the vector L1.
+//   BITS     (with MARK) the flags this wave decides on are a bitmap in LDS (`bits`); `used` is only written — for the waves of other CUs.
+//   RING     points of the ring in LDS.
+//   STRIKE   the pixels taken strike the later seeds of the batch `sd` off (else sd is not looked at).
+//   SKIP_AT_CAP  what happens where a sub-group might not fit the list of `cap` entries: the sub-group is passed over, or (else) the
+//            growth ends and -1 is returned.  With cap = w h the bound can only bind if a flag were lost or in an image of w + h <= 64
+//            (the gradient leaves the last row and column undefined: a region has at most (w - 1)(h - 1) pixels); each caller keeps
+//            the behaviour it always had.
+// The list goes to `list`, the final region angle to `angle_out`, the size is returned.
+template <bool MARK, bool FAR, bool BITS, int RING, bool STRIKE, bool SKIP_AT_CAP, bool PROF>
+__device__ __forceinline__ int lsd_grow_fast(LsdPx* px, int32_t* stamp, int id, unsigned* bits, int32_t* list, int cap, int* ring, int seed,
+                                             float seed_ang, int w, int h, double prec, LsdSeeds* sd, double& angle_out, LsdProbe<PROF>& pr) {
+    const int lane = threadIdx.x & 63;
+    const long long tg0 = pr.now();
+    pr.add(OW_REGIONS, 1);
+    const int sx0 = seed % w, sy0 = seed / w;
+    double reg_angle = (double)seed_ang * LSD_DEG2RAD;
+    double sn0, cs0;
+    sincos_det(reg_angle, sn0, cs0);
+    float sumdx = (float)cs0, sumdy = (float)sn0;
+    int n_reg = 1;
+    if (lane == 0) {
+        if (MARK) st_coherent(&px[seed].used, 1);
+        else st_coherent(stamp + seed, id);
+        if (BITS) bit_set(bits, seed);
+        st_coherent(list, sx0 | (sy0 << 16));
+        ring[0] = sx0 | (sy0 << 16);
+    }
+    pr.add(OW_SEED, pr.now() - tg0);
+    for (int i = 0; i < n_reg;) {
+        const int cnt = n_reg - i < 7 * LSD_GR ? n_reg - i : 7 * LSD_GR;  // uniform
+        const int slot0 = lane / 9, nb = lane - slot0 * 9;
+        int qq[LSD_GR], xy[LSD_GR], pxyv[LSD_GR], u[LSD_GR], own[LSD_GR];
+        float2 cs[LSD_GR];
+        float a[LSD_GR];
+        double ad[LSD_GR];
+        bool val[LSD_GR];
+        const long long tp0 = pr.now();
+        wave_publish();  // the stores of the earlier rounds before the flag / list loads below
+        pr.settle();
+        const long long tp1 = pr.now();
+        pr.add(OW_PUB, tp1 - tp0);
+        // every sub-group's region point first, then every load, then the uses: the flag / angle / (cos, sin) loads of the sub-groups
+        // overlap (one after the other they were two memory round trips per round).  Lanes without a neighbour load pixel 0 and drop
+        // the values
+        const bool in_ring = n_reg - i <= RING;  // uniform: the round's oldest point is still in the LDS ring
+#pragma unroll
+        for (int r = 0; r < LSD_GR; ++r) {
+            const int slot = 7 * r + slot0;
+            val[r] = lane < 63 && slot < cnt && nb != 4;  // (the centre is the region point itself)
+            const int at = val[r] ? i + slot : i;
+            pxyv[r] = in_ring ? ring[at & (RING - 1)] : ld_coherent(list + at);
+        }
+#pragma unroll
+        for (int r = 0; r < LSD_GR; ++r) {
+            const int xx = (pxyv[r] & 0xFFFF) + (nb % 3) - 1, yy = (pxyv[r] >> 16) + nb / 3 - 1;  // neighbours row by row
+            val[r] = val[r] && xx >= 0 && xx < w && yy >= 0 && yy < h;
+            qq[r] = val[r] ? yy * w + xx : 0;
+            xy[r] = xx | (yy << 16);
+            own[r] = MARK ? 0 : ld_coherent(stamp + qq[r]);
+        }
+        {   // the records: one 16-byte gather per sub-group
+            LsdPx t[LSD_GR];
+            if constexpr (FAR) {
+                static_assert(LSD_GR == 2, "two loads in one statement");
+                lsd_f4 v0, v1;
+                asm volatile("global_load_dwordx4 %0, %2, off sc1\n\tglobal_load_dwordx4 %1, %3, off sc1\n\ts_waitcnt vmcnt(0)"
+                             : "=&v"(v0), "=&v"(v1)
+                             : "v"(px + qq[0]), "v"(px + qq[1])
+                             : "memory");
+                t[0].ang = v0.x; t[0].c = v0.y; t[0].s = v0.z; t[0].used = __float_as_int(v0.w);
+                t[1].ang = v1.x; t[1].c = v1.y; t[1].s = v1.z; t[1].used = __float_as_int(v1.w);
+            } else {
+#pragma unroll
+                for (int r = 0; r < LSD_GR; ++r) t[r] = px_ld(px + qq[r]);
+            }
+#pragma unroll
+            for (int r = 0; r < LSD_GR; ++r) {
+                u[r] = BITS ? (int)bit_ld(bits, qq[r]) : t[r].used;
+                a[r] = t[r].ang;
+                cs[r] = make_float2(t[r].c, t[r].s);
+            }
+        }
+        // Every per-lane flag is kept as a 64-bit lane mask in scalar registers (they are compare results to begin with).
+        unsigned long long cand_m[LSD_GR];
+#pragma unroll
+        for (int r = 0; r < LSD_GR; ++r) {
+            cand_m[r] = __ballot(val[r] && u[r] == 0 && (MARK || own[r] != id) && a[r] >= 0.f);
+            ad[r] = (double)a[r] * LSD_DEG2RAD;
+        }
+        const long long ti1 = pr.now();  // the loads are issued ...
+        pr.settle();
+        const long long tr0 = pr.now();  // ... and have arrived
+        pr.add(OW_ISSUE, ti1 - tp1);
+        pr.add(OW_WAIT, tr0 - ti1);
+        pr.add(OW_ROUNDS, 1);
+        // Guess + verification (tools/experiments/lsd_resolve_model.c has the CPU model and the argument).  Only the two float
+        // additions per pixel depend on the order; the ~30 operations of the angle update run for all lanes at once:
+        //   A   = the lanes aligned with the angle at the start of the sub-group
+        //   A'  = A walked from the lowest lane: a lane taken removes the later lanes that hold the same pixel
+        //   lane k: sums_k = start sums + (cos, sin) of A's lanes below k, added in lane order; angle_k = fastAtan2(sums_k), or
+        //           the start angle if A' has no lane below k;  dup_k = a lane of A' below k holds the same pixel
+        //   D   = the lanes aligned with their angle_k and not dup.  D == A': A' is what the sequential loop accepts
+        //         (induction over the lanes); else the lanes below the first difference m are final, lane m's decision is
+        //         D[m]: again with A = A' below m | D from m on (2 % of the sub-groups of a KITTI-size scene).
+        unsigned long long key_m = 0ull;
+        if constexpr (STRIKE) key_m = __ballot(sd->key_ok);
+#pragma unroll
+        for (int r = 0; r < LSD_GR; ++r) {
+            if (7 * r >= cnt) break;  // uniform
+            unsigned long long A = __ballot(lsd_angle_dist(reg_angle, ad[r]) <= prec) & cand_m[r];
+            if (!A) continue;
+            if (n_reg + 64 > cap) {  // uniform
+                if constexpr (SKIP_AT_CAP) continue;
+                else return -1;
+            }
+            unsigned long long acc, kill, hit_m[LSD_GR];
+            float sx, sy;
+            double th;
+            for (;;) {
+                unsigned long long rem = A, dup_m = 0ull;
+                acc = 0ull;
+                kill = 0ull;
+#pragma unroll
+                for (int r2 = 0; r2 < LSD_GR; ++r2) hit_m[r2] = 0ull;
+                sx = sumdx;
+                sy = sumdy;
+                while (rem) {  // uniform: the lanes of the guess, lowest first
+                    const int j = __builtin_ctzll(rem);
+                    const int qj = __builtin_amdgcn_readlane(qq[r], j);
+                    const float cj = readlane_f32(cs[r].x, j), sj = readlane_f32(cs[r].y, j);
+                    const unsigned long long later = j == 63 ? 0ull : ~0ull << (j + 1);
+                    const unsigned long long same = __ballot(qq[r] == qj);
+                    acc |= 1ull << j;
+                    rem &= ~same;  // lane j itself and the later lanes that hold the same pixel
+                    dup_m |= same & later;
+                    const float nx = sx + cj, ny = sy + sj;  // (a select, not a masked addition of zero: x + 0 is not x for x = -0)
+                    const bool is_later = lane > j;
+                    sx = is_later ? nx : sx;
+                    sy = is_later ? ny : sy;
+                    if constexpr (STRIKE) kill |= __ballot(sd->q_l == qj);
+#pragma unroll
+                    for (int r2 = 0; r2 < LSD_GR; ++r2)
+                        if (r2 > r) hit_m[r2] |= __ballot(qq[r2] == qj);
+                }
+                const bool any = lane > __builtin_ctzll(acc);
+                th = any ? (double)fast_atan2_deg(sy, sx) * LSD_DEG2RAD : reg_angle;
+                const unsigned long long D = __ballot(lsd_angle_dist(th, ad[r]) <= prec) & cand_m[r] & ~dup_m;
+                if (D == acc) break;
+                const unsigned long long below = (1ull << __builtin_ctzll(D ^ acc)) - 1ull;
+                A = (acc & below) | (D & ~below);  // (never empty: the lowest lane of a guess sees the start angle, as the guess did)
+            }
+            // acc is the sequential result: every accepted lane stores its own pixel, in lane order
+            if ((acc >> lane) & 1ull) {
+                const int idx = n_reg + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(acc >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)acc, 0u));
+                if (MARK) st_coherent(&px[qq[r]].used, 1);
+                else st_coherent(stamp + qq[r], id);
+                if (BITS) bit_set(bits, qq[r]);
+                st_coherent(list + idx, xy[r]);
+                ring[idx & (RING - 1)] = xy[r];
+            }
+            n_reg += __builtin_popcountll(acc);
+            sumdx = readlane_f32(sx, 63);  // lane 63 is never a candidate: its sums are the sums over all of acc
+            sumdy = readlane_f32(sy, 63);
+            reg_angle = readlane_f64(th, 63);
+            if constexpr (STRIKE) sd->todo &= ~(kill & key_m);
+#pragma unroll
+            for (int r2 = 0; r2 < LSD_GR; ++r2)
+                if (r2 > r) cand_m[r2] &= ~hit_m[r2];
+        }
+        pr.add(OW_RES, pr.now() - tr0);
+        i += cnt;
+        wave_lds_sync();  // the ring: this round's writes before the next round's reads
+    }
+    pr.add(OW_GROW, pr.now() - tg0);
+    pr.add(OW_ADD, n_reg);
+    angle_out = reg_angle;
+    return n_reg;
+}
+
+// region2rect: what the rectangle of a region is made of
+struct LsdRect {
+    double cx, cy;         // the centre of mass
+    double Ixx, Iyy, Ixy;  // the inertia sums
+    double theta, dx, dy;  // the direction and its cos / sin
+    double l_min, l_max;   // the region's extent along it
+    double width;          // and across it, at least 1 (lsd_refine = 1 asks for it)
+};
+
+// The three ordered sums of a pass of region2rect as three independent chains: lane l < 3 adds row l of `term` ([3][64] doubles of
+// LDS) term by term into its `chain` (one LDS read + one addition per region point instead of six v_readlane + three additions)
+__device__ __forceinline__ void add_ordered(double (*term)[64], double t0, double t1, double t2, int cn, double& chain) {
+    const int lane = threadIdx.x & 63;
+    term[0][lane] = t0;
+    term[1][lane] = t1;
+    term[2][lane] = t2;
+    wave_lds_sync();
+    if (lane < 3) {
+        const double* row = term[lane];
+#pragma unroll 8
+        for (int k = 0; k < cn; ++k) chain += row[k];
+    }
+    wave_lds_sync();  // the reads before the next chunk's writes
+}
+
+// region2rect of list[0 .. n_reg): every sum strictly in region order, so that every addition rounds as the oracle's.  The lanes form
+// the products; the additions are serial — CHAINS (the fast form): through add_ordered, else through v_readlane.
+template <bool CHAINS>
+__device__ __forceinline__ LsdRect lsd_region2rect(const int32_t* list, int n_reg, const int32_t* __restrict__ k32, int w, double reg_angle, double prec,
+                                                   double (*term)[64]) {
+    const int lane = threadIdx.x & 63;
+    wave_publish();
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;  // the running sums (CHAINS: s0 is the lane's chain)
+    auto add3 = [&](double t0, double t1, double t2, int cn) {
+        if constexpr (CHAINS) {
+            add_ordered(term, t0, t1, t2, cn, s0);
+        } else {
+            for (int k = 0; k < cn; ++k) {
+                s0 += readlane_f64(t0, k);
+                s1 += readlane_f64(t1, k);
+                s2 += readlane_f64(t2, k);
+            }
+        }
+    };
+    auto take3 = [&](double& a, double& b, double& c) {
+        a = CHAINS ? readlane_f64(s0, 0) : s0;
+        b = CHAINS ? readlane_f64(s0, 1) : s1;
+        c = CHAINS ? readlane_f64(s0, 2) : s2;
+        s0 = s1 = s2 = 0.0;
+    };
+    LsdRect rc;
+    for (int c0 = 0; c0 < n_reg; c0 += 64) {
+        const int t = c0 + lane, cn = n_reg - c0 < 64 ? n_reg - c0 : 64;
+        int pxy = 0;
+        double wgt = 0.0;
+        if (t < n_reg) {
+            pxy = ld_coherent(list + t);
+            wgt = sqrt((double)k32[(pxy >> 16) * w + (pxy & 0xFFFF)] / 4.0);  // the gradient norm (ll_angle's expression)
+        }
+        add3((double)(pxy & 0xFFFF) * wgt, (double)(pxy >> 16) * wgt, wgt, cn);
+    }
+    double X, Y, S;
+    take3(X, Y, S);
+    const double cx = X / S, cy = Y / S;
+    for (int c0 = 0; c0 < n_reg; c0 += 64) {
+        const int t = c0 + lane, cn = n_reg - c0 < 64 ? n_reg - c0 : 64;
+        double t_xx = 0.0, t_yy = 0.0, t_xy = 0.0;
+        if (t < n_reg) {
+            const int pxy = ld_coherent(list + t);
+            const double wgt = sqrt((double)k32[(pxy >> 16) * w + (pxy & 0xFFFF)] / 4.0);
+            const double ddx = (double)(pxy & 0xFFFF) - cx, ddy = (double)(pxy >> 16) - cy;
+            t_xx = ddy * ddy * wgt;
+            t_yy = ddx * ddx * wgt;
+            t_xy = ddx * ddy * wgt;
+        }
+        add3(t_xx, t_yy, -t_xy, cn);  // (a - b and a + (-b) round alike)
+    }
+    double Ixx, Iyy, Ixy;
+    take3(Ixx, Iyy, Ixy);
+    const double lambda = 0.5 * (Ixx + Iyy - sqrt((Ixx - Iyy) * (Ixx - Iyy) + 4.0 * Ixy * Ixy));
+    double theta = (fabs(Ixx) > fabs(Iyy)) ? (double)fast_atan2_deg((float)(lambda - Ixx), (float)Ixy)
+                                           : (double)fast_atan2_deg((float)Ixy, (float)(lambda - Iyy));
+    theta *= LSD_DEG2RAD;
+    {
+        double diff = theta - reg_angle;  // angle_diff
+        while (diff <= -LSD_PI) diff += LSD_2_PI;
+        while (diff > LSD_PI) diff -= LSD_2_PI;
+        if (fabs(diff) > prec) theta += LSD_PI;
+    }
+    double dx, dy;
+    sincos_det(theta, dy, dx);
+    double l_min = 0.0, l_max = 0.0, w_min = 0.0, w_max = 0.0;
+    for (int t = lane; t < n_reg; t += 64) {
+        const int pxy = ld_coherent(list + t);
+        const double rdx = (double)(pxy & 0xFFFF) - cx, rdy = (double)(pxy >> 16) - cy;
+        const double l = rdx * dx + rdy * dy, ww = -rdx * dy + rdy * dx;
+        l_max = l > l_max ? l : l_max;
+        l_min = l < l_min ? l : l_min;
+        w_max = ww > w_max ? ww : w_max;
+        w_min = ww < w_min ? ww : w_min;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {  // maxima / minima: any order
+        const double a0 = __shfl_xor(l_max, off, 64), a1 = __shfl_xor(l_min, off, 64), a2 = __shfl_xor(w_max, off, 64), a3 = __shfl_xor(w_min, off, 64);
+        l_max = a0 > l_max ? a0 : l_max;
+        l_min = a1 < l_min ? a1 : l_min;
+        w_max = a2 > w_max ? a2 : w_max;
+        w_min = a3 < w_min ? a3 : w_min;
+    }
+    rc.cx = cx; rc.cy = cy; rc.Ixx = Ixx; rc.Iyy = Iyy; rc.Ixy = Ixy; rc.theta = theta; rc.dx = dx; rc.dy = dy;
+    rc.l_min = l_min; rc.l_max = l_max;
+    rc.width = w_max - w_min < 1.0 ? 1.0 : w_max - w_min;  // (where only the segment is wanted, none of the width survives in the code)
+    return rc;
+}
+
+// the end points of a rectangle's axis, in the scaled image
+__device__ __forceinline__ void lsd_rect_ends(const LsdRect& rc, double& x1, double& y1, double& x2, double& y2) {
+    x1 = rc.cx + rc.l_min * rc.dx; y1 = rc.cy + rc.l_min * rc.dy; x2 = rc.cx + rc.l_max * rc.dx; y2 = rc.cy + rc.l_max * rc.dy;
+}
+// rect -> the segment in the input image: pixel centres, 1 / scale
+__device__ __forceinline__ float4 lsd_segment(const LsdRect& rc, double scale) {
+    double x1, y1, x2, y2;
+    lsd_rect_ends(rc, x1, y1, x2, y2);
+    x1 += 0.5; y1 += 0.5; x2 += 0.5; y2 += 0.5;
+    if (scale != 1) {
+        x1 /= scale; y1 /= scale; x2 /= scale; y2 /= scale;
+    }
+    return make_float4((float)x1, (float)y1, (float)x2, (float)y2);
+}
+
+// what a one-wave kernel does with a rectangle: segment n_seg of image b — and, PROF, the rectangle's row for stvo_lsd_debug
+template <bool PROF>
+__device__ __forceinline__ void lsd_store_segment(const LsdDev& d, int b, int n_seg, const LsdRect& rc) {
+    const float4 sg = lsd_segment(rc, d.scale);
+    if ((threadIdx.x & 63) != 0 || n_seg >= d.seg_cap) return;
+    d.seg[(size_t)b * d.seg_cap + n_seg] = sg;
+    if constexpr (PROF) {
+        double* q = d.dbg + ((size_t)b * d.seg_cap + n_seg) * 8;
+        q[0] = rc.cx; q[1] = rc.cy; q[2] = rc.Ixx; q[3] = rc.Iyy; q[4] = rc.Ixy; q[5] = rc.theta; q[6] = rc.l_min; q[7] = rc.l_max;
+    }
+}
+// tools/lsd_probe.py: the counters of image 0's wave in the last 16 doubles of image 0's block
+__device__ __forceinline__ void lsd_store_counters(const LsdDev& d, int b, const LsdProbe<true>& pr, long long t_begin) {
+    if ((threadIdx.x & 63) != 0 || b != 0) return;
+    double* q = d.dbg + ((size_t)d.seg_cap - 2) * 8;
+    q[0] = (double)(pr.now() - t_begin);
+    for (int i = 0; i < OW_N; ++i) q[1 + i] = (double)pr.v[i];
+}
+
+// The search, ONE wave per image: the batch loop over the seeds in their pseudo-order, the fast growth, region2rect with its sums from
+// LDS.  The default where lsd_grow_xcd_kernel does not run (batches above LSD_WAVES_MAX_B images, STVO_LSD_WAVES=0).
+template <bool PROF>
 __global__ __launch_bounds__(64) void lsd_grow_kernel(LsdDev d) {
     __shared__ int s_ring[LSD_RING];
-    __shared__ double s_term[3][64];  // region2rect (FAST): the terms of one chunk, lane l < 3 adds row l in order
+    __shared__ double s_term[3][64];  // region2rect: the terms of one chunk
     const int b = blockIdx.x, lane = threadIdx.x;
     const int w = d.w, h = d.h, npx = w * h;
     const size_t base = (size_t)b * npx;
@@ -285,383 +779,48 @@ __global__ __launch_bounds__(64) void lsd_grow_kernel(LsdDev d) {
     const int32_t* __restrict__ k32 = d.k32 + base;
     const uint32_t* __restrict__ order = d.order + base;
     int32_t* reg = d.reg + base;
-    const double prec = d.prec;
     int n_seg = 0;
-    const bool prof = d.dbg != nullptr;
-    long long t_grow = 0, t_res = 0, t_rect = 0, n_rounds = 0, n_add = 0, n_regions = 0, n_batches = 0;
-    long long t_pub = 0, t_issue = 0, t_wait = 0, t_seed = 0;  // phases of a round (profiling only: explicit waits make them attributable)
-    auto tick = [&]() -> long long { return prof ? (long long)__builtin_readcyclecounter() : 0ll; };
-    const long long t_begin = tick();
+    LsdProbe<PROF> pr(true);
+    const long long t_begin = pr.now();
     for (int o0 = 0; o0 < npx; o0 += 64) {
-        ++n_batches;
+        pr.add(OW_BATCHES, 1);
         const uint32_t key = o0 + lane < npx ? order[o0 + lane] : LSD_NOKEY;
         if ((uint32_t)__builtin_amdgcn_readfirstlane((int)key) == LSD_NOKEY) break;  // sorted: only undefined pixels from here on
-        const int q_l = (int)(key & ((1u << LSD_IDX_BITS) - 1u));
-        const bool key_ok = key != LSD_NOKEY;
-        const LsdPx seed_l = px_ld(px + (key_ok ? q_l : 0));  // the seeds' angles, fetched with the batch
-        const float ang_l = key_ok ? seed_l.ang : -1.f;
-        unsigned long long todo = __ballot(key_ok && seed_l.used == 0);
-        // seeds of this batch that a region grown from an earlier seed of the batch takes are struck off as they are taken (one
-        // compare + ballot per pixel added) — re-reading the flags after every region cost a memory round trip per region
-        while (todo) {
-            const int j = __builtin_ctzll(todo);
-            todo &= todo - 1ull;
-            const int seed = __builtin_amdgcn_readlane(q_l, j);
-            // ---------------- region_grow ----------------
-            const long long tg0 = tick();
-            ++n_regions;
-            const int sx0 = seed % w, sy0 = seed / w;
-            double reg_angle = (double)readlane_f32(ang_l, j) * LSD_DEG2RAD;
-            double sn0, cs0;
-            sincos_det(reg_angle, sn0, cs0);
-            float sumdx = (float)cs0, sumdy = (float)sn0;
-            int n_reg = 1;
-            if (lane == 0) {
-                st_coherent(&px[seed].used, 1);
-                st_coherent(reg, sx0 | (sy0 << 16));
-                s_ring[0] = sx0 | (sy0 << 16);
-            }
-            t_seed += tick() - tg0;
-            for (int i = 0; i < n_reg;) {
-                const long long tp0 = tick();
-                wave_publish();  // lane 0's stores of the earlier rounds before the flag / list loads below
-                if (prof) __builtin_amdgcn_s_waitcnt(0);
-                const long long tp1 = tick();
-                t_pub += tp1 - tp0;
-                // one round: the next (up to) 7 LSD_GR region points — sub-group r holds points i + 7 r .. i + 7 r + 6, lane = 9 x point
-                // + neighbour — fetched together, then resolved sub-group after sub-group, lane after lane: the oracle's order
-                const int cnt = n_reg - i < 7 * LSD_GR ? n_reg - i : 7 * LSD_GR;  // uniform
-                const int slot0 = lane / 9, nb = lane - slot0 * 9;
-                int qq[LSD_GR], xy[LSD_GR];
-                float2 cs[LSD_GR];
-                double ad[LSD_GR];
-                bool cand[LSD_GR];
-                if constexpr (FAST) {
-                    // every sub-group's region point first, then every load, then the uses: the flag / angle / (cos, sin) loads of
-                    // the sub-groups overlap (one after the other they were two memory round trips per round).  Lanes without a
-                    // neighbour load pixel 0 and drop the values
-                    int pxyv[LSD_GR], u[LSD_GR];
-                    float a[LSD_GR];
-                    bool val[LSD_GR];
-                    const bool in_ring = n_reg - i <= LSD_RING;  // uniform: the round's oldest point is still in the LDS ring
-#pragma unroll
-                    for (int r = 0; r < LSD_GR; ++r) {
-                        const int slot = 7 * r + slot0;
-                        val[r] = lane < 63 && slot < cnt && nb != 4;
-                        const int at = val[r] ? i + slot : i;
-                        pxyv[r] = in_ring ? s_ring[at & (LSD_RING - 1)] : ld_coherent(reg + at);
-                    }
-#pragma unroll
-                    for (int r = 0; r < LSD_GR; ++r) {
-                        const int xx = (pxyv[r] & 0xFFFF) + (nb % 3) - 1, yy = (pxyv[r] >> 16) + nb / 3 - 1;
-                        val[r] = val[r] && xx >= 0 && xx < w && yy >= 0 && yy < h;
-                        qq[r] = val[r] ? yy * w + xx : 0;
-                        xy[r] = xx | (yy << 16);
-                        const LsdPx t = px_ld(px + qq[r]);
-                        u[r] = t.used;
-                        a[r] = t.ang;
-                        cs[r] = make_float2(t.c, t.s);
-                    }
-#pragma unroll
-                    for (int r = 0; r < LSD_GR; ++r) {
-                        cand[r] = val[r] && u[r] == 0 && a[r] >= 0.f;
-                        ad[r] = (double)a[r] * LSD_DEG2RAD;
-                    }
-                } else {
-#pragma unroll
-                for (int r = 0; r < LSD_GR; ++r) {
-                    const int slot = 7 * r + slot0;
-                    bool valid = lane < 63 && slot < cnt && nb != 4;  // (the centre is the region point itself)
-                    int pxy = 0;
-                    if (valid) pxy = (n_reg - (i + slot) <= LSD_RING) ? s_ring[(i + slot) & (LSD_RING - 1)] : ld_coherent(reg + i + slot);
-                    const int xx = (pxy & 0xFFFF) + (nb % 3) - 1, yy = (pxy >> 16) + nb / 3 - 1;  // neighbours row by row
-                    valid = valid && xx >= 0 && xx < w && yy >= 0 && yy < h;
-                    qq[r] = valid ? yy * w + xx : 0;
-                    xy[r] = xx | (yy << 16);
-                    int u = 1;
-                    float a = -1.f;
-                    cs[r] = make_float2(0.f, 0.f);
-                    if (valid) {
-                        const LsdPx t = px_ld(px + qq[r]);
-                        u = t.used;
-                        a = t.ang;
-                        cs[r] = make_float2(t.c, t.s);
-                    }
-                    cand[r] = valid && u == 0 && a >= 0.f;
-                    ad[r] = (double)a * LSD_DEG2RAD;
-                }
-                }
-                const long long ti1 = tick();  // the loads are issued ...
-                if (prof) __builtin_amdgcn_s_waitcnt(0);
-                const long long tr0 = tick();  // ... and have arrived
-                t_issue += ti1 - tp1;
-                t_wait += tr0 - ti1;
-                ++n_rounds;
-                if constexpr (!FAST) {
-#pragma unroll
-                for (int r = 0; r < LSD_GR; ++r) {
-                    if (7 * r >= cnt) break;  // uniform
-                    int next = 0;  // lanes below `next` have had their turn
-                    for (;;) {
-                        double n_theta = reg_angle - ad[r];  // isAligned
-                        if (n_theta < 0) n_theta = -n_theta;
-                        if (n_theta > LSD_3_2_PI) {
-                            n_theta -= LSD_2_PI;
-                            if (n_theta < 0) n_theta = -n_theta;
-                        }
-                        const unsigned long long m = __ballot(cand[r] && lane >= next && n_theta <= prec);
-                        if (!m || n_reg >= npx) break;  // (the bound can only bind if a flag were lost: never write past the list)
-                        const int L = __builtin_ctzll(m);
-                        const int qL = __builtin_amdgcn_readlane(qq[r], L), xyL = __builtin_amdgcn_readlane(xy[r], L);
-                        const float cL = readlane_f32(cs[r].x, L), sL = readlane_f32(cs[r].y, L);
-                        if (lane == 0) {
-                            st_coherent(&px[qL].used, 1);
-                            st_coherent(reg + n_reg, xyL);
-                            s_ring[n_reg & (LSD_RING - 1)] = xyL;
-                        }
-                        ++n_reg;
-#pragma unroll
-                        for (int r2 = 0; r2 < LSD_GR; ++r2) cand[r2] = cand[r2] && qq[r2] != qL;  // the same pixel seen from another point of the round
-                        todo &= ~__ballot(key_ok && q_l == qL);
-                        sumdx += cL;
-                        sumdy += sL;
-                        reg_angle = (double)fast_atan2_deg(sumdy, sumdx) * LSD_DEG2RAD;
-                        next = L + 1;
-                    }
-                }
-                } else {
-                // Guess + verification (tools/experiments/lsd_resolve_model.c has the CPU model and the argument).  Only the two float
-                // additions per pixel depend on the order; the ~30 operations of the angle update run for all lanes at once:
-                //   A   = the lanes aligned with the angle at the start of the sub-group
-                //   A'  = A walked from the lowest lane: a lane taken removes the later lanes that hold the same pixel
-                //   lane k: sums_k = start sums + (cos, sin) of A's lanes below k, added in lane order; angle_k = fastAtan2(sums_k), or
-                //           the start angle if A' has no lane below k;  dup_k = a lane of A' below k holds the same pixel
-                //   D   = the lanes aligned with their angle_k and not dup.  D == A': A' is what the sequential loop accepts
-                //         (induction over the lanes); else the lanes below the first difference m are final, lane m's decision is
-                //         D[m]: again with A = A' below m | D from m on (2 % of the sub-groups of a KITTI-size scene).
-                // Every per-lane flag is kept as a 64-bit lane mask in scalar registers (they are compare results to begin with).
-                unsigned long long cand_m[LSD_GR];
-#pragma unroll
-                for (int r = 0; r < LSD_GR; ++r) cand_m[r] = __ballot(cand[r]);
-                const unsigned long long key_m = __ballot(key_ok);
-#pragma unroll
-                for (int r = 0; r < LSD_GR; ++r) {
-                    if (7 * r >= cnt) break;  // uniform
-                    unsigned long long A;
-                    {
-                        double n_theta = reg_angle - ad[r];  // isAligned
-                        if (n_theta < 0) n_theta = -n_theta;
-                        if (n_theta > LSD_3_2_PI) {
-                            n_theta -= LSD_2_PI;
-                            if (n_theta < 0) n_theta = -n_theta;
-                        }
-                        A = __ballot(n_theta <= prec) & cand_m[r];
-                    }
-                    if (!A || n_reg + 64 > npx) continue;  // (the bound can only bind if a flag were lost: never write past the list)
-                    unsigned long long acc, kill, hit_m[LSD_GR];
-                    float sx, sy;
-                    double th;
-                    for (;;) {
-                        unsigned long long rem = A, dup_m = 0ull;
-                        acc = 0ull;
-                        kill = 0ull;
-#pragma unroll
-                        for (int r2 = 0; r2 < LSD_GR; ++r2) hit_m[r2] = 0ull;
-                        sx = sumdx;
-                        sy = sumdy;
-                        while (rem) {  // uniform: the lanes of the guess, lowest first
-                            const int j = __builtin_ctzll(rem);
-                            const int qj = __builtin_amdgcn_readlane(qq[r], j);
-                            const float cj = readlane_f32(cs[r].x, j), sj = readlane_f32(cs[r].y, j);
-                            const unsigned long long later = j == 63 ? 0ull : ~0ull << (j + 1);
-                            const unsigned long long same = __ballot(qq[r] == qj);
-                            acc |= 1ull << j;
-                            rem &= ~same;  // lane j itself and the later lanes that hold the same pixel
-                            dup_m |= same & later;
-                            const float nx = sx + cj, ny = sy + sj;  // (a select, not a masked addition of zero: x + 0 is not x for x = -0)
-                            const bool is_later = lane > j;
-                            sx = is_later ? nx : sx;
-                            sy = is_later ? ny : sy;
-                            kill |= __ballot(q_l == qj);
-#pragma unroll
-                            for (int r2 = 0; r2 < LSD_GR; ++r2)
-                                if (r2 > r) hit_m[r2] |= __ballot(qq[r2] == qj);
-                        }
-                        const bool any = lane > __builtin_ctzll(acc);
-                        th = any ? (double)fast_atan2_deg(sy, sx) * LSD_DEG2RAD : reg_angle;
-                        double n_theta = th - ad[r];
-                        if (n_theta < 0) n_theta = -n_theta;
-                        if (n_theta > LSD_3_2_PI) {
-                            n_theta -= LSD_2_PI;
-                            if (n_theta < 0) n_theta = -n_theta;
-                        }
-                        const unsigned long long D = __ballot(n_theta <= prec) & cand_m[r] & ~dup_m;
-                        if (D == acc) break;
-                        const unsigned long long below = (1ull << __builtin_ctzll(D ^ acc)) - 1ull;
-                        A = (acc & below) | (D & ~below);  // (never empty: the lowest lane of a guess sees the start angle, as the guess did)
-                    }
-                    // acc is the sequential result: every accepted lane stores its own pixel, in lane order
-                    if ((acc >> lane) & 1ull) {
-                        const int idx = n_reg + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(acc >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)acc, 0u));
-                        st_coherent(&px[qq[r]].used, 1);
-                        st_coherent(reg + idx, xy[r]);
-                        s_ring[idx & (LSD_RING - 1)] = xy[r];
-                    }
-                    n_reg += __builtin_popcountll(acc);
-                    sumdx = readlane_f32(sx, 63);  // lane 63 is never a candidate: its sums are the sums over all of acc
-                    sumdy = readlane_f32(sy, 63);
-                    reg_angle = readlane_f64(th, 63);
-                    todo &= ~(kill & key_m);
-#pragma unroll
-                    for (int r2 = 0; r2 < LSD_GR; ++r2)
-                        if (r2 > r) cand_m[r2] &= ~hit_m[r2];
-                }
-                }
-                t_res += tick() - tr0;
-                i += cnt;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // s_ring: lane 0's writes before the next round's reads
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            }
-            t_grow += tick() - tg0;
-            n_add += n_reg;
+        LsdSeeds sd;
+        sd.q_l = (int)(key & ((1u << LSD_IDX_BITS) - 1u));
+        sd.key_ok = key != LSD_NOKEY;
+        const LsdPx seed_l = px_ld(px + (sd.key_ok ? sd.q_l : 0));  // the seeds' angles, fetched with the batch
+        const float ang_l = sd.key_ok ? seed_l.ang : -1.f;
+        sd.todo = __ballot(sd.key_ok && seed_l.used == 0);
+        while (sd.todo) {
+            const int j = __builtin_ctzll(sd.todo);
+            sd.todo &= sd.todo - 1ull;
+            const int seed = __builtin_amdgcn_readlane(sd.q_l, j);
+            double reg_angle;
+            const int n_reg = lsd_grow_fast<true, false, false, LSD_RING, true, true>(px, nullptr, 0, nullptr, reg, npx, s_ring, seed, readlane_f32(ang_l, j),
+                                                                                      w, h, d.prec, &sd, reg_angle, pr);
             if (n_reg < d.min_reg_size) continue;
-            // ---------------- region2rect ----------------
-            const long long tq0 = tick();
-            wave_publish();
-            double X = 0.0, Y = 0.0, S = 0.0;
-            // FAST: the three ordered sums of a pass are three independent chains — lane l < 3 adds row l of s_term term by term
-            // (one LDS read + one addition per region point instead of six v_readlane + three additions)
-            double chain = 0.0;
-            auto add_ordered = [&](double t0, double t1, double t2, int cn) {
-                s_term[0][lane] = t0;
-                s_term[1][lane] = t1;
-                s_term[2][lane] = t2;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                if (lane < 3) {
-                    const double* row = s_term[lane];
-#pragma unroll 8
-                    for (int k = 0; k < cn; ++k) chain += row[k];
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the reads before the next chunk's writes
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            };
-            for (int c0 = 0; c0 < n_reg; c0 += 64) {
-                const int t = c0 + lane, cn = n_reg - c0 < 64 ? n_reg - c0 : 64;
-                int pxy = 0;
-                double wgt = 0.0;
-                if (t < n_reg) {
-                    pxy = ld_coherent(reg + t);
-                    wgt = sqrt((double)k32[(pxy >> 16) * w + (pxy & 0xFFFF)] / 4.0);  // the gradient norm (ll_angle's expression)
-                }
-                const double px = (double)(pxy & 0xFFFF) * wgt, py = (double)(pxy >> 16) * wgt;
-                if constexpr (FAST) {
-                    add_ordered(px, py, wgt, cn);
-                } else {
-                    for (int k = 0; k < cn; ++k) {  // strictly in region order: every addition rounds as the oracle's
-                        X += readlane_f64(px, k);
-                        Y += readlane_f64(py, k);
-                        S += readlane_f64(wgt, k);
-                    }
-                }
-            }
-            if constexpr (FAST) {
-                X = readlane_f64(chain, 0);
-                Y = readlane_f64(chain, 1);
-                S = readlane_f64(chain, 2);
-                chain = 0.0;
-            }
-            const double cx = X / S, cy = Y / S;
-            double Ixx = 0.0, Iyy = 0.0, Ixy = 0.0;
-            for (int c0 = 0; c0 < n_reg; c0 += 64) {
-                const int t = c0 + lane, cn = n_reg - c0 < 64 ? n_reg - c0 : 64;
-                double t_xx = 0.0, t_yy = 0.0, t_xy = 0.0;
-                if (t < n_reg) {
-                    const int pxy = ld_coherent(reg + t);
-                    const double wgt = sqrt((double)k32[(pxy >> 16) * w + (pxy & 0xFFFF)] / 4.0);  // the gradient norm (ll_angle's expression)
-                    const double ddx = (double)(pxy & 0xFFFF) - cx, ddy = (double)(pxy >> 16) - cy;
-                    t_xx = ddy * ddy * wgt;
-                    t_yy = ddx * ddx * wgt;
-                    t_xy = ddx * ddy * wgt;
-                }
-                if constexpr (FAST) {
-                    add_ordered(t_xx, t_yy, -t_xy, cn);  // (a - b and a + (-b) round alike)
-                } else {
-                    for (int k = 0; k < cn; ++k) {
-                        Ixx += readlane_f64(t_xx, k);
-                        Iyy += readlane_f64(t_yy, k);
-                        Ixy -= readlane_f64(t_xy, k);
-                    }
-                }
-            }
-            if constexpr (FAST) {
-                Ixx = readlane_f64(chain, 0);
-                Iyy = readlane_f64(chain, 1);
-                Ixy = readlane_f64(chain, 2);
-            }
-            const double lambda = 0.5 * (Ixx + Iyy - sqrt((Ixx - Iyy) * (Ixx - Iyy) + 4.0 * Ixy * Ixy));
-            double theta = (fabs(Ixx) > fabs(Iyy)) ? (double)fast_atan2_deg((float)(lambda - Ixx), (float)Ixy)
-                                                   : (double)fast_atan2_deg((float)Ixy, (float)(lambda - Iyy));
-            theta *= LSD_DEG2RAD;
-            {
-                double diff = theta - reg_angle;  // angle_diff
-                while (diff <= -LSD_PI) diff += LSD_2_PI;
-                while (diff > LSD_PI) diff -= LSD_2_PI;
-                if (fabs(diff) > prec) theta += LSD_PI;
-            }
-            double dx, dy;
-            sincos_det(theta, dy, dx);
-            double l_min = 0.0, l_max = 0.0;  // (the width of the rectangle is not part of the segment)
-            for (int t = lane; t < n_reg; t += 64) {
-                const int pxy = ld_coherent(reg + t);
-                const double rdx = (double)(pxy & 0xFFFF) - cx, rdy = (double)(pxy >> 16) - cy;
-                const double l = rdx * dx + rdy * dy;
-                l_max = l > l_max ? l : l_max;
-                l_min = l < l_min ? l : l_min;
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {  // maxima / minima: any order
-                const double om = __shfl_xor(l_max, off, 64), on = __shfl_xor(l_min, off, 64);
-                l_max = om > l_max ? om : l_max;
-                l_min = on < l_min ? on : l_min;
-            }
-            double x1 = cx + l_min * dx, y1 = cy + l_min * dy, x2 = cx + l_max * dx, y2 = cy + l_max * dy;
-            x1 += 0.5; y1 += 0.5; x2 += 0.5; y2 += 0.5;
-            if (d.scale != 1) {
-                x1 /= d.scale; y1 /= d.scale; x2 /= d.scale; y2 /= d.scale;
-            }
-            if (lane == 0 && n_seg < d.seg_cap) d.seg[(size_t)b * d.seg_cap + n_seg] = make_float4((float)x1, (float)y1, (float)x2, (float)y2);
-            if (d.dbg && lane == 0 && n_seg < d.seg_cap) {
-                double* q = d.dbg + ((size_t)b * d.seg_cap + n_seg) * 8;
-                q[0] = cx; q[1] = cy; q[2] = Ixx; q[3] = Iyy; q[4] = Ixy; q[5] = theta; q[6] = l_min; q[7] = l_max;
-            }
+            const long long tq0 = pr.now();
+            lsd_store_segment<PROF>(d, b, n_seg, lsd_region2rect<true>(reg, n_reg, k32, w, reg_angle, d.prec, s_term));
             ++n_seg;
-            t_rect += tick() - tq0;
+            pr.add(OW_RECT, pr.now() - tq0);
         }
     }
     if (lane == 0) d.n_seg[b] = n_seg;
-    if (prof && lane == 0 && b == 0) {  // tools/lsd_probe.py: the last 16 doubles of image 0's block
-        double* q = d.dbg + ((size_t)d.seg_cap - 2) * 8;
-        q[0] = (double)(tick() - t_begin); q[1] = (double)t_grow; q[2] = (double)t_res; q[3] = (double)t_rect; q[4] = (double)n_rounds;
-        q[5] = (double)n_add; q[6] = (double)n_regions; q[7] = (double)n_batches;
-        q[8] = (double)t_pub; q[9] = (double)t_issue; q[10] = (double)t_wait; q[11] = (double)t_seed;
-    }
+    if constexpr (PROF) lsd_store_counters(d, b, pr, t_begin);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// lsd_refine = 1 (LSD_REFINE_STD; oracle/stvo_lsd_oracle.c: refine_region / reduce_region_radius): a region too sparse for its rectangle
-// is given back (its pixels are FREE again), grown once more from the same seed under a tolerance of twice the standard deviation of
-// the angles near the seed and, if still too sparse, cut back to 75 % of its radius until it is dense enough or gone.  Flags that turn
-// OFF break what the other forms of the search rely on (a batch's seeds struck off for good, speculation against flags that only ever
-// turn on), so this mode has its own kernel: one wave per image, the direct statement of the oracle's loops (the plain form above)
-// with the growth and the rectangle as routines, for every batch size.  No shipped configuration uses the mode (config/*.yaml:
-// lsd_refine : 0); it is there so that a caller who sets it gets the detector it asked for rather than an error.
-struct LsdRect {
-    double x1, y1, x2, y2, width;
-};
+// The plain search, one wave per image for every batch size: the direct statement of the oracle's loops.
+//   !REFINE  STVO_LSD_GROW=0: the cross-check of the fast forms.
+//   REFINE   lsd_refine = 1 (LSD_REFINE_STD; oracle/stvo_lsd_oracle.c: refine_region / reduce_region_radius): a region too sparse for
+//            its rectangle is given back (its pixels are FREE again), grown once more from the same seed under a tolerance of twice
+//            the standard deviation of the angles near the seed and, if still too sparse, cut back to 75 % of its radius until it is
+//            dense enough or gone.  Flags that turn OFF break what the other forms of the search rely on (a batch's seeds struck off
+//            for good, speculation against flags that only ever turn on), so the mode runs here whatever the batch.  No shipped
+//            configuration uses it (config/*.yaml: lsd_refine : 0); it is there so that a caller who sets it gets the detector it
+//            asked for rather than an error.
+template <bool REFINE, bool PROF>
 __global__ __launch_bounds__(64) void lsd_grow_refine_kernel(LsdDev d, const double density_th) {
     __shared__ int s_ring[LSD_RING];
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -673,283 +832,133 @@ __global__ __launch_bounds__(64) void lsd_grow_refine_kernel(LsdDev d, const dou
     int32_t* reg = d.reg + base;
     const double prec = d.prec;
     int n_seg = 0;
-    int q_l = 0;
-    bool key_ok = false;
-    unsigned long long todo = 0ull;
-
-    // region_grow from `seed` (angle ang_deg) under the tolerance tol: the list in reg (and the ring), the size returned
-    auto grow = [&](const int seed, const float ang_deg, const double tol, double& reg_angle) -> int {
-        const int sx0 = seed % w, sy0 = seed / w;
-        reg_angle = (double)ang_deg * LSD_DEG2RAD;
-        double sn0, cs0;
-        sincos_det(reg_angle, sn0, cs0);
-        float sumdx = (float)cs0, sumdy = (float)sn0;
-        int n_reg = 1;
-        if (lane == 0) {
-            st_coherent(&px[seed].used, 1);
-            st_coherent(reg, sx0 | (sy0 << 16));
-            s_ring[0] = sx0 | (sy0 << 16);
-        }
-        for (int i = 0; i < n_reg;) {
-            wave_publish();
-            const int cnt = n_reg - i < 7 * LSD_GR ? n_reg - i : 7 * LSD_GR;  // uniform
-            const int slot0 = lane / 9, nb = lane - slot0 * 9;
-            int qq[LSD_GR], xy[LSD_GR];
-            float2 cs[LSD_GR];
-            double ad[LSD_GR];
-            bool cand[LSD_GR];
-#pragma unroll
-            for (int r = 0; r < LSD_GR; ++r) {
-                const int slot = 7 * r + slot0;
-                bool valid = lane < 63 && slot < cnt && nb != 4;  // (the centre is the region point itself)
-                int pxy = 0;
-                if (valid) pxy = (n_reg - (i + slot) <= LSD_RING) ? s_ring[(i + slot) & (LSD_RING - 1)] : ld_coherent(reg + i + slot);
-                const int xx = (pxy & 0xFFFF) + (nb % 3) - 1, yy = (pxy >> 16) + nb / 3 - 1;  // neighbours row by row
-                valid = valid && xx >= 0 && xx < w && yy >= 0 && yy < h;
-                qq[r] = valid ? yy * w + xx : 0;
-                xy[r] = xx | (yy << 16);
-                int u = 1;
-                float a = -1.f;
-                cs[r] = make_float2(0.f, 0.f);
-                if (valid) {
-                    const LsdPx t = px_ld(px + qq[r]);
-                    u = t.used;
-                    a = t.ang;
-                    cs[r] = make_float2(t.c, t.s);
-                }
-                cand[r] = valid && u == 0 && a >= 0.f;
-                ad[r] = (double)a * LSD_DEG2RAD;
-            }
-#pragma unroll
-            for (int r = 0; r < LSD_GR; ++r) {
-                if (7 * r >= cnt) break;  // uniform
-                int next = 0;  // lanes below `next` have had their turn
-                for (;;) {
-                    double n_theta = reg_angle - ad[r];  // isAligned
-                    if (n_theta < 0) n_theta = -n_theta;
-                    if (n_theta > LSD_3_2_PI) {
-                        n_theta -= LSD_2_PI;
-                        if (n_theta < 0) n_theta = -n_theta;
-                    }
-                    const unsigned long long m = __ballot(cand[r] && lane >= next && n_theta <= tol);
-                    if (!m || n_reg >= npx) break;
-                    const int L = __builtin_ctzll(m);
-                    const int qL = __builtin_amdgcn_readlane(qq[r], L), xyL = __builtin_amdgcn_readlane(xy[r], L);
-                    const float cL = readlane_f32(cs[r].x, L), sL = readlane_f32(cs[r].y, L);
-                    if (lane == 0) {
-                        st_coherent(&px[qL].used, 1);
-                        st_coherent(reg + n_reg, xyL);
-                        s_ring[n_reg & (LSD_RING - 1)] = xyL;
-                    }
-                    ++n_reg;
-#pragma unroll
-                    for (int r2 = 0; r2 < LSD_GR; ++r2) cand[r2] = cand[r2] && qq[r2] != qL;  // the same pixel seen from another point of the round
-                    todo &= ~__ballot(key_ok && q_l == qL);
-                    sumdx += cL;
-                    sumdy += sL;
-                    reg_angle = (double)fast_atan2_deg(sumdy, sumdx) * LSD_DEG2RAD;
-                    next = L + 1;
-                }
-            }
-            i += cnt;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // s_ring: lane 0's writes before the next round's reads
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-        return n_reg;
-    };
-
-    // region2rect of reg[0 .. n_reg): every sum strictly in region order
-    auto rect = [&](const int n_reg, const double reg_angle) -> LsdRect {
-        wave_publish();
-        double X = 0.0, Y = 0.0, S = 0.0;
-        for (int c0 = 0; c0 < n_reg; c0 += 64) {
-            const int t = c0 + lane, cn = n_reg - c0 < 64 ? n_reg - c0 : 64;
-            int pxy = 0;
-            double wgt = 0.0;
-            if (t < n_reg) {
-                pxy = ld_coherent(reg + t);
-                wgt = sqrt((double)k32[(pxy >> 16) * w + (pxy & 0xFFFF)] / 4.0);
-            }
-            const double pxw = (double)(pxy & 0xFFFF) * wgt, pyw = (double)(pxy >> 16) * wgt;
-            for (int k = 0; k < cn; ++k) {
-                X += readlane_f64(pxw, k);
-                Y += readlane_f64(pyw, k);
-                S += readlane_f64(wgt, k);
-            }
-        }
-        const double cx = X / S, cy = Y / S;
-        double Ixx = 0.0, Iyy = 0.0, Ixy = 0.0;
-        for (int c0 = 0; c0 < n_reg; c0 += 64) {
-            const int t = c0 + lane, cn = n_reg - c0 < 64 ? n_reg - c0 : 64;
-            double t_xx = 0.0, t_yy = 0.0, t_xy = 0.0;
-            if (t < n_reg) {
-                const int pxy = ld_coherent(reg + t);
-                const double wgt = sqrt((double)k32[(pxy >> 16) * w + (pxy & 0xFFFF)] / 4.0);
-                const double ddx = (double)(pxy & 0xFFFF) - cx, ddy = (double)(pxy >> 16) - cy;
-                t_xx = ddy * ddy * wgt;
-                t_yy = ddx * ddx * wgt;
-                t_xy = ddx * ddy * wgt;
-            }
-            for (int k = 0; k < cn; ++k) {
-                Ixx += readlane_f64(t_xx, k);
-                Iyy += readlane_f64(t_yy, k);
-                Ixy -= readlane_f64(t_xy, k);
-            }
-        }
-        const double lambda = 0.5 * (Ixx + Iyy - sqrt((Ixx - Iyy) * (Ixx - Iyy) + 4.0 * Ixy * Ixy));
-        double theta = (fabs(Ixx) > fabs(Iyy)) ? (double)fast_atan2_deg((float)(lambda - Ixx), (float)Ixy)
-                                               : (double)fast_atan2_deg((float)Ixy, (float)(lambda - Iyy));
-        theta *= LSD_DEG2RAD;
-        {
-            double diff = theta - reg_angle;  // angle_diff
-            while (diff <= -LSD_PI) diff += LSD_2_PI;
-            while (diff > LSD_PI) diff -= LSD_2_PI;
-            if (fabs(diff) > prec) theta += LSD_PI;
-        }
-        double dx, dy;
-        sincos_det(theta, dy, dx);
-        double l_min = 0.0, l_max = 0.0, w_min = 0.0, w_max = 0.0;
-        for (int t = lane; t < n_reg; t += 64) {
-            const int pxy = ld_coherent(reg + t);
-            const double rdx = (double)(pxy & 0xFFFF) - cx, rdy = (double)(pxy >> 16) - cy;
-            const double l = rdx * dx + rdy * dy, ww = -rdx * dy + rdy * dx;
-            l_max = l > l_max ? l : l_max;
-            l_min = l < l_min ? l : l_min;
-            w_max = ww > w_max ? ww : w_max;
-            w_min = ww < w_min ? ww : w_min;
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {  // maxima / minima: any order
-            const double a0 = __shfl_xor(l_max, off, 64), a1 = __shfl_xor(l_min, off, 64), a2 = __shfl_xor(w_max, off, 64), a3 = __shfl_xor(w_min, off, 64);
-            l_max = a0 > l_max ? a0 : l_max;
-            l_min = a1 < l_min ? a1 : l_min;
-            w_max = a2 > w_max ? a2 : w_max;
-            w_min = a3 < w_min ? a3 : w_min;
-        }
-        LsdRect rc;
-        rc.x1 = cx + l_min * dx; rc.y1 = cy + l_min * dy; rc.x2 = cx + l_max * dx; rc.y2 = cy + l_max * dy;
-        rc.width = w_max - w_min;
-        if (rc.width < 1.0) rc.width = 1.0;
-        return rc;
-    };
+    LsdProbe<PROF> pr(true);
+    const long long t_begin = pr.now();
     auto dist_sq = [](double x1, double y1, double x2, double y2) { return (x2 - x1) * (x2 - x1) + (y2 - y1) * (y2 - y1); };
-    auto density_of = [&](const LsdRect& rc, int n_reg) { return (double)n_reg / (sqrt(dist_sq(rc.x1, rc.y1, rc.x2, rc.y2)) * rc.width); };
-
+    auto density_of = [&](const LsdRect& rc, int n_reg) {
+        double x1, y1, x2, y2;
+        lsd_rect_ends(rc, x1, y1, x2, y2);
+        return (double)n_reg / (sqrt(dist_sq(x1, y1, x2, y2)) * rc.width);
+    };
     for (int o0 = 0; o0 < npx; o0 += 64) {
+        pr.add(OW_BATCHES, 1);
         const uint32_t key = o0 + lane < npx ? order[o0 + lane] : LSD_NOKEY;
         if ((uint32_t)__builtin_amdgcn_readfirstlane((int)key) == LSD_NOKEY) break;  // sorted: only undefined pixels from here on
-        q_l = (int)(key & ((1u << LSD_IDX_BITS) - 1u));
-        key_ok = key != LSD_NOKEY;
-        wave_publish();
-        const LsdPx seed_l = px_ld(px + (key_ok ? q_l : 0));
-        const float ang_l = key_ok ? seed_l.ang : -1.f;
-        todo = __ballot(key_ok && seed_l.used == 0);
-        while (todo) {
-            const int j = __builtin_ctzll(todo);
-            todo &= todo - 1ull;
-            const int seed = __builtin_amdgcn_readlane(q_l, j);
+        LsdSeeds sd;
+        sd.q_l = (int)(key & ((1u << LSD_IDX_BITS) - 1u));
+        sd.key_ok = key != LSD_NOKEY;
+        if constexpr (REFINE) wave_publish();  // (flags the last batch turned off)
+        const LsdPx seed_l = px_ld(px + (sd.key_ok ? sd.q_l : 0));  // the seeds' angles, fetched with the batch
+        const float ang_l = sd.key_ok ? seed_l.ang : -1.f;
+        sd.todo = __ballot(sd.key_ok && seed_l.used == 0);
+        while (sd.todo) {
+            const int j = __builtin_ctzll(sd.todo);
+            sd.todo &= sd.todo - 1ull;
+            const int seed = __builtin_amdgcn_readlane(sd.q_l, j);
             const float seed_ang = readlane_f32(ang_l, j);
             double reg_angle;
-            int n_reg = grow(seed, seed_ang, prec, reg_angle);
+            int n_reg = lsd_grow_plain(px, reg, s_ring, seed, seed_ang, w, h, prec, sd, reg_angle, pr);
             if (n_reg < d.min_reg_size) continue;
-            LsdRect rc = rect(n_reg, reg_angle);
-            double density = density_of(rc, n_reg);
-            if (!(density >= density_th)) {
-                // ---- refine: the angles near the seed (within the rectangle's width), every pixel of the region free again ----
-                const int xy0 = ld_coherent(reg);
-                const double xc = (double)(xy0 & 0xFFFF), yc = (double)(xy0 >> 16);
-                const double ang_c = (double)seed_ang * LSD_DEG2RAD;
-                double sum = 0.0, s_sum = 0.0;
-                int n = 0;
-                for (int c0 = 0; c0 < n_reg; c0 += 64) {
-                    const int t = c0 + lane, cn = n_reg - c0 < 64 ? n_reg - c0 : 64;
-                    bool in = false;
-                    double ang_d = 0.0;
-                    if (t < n_reg) {
-                        const int pxy = ld_coherent(reg + t);
-                        const int q = (pxy >> 16) * w + (pxy & 0xFFFF);
-                        const LsdPx tq = px_ld(px + q);
-                        st_coherent(&px[q].used, 0);
-                        in = sqrt(dist_sq(xc, yc, (double)(pxy & 0xFFFF), (double)(pxy >> 16))) < rc.width;
-                        double diff = (double)tq.ang * LSD_DEG2RAD - ang_c;  // angle_diff_signed
-                        while (diff <= -LSD_PI) diff += LSD_2_PI;
-                        while (diff > LSD_PI) diff -= LSD_2_PI;
-                        ang_d = diff;
-                    }
-                    const double sq = ang_d * ang_d;
-                    const unsigned long long in_m = __ballot(in);
-                    for (int k = 0; k < cn; ++k)
-                        if ((in_m >> k) & 1ull) {  // uniform
-                            sum += readlane_f64(ang_d, k);
-                            s_sum += readlane_f64(sq, k);
-                            ++n;
+            const long long tq0 = pr.now();
+            LsdRect rc = lsd_region2rect<false>(reg, n_reg, k32, w, reg_angle, prec, nullptr);
+            if constexpr (REFINE) {
+                double density = density_of(rc, n_reg);
+                if (!(density >= density_th)) {
+                    // ---- refine: the angles near the seed (within the rectangle's width), every pixel of the region free again ----
+                    const int xy0 = ld_coherent(reg);
+                    const double xc = (double)(xy0 & 0xFFFF), yc = (double)(xy0 >> 16);
+                    const double ang_c = (double)seed_ang * LSD_DEG2RAD;
+                    double sum = 0.0, s_sum = 0.0;
+                    int n = 0;
+                    for (int c0 = 0; c0 < n_reg; c0 += 64) {
+                        const int t = c0 + lane, cn = n_reg - c0 < 64 ? n_reg - c0 : 64;
+                        bool in = false;
+                        double ang_d = 0.0;
+                        if (t < n_reg) {
+                            const int pxy = ld_coherent(reg + t);
+                            const int q = (pxy >> 16) * w + (pxy & 0xFFFF);
+                            const LsdPx tq = px_ld(px + q);
+                            st_coherent(&px[q].used, 0);
+                            in = sqrt(dist_sq(xc, yc, (double)(pxy & 0xFFFF), (double)(pxy >> 16))) < rc.width;
+                            double diff = (double)tq.ang * LSD_DEG2RAD - ang_c;  // angle_diff_signed
+                            while (diff <= -LSD_PI) diff += LSD_2_PI;
+                            while (diff > LSD_PI) diff -= LSD_2_PI;
+                            ang_d = diff;
                         }
-                }
-                const double mean_angle = sum / (double)n;
-                const double tau = 2.0 * sqrt((s_sum - 2.0 * mean_angle * sum) / (double)n + mean_angle * mean_angle);
-                n_reg = grow(seed, seed_ang, tau, reg_angle);
-                bool gone = n_reg < 2;
-                if (!gone) {
-                    rc = rect(n_reg, reg_angle);
-                    density = density_of(rc, n_reg);
-                    if (density < density_th) {
-                        // ---- reduce_region_radius: points farther than the (shrinking) radius from the seed leave, the LAST point of the
-                        // list takes a leaving point's place (and is looked at next) — one point after the other, as the oracle does
-                        const double r1 = dist_sq(xc, yc, rc.x1, rc.y1), r2 = dist_sq(xc, yc, rc.x2, rc.y2);
-                        double rad_sq = r1 > r2 ? r1 : r2;
-                        while (density < density_th) {
-                            rad_sq *= 0.75 * 0.75;
-                            wave_publish();
-                            for (int c0 = 0; c0 < n_reg; c0 += 64) {
-                                const int t = c0 + lane;
-                                const int pxy = t < n_reg ? ld_coherent(reg + t) : 0;
-                                const bool far = t < n_reg && dist_sq(xc, yc, (double)(pxy & 0xFFFF), (double)(pxy >> 16)) > rad_sq;
-                                unsigned long long far_m = __ballot(far);
-                                while (far_m) {
-                                    const int k = __builtin_ctzll(far_m);
-                                    far_m &= far_m - 1ull;
-                                    const int i = c0 + k;
-                                    if (i >= n_reg) break;  // (the list has shrunk below this position: its point left as a LAST point)
-                                    int out_xy = __builtin_amdgcn_readlane(pxy, k);
-                                    for (;;) {  // the point at position i leaves; the last point moves in and is tested in turn
-                                        if (lane == 0) st_coherent(&px[(out_xy >> 16) * w + (out_xy & 0xFFFF)].used, 0);
-                                        --n_reg;
-                                        if (i >= n_reg) break;  // (it was the last point itself)
-                                        const int last_xy = __builtin_amdgcn_readfirstlane(ld_coherent(reg + n_reg));
-                                        if (!(dist_sq(xc, yc, (double)(last_xy & 0xFFFF), (double)(last_xy >> 16)) > rad_sq)) {
-                                            if (lane == 0) st_coherent(reg + i, last_xy);
-                                            break;
+                        const double sq = ang_d * ang_d;
+                        const unsigned long long in_m = __ballot(in);
+                        for (int k = 0; k < cn; ++k)
+                            if ((in_m >> k) & 1ull) {  // uniform
+                                sum += readlane_f64(ang_d, k);
+                                s_sum += readlane_f64(sq, k);
+                                ++n;
+                            }
+                    }
+                    const double mean_angle = sum / (double)n;
+                    const double tau = 2.0 * sqrt((s_sum - 2.0 * mean_angle * sum) / (double)n + mean_angle * mean_angle);
+                    n_reg = lsd_grow_plain(px, reg, s_ring, seed, seed_ang, w, h, tau, sd, reg_angle, pr);
+                    bool gone = n_reg < 2;
+                    if (!gone) {
+                        rc = lsd_region2rect<false>(reg, n_reg, k32, w, reg_angle, prec, nullptr);
+                        density = density_of(rc, n_reg);
+                        if (density < density_th) {
+                            // ---- reduce_region_radius: points farther than the (shrinking) radius from the seed leave, the LAST point of the
+                            // list takes a leaving point's place (and is looked at next) — one point after the other, as the oracle does
+                            double ex1, ey1, ex2, ey2;
+                            lsd_rect_ends(rc, ex1, ey1, ex2, ey2);
+                            const double r1 = dist_sq(xc, yc, ex1, ey1), r2 = dist_sq(xc, yc, ex2, ey2);
+                            double rad_sq = r1 > r2 ? r1 : r2;
+                            while (density < density_th) {
+                                rad_sq *= 0.75 * 0.75;
+                                wave_publish();
+                                for (int c0 = 0; c0 < n_reg; c0 += 64) {
+                                    const int t = c0 + lane;
+                                    const int pxy = t < n_reg ? ld_coherent(reg + t) : 0;
+                                    const bool far = t < n_reg && dist_sq(xc, yc, (double)(pxy & 0xFFFF), (double)(pxy >> 16)) > rad_sq;
+                                    unsigned long long far_m = __ballot(far);
+                                    while (far_m) {
+                                        const int k = __builtin_ctzll(far_m);
+                                        far_m &= far_m - 1ull;
+                                        const int i = c0 + k;
+                                        if (i >= n_reg) break;  // (the list has shrunk below this position: its point left as a LAST point)
+                                        int out_xy = __builtin_amdgcn_readlane(pxy, k);
+                                        for (;;) {  // the point at position i leaves; the last point moves in and is tested in turn
+                                            if (lane == 0) st_coherent(&px[(out_xy >> 16) * w + (out_xy & 0xFFFF)].used, 0);
+                                            --n_reg;
+                                            if (i >= n_reg) break;  // (it was the last point itself)
+                                            const int last_xy = __builtin_amdgcn_readfirstlane(ld_coherent(reg + n_reg));
+                                            if (!(dist_sq(xc, yc, (double)(last_xy & 0xFFFF), (double)(last_xy >> 16)) > rad_sq)) {
+                                                if (lane == 0) st_coherent(reg + i, last_xy);
+                                                break;
+                                            }
+                                            out_xy = last_xy;  // the point that moved in is too far as well: it leaves from position i
                                         }
-                                        out_xy = last_xy;  // the point that moved in is too far as well: it leaves from position i
                                     }
+                                    wave_publish();  // (a later chunk may hold positions this one has just filled)
                                 }
-                                wave_publish();  // (a later chunk may hold positions this one has just filled)
+                                if (n_reg < 2) {
+                                    gone = true;
+                                    break;
+                                }
+                                rc = lsd_region2rect<false>(reg, n_reg, k32, w, reg_angle, prec, nullptr);
+                                density = density_of(rc, n_reg);
                             }
-                            if (n_reg < 2) {
-                                gone = true;
-                                break;
-                            }
-                            rc = rect(n_reg, reg_angle);
-                            density = density_of(rc, n_reg);
                         }
                     }
+                    // flags have been turned off: the batch's later seeds as they stand now
+                    wave_publish();
+                    const int u_now = sd.key_ok ? ld_coherent(&px[sd.q_l].used) : 1;
+                    sd.todo = __ballot(sd.key_ok && lane > j && u_now == 0);
+                    if (gone) continue;
                 }
-                // flags have been turned off: the batch's later seeds as they stand now
-                wave_publish();
-                const int u_now = key_ok ? ld_coherent(&px[q_l].used) : 1;
-                todo = __ballot(key_ok && lane > j && u_now == 0);
-                if (gone) continue;
             }
-            double x1 = rc.x1 + 0.5, y1 = rc.y1 + 0.5, x2 = rc.x2 + 0.5, y2 = rc.y2 + 0.5;
-            if (d.scale != 1) {
-                x1 /= d.scale; y1 /= d.scale; x2 /= d.scale; y2 /= d.scale;
-            }
-            if (lane == 0 && n_seg < d.seg_cap) d.seg[(size_t)b * d.seg_cap + n_seg] = make_float4((float)x1, (float)y1, (float)x2, (float)y2);
+            lsd_store_segment<PROF>(d, b, n_seg, rc);
             ++n_seg;
+            pr.add(OW_RECT, pr.now() - tq0);
         }
     }
     if (lane == 0) d.n_seg[b] = n_seg;
+    if constexpr (PROF) lsd_store_counters(d, b, pr, t_begin);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -967,7 +976,6 @@ __global__ __launch_bounds__(64) void lsd_grow_refine_kernel(LsdDev d, const dou
 // Round 5 ran this inside ONE workgroup of sixteen waves (22.8 ms per KITTI-size image: the waves share a CU's four SIMDs and a
 // growth round is ~1500 cycles of dependent instructions — fifteen speculators delivered ~2.7 waves' worth of growth); round 6
 // spreads it over the CUs of one XCD: lsd_grow_xcd_kernel below (9.9 ms; the oracle takes 17 ms on one host core).
-constexpr int LSD_WRING = 256;       // per wave: the most recent region points in LDS
 constexpr int LSD_SEP = 8;            // (4 … 16 give the same ~130 failed validations per KITTI-size image, 0: 390; 24 … 32: more seeds reach the committer unclaimed)
 constexpr int LSD_LOOK = 2048;       // ranks the dispatcher examines per pass, from the front
 constexpr int LSD_AHEAD = 16384;     // the front's lead over the committer (ranks; ~200 seeds of a KITTI-size scene)
@@ -994,247 +1002,6 @@ __device__ __forceinline__ long long ld_l2_64(const long long* p) { return __hip
 __device__ __forceinline__ int lds_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void lds_st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
-// region_grow from `seed`, the fast form of lsd_grow_kernel.  MARK (the committer): a pixel is taken by setting its flag.  !MARK (a
-// speculating wave): the flags are only read; the wave's own pixels carry `id` in `stamp`.  The list goes to `list` (at most `cap`
-// entries: -1 if it does not fit), the final region angle to `angle_out`.
-// BITS (with MARK): the flags this wave decides on are a bitmap in LDS (`bits`); `used` is only written — for the waves of other CUs.
-__device__ __forceinline__ unsigned bit_ld(const unsigned* bits, int q) { return (__hip_atomic_load(bits + (q >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> (q & 31)) & 1u; }
-__device__ __forceinline__ void bit_set(unsigned* bits, int q) { (void)__hip_atomic_fetch_or(bits + (q >> 5), 1u << (q & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-template <bool MARK, bool FAR = false, bool BITS = false>
-__device__ __forceinline__ int grow_region_w(LsdPx* px, int32_t* stamp, int id,
-                                             int32_t* list, int cap, int* ring, int seed, float seed_ang, int w, int h, double prec,
-                                             double& angle_out, unsigned* bits = nullptr) {
-    const int lane = threadIdx.x & 63;
-    const int sx0 = seed % w, sy0 = seed / w;
-    double reg_angle = (double)seed_ang * LSD_DEG2RAD;
-    double sn0, cs0;
-    sincos_det(reg_angle, sn0, cs0);
-    float sumdx = (float)cs0, sumdy = (float)sn0;
-    int n_reg = 1;
-    if (lane == 0) {
-        if (MARK) st_coherent(&px[seed].used, 1);
-        else st_coherent(stamp + seed, id);
-        if (BITS) bit_set(bits, seed);
-        st_coherent(list, sx0 | (sy0 << 16));
-        ring[0] = sx0 | (sy0 << 16);
-    }
-    for (int i = 0; i < n_reg;) {
-        const int cnt = n_reg - i < 7 * LSD_GR ? n_reg - i : 7 * LSD_GR;  // uniform
-        const int slot0 = lane / 9, nb = lane - slot0 * 9;
-        int qq[LSD_GR], xy[LSD_GR], pxyv[LSD_GR], u[LSD_GR], own[LSD_GR];
-        float2 cs[LSD_GR];
-        float a[LSD_GR];
-        double ad[LSD_GR];
-        bool val[LSD_GR];
-        wave_publish();
-        const bool in_ring = n_reg - i <= LSD_WRING;  // uniform
-#pragma unroll
-        for (int r = 0; r < LSD_GR; ++r) {
-            const int slot = 7 * r + slot0;
-            val[r] = lane < 63 && slot < cnt && nb != 4;
-            const int at = val[r] ? i + slot : i;
-            pxyv[r] = in_ring ? ring[at & (LSD_WRING - 1)] : ld_coherent(list + at);
-        }
-#pragma unroll
-        for (int r = 0; r < LSD_GR; ++r) {
-            const int xx = (pxyv[r] & 0xFFFF) + (nb % 3) - 1, yy = (pxyv[r] >> 16) + nb / 3 - 1;
-            val[r] = val[r] && xx >= 0 && xx < w && yy >= 0 && yy < h;
-            qq[r] = val[r] ? yy * w + xx : 0;
-            xy[r] = xx | (yy << 16);
-            own[r] = MARK ? 0 : ld_coherent(stamp + qq[r]);
-        }
-        {   // the records: one 16-byte gather per sub-group.  FAR: the flag in it is stored by ANOTHER CU — the load bypasses the vector L1
-            LsdPx t[LSD_GR];
-            if constexpr (FAR) {
-                static_assert(LSD_GR == 2, "two loads in one statement");
-                lsd_f4 v0, v1;
-                asm volatile("global_load_dwordx4 %0, %2, off sc1\n\tglobal_load_dwordx4 %1, %3, off sc1\n\ts_waitcnt vmcnt(0)"
-                             : "=&v"(v0), "=&v"(v1)
-                             : "v"(px + qq[0]), "v"(px + qq[1])
-                             : "memory");
-                t[0].ang = v0.x; t[0].c = v0.y; t[0].s = v0.z; t[0].used = __float_as_int(v0.w);
-                t[1].ang = v1.x; t[1].c = v1.y; t[1].s = v1.z; t[1].used = __float_as_int(v1.w);
-            } else {
-#pragma unroll
-                for (int r = 0; r < LSD_GR; ++r) t[r] = px_ld(px + qq[r]);
-            }
-#pragma unroll
-            for (int r = 0; r < LSD_GR; ++r) {
-                u[r] = BITS ? (int)bit_ld(bits, qq[r]) : t[r].used;
-                a[r] = t[r].ang;
-                cs[r] = make_float2(t[r].c, t[r].s);
-            }
-        }
-        unsigned long long cand_m[LSD_GR];
-#pragma unroll
-        for (int r = 0; r < LSD_GR; ++r) {
-            cand_m[r] = __ballot(val[r] && u[r] == 0 && (MARK || own[r] != id) && a[r] >= 0.f);
-            ad[r] = (double)a[r] * LSD_DEG2RAD;
-        }
-        // guess + verification of a sub-group: lsd_grow_kernel<true> has the explanation
-#pragma unroll
-        for (int r = 0; r < LSD_GR; ++r) {
-            if (7 * r >= cnt) break;  // uniform
-            unsigned long long A;
-            {
-                double n_theta = reg_angle - ad[r];
-                if (n_theta < 0) n_theta = -n_theta;
-                if (n_theta > LSD_3_2_PI) {
-                    n_theta -= LSD_2_PI;
-                    if (n_theta < 0) n_theta = -n_theta;
-                }
-                A = __ballot(n_theta <= prec) & cand_m[r];
-            }
-            if (!A) continue;
-            if (n_reg + 64 > cap) return -1;  // uniform
-            unsigned long long acc, hit_m[LSD_GR];
-            float sx, sy;
-            double th;
-            for (;;) {
-                unsigned long long rem = A, dup_m = 0ull;
-                acc = 0ull;
-#pragma unroll
-                for (int r2 = 0; r2 < LSD_GR; ++r2) hit_m[r2] = 0ull;
-                sx = sumdx;
-                sy = sumdy;
-                while (rem) {
-                    const int j = __builtin_ctzll(rem);
-                    const int qj = __builtin_amdgcn_readlane(qq[r], j);
-                    const float cj = readlane_f32(cs[r].x, j), sj = readlane_f32(cs[r].y, j);
-                    const unsigned long long later = j == 63 ? 0ull : ~0ull << (j + 1);
-                    const unsigned long long same = __ballot(qq[r] == qj);
-                    acc |= 1ull << j;
-                    rem &= ~same;
-                    dup_m |= same & later;
-                    const float nx = sx + cj, ny = sy + sj;
-                    const bool is_later = lane > j;
-                    sx = is_later ? nx : sx;
-                    sy = is_later ? ny : sy;
-#pragma unroll
-                    for (int r2 = 0; r2 < LSD_GR; ++r2)
-                        if (r2 > r) hit_m[r2] |= __ballot(qq[r2] == qj);
-                }
-                const bool any = lane > __builtin_ctzll(acc);
-                th = any ? (double)fast_atan2_deg(sy, sx) * LSD_DEG2RAD : reg_angle;
-                double n_theta = th - ad[r];
-                if (n_theta < 0) n_theta = -n_theta;
-                if (n_theta > LSD_3_2_PI) {
-                    n_theta -= LSD_2_PI;
-                    if (n_theta < 0) n_theta = -n_theta;
-                }
-                const unsigned long long D = __ballot(n_theta <= prec) & cand_m[r] & ~dup_m;
-                if (D == acc) break;
-                const unsigned long long below = (1ull << __builtin_ctzll(D ^ acc)) - 1ull;
-                A = (acc & below) | (D & ~below);
-            }
-            if ((acc >> lane) & 1ull) {
-                const int idx = n_reg + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(acc >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)acc, 0u));
-                if (MARK) st_coherent(&px[qq[r]].used, 1);
-                else st_coherent(stamp + qq[r], id);
-                if (BITS) bit_set(bits, qq[r]);
-                st_coherent(list + idx, xy[r]);
-                ring[idx & (LSD_WRING - 1)] = xy[r];
-            }
-            n_reg += __builtin_popcountll(acc);
-            sumdx = readlane_f32(sx, 63);
-            sumdy = readlane_f32(sy, 63);
-            reg_angle = readlane_f64(th, 63);
-#pragma unroll
-            for (int r2 = 0; r2 < LSD_GR; ++r2)
-                if (r2 > r) cand_m[r2] &= ~hit_m[r2];
-        }
-        i += cnt;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the ring: this round's writes before the next round's reads
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    angle_out = reg_angle;
-    return n_reg;
-}
-
-// region2rect + the segment of a region of n >= min_reg_size pixels (the fast form of lsd_grow_kernel); term: [3][64] doubles of LDS
-__device__ __forceinline__ float4 region_segment_w(const LsdDev& d, const int32_t* list, int n_reg, const int32_t* __restrict__ k32, double reg_angle,
-                                                   double (*term)[64]) {
-    const int lane = threadIdx.x & 63, w = d.w;
-    wave_publish();
-    double chain = 0.0;
-    auto add_ordered = [&](double t0, double t1, double t2, int cn) {
-        term[0][lane] = t0;
-        term[1][lane] = t1;
-        term[2][lane] = t2;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (lane < 3) {
-            const double* row = term[lane];
-#pragma unroll 8
-            for (int k = 0; k < cn; ++k) chain += row[k];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    for (int c0 = 0; c0 < n_reg; c0 += 64) {
-        const int t = c0 + lane, cn = n_reg - c0 < 64 ? n_reg - c0 : 64;
-        int pxy = 0;
-        double wgt = 0.0;
-        if (t < n_reg) {
-            pxy = ld_coherent(list + t);
-            wgt = sqrt((double)k32[(pxy >> 16) * w + (pxy & 0xFFFF)] / 4.0);  // the gradient norm (ll_angle's expression)
-        }
-        add_ordered((double)(pxy & 0xFFFF) * wgt, (double)(pxy >> 16) * wgt, wgt, cn);
-    }
-    const double X = readlane_f64(chain, 0), Y = readlane_f64(chain, 1), S = readlane_f64(chain, 2);
-    chain = 0.0;
-    const double cx = X / S, cy = Y / S;
-    for (int c0 = 0; c0 < n_reg; c0 += 64) {
-        const int t = c0 + lane, cn = n_reg - c0 < 64 ? n_reg - c0 : 64;
-        double t_xx = 0.0, t_yy = 0.0, t_xy = 0.0;
-        if (t < n_reg) {
-            const int pxy = ld_coherent(list + t);
-            const double wgt = sqrt((double)k32[(pxy >> 16) * w + (pxy & 0xFFFF)] / 4.0);  // the gradient norm (ll_angle's expression)
-            const double ddx = (double)(pxy & 0xFFFF) - cx, ddy = (double)(pxy >> 16) - cy;
-            t_xx = ddy * ddy * wgt;
-            t_yy = ddx * ddx * wgt;
-            t_xy = ddx * ddy * wgt;
-        }
-        add_ordered(t_xx, t_yy, -t_xy, cn);
-    }
-    const double Ixx = readlane_f64(chain, 0), Iyy = readlane_f64(chain, 1), Ixy = readlane_f64(chain, 2);
-    const double lambda = 0.5 * (Ixx + Iyy - sqrt((Ixx - Iyy) * (Ixx - Iyy) + 4.0 * Ixy * Ixy));
-    double theta = (fabs(Ixx) > fabs(Iyy)) ? (double)fast_atan2_deg((float)(lambda - Ixx), (float)Ixy)
-                                           : (double)fast_atan2_deg((float)Ixy, (float)(lambda - Iyy));
-    theta *= LSD_DEG2RAD;
-    {
-        double diff = theta - reg_angle;
-        while (diff <= -LSD_PI) diff += LSD_2_PI;
-        while (diff > LSD_PI) diff -= LSD_2_PI;
-        if (fabs(diff) > d.prec) theta += LSD_PI;
-    }
-    double dx, dy;
-    sincos_det(theta, dy, dx);
-    double l_min = 0.0, l_max = 0.0;
-    for (int t = lane; t < n_reg; t += 64) {
-        const int pxy = ld_coherent(list + t);
-        const double rdx = (double)(pxy & 0xFFFF) - cx, rdy = (double)(pxy >> 16) - cy;
-        const double l = rdx * dx + rdy * dy;
-        l_max = l > l_max ? l : l_max;
-        l_min = l < l_min ? l : l_min;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double om = __shfl_xor(l_max, off, 64), on = __shfl_xor(l_min, off, 64);
-        l_max = om > l_max ? om : l_max;
-        l_min = on < l_min ? on : l_min;
-    }
-    double x1 = cx + l_min * dx, y1 = cy + l_min * dy, x2 = cx + l_max * dx, y2 = cy + l_max * dy;
-    x1 += 0.5; y1 += 0.5; x2 += 0.5; y2 += 0.5;
-    if (d.scale != 1) {
-        x1 /= d.scale; y1 /= d.scale; x2 /= d.scale; y2 /= d.scale;
-    }
-    return make_float4((float)x1, (float)y1, (float)x2, (float)y2);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The protocol above across the CUs of ONE XCD.  A workgroup is four waves, one per SIMD (84 KB of LDS at least: a CU holds one).
 // Image b is served by the workgroups b, b + 8, b + 16, ... — the dispatcher of the hardware places those on one XCD:
@@ -1247,8 +1014,8 @@ __device__ __forceinline__ float4 region_segment_w(const LsdDev& d, const int32_
 //                            waves 38 ms, 125 waves 57 ms per image; with the dispatcher 13 ms before the two items above);
 //                     wave 2 the FEEDER: for the free seeds within LSD_FEED_AHEAD ranks of the committer whose table entry shows a
 //                            finished region, segment + pixel list from the L2 into a record ring in LDS, in rank order;
-//   workgroups b + 8 k  four SPECULATING waves each: mail box -> grow_region_w against the global flags (loads that bypass the L1) ->
-//                            region_segment_w -> list + segment stored, waited for (vmcnt), table entry, mail box "idle".
+//   workgroups b + 8 k  four SPECULATING waves each: mail box -> lsd_grow_fast against the global flags (loads that bypass the L1) ->
+//                            lsd_region2rect -> list + segment stored, waited for (vmcnt), table entry, mail box "idle".
 // What the workgroups exchange lives in HBM and meets in that XCD's L2: stores are ordinary (write-through L1, the line stays in the
 // L2), loads of anything another CU stores during the launch bypass the vector L1 (sc1).  The flags and the mail boxes are ADVISORY
 // for a speculating wave — a stale flag costs a failed validation, never a wrong region; what the committer (or the feeder) takes on
@@ -1279,6 +1046,13 @@ struct LsdXcd {
 };
 __device__ __forceinline__ long long lsd_entry_x(int wave, int n, int off) { return (1ll << 62) | ((long long)wave << 42) | ((long long)n << 21) | (long long)off; }
 
+// what the committer counts (PROF), in the order of its counter rows; the dispatcher and the speculating waves have rows of their own
+enum { CM_T_SELF, CM_T_WAIT, CM_T_TAKE, CM_TOOK, CM_SELF, CM_BAD, CM_WAITED, CM_FAST, CM_STALE, CM_BATCH, CM_MULTI, CM_MULTI_UNDO,
+       CM_T_MULTI, CM_T_PEEK, CM_T_REFRESH, CM_MULTI_TRY };
+enum { DP_ITER, DP_CHUNKS, DP_GIVEN, DP_NOIDLE, DP_BLOCKED, DP_N };
+enum { SP_BUSY, SP_REGIONS };
+
+template <bool PROF>
 __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, LsdXcd x) {
     __shared__ int s_ring[LSD_XW][LSD_WRING];
     __shared__ double s_term[LSD_XW][3][64];
@@ -1356,11 +1130,9 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
         int32_t* wlist = x.wlist + (size_t)b * nw * npx;
         if (lane == 0) __hip_atomic_store(ctl + XC_ALIVE, xcc + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         int n_seg = 0;
-        const bool prof = d.dbg != nullptr && b == 0;  // tools/lsd_probe.py: where the committer's time goes
-        auto tick = [&]() -> long long { return prof ? (long long)__builtin_readcyclecounter() : 0ll; };
-        const long long t_begin = tick();
-        long long t_self = 0, t_wait = 0, t_take = 0, t_multi = 0, t_peek = 0, t_refresh = 0;
-        int n_took = 0, n_self = 0, n_bad = 0, n_waited = 0, n_fast = 0, n_stale = 0, n_batch = 0, n_multi = 0, n_multi_undo = 0, n_multi_try = 0;
+        LsdProbe<PROF> pr(b == 0);  // tools/lsd_probe.py: where the committer's time goes
+        LsdProbe<false> quiet(false);
+        const long long t_begin = pr.now();
         int qt = 0, qh = 0;  // records consumed / known to be there
         request(0, false);
         bool at_end = false;
@@ -1375,7 +1147,7 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                 at_end = true;
                 break;
             }
-            ++n_batch;
+            pr.add(CM_BATCH, 1);
             const int q_l = (int)(key & ((1u << LSD_IDX_BITS) - 1u));
             const bool key_ok = key != LSD_NOKEY;
             unsigned long long todo = __ballot(key_ok && bit_ld(s_bits, key_ok ? q_l : 0) == 0u);
@@ -1387,8 +1159,8 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                 // at most 128 pixels.  All their pixels are tested in one LDS round trip and taken together as far as the sequential
                 // search would take them — up to the first region with a used pixel — unless two of them share a pixel (the returning
                 // ds_or of the take shows it: then the bits are cleared again and the first record goes alone).
-                const long long tm0 = tick();
-                ++n_multi_try;
+                const long long tm0 = pr.now();
+                pr.add(CM_MULTI_TRY, 1);
                 if (qh - qt < 8) qh = __hip_atomic_load(&s_qhead, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 const int have = qh - qt < 8 ? qh - qt : 8;
                 const int4 dl = s_desc[(qt + (lane & 7)) & (LSD_FEED_Q - 1)];  // {rank, pixels, position, words fed up to its end}
@@ -1425,7 +1197,7 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                     if (kk == 0) {  // the first record has lost a pixel: its region is grown again below
                         regrow_first = true;
                         ++qt;
-                        ++n_bad;
+                        pr.add(CM_BAD, 1);
                         if (lane == 0) {
                             lds_st(&s_cwords, __builtin_amdgcn_readfirstlane(dl.w));
                             lds_st(&s_qtail, qt);
@@ -1439,12 +1211,12 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                         if (__ballot(c0 || c1)) {  // two of the regions share a pixel: undo (the bits were clear before), the first record alone next
                             if (t0 && !c0) (void)__hip_atomic_fetch_and(s_bits + (q0 >> 5), ~(1u << (q0 & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                             if (t1 && !c1) (void)__hip_atomic_fetch_and(s_bits + (q1 >> 5), ~(1u << (q1 & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            ++n_multi_undo;
+                            pr.add(CM_MULTI_UNDO, 1);
                             one_record = true;
                             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                             __builtin_amdgcn_wave_barrier();
                             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                            t_multi += tick() - tm0;
+                            pr.add(CM_T_MULTI, pr.now() - tm0);
                             continue;
                         }
                         if (t0) st_coherent(&px[q0].used, 1);
@@ -1459,9 +1231,9 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                         todo &= ~__ballot(is_seed && ord < kk);
                         const int last_rank = __builtin_amdgcn_readlane(dl.x, kk - 1), last_end = __builtin_amdgcn_readlane(dl.w, kk - 1);
                         qt += kk;
-                        n_took += kk;
-                        n_fast += kk;
-                        ++n_multi;
+                        pr.add(CM_TOOK, kk);
+                        pr.add(CM_FAST, kk);
+                        pr.add(CM_MULTI, 1);
                         if (lane == 0) {
                             lds_st(&s_scan, last_rank);
                             lds_st(&s_cwords, last_end);
@@ -1471,7 +1243,7 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                         __builtin_amdgcn_wave_barrier();
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                         todo &= __ballot(key_ok && bit_ld(s_bits, key_ok ? q_l : 0) == 0u);
-                        t_multi += tick() - tm0;
+                        pr.add(CM_T_MULTI, pr.now() - tm0);
                         continue;
                     }
                 } else if (have >= 1 && __builtin_amdgcn_readfirstlane(dl.x) == first_rank) {
@@ -1491,11 +1263,11 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                             ++n_seg;
                         }
                         todo &= todo - 1ull;
-                        ++n_took;
-                        ++n_fast;
+                        pr.add(CM_TOOK, 1);
+                        pr.add(CM_FAST, 1);
                     } else {
                         regrow_first = true;
-                        ++n_bad;
+                        pr.add(CM_BAD, 1);
                     }
                     ++qt;
                     if (lane == 0) {
@@ -1508,7 +1280,7 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                         __builtin_amdgcn_wave_barrier();
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                         todo &= __ballot(key_ok && bit_ld(s_bits, key_ok ? q_l : 0) == 0u);
-                        t_multi += tick() - tm0;
+                        pr.add(CM_T_MULTI, pr.now() - tm0);
                         continue;
                     }
                 } else {
@@ -1518,36 +1290,36 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                     if (ns > 0) {
                         const int cend = __builtin_amdgcn_readlane(dl.w, ns - 1);
                         qt += ns;
-                        n_stale += ns;
+                        pr.add(CM_STALE, ns);
                         if (lane == 0) {
                             lds_st(&s_cwords, cend);
                             lds_st(&s_qtail, qt);
                         }
-                        t_multi += tick() - tm0;
+                        pr.add(CM_T_MULTI, pr.now() - tm0);
                         continue;
                     }
                 }
                 // ---- ... and ONE seed goes through the table (its region was not finished when the feeder passed, is larger than a
                 // record, or the feeder is behind), or — the record's region has lost a pixel — is grown again
-                const long long tp0 = tick();
-                t_multi += tp0 - tm0;
+                const long long tp0 = pr.now();
+                pr.add(CM_T_MULTI, tp0 - tm0);
                 const int j = __builtin_ctzll(todo);
                 todo &= todo - 1ull;
                 const int seed = __builtin_amdgcn_readlane(q_l, j), rank = o0 + j;
                 if (lane == 0) lds_st(&s_scan, rank);
                 bool took = false;
                 long long p = 1;
-                const long long tk = tick();
-                t_peek += tk - tp0;
+                const long long tk = pr.now();
+                pr.add(CM_T_PEEK, tk - tp0);
                 if (!regrow_first) {
                     auto table = [&]() { return readfirstlane64(ld_l2_64(pend + rank)); };  // (one address: a scalar result)
                     p = table();
                     if (p < 0) {  // a speculating wave is growing this very seed: its work is the work this wave would do (bounded wait)
-                        const long long tw = tick();
+                        const long long tw = pr.now();
                         for (int spin = 0; spin < (1 << 20) && (p = table()) < 0; ++spin) __builtin_amdgcn_s_sleep(2);
                         if (p < 0) p = 0;  // (gave up: this wave grows the seed itself, whatever the other one publishes later is never read)
-                        t_wait += tick() - tw;
-                        ++n_waited;
+                        pr.add(CM_T_WAIT, pr.now() - tw);
+                        pr.add(CM_WAITED, 1);
                     }
                     if (p) {
                         const int off = (int)(p & 0x1FFFFF), n = (int)((p >> 21) & 0x1FFFFF), pw = (int)((p >> 42) & 0x7F);
@@ -1580,30 +1352,30 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                             }
                         }
                     }
-                    if (took) ++n_took;
-                    else if (p) ++n_bad;
-                    else ++n_self;
+                    if (took) pr.add(CM_TOOK, 1);
+                    else if (p) pr.add(CM_BAD, 1);
+                    else pr.add(CM_SELF, 1);
                 }
-                const long long ts = tick();
-                t_take += ts - tk;
+                const long long ts = pr.now();
+                pr.add(CM_T_TAKE, ts - tk);
                 if (!took) {
                     double reg_angle;
-                    const int n = grow_region_w<true, false, true>(px, nullptr, 0, wlist, npx, s_ring[0], seed, px[seed].ang, w, h, d.prec,
-                                                                   reg_angle, s_bits);
+                    const int n = lsd_grow_fast<true, false, true, LSD_WRING, false, false>(px, nullptr, 0, s_bits, wlist, npx, s_ring[0], seed, px[seed].ang, w, h,
+                                                                                            d.prec, nullptr, reg_angle, quiet);
                     if (n >= d.min_reg_size) {
-                        const float4 sg = region_segment_w(d, wlist, n, k32, reg_angle, s_term[0]);
+                        const float4 sg = lsd_segment(lsd_region2rect<true>(wlist, n, k32, w, reg_angle, d.prec, s_term[0]), d.scale);
                         if (lane == 0 && n_seg < d.seg_cap) d.seg[(size_t)b * d.seg_cap + n_seg] = sg;
                         ++n_seg;
                     }
-                    t_self += tick() - ts;
+                    pr.add(CM_T_SELF, pr.now() - ts);
                 }
                 // seeds of the batch taken meanwhile (an LDS round trip)
-                const long long tr0 = tick();
+                const long long tr0 = pr.now();
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 todo &= __ballot(key_ok && bit_ld(s_bits, key_ok ? q_l : 0) == 0u);
-                t_refresh += tick() - tr0;
+                pr.add(CM_T_REFRESH, pr.now() - tr0);
             }
         }
         }
@@ -1612,14 +1384,15 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
             lds_st(&s_done, 1);
             st_coherent(ctl + XC_DONE, 1);
         }
-        if (prof && lane == 0) {  // the last 16 doubles of image 0's block (row seg_cap - 1: marker -1 = a committer's counters)
-            double* q = d.dbg + ((size_t)d.seg_cap - 2) * 8;
-            q[0] = (double)(tick() - t_begin); q[1] = (double)t_self; q[2] = (double)t_wait; q[3] = (double)t_take;
-            q[4] = (double)n_took; q[5] = (double)n_self; q[6] = (double)n_bad; q[7] = (double)n_waited;
-            q[8] = -1.0;
-            q[9] = (double)n_fast; q[10] = (double)n_stale; q[11] = (double)n_batch; q[12] = (double)n_multi; q[13] = (double)n_multi_undo;
-            d.dbg[((size_t)d.seg_cap - 5) * 8 + 0] = (double)t_multi; d.dbg[((size_t)d.seg_cap - 5) * 8 + 1] = (double)t_peek;
-            d.dbg[((size_t)d.seg_cap - 5) * 8 + 2] = (double)t_refresh; d.dbg[((size_t)d.seg_cap - 5) * 8 + 3] = (double)n_multi_try;
+        if constexpr (PROF) {  // the last 16 doubles of image 0's block (row seg_cap - 1: marker -1 = a committer's counters), and row seg_cap - 5
+            if (pr.on && lane == 0) {
+                double* q = d.dbg + ((size_t)d.seg_cap - 2) * 8, *q5 = d.dbg + ((size_t)d.seg_cap - 5) * 8;
+                q[0] = (double)(pr.now() - t_begin);
+                for (int i = CM_T_SELF; i <= CM_WAITED; ++i) q[1 + i] = (double)pr.v[i];
+                q[8] = -1.0;
+                for (int i = CM_FAST; i <= CM_MULTI_UNDO; ++i) q[2 + i] = (double)pr.v[i];
+                for (int i = CM_T_MULTI; i <= CM_MULTI_TRY; ++i) q5[i - CM_T_MULTI] = (double)pr.v[i];
+            }
         }
     } else if (role == 0 && wv == 2) {
         // ---------------- the feeder: the finished regions in front of the committer, from the L2 into LDS, in rank order ----------------
@@ -1709,17 +1482,16 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
         const int ns = nw - 1;
         int sxy0 = -1, sxy1 = -1;  // x | y << 16 of the seed in flight, -1: none
         int front = 0;             // every rank below is used, pending or claimed — for good
-        const bool dprof = d.dbg != nullptr && b == 0;
-        long long dp_iter = 0, dp_chunks = 0, dp_given = 0, dp_noidle = 0, dp_blocked = 0;
+        LsdProbe<PROF> pr(b == 0);
         for (int idle = 0; idle < (1 << 24); ++idle) {  // (bounded)
             if (lds_ld(&s_done)) break;
             const bool idle0 = lane < ns && ld_l2_64(mbox + lane) == 1, idle1 = lane + 64 < ns && ld_l2_64(mbox + 64 + lane) == 1;  // (1: the wave is there and idle)
             if (idle0) sxy0 = -1;
             if (idle1) sxy1 = -1;
             unsigned long long I0 = __ballot(idle0), I1 = __ballot(idle1);
-            ++dp_iter;
+            pr.add(DP_ITER, 1);
             if (!(I0 | I1)) {
-                ++dp_noidle;
+                pr.add(DP_NOIDLE, 1);
                 __builtin_amdgcn_s_sleep(4);
                 continue;
             }
@@ -1741,7 +1513,7 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                 const int qx = q % w, qy = q / w;
                 const unsigned long long m_open = __ballot(open);
                 unsigned long long mm = m_open, given = 0ull;
-                ++dp_chunks;
+                pr.add(DP_CHUNKS, 1);
                 while (mm && (I0 | I1)) {
                     const int L = __builtin_ctzll(mm);
                     mm &= mm - 1ull;
@@ -1752,7 +1524,7 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                         return sxy >= 0 && (adx > ady ? adx : ady) < x.sep;
                     };
                     if (__ballot(near(sxy0) || near(sxy1))) {  // too close to a growth in flight: later (the front stays in front of it)
-                        ++dp_blocked;
+                        pr.add(DP_BLOCKED, 1);
                         continue;
                     }
                     const int u = I0 ? __builtin_ctzll(I0) : 64 + __builtin_ctzll(I1);
@@ -1767,7 +1539,7 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                         st_coherent64(mbox + u, (1ll << 62) | ((long long)r << 21) | (long long)q);
                     }
                     given |= 1ull << L;
-                    ++dp_given;
+                    pr.add(DP_GIVEN, 1);
                     idle = 0;
                 }
                 if (contiguous) {  // the ranks of this chunk in front of the first one still open join the solid part
@@ -1777,9 +1549,9 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                 }
             }
         }
-        if (dprof && lane == 0) {
-            double* q = d.dbg + ((size_t)d.seg_cap - 4) * 8;
-            q[0] = (double)dp_iter; q[1] = (double)dp_chunks; q[2] = (double)dp_given; q[3] = (double)dp_noidle; q[4] = (double)dp_blocked;
+        if constexpr (PROF) {
+            if (pr.on && lane == 0)
+                for (int i = 0; i < DP_N; ++i) d.dbg[((size_t)d.seg_cap - 4) * 8 + i] = (double)pr.v[i];
         }
     } else if (role != 0) {
         // ---------------- a speculating wave ----------------
@@ -1792,9 +1564,9 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
         int32_t* stamp = x.stamp + ((size_t)b * nw + v) * npx;
         int32_t* wl = x.wlist + ((size_t)b * nw + v) * npx;
         int id = 0, off = 0;
-        const bool sprof = d.dbg != nullptr && b == 0;
-        long long sp_busy = 0, sp_n = 0, sp_grow = 0;
-        const long long sp_t0 = sprof ? (long long)__builtin_readcyclecounter() : 0ll;
+        LsdProbe<PROF> pr(b == 0);
+        LsdProbe<false> quiet(false);
+        const long long sp_t0 = pr.now();
         if (lane == 0) st_coherent64(mbox + (v - 1), 1ll);  // here, and idle
         for (int idle = 0; idle < (1 << 24); ++idle) {  // (bounded: a wave that is handed nothing for this long gives up)
             const long long m = readfirstlane64(ld_l2_64(mbox + (v - 1)));
@@ -1804,15 +1576,16 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                 continue;
             }
             idle = 0;
-            const long long sp_a = sprof ? (long long)__builtin_readcyclecounter() : 0ll;
+            const long long sp_a = pr.now();
             const int pick_r = (int)((m >> 21) & 0x1FFFFF), pick_q = (int)(m & 0x1FFFFF);
             int n = 0;
             if (npx - off >= 4096) {  // (out of room: empty records from here on — the committer grows those seeds itself)
                 ++id;
                 double reg_angle = 0.0;
-                n = grow_region_w<false, true>(px, stamp, id, wl + off + 4, npx - off - 4, s_ring[wv], pick_q, px[pick_q].ang, w, h, d.prec, reg_angle);
+                n = lsd_grow_fast<false, true, false, LSD_WRING, false, false>(px, stamp, id, nullptr, wl + off + 4, npx - off - 4, s_ring[wv], pick_q, px[pick_q].ang, w, h,
+                                                                        d.prec, nullptr, reg_angle, quiet);
                 if (n >= d.min_reg_size) {
-                    const float4 sg = region_segment_w(d, wl + off + 4, n, k32, reg_angle, s_term[wv]);
+                    const float4 sg = lsd_segment(lsd_region2rect<true>(wl + off + 4, n, k32, w, reg_angle, d.prec, s_term[wv]), d.scale);
                     if (lane == 0) {
                         st_coherent(wl + off, __float_as_int(sg.x));
                         st_coherent(wl + off + 1, __float_as_int(sg.y));
@@ -1828,18 +1601,17 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (lane == 0) st_coherent64(mbox + (v - 1), 1ll);  // idle again
             if (n > 0) off += 4 + n;
-            if (sprof) {
-                sp_busy += (long long)__builtin_readcyclecounter() - sp_a;
-                ++sp_n;
-            }
+            pr.add(SP_BUSY, pr.now() - sp_a);
+            pr.add(SP_REGIONS, 1);
         }
-        if (sprof && lane == 0) {  // tools/lsd_probe.py: the speculating waves together (row seg_cap - 3 of image 0's block, as integers)
-            unsigned long long* q = reinterpret_cast<unsigned long long*>(d.dbg + ((size_t)d.seg_cap - 3) * 8);
-            atomicAdd(q + 0, (unsigned long long)sp_busy);
-            atomicAdd(q + 1, (unsigned long long)((long long)__builtin_readcyclecounter() - sp_t0));
-            atomicAdd(q + 2, (unsigned long long)sp_n);
-            atomicAdd(q + 3, 1ull);
-            (void)sp_grow;
+        if constexpr (PROF) {  // tools/lsd_probe.py: the speculating waves together (row seg_cap - 3 of image 0's block, as integers)
+            if (pr.on && lane == 0) {
+                unsigned long long* q = reinterpret_cast<unsigned long long*>(d.dbg + ((size_t)d.seg_cap - 3) * 8);
+                atomicAdd(q + 0, (unsigned long long)pr.v[SP_BUSY]);
+                atomicAdd(q + 1, (unsigned long long)(pr.now() - sp_t0));
+                atomicAdd(q + 2, (unsigned long long)pr.v[SP_REGIONS]);
+                atomicAdd(q + 3, 1ull);
+            }
         }
     }
 }
@@ -1998,16 +1770,21 @@ int lsd_enqueue(stvo_lsd* o, const uint8_t* images, stvo_keyline* lines, float* 
         hipLaunchKernelGGL(stvo::lsd_scan_kernel, dim3(d.B), dim3(1024), 0, s, d);
         hipLaunchKernelGGL(stvo::lsd_scatter_kernel, ug, dim3(256), lds_h, s, d);
     }
-    if (o->prm.refine == 1) {  // LSD_REFINE_STD: regions may give their pixels back — its own one-wave kernel, for every batch size
-        hipLaunchKernelGGL(stvo::lsd_grow_refine_kernel, dim3(d.B), dim3(64), 0, s, d, o->prm.density_th);
+    const bool prof = d.dbg != nullptr;  // stvo_lsd_debug has the probes on: the PROF instance of the route's kernel
+    if (o->prm.refine == 1) {  // LSD_REFINE_STD: regions may give their pixels back — the plain one-wave kernel with refinement, for every batch size
+        hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<true, false>), dim3(d.B), dim3(64), 0, s, d, o->prm.density_th);
     } else if (o->wdev) {  // small batches: a committing wave + speculating workgroups on the CUs of one XCD per image (lsd_grow_xcd_kernel)
         HIP_TRY(ctx, hipMemsetAsync(o->xx.stamp, 0, o->stamp_bytes, s));
         HIP_TRY(ctx, hipMemsetAsync(o->xx.pend, 0, o->pend_bytes + (size_t)d.B * stvo::LSD_CTL * 4, s));  // (the control words lie behind the table)
-        hipLaunchKernelGGL(stvo::lsd_grow_xcd_kernel, dim3(8 * ((d.B + 7) / 8) * (1 + o->xx.nsb)), dim3(stvo::LSD_XW * 64), o->xcd_lds, s, d, o->xx);
-    } else if (stvo::dbg().lsd_grow == 0) {
-        hipLaunchKernelGGL(stvo::lsd_grow_kernel<false>, dim3(d.B), dim3(64), 0, s, d);
+        const dim3 xg(8 * ((d.B + 7) / 8) * (1 + o->xx.nsb)), xb(stvo::LSD_XW * 64);
+        if (prof) hipLaunchKernelGGL(stvo::lsd_grow_xcd_kernel<true>, xg, xb, o->xcd_lds, s, d, o->xx);
+        else hipLaunchKernelGGL(stvo::lsd_grow_xcd_kernel<false>, xg, xb, o->xcd_lds, s, d, o->xx);
+    } else if (stvo::dbg().lsd_grow == 0) {  // STVO_LSD_GROW=0: the plain one-wave kernel, nothing refined
+        if (prof) hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<false, true>), dim3(d.B), dim3(64), 0, s, d, 0.0);
+        else hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<false, false>), dim3(d.B), dim3(64), 0, s, d, 0.0);
     } else {
-        hipLaunchKernelGGL(stvo::lsd_grow_kernel<true>, dim3(d.B), dim3(64), 0, s, d);
+        if (prof) hipLaunchKernelGGL(stvo::lsd_grow_kernel<true>, dim3(d.B), dim3(64), 0, s, d);
+        else hipLaunchKernelGGL(stvo::lsd_grow_kernel<false>, dim3(d.B), dim3(64), 0, s, d);
     }
     const size_t lds = (size_t)d.seg_cap * 8;
     hipLaunchKernelGGL(stvo::lsd_keylines_kernel, dim3(d.B), dim3(stvo::KL_T), lds, s, d);
@@ -2134,7 +1911,8 @@ int stvo_lsd_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, 
         const size_t w_stamp = cw.take(nb * nw * npx * 4), w_list = cw.take(nb * nw * npx * 4), w_pend = cw.take(nb * npx * 8 + nb * stvo::LSD_CTL * 4);
         o->xcd_lds = (int)(((((npx + 31) / 32) + 3) & ~size_t(3)) * 4) + stvo::LSD_FEED_PX * 4 + stvo::LSD_FEED_Q * 32;
         if (o->xcd_lds < 84 * 1024) o->xcd_lds = 84 * 1024;
-        ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_grow_xcd_kernel), o->xcd_lds) &&
+        ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_grow_xcd_kernel<false>), o->xcd_lds) &&
+             stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_grow_xcd_kernel<true>), o->xcd_lds) &&
              hip_ok(ctx, hipMalloc((void**)&o->wdev, cw.off), "hipMalloc lsd xcd");
         if (ok) {
             o->xx.stamp = (int32_t*)(o->wdev + w_stamp); o->xx.wlist = (int32_t*)(o->wdev + w_list);
@@ -2192,9 +1970,12 @@ int stvo_lsd_detect(stvo_lsd* o, const uint8_t* images, stvo_keyline* lines, flo
     return STVO_OK;
 }
 
-// developer aid, not part of include/: the rectangle intermediates of the last stvo_lsd_segments call's first image
+// developer aid, not part of include/: switches the detector to the PROF instances of its search kernel (enable) or back, and hands out
+// what the last detection under them left for its first image — the rectangle intermediates per segment (the one-wave kernels) and the
+// counter rows at the end of the block (tools/lsd_probe.py).  lsd_refine = 1 has no such instance.
 extern "C" int stvo_lsd_debug(stvo_lsd* o, int enable, double* out /* [seg_cap][8] or NULL */) {
     if (!o) return STVO_ERR_INVALID_ARG;
+    if (o->prm.refine == 1) return STVO_ERR_UNSUPPORTED;
     stvo_ctx* ctx = o->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (enable && !o->dbg) {
@@ -2202,7 +1983,10 @@ extern "C" int stvo_lsd_debug(stvo_lsd* o, int enable, double* out /* [seg_cap][
         if (!zero_device(ctx, o->dbg, (size_t)o->d.B * o->d.seg_cap * 64, "hipMemset lsd dbg")) return STVO_ERR_HIP;
     }
     o->d.dbg = enable ? o->dbg : nullptr;
-    if (out && o->dbg) HIP_TRY(ctx, hipMemcpy(out, o->dbg, (size_t)o->d.seg_cap * 64, hipMemcpyDeviceToHost));
+    if (out && o->dbg) {  // (on the context's stream, which the kernels ran on: the null stream does not wait for it)
+        HIP_TRY(ctx, hipMemcpyAsync(out, o->dbg, (size_t)o->d.seg_cap * 64, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
     return STVO_OK;
 }
 

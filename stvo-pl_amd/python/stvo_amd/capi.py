@@ -250,6 +250,7 @@ def load():
     L.stvo_lsd_geometry.argtypes = [C.POINTER(LsdParams), C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                     C.POINTER(C.c_int32), i32p]
     L.stvo_lsd_scaled_image.argtypes = [C.c_void_p, u8p, u8p]
+    L.stvo_lsd_debug.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.stvo_fld_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FldParams), C.POINTER(C.c_void_p)]
     L.stvo_fld_destroy.argtypes = [C.c_void_p]
     L.stvo_fld_detect.argtypes = [C.c_void_p, u8p, C.c_void_p, C.c_void_p, i32p]
@@ -578,6 +579,15 @@ class Lsd:
         n = np.zeros(self.B, np.int32)
         self.ctx._chk(self.ctx.lib.stvo_lsd_segments(self.h, images.reshape(-1), seg.reshape(-1), cap, n))
         return [seg[b, :min(n[b], cap)].copy() for b in range(self.B)], n
+
+    def debug(self, enable):
+        """Developer aid (stvo_lsd_debug): switches the probe instances of the search kernels on or off for the calls that follow, and
+        returns what the last detection under them left for image 0 as float64 [8192, 8] — per segment of a one-wave kernel the row
+        (cx, cy, Ixx, Iyy, Ixy, theta, l_min, l_max) in the scaled image, counter rows at the end (tools/lsd_probe.py reads them);
+        zeros before the first such detection.  StvoError for lsd_refine = 1, which has no probe instance."""
+        rows = np.zeros((8192, 8), np.float64)
+        self.ctx._chk(self.ctx.lib.stvo_lsd_debug(self.h, 1 if enable else 0, _ptr(rows)))
+        return rows
 
     def scaled_image(self, images):
         """The image the detector core sees (blurred and resized; the input itself at scale 1): uint8 [B, scaled rows, scaled cols]."""

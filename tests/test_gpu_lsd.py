@@ -75,6 +75,45 @@ def test_lsd_plain_growth_is_the_same(hip, oracle, switches):
             lsd.close()
 
 
+def test_lsd_probe_instances_find_the_same_segments(hip, switches):
+    """stvo_lsd_debug (capi.Lsd.debug) switches a detector to the PROF instances of its search kernel — the same search with the
+    developer's cycle counters and debug rows compiled in, distinct code from the shipped instances — and back.  On every route that
+    has one (many waves per image; one wave, fast; one wave, plain) both give the pinned segments of the oracle (tests/golden/,
+    test_oracle_output_is_pinned) for both images of a batch; the one-wave instances leave a rectangle row per segment of image 0 whose
+    centre lies in the scaled image; lsd_refine = 1 has no such instance and says so."""
+    from stvo_amd import capi
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lsd_oracle_320x200.npz"))
+    imgs, ref = np.stack([g["img"], g["img"]]), g["segments"]
+    rows, cols = g["img"].shape
+
+    def check(lsd):
+        segs, n = lsd.segments(imgs)
+        for b in range(2):
+            assert n[b] == len(ref) and np.array_equal(segs[b], ref), b
+
+    for env in ({}, {"STVO_LSD_WAVES": "0"}, {"STVO_LSD_WAVES": "0", "STVO_LSD_GROW": "0"}):  # (each adds to the one before)
+        switches(env)
+        lsd = capi.Lsd(hip, 2, cols, rows, capi.lsd_params(), max_keylines=512)
+        try:
+            assert not lsd.debug(True).any()  # (nothing has run under the probes yet)
+            check(lsd)
+            dbg = lsd.debug(True)[:len(ref)]
+            if env:  # a one-wave kernel: cx, cy of every segment's rectangle
+                assert np.isfinite(dbg).all(), env
+                assert (dbg[:, 0] >= 0).all() and (dbg[:, 0] < lsd.geometry["cols"]).all(), env
+                assert (dbg[:, 1] >= 0).all() and (dbg[:, 1] < lsd.geometry["rows"]).all(), env
+            lsd.debug(False)
+            check(lsd)
+        finally:
+            lsd.close()
+    lsd = capi.Lsd(hip, 2, cols, rows, capi.lsd_params(refine=1), max_keylines=512)
+    try:
+        with pytest.raises(capi.StvoError, match="unsupported"):  # STVO_ERR_UNSUPPORTED
+            lsd.debug(True)
+    finally:
+        lsd.close()
+
+
 @pytest.mark.parametrize("waves", ["", "0"])
 def test_lsd_many_waves_and_one_wave_per_image_are_the_same(hip, oracle, switches, waves):
     """Batches of <= 8 images run one image per XCD by default — a committing wave, a dispatcher and a feeder in one workgroup,

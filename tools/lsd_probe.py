@@ -15,10 +15,9 @@ imgs = np.stack([imgs[b % len(imgs)] for b in range(B)])
 ctx = capi.Context(0, 2048, 4)
 lsd = capi.Lsd(ctx, B, cols, rows, capi.lsd_params(min_length=0.025 * rows, nfeatures=300), max_keylines=512)
 import ctypes as C
-ctx.lib.stvo_lsd_debug.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-ctx.lib.stvo_lsd_debug(lsd.h, 1, None)
+lsd.debug(True)
 segs, n = lsd.segments(imgs)
-gd = np.zeros((8192, 8)); ctx.lib.stvo_lsd_debug(lsd.h, 1, gd.ctypes.data_as(C.c_void_p))
+gd = lsd.debug(True)
 od = np.zeros((65536, 8)); o.lib.orc_lsd_set_debug.argtypes = [C.c_void_p]; o.lib.orc_lsd_set_debug(od.ctypes.data_as(C.c_void_p))
 for b in range(min(B, 2)):
     ref = o.lsd_segments(imgs[b], o.lsd_opts())
