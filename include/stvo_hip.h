@@ -573,6 +573,39 @@ int stvo_rectify_images(stvo_rectify* rect, int n, const uint8_t* src_l, const u
 /* The same with DEVICE pointers, enqueued on the context's stream (no synchronisation). */
 int stvo_rectify_images_dev(stvo_rectify* rect, int n, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l, uint8_t* dst_r);
 
+/* ---- colour images in (8-bit interleaved B, G, R or B, G, R, A; alpha is ignored) -------------------------------------- */
+
+/* The reference reads its images unchanged and rectifies them with all their channels; every consumer then makes its own grey
+ * image: cv::ORB, LSDDetectorC::detect and BinaryDescriptor::compute with COLOR_BGR2GRAY, the FLD branch with CV_RGB2GRAY on the
+ * same bytes (src/stereoFrame.cpp:249-258), which swaps the weights of channels 0 and 2.  weights: cvtColor's 8-bit integer form,
+ * (wb blue + wg green + wr red + 2^(s-1)) >> s with (1868, 9617, 4899), s = 14 (OpenCV 3.0 - 3.4.1) or (3735, 19235, 9798), s = 15
+ * (later releases); the two differ by one grey level on 43 864 of the 2^24 triples.  order: which colour channel 0 holds. */
+#define STVO_GRAY_Q14 0
+#define STVO_GRAY_Q15 1
+#define STVO_ORDER_BGR 0
+#define STVO_ORDER_RGB 1
+/* src [n][rows][cols][channels] -> gray [n][rows][cols] in the given order and, where gray_swapped is not NULL, the plane of the
+ * other order (red and blue weights swapped) from the same pass.  channels other than 3 and 4, a NULL src / gray, or a plane that
+ * overlaps the source or the other plane: STVO_ERR_INVALID_ARG.  Host buffers, synchronises. */
+int stvo_color_to_gray(stvo_ctx* ctx, int n, int rows, int cols, int channels, int order, int weights, const uint8_t* src, uint8_t* gray,
+                       uint8_t* gray_swapped);
+/* The same with DEVICE pointers of any alignment, enqueued on the context's stream (no synchronisation). */
+int stvo_color_to_gray_dev(stvo_ctx* ctx, int n, int rows, int cols, int channels, int order, int weights, const uint8_t* src,
+                           uint8_t* gray, uint8_t* gray_swapped);
+/* rectifyImagesLR on colour images: stvo_rectify_images with rows * cols * channels bytes per image, every channel remapped and
+ * rounded as a grey image is (a copy when dist is 0).  n > B, channels other than 3 and 4, a NULL pointer or a destination that
+ * overlaps a source or the other destination: STVO_ERR_INVALID_ARG.  Host buffers, synchronises. */
+int stvo_rectify_color_images(stvo_rectify* rect, int n, int channels, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l,
+                              uint8_t* dst_r);
+/* The same with DEVICE pointers, enqueued on the context's stream (no synchronisation). */
+int stvo_rectify_color_images_dev(stvo_rectify* rect, int n, int channels, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l,
+                                  uint8_t* dst_r);
+/* Raw colour pairs -> the grey planes of the rectified colour images in one kernel: every colour channel is remapped and rounded to
+ * 8 bits, then weighted; the rectified colour image is never written (with dist 0: the plain conversion).  gray_l / gray_r [n][rows]
+ * [cols] in the given order; swapped_l / swapped_r the other order, both or neither NULL.  DEVICE pointers, no synchronisation. */
+int stvo_rectify_color_to_gray_dev(stvo_rectify* rect, int n, int channels, int order, int weights, const uint8_t* src_l,
+                                   const uint8_t* src_r, uint8_t* gray_l, uint8_t* gray_r, uint8_t* swapped_l, uint8_t* swapped_r);
+
 /* ---- measurement helpers --------------------------------------------------------------------- */
 /* Times `iters` launches of the named kernel stage on the context's stream with hipEvents and
  * returns the average milliseconds per launch (used by bench.py for the roofline line).

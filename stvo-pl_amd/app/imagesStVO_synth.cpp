@@ -16,6 +16,9 @@
 // A sequence file that starts with "STVOIMG1" holds stereo IMAGES (n_frames, cols, rows, camera, then per frame the left and the
 // right 8-bit image): the loop then calls the reference's own entry points initialize / insertStereoPair(img_l, img_r, idx)
 // (include/stereoFrameHandler.h:44-45), whose ORB point front-end runs on the GPU (key-points only: no LSD / LBD here).
+// "STVOIMG2" is the same header followed by an int32 channels field (1, 3: B, G, R or 4: B, G, R, A), the images interleaved:
+// colour frames as Dataset::nextFrame reads them; the grey conversions of the reference's consumers and, with --dataset-params, the
+// rectification of the colour pair run on the GPU.  --gray-weights q14|q15 picks cvtColor's integer weight set (default q14).
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -108,6 +111,7 @@ int main(int argc, char** argv) {
     int mode = 0, max_frames = 0, frame_offset = 0, frame_step = 1;
     bool keyframes = false;
     bool device_pipeline = false, no_lines = false, tracks = false;
+    int gray_weights = STVO_GRAY_Q14;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--preset") && i + 1 < argc) preset = argv[++i];
         else if (!std::strcmp(argv[i], "-c") && i + 1 < argc) cfg = argv[++i];
@@ -118,6 +122,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--no-lines")) no_lines = true;
         else if (!std::strcmp(argv[i], "--tracks")) tracks = true;
         else if (!std::strcmp(argv[i], "--dataset-params") && i + 1 < argc) dataset_params = argv[++i];
+        else if (!std::strcmp(argv[i], "--gray-weights") && i + 1 < argc) gray_weights = std::strcmp(argv[++i], "q15") ? STVO_GRAY_Q14 : STVO_GRAY_Q15;
         else if (!std::strcmp(argv[i], "-o") && i + 1 < argc) frame_offset = std::atoi(argv[++i]);  // imagesStVO.cpp:158-159
         else if (!std::strcmp(argv[i], "-s") && i + 1 < argc) frame_step = std::atoi(argv[++i]);    // imagesStVO.cpp:162-163
     }
@@ -129,14 +134,19 @@ int main(int argc, char** argv) {
 
     std::ifstream in(argv[1], std::ios::binary);
     char magic[8];
-    int32_t n_frames = 0, cols = 0, rows = 0;
+    int32_t n_frames = 0, cols = 0, rows = 0, channels = 1;
     double camv[5];
-    if (!in || !rd(in, magic, 8) || (std::memcmp(magic, "STVOSEQ1", 8) != 0 && std::memcmp(magic, "STVOIMG1", 8) != 0) || !rd(in, &n_frames) ||
-        !rd(in, &cols) || !rd(in, &rows) || !rd(in, camv, 5)) {
+    if (!in || !rd(in, magic, 8) ||
+        (std::memcmp(magic, "STVOSEQ1", 8) != 0 && std::memcmp(magic, "STVOIMG1", 8) != 0 && std::memcmp(magic, "STVOIMG2", 8) != 0) ||
+        !rd(in, &n_frames) || !rd(in, &cols) || !rd(in, &rows) || !rd(in, camv, 5)) {
         std::cerr << "bad sequence file\n";
         return -1;
     }
-    const bool image_file = std::memcmp(magic, "STVOIMG1", 8) == 0;
+    const bool image_file = std::memcmp(magic, "STVOIMG", 7) == 0;
+    if (image_file && magic[7] == '2' && (!rd(in, &channels) || (channels != 1 && channels != 3 && channels != 4))) {
+        std::cerr << "bad sequence file: " << channels << " channels (1, 3 or 4)\n";
+        return -1;
+    }
     if (image_file && device_pipeline) {
         std::cerr << "--device-pipeline takes feature files; image files go through the handler" << std::endl;
         return -1;
@@ -304,6 +314,7 @@ int main(int argc, char** argv) {
         return -2;
     }
     StVO->mode = mode;
+    StVO->gray_weights = gray_weights;
     double t_total = 0.0, t_st = 0.0, t_ff = 0.0, t_po = 0.0;
     std::vector<double> t_all;
     // -o / -s / -n as the reference's Dataset applies them (src/dataset.cpp: skip `offset` frames, then take every `step`-th
@@ -316,7 +327,7 @@ int main(int argc, char** argv) {
         feat.img_rows = rows;
         std::vector<uint8_t> img_l, img_r;
         if (image_file) {
-            const size_t px = (size_t)cols * rows;
+            const size_t px = (size_t)cols * rows * channels;
             img_l.resize(px);
             img_r.resize(px);
             if (!rd(in, img_l.data(), px) || !rd(in, img_r.data(), px)) {
@@ -337,7 +348,7 @@ int main(int argc, char** argv) {
         ++frame_counter;
         ++n_done;
         if (image_file && !dataset_params.empty()) {  // cam->rectifyImagesLR(img_l, img_l, img_r, img_r), src/dataset.cpp:155
-            const GrayImage rl{img_l.data(), rows, cols, (size_t)cols}, rr{img_r.data(), rows, cols, (size_t)cols};
+            const Image rl{img_l.data(), rows, cols, channels, (size_t)cols * channels}, rr{img_r.data(), rows, cols, channels, (size_t)cols * channels};
             try {
                 cam_pin->rectifyImagesLR(rl, img_l, rr, img_r);
             } catch (const std::exception& e) {
@@ -345,7 +356,7 @@ int main(int argc, char** argv) {
                 return -2;
             }
         }
-        const GrayImage gl{img_l.data(), rows, cols, (size_t)cols}, gr{img_r.data(), rows, cols, (size_t)cols};
+        const Image gl{img_l.data(), rows, cols, channels, (size_t)cols * channels}, gr{img_r.data(), rows, cols, channels, (size_t)cols * channels};
         if (frame_counter == 0) {
             if (image_file) StVO->initialize(gl, gr, 0);  // initialize(img_l, img_r, 0), imagesStVO.cpp:90
             else StVO->initialize(feat, 0);

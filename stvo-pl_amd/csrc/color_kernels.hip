@@ -1,0 +1,416 @@
+// color_kernels.hip — 8-bit interleaved colour images (B, G, R or B, G, R, A) in: the grey planes the detectors read, and the
+// rectification of colour pairs (stvo_color_to_gray*, stvo_rectify_color_*).
+//
+// The reference reads its images unchanged and rectifies them with all their channels (src/dataset.cpp:147-157,
+// src/pinholeStereoCamera.cpp:196-208); every consumer then makes its own grey image: cv::ORB, LSDDetectorC::detect and
+// BinaryDescriptor::compute with COLOR_BGR2GRAY, the FLD branch with CV_RGB2GRAY on the same bytes (src/stereoFrame.cpp:249-258),
+// which swaps the weights of channels 0 and 2.  So one pass may write two planes: A with the requested order, B with the other one.
+//
+//   color_to_gray_kernel   the batch [n, rows, cols, ch] is one pixel stream.  One thread = 16 pixels: ch 16-byte loads, one 16-byte
+//                          store per plane; the thread after the last whole group does the tail (< 16 pixels) by bytes.  Needs the
+//                          source and the planes 16-byte aligned.
+//   color_to_gray_bytes    one thread = one pixel, byte loads and stores: bases that are not 16-byte aligned.
+//   rectify_color_kernel   rectify_remap_kernel's thread layout (4 consecutive output pixels, maps in registers, a loop over the
+//                          images of the block's chunk) and arithmetic ((X + 512) >> 10 per channel, a tap outside the source reads
+//                          0, the inside flag of map2) for ch channels.  GRAY = false writes the rectified colour image, which is
+//                          rectifyImagesLR on a colour Mat; GRAY = true rounds every colour channel to 8 bits as remap does, weights
+//                          them and writes the plane(s) only: the rectified colour image never reaches memory.
+//
+// Grey arithmetic (cvtColor's 8-bit integer form): (w0 c0 + w1 c1 + w2 c2 + 2^(shift-1)) >> shift with (blue, green, red) weights
+// (1868, 9617, 4899) and shift 14, the table form of OpenCV 3.0 - 3.4.1, or (3735, 19235, 9798) and shift 15 of the later releases.
+// The sum stays below 2^23 + 2^14, so 32-bit arithmetic is exact.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "ctx_internal.h"
+#include "rectify_internal.h"
+
+namespace {
+
+constexpr int COLOR_BLOCK = 256;
+constexpr int GROUP = 16;  // pixels per thread of the stream kernel
+constexpr uint32_t INSIDE = 0x8000u;
+
+struct GrayWeights {
+    uint32_t w0, w1, w2, rnd, shift;  // plane A; plane B swaps w0 and w2
+};
+
+__device__ __forceinline__ uint32_t weigh(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t w0, uint32_t w1, uint32_t w2,
+                                          const GrayWeights& w) {
+    return (w0 * c0 + w1 * c1 + w2 * c2 + w.rnd) >> w.shift;
+}
+
+template <int CH, bool TWO>
+__global__ void __launch_bounds__(COLOR_BLOCK) color_to_gray_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ pa,
+                                                                    uint8_t* __restrict__ pb, size_t npix, size_t ngroups,
+                                                                    GrayWeights w) {
+    const size_t g = (size_t)blockIdx.x * COLOR_BLOCK + threadIdx.x;
+    if (g < ngroups) {
+        const uint4* s = reinterpret_cast<const uint4*>(src) + g * CH;
+        uint32_t d[4 * CH];
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+            const uint4 v = s[k];
+            d[4 * k] = v.x; d[4 * k + 1] = v.y; d[4 * k + 2] = v.z; d[4 * k + 3] = v.w;
+        }
+        uint32_t a[4] = {0u, 0u, 0u, 0u}, b[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < GROUP; ++k) {
+            const int j = k * CH;
+            const uint32_t c0 = (d[j >> 2] >> ((j & 3) * 8)) & 0xffu;
+            const uint32_t c1 = (d[(j + 1) >> 2] >> (((j + 1) & 3) * 8)) & 0xffu;
+            const uint32_t c2 = (d[(j + 2) >> 2] >> (((j + 2) & 3) * 8)) & 0xffu;
+            a[k >> 2] |= weigh(c0, c1, c2, w.w0, w.w1, w.w2, w) << ((k & 3) * 8);
+            if (TWO) b[k >> 2] |= weigh(c0, c1, c2, w.w2, w.w1, w.w0, w) << ((k & 3) * 8);
+        }
+        reinterpret_cast<uint4*>(pa)[g] = make_uint4(a[0], a[1], a[2], a[3]);
+        if (TWO) reinterpret_cast<uint4*>(pb)[g] = make_uint4(b[0], b[1], b[2], b[3]);
+    } else if (g == ngroups) {  // the tail
+        for (size_t p = ngroups * GROUP; p < npix; ++p) {
+            const uint8_t* s = src + p * CH;
+            pa[p] = (uint8_t)weigh(s[0], s[1], s[2], w.w0, w.w1, w.w2, w);
+            if (TWO) pb[p] = (uint8_t)weigh(s[0], s[1], s[2], w.w2, w.w1, w.w0, w);
+        }
+    }
+}
+
+template <int CH, bool TWO>
+__global__ void __launch_bounds__(COLOR_BLOCK) color_to_gray_bytes(const uint8_t* __restrict__ src, uint8_t* __restrict__ pa,
+                                                                   uint8_t* __restrict__ pb, size_t npix, GrayWeights w) {
+    const size_t p = (size_t)blockIdx.x * COLOR_BLOCK + threadIdx.x;
+    if (p >= npix) return;
+    const uint8_t* s = src + p * CH;
+    const uint32_t c0 = s[0], c1 = s[1], c2 = s[2];
+    pa[p] = (uint8_t)weigh(c0, c1, c2, w.w0, w.w1, w.w2, w);
+    if (TWO) pb[p] = (uint8_t)weigh(c0, c1, c2, w.w2, w.w1, w.w0, w);
+}
+
+__device__ __forceinline__ uint32_t blend(uint32_t s00, uint32_t s01, uint32_t s10, uint32_t s11, uint32_t m2) {
+    const uint32_t ax = m2 & 31u, ay = (m2 >> 5) & 31u;
+    const uint32_t top = __umul24(32u - ax, s00) + __umul24(ax, s01);
+    const uint32_t bot = __umul24(32u - ax, s10) + __umul24(ax, s11);
+    return (__umul24(32u - ay, top) + __umul24(ay, bot) + 512u) >> 10;
+}
+
+// The first NC channels of the pixel at p.  A 4-channel pixel is one (unaligned) 32-bit load: three byte loads per tap made the fused
+// kernel slower on B, G, R, A than remap-then-convert; a 3-channel pixel is read by bytes (a word would run past the last pixel).
+template <int CH, int NC>
+__device__ __forceinline__ void load_px(const uint8_t* __restrict__ p, uint32_t (&c)[NC]) {
+    if (CH == 4) {
+        uint32_t w;
+        __builtin_memcpy(&w, p, 4);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) c[k] = (w >> (8 * k)) & 0xffu;
+    } else {
+#pragma unroll
+        for (int k = 0; k < NC; ++k) c[k] = p[k];
+    }
+}
+
+template <int CH, int NC>
+__device__ __forceinline__ void tap_px(const uint8_t* __restrict__ S, int x, int y, int cols, int rows, uint32_t (&c)[NC]) {
+    if ((unsigned)x < (unsigned)cols && (unsigned)y < (unsigned)rows) {
+        load_px<CH, NC>(S + ((size_t)y * cols + x) * CH, c);
+    } else {
+#pragma unroll
+        for (int k = 0; k < NC; ++k) c[k] = 0u;
+    }
+}
+
+// src / dst: this side's first image; source images npx * CH bytes apart.  GRAY = false: dst holds colour images (npx * CH bytes
+// apart), dstb unused.  GRAY = true: dst is plane A, dstb plane B or NULL (both sides), images npx bytes apart.
+template <int CH, bool GRAY>
+__global__ void __launch_bounds__(COLOR_BLOCK) rectify_color_kernel(const int4* __restrict__ map1q_l, const uint2* __restrict__ map2q_l,
+                                                                    const int4* __restrict__ map1q_r, const uint2* __restrict__ map2q_r,
+                                                                    const uint8_t* __restrict__ src_l, const uint8_t* __restrict__ src_r,
+                                                                    uint8_t* __restrict__ dst_l, uint8_t* __restrict__ dst_r,
+                                                                    uint8_t* __restrict__ dstb_l, uint8_t* __restrict__ dstb_r, int n,
+                                                                    int per_chunk, int cols, int rows, int nquads, GrayWeights w) {
+    constexpr int NC = GRAY ? 3 : CH;  // channels computed: the grey planes never read alpha
+    const int q = blockIdx.x * COLOR_BLOCK + threadIdx.x;
+    if (q >= nquads) return;
+    const bool right = blockIdx.z != 0;
+    const int i0 = blockIdx.y * per_chunk;
+    const int i1 = min(n, i0 + per_chunk);
+    if (i0 >= i1) return;
+    const int4 m1 = (right ? map1q_r : map1q_l)[q];
+    const uint2 m2v = (right ? map2q_r : map2q_l)[q];
+    const uint8_t* src = right ? src_r : src_l;
+    uint8_t* dst = right ? dst_r : dst_l;
+    uint8_t* dstb = right ? dstb_r : dstb_l;
+    const size_t npx = (size_t)cols * rows;
+    const size_t p0 = (size_t)q * 4;
+    const size_t row_b = (size_t)cols * CH;
+    const int m1s[4] = {m1.x, m1.y, m1.z, m1.w};
+    const uint32_t m2s[4] = {m2v.x & 0xffffu, m2v.x >> 16, m2v.y & 0xffffu, m2v.y >> 16};
+    bool all_inside = true;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) all_inside = all_inside && (m2s[k] & INSIDE);
+    const bool full = p0 + 4 <= npx;
+    for (int i = i0; i < i1; ++i) {
+        const uint8_t* S = src + (size_t)i * npx * CH;
+        uint32_t v[4][NC];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int x = (int)(int16_t)(m1s[k] & 0xffff), y = m1s[k] >> 16;
+            uint32_t t00[NC], t01[NC], t10[NC], t11[NC];
+            if (all_inside) {
+                const uint8_t* s = S + ((size_t)y * cols + x) * CH;
+                load_px<CH, NC>(s, t00);
+                load_px<CH, NC>(s + CH, t01);
+                load_px<CH, NC>(s + row_b, t10);
+                load_px<CH, NC>(s + row_b + CH, t11);
+            } else {
+                tap_px<CH, NC>(S, x, y, cols, rows, t00);
+                tap_px<CH, NC>(S, x + 1, y, cols, rows, t01);
+                tap_px<CH, NC>(S, x, y + 1, cols, rows, t10);
+                tap_px<CH, NC>(S, x + 1, y + 1, cols, rows, t11);
+            }
+#pragma unroll
+            for (int c = 0; c < NC; ++c) v[k][c] = blend(t00[c], t01[c], t10[c], t11[c], m2s[k]);
+        }
+        if (GRAY) {
+            uint8_t* D = dst + (size_t)i * npx + p0;
+            uint32_t ga[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ga[k] = weigh(v[k][0], v[k][1], v[k][2], w.w0, w.w1, w.w2, w);
+            if (full && ((reinterpret_cast<uintptr_t>(D) & 3) == 0)) {
+                *reinterpret_cast<uint32_t*>(D) = ga[0] | (ga[1] << 8) | (ga[2] << 16) | (ga[3] << 24);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (p0 + k < npx) D[k] = (uint8_t)ga[k];
+            }
+            if (dstb) {
+                uint8_t* E = dstb + (size_t)i * npx + p0;
+                uint32_t gb[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) gb[k] = weigh(v[k][0], v[k][1], v[k][2], w.w2, w.w1, w.w0, w);
+                if (full && ((reinterpret_cast<uintptr_t>(E) & 3) == 0)) {
+                    *reinterpret_cast<uint32_t*>(E) = gb[0] | (gb[1] << 8) | (gb[2] << 16) | (gb[3] << 24);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (p0 + k < npx) E[k] = (uint8_t)gb[k];
+                }
+            }
+        } else {
+            uint8_t* D = dst + ((size_t)i * npx + p0) * CH;
+            if (full && ((reinterpret_cast<uintptr_t>(D) & 3) == 0)) {
+                uint32_t o[CH] = {};
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+                        const int j = k * CH + c;
+                        o[j >> 2] |= v[k][c] << ((j & 3) * 8);
+                    }
+#pragma unroll
+                for (int c = 0; c < CH; ++c) reinterpret_cast<uint32_t*>(D)[c] = o[c];
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (p0 + k < npx) {
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) D[k * CH + c] = (uint8_t)v[k][c];
+                    }
+            }
+        }
+    }
+}
+
+bool gray_weights(int order, int weights, GrayWeights* w) {
+    uint32_t blue, green, red;
+    if (weights == STVO_GRAY_Q14) {
+        blue = 1868u; green = 9617u; red = 4899u; w->shift = 14u;
+    } else if (weights == STVO_GRAY_Q15) {
+        blue = 3735u; green = 19235u; red = 9798u; w->shift = 15u;
+    } else
+        return false;
+    if (order != STVO_ORDER_BGR && order != STVO_ORDER_RGB) return false;
+    w->w0 = order == STVO_ORDER_BGR ? blue : red;
+    w->w1 = green;
+    w->w2 = order == STVO_ORDER_BGR ? red : blue;
+    w->rnd = 1u << (w->shift - 1u);
+    return true;
+}
+
+template <int CH>
+void launch_gray_ch(hipStream_t st, const uint8_t* src, uint8_t* pa, uint8_t* pb, size_t npix, const GrayWeights& w) {
+    const bool aligned = (((uintptr_t)src | (uintptr_t)pa | (uintptr_t)pb) & 15) == 0;
+    if (aligned) {
+        const size_t ngroups = npix / GROUP;
+        const unsigned blocks = (unsigned)((ngroups + 1 + COLOR_BLOCK - 1) / COLOR_BLOCK);
+        if (pb)
+            hipLaunchKernelGGL((color_to_gray_kernel<CH, true>), dim3(blocks), dim3(COLOR_BLOCK), 0, st, src, pa, pb, npix, ngroups, w);
+        else
+            hipLaunchKernelGGL((color_to_gray_kernel<CH, false>), dim3(blocks), dim3(COLOR_BLOCK), 0, st, src, pa, pb, npix, ngroups, w);
+    } else {
+        const unsigned blocks = (unsigned)((npix + COLOR_BLOCK - 1) / COLOR_BLOCK);
+        if (pb)
+            hipLaunchKernelGGL((color_to_gray_bytes<CH, true>), dim3(blocks), dim3(COLOR_BLOCK), 0, st, src, pa, pb, npix, w);
+        else
+            hipLaunchKernelGGL((color_to_gray_bytes<CH, false>), dim3(blocks), dim3(COLOR_BLOCK), 0, st, src, pa, pb, npix, w);
+    }
+}
+
+// pixel counts the one-dimensional grids hold: the byte kernel has one thread per pixel
+constexpr size_t MAX_STREAM_PIXELS = (size_t)0x7fffffffu * COLOR_BLOCK;
+
+int launch_gray(stvo_ctx* ctx, int ch, const uint8_t* src, uint8_t* pa, uint8_t* pb, size_t npix, const GrayWeights& w) {
+    if (ch == 3)
+        launch_gray_ch<3>(ctx->stream, src, pa, pb, npix, w);
+    else
+        launch_gray_ch<4>(ctx->stream, src, pa, pb, npix, w);
+    return check_launch(ctx);
+}
+
+int check_gray(int n, int rows, int cols, int ch, const uint8_t* src, const uint8_t* pa, const uint8_t* pb, size_t* npix) {
+    if (n <= 0 || rows <= 0 || cols <= 0 || (ch != 3 && ch != 4) || !src || !pa) return STVO_ERR_INVALID_ARG;
+    const size_t px = (size_t)n * rows * cols;
+    if (px > MAX_STREAM_PIXELS) return STVO_ERR_CAPACITY;
+    if (overlaps(src, px * ch, pa, px) || (pb && (overlaps(src, px * ch, pb, px) || overlaps(pa, px, pb, px)))) return STVO_ERR_INVALID_ARG;
+    *npix = px;
+    return STVO_OK;
+}
+
+template <int CH, bool GRAY>
+void launch_rect_ch(stvo_rectify* r, int n, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l, uint8_t* dst_r, uint8_t* dstb_l,
+                    uint8_t* dstb_r, const GrayWeights& w) {
+    // image chunks as launch_remap's: enough blocks to fill 256 CUs a few times over, at least 4 images per thread where n allows
+    const int bx = (r->nquads + COLOR_BLOCK - 1) / COLOR_BLOCK;
+    const int want = std::max(1, (256 * 8 + 2 * bx - 1) / (2 * bx));
+    const int chunks = std::max(1, std::min(want, (n + 3) / 4));
+    const int per_chunk = (n + chunks - 1) / chunks;
+    const int gy = (n + per_chunk - 1) / per_chunk;
+    hipLaunchKernelGGL((rectify_color_kernel<CH, GRAY>), dim3(bx, gy, 2), dim3(COLOR_BLOCK), 0, r->ctx->stream, r->map1q(0), r->map2q(0),
+                       r->map1q(1), r->map2q(1), src_l, src_r, dst_l, dst_r, dstb_l, dstb_r, n, per_chunk, r->cols, r->rows, r->nquads, w);
+}
+
+int check_color_images(const stvo_rectify* r, int n, int ch, const uint8_t* src_l, const uint8_t* src_r, const uint8_t* dst_l,
+                       const uint8_t* dst_r) {
+    if (!r || !src_l || !src_r || !dst_l || !dst_r || n <= 0 || n > r->B || (ch != 3 && ch != 4)) return STVO_ERR_INVALID_ARG;
+    const size_t bytes = (size_t)n * r->cols * r->rows * ch;
+    if (overlaps(dst_l, src_l, bytes) || overlaps(dst_l, src_r, bytes) || overlaps(dst_r, src_l, bytes) || overlaps(dst_r, src_r, bytes) ||
+        overlaps(dst_l, dst_r, bytes))
+        return STVO_ERR_INVALID_ARG;
+    return STVO_OK;
+}
+
+int launch_color_remap(stvo_rectify* r, int n, int ch, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l, uint8_t* dst_r) {
+    stvo_ctx* ctx = r->ctx;
+    if (!r->cam.dist) {  // the reference copies (copyTo)
+        const size_t bytes = (size_t)n * r->cols * r->rows * ch;
+        HIP_TRY(ctx, hipMemcpyAsync(dst_l, src_l, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(dst_r, src_r, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        return STVO_OK;
+    }
+    const GrayWeights none{};
+    if (ch == 3)
+        launch_rect_ch<3, false>(r, n, src_l, src_r, dst_l, dst_r, nullptr, nullptr, none);
+    else
+        launch_rect_ch<4, false>(r, n, src_l, src_r, dst_l, dst_r, nullptr, nullptr, none);
+    return check_launch(ctx);
+}
+
+}  // namespace
+
+extern "C" {
+
+int stvo_color_to_gray_dev(stvo_ctx* ctx, int n, int rows, int cols, int channels, int order, int weights, const uint8_t* src,
+                           uint8_t* gray, uint8_t* gray_swapped) {
+    GrayWeights w;
+    size_t npix = 0;
+    if (!ctx || !gray_weights(order, weights, &w)) return STVO_ERR_INVALID_ARG;
+    TRY(check_gray(n, rows, cols, channels, src, gray, gray_swapped, &npix));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return launch_gray(ctx, channels, src, gray, gray_swapped, npix, w);
+}
+
+int stvo_color_to_gray(stvo_ctx* ctx, int n, int rows, int cols, int channels, int order, int weights, const uint8_t* src, uint8_t* gray,
+                       uint8_t* gray_swapped) {
+    GrayWeights w;
+    size_t npix = 0;
+    if (!ctx || !gray_weights(order, weights, &w)) return STVO_ERR_INVALID_ARG;
+    TRY(check_gray(n, rows, cols, channels, src, gray, gray_swapped, &npix));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // staging: the colour batch, then one or two planes (256-byte aligned each)
+    const size_t in_bytes = (npix * channels + 255) & ~(size_t)255, plane = (npix + 255) & ~(size_t)255;
+    uint8_t* io = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&io, in_bytes + 2 * plane));
+    uint8_t *da = io + in_bytes, *db = gray_swapped ? da + plane : nullptr;
+    int rc = STVO_ERR_HIP;
+    if (hip_ok(ctx, hipMemcpyAsync(io, src, npix * channels, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync colour images") &&
+        (rc = launch_gray(ctx, channels, io, da, db, npix, w)) == STVO_OK) {
+        rc = STVO_ERR_HIP;
+        if (hip_ok(ctx, hipMemcpyAsync(gray, da, npix, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync grey plane") &&
+            (!db || hip_ok(ctx, hipMemcpyAsync(gray_swapped, db, npix, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync grey plane")) &&
+            hip_ok(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
+            rc = STVO_OK;
+    }
+    if (rc != STVO_OK) (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(io);
+    return rc;
+}
+
+int stvo_rectify_color_images_dev(stvo_rectify* r, int n, int channels, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l,
+                                  uint8_t* dst_r) {
+    TRY(check_color_images(r, n, channels, src_l, src_r, dst_l, dst_r));
+    HIP_TRY(r->ctx, hipSetDevice(r->ctx->device));
+    return launch_color_remap(r, n, channels, src_l, src_r, dst_l, dst_r);
+}
+
+int stvo_rectify_color_images(stvo_rectify* r, int n, int channels, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l,
+                              uint8_t* dst_r) {
+    TRY(check_color_images(r, n, channels, src_l, src_r, dst_l, dst_r));
+    stvo_ctx* ctx = r->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n * r->cols * r->rows * channels, side = (bytes + 255) & ~(size_t)255;
+    uint8_t* io = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&io, 4 * side));
+    uint8_t *sl = io, *sr = io + side, *dl = io + 2 * side, *dr = io + 3 * side;
+    int rc = STVO_ERR_HIP;
+    if (hip_ok(ctx, hipMemcpyAsync(sl, src_l, bytes, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync colour images") &&
+        hip_ok(ctx, hipMemcpyAsync(sr, src_r, bytes, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync colour images") &&
+        (rc = launch_color_remap(r, n, channels, sl, sr, dl, dr)) == STVO_OK) {
+        rc = STVO_ERR_HIP;
+        if (hip_ok(ctx, hipMemcpyAsync(dst_l, dl, bytes, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync rectified images") &&
+            hip_ok(ctx, hipMemcpyAsync(dst_r, dr, bytes, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync rectified images") &&
+            hip_ok(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
+            rc = STVO_OK;
+    }
+    if (rc != STVO_OK) (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(io);
+    return rc;
+}
+
+int stvo_rectify_color_to_gray_dev(stvo_rectify* r, int n, int channels, int order, int weights, const uint8_t* src_l, const uint8_t* src_r,
+                                   uint8_t* gray_l, uint8_t* gray_r, uint8_t* swapped_l, uint8_t* swapped_r) {
+    GrayWeights w;
+    if (!r || !src_l || !src_r || !gray_l || !gray_r || n <= 0 || n > r->B || (channels != 3 && channels != 4) ||
+        (swapped_l == nullptr) != (swapped_r == nullptr) || !gray_weights(order, weights, &w))
+        return STVO_ERR_INVALID_ARG;
+    const size_t px = (size_t)n * r->cols * r->rows, sb = px * channels;
+    const uint8_t* planes[4] = {gray_l, gray_r, swapped_l, swapped_r};
+    const int np = swapped_l ? 4 : 2;
+    for (int a = 0; a < np; ++a) {
+        if (overlaps(planes[a], px, src_l, sb) || overlaps(planes[a], px, src_r, sb)) return STVO_ERR_INVALID_ARG;
+        for (int b = a + 1; b < np; ++b)
+            if (overlaps(planes[a], planes[b], px)) return STVO_ERR_INVALID_ARG;
+    }
+    stvo_ctx* ctx = r->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!r->cam.dist) {  // the reference's copy, then the consumers' conversion: the plain conversion of each side
+        TRY(launch_gray(ctx, channels, src_l, gray_l, swapped_l, px, w));
+        return launch_gray(ctx, channels, src_r, gray_r, swapped_r, px, w);
+    }
+    if (channels == 3)
+        launch_rect_ch<3, true>(r, n, src_l, src_r, gray_l, gray_r, swapped_l, swapped_r, w);
+    else
+        launch_rect_ch<4, true>(r, n, src_l, src_r, gray_l, gray_r, swapped_l, swapped_r, w);
+    return check_launch(ctx);
+}
+
+}  // extern "C"

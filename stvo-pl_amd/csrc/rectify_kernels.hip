@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "ctx_internal.h"
+#include "rectify_internal.h"
 
 namespace {
 
@@ -98,22 +99,7 @@ __global__ void __launch_bounds__(RECT_BLOCK) rectify_remap_kernel(const int4* _
     }
 }
 
-bool overlaps(const void* a, const void* b, size_t bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bytes && y < x + bytes;
-}
-
 }  // namespace
-
-struct stvo_rectify {
-    stvo_ctx* ctx = nullptr;
-    int B = 0, cols = 0, rows = 0, nquads = 0;
-    stvo_rect_camera cam{};
-    char* dev = nullptr;  // [side][nquads] int4 map1, then [side][nquads] uint2 map2 (dist = 1 only)
-    uint8_t* io = nullptr;  // staging of the host-buffer entry point: 2 B source images, 2 B destinations (lazy)
-    int4* map1q(int side) const { return reinterpret_cast<int4*>(dev) + (size_t)side * nquads; }
-    uint2* map2q(int side) const { return reinterpret_cast<uint2*>(dev + (size_t)2 * nquads * sizeof(int4)) + (size_t)side * nquads; }
-};
 
 namespace {
 

@@ -170,4 +170,30 @@ void PinholeStereoCamera::rectifyImage(const GrayImage& img_src, std::vector<uin
     rectifyImagesLR(img_src, img_rec, img_src, unused);
 }
 
+// Colour images: cv::remap works on every channel of the Mat, each rounded to 8 bits on its own (stvo_rectify_color_images).
+void PinholeStereoCamera::rectifyImagesLR(const Image& src_l, std::vector<uint8_t>& dst_l, const Image& src_r, std::vector<uint8_t>& dst_r) const {
+    if (src_l.channels == 1 && src_r.channels == 1) return rectifyImagesLR(src_l.gray(), dst_l, src_r.gray(), dst_r);
+    const int ch = src_l.channels;
+    if (src_l.rows != height || src_l.cols != width || src_r.rows != height || src_r.cols != width || src_l.empty() || src_r.empty() ||
+        src_r.channels != ch || (ch != 3 && ch != 4))
+        throw std::invalid_argument("[PinholeStereoCamera] rectifyImagesLR: images must be width x height with 1, 3 or 4 channels, both alike");
+    ensure_rectifier();
+    const size_t row = (size_t)width * ch, bytes = row * height;
+    std::vector<uint8_t> in(2 * bytes), out(2 * bytes);  // contiguous copies, as above
+    for (int s = 0; s < 2; ++s) {
+        const Image& g = s ? src_r : src_l;
+        const size_t step = g.step ? g.step : row;
+        for (int y = 0; y < height; ++y) std::memcpy(in.data() + s * bytes + (size_t)y * row, g.data + y * step, row);
+    }
+    const int rc = stvo_rectify_color_images(rectifier, 1, ch, in.data(), in.data() + bytes, out.data(), out.data() + bytes);
+    if (rc != STVO_OK) throw std::runtime_error(std::string("[PinholeStereoCamera] stvo_rectify_color_images: ") + stvo_error_string(rc));
+    dst_l.assign(out.begin(), out.begin() + bytes);
+    dst_r.assign(out.begin() + bytes, out.end());
+}
+
+void PinholeStereoCamera::rectifyImage(const Image& img_src, std::vector<uint8_t>& img_rec) const {
+    std::vector<uint8_t> unused;
+    rectifyImagesLR(img_src, img_rec, img_src, unused);
+}
+
 }  // namespace StVO

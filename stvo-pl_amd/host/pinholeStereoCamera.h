@@ -58,6 +58,10 @@ public:
     void rectifyImage(const GrayImage& img_src, std::vector<uint8_t>& img_rec) const;
     void rectifyImagesLR(const GrayImage& img_src_l, std::vector<uint8_t>& img_rec_l, const GrayImage& img_src_r,
                          std::vector<uint8_t>& img_rec_r) const;
+    // The same on colour images (3 or 4 interleaved channels, every channel remapped; one channel forwards to the overloads above):
+    // dst is resized to width * height * channels.
+    void rectifyImage(const Image& img_src, std::vector<uint8_t>& img_rec) const;
+    void rectifyImagesLR(const Image& img_src_l, std::vector<uint8_t>& img_rec_l, const Image& img_src_r, std::vector<uint8_t>& img_rec_r) const;
 
 private:
     void ensure_rectifier() const;

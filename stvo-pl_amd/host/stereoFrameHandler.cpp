@@ -88,12 +88,46 @@ FrameFeatures StereoFrameHandler::detectStereoFeatures(const GrayImage& img_l, c
         const size_t step = im[s]->step ? im[s]->step : (size_t)im[s]->cols;
         for (int r = 0; r < im[s]->rows; ++r) std::memcpy(pair.data() + s * px + (size_t)r * im[s]->cols, im[s]->data + r * step, (size_t)im[s]->cols);
     }
-    if (Config::hasLines()) detectStereoLines(pair.data(), img_l.cols, img_l.rows, feat);  // src/stereoFrame.cpp:191-203
-    if (!Config::hasPoints()) return feat;  // src/stereoFrame.cpp:106
+    detectOnPlanes(pair.data(), pair.data(), feat);
+    return feat;
+}
+
+// Colour frames: both images gathered into one [2][rows][cols][channels] batch, one launch for the grey plane every consumer but
+// FLD reads and, with use_fld_lines, the plane with the red and blue weights swapped that the FLD branch hands to FLD and LBD.
+FrameFeatures StereoFrameHandler::detectStereoFeatures(const Image& img_l, const Image& img_r) {
+    if (img_l.channels == 1 && img_r.channels == 1) return detectStereoFeatures(img_l.gray(), img_r.gray());
+    const int ch = img_l.channels;
+    if (img_l.empty() || img_r.empty() || img_l.rows != img_r.rows || img_l.cols != img_r.cols || img_r.channels != ch || (ch != 3 && ch != 4))
+        throw std::runtime_error("[StVO-HIP] detectStereoFeatures: two non-empty 8-bit images of one size with 1, 3 or 4 channels expected");
+    FrameFeatures feat;
+    feat.img_cols = img_l.cols;
+    feat.img_rows = img_l.rows;
+    const size_t px = (size_t)img_l.rows * img_l.cols, row = (size_t)img_l.cols * ch;
+    std::vector<uint8_t> color(2 * px * ch), bgr(2 * px), rgb;
+    const Image* im[2] = {&img_l, &img_r};
+    for (int s = 0; s < 2; ++s) {
+        const size_t step = im[s]->step ? im[s]->step : row;
+        for (int r = 0; r < im[s]->rows; ++r) std::memcpy(color.data() + s * px * ch + (size_t)r * row, im[s]->data + r * step, row);
+    }
+    const bool swapped = Config::hasLines() && Config::useFLDLines();
+    if (swapped) rgb.resize(2 * px);
+    check(stvo_color_to_gray(ctx, 2, img_l.rows, img_l.cols, ch, STVO_ORDER_BGR, gray_weights, color.data(), bgr.data(),
+                             swapped ? rgb.data() : nullptr),
+          "stvo_color_to_gray", ctx);
+    detectOnPlanes(bgr.data(), swapped ? rgb.data() : bgr.data(), feat);
+    return feat;
+}
+
+// pair: what ORB reads, pair_lines: what the line detector and LBD read (the same plane but for colour frames with use_fld_lines);
+// both [2][rows][cols] of feat.img_rows x feat.img_cols.
+void StereoFrameHandler::detectOnPlanes(const uint8_t* pair_points, const uint8_t* pair_lines, FrameFeatures& feat) {
+    const int cols = feat.img_cols, rows = feat.img_rows;
+    if (Config::hasLines()) detectStereoLines(pair_lines, cols, rows, feat);  // src/stereoFrame.cpp:191-203
+    if (!Config::hasPoints()) return;  // src/stereoFrame.cpp:106
     const int K = 4096;  // capacity per image: orb_nfeatures plus the ties at the cut
     // fast_th == 0 means "the configured threshold" (src/stereoFrame.cpp:109-112), otherwise the adaptive one; cv::FAST's range
     const int fast_th = std::min(254, std::max(1, orb_fast_th == 0 ? Config::orbFastTh() : orb_fast_th));
-    if (orb && (orb_cols != img_l.cols || orb_rows != img_l.rows)) {
+    if (orb && (orb_cols != cols || orb_rows != rows)) {
         stvo_orb_destroy(orb);
         orb = nullptr;
     }
@@ -104,9 +138,9 @@ FrameFeatures StereoFrameHandler::detectStereoFeatures(const GrayImage& img_l, c
         prm.edge_threshold = Config::orbEdgeTh();
         prm.nlevels = Config::orbNLevels();
         prm.scale_factor = Config::orbScaleFactor();
-        check(stvo_orb_create(ctx, 2, img_l.cols, img_l.rows, K, &prm, &orb), "stvo_orb_create", ctx);
-        orb_cols = img_l.cols;
-        orb_rows = img_l.rows;
+        check(stvo_orb_create(ctx, 2, cols, rows, K, &prm, &orb), "stvo_orb_create", ctx);
+        orb_cols = cols;
+        orb_rows = rows;
     }
     check(stvo_orb_set_fast_threshold(orb, fast_th), "stvo_orb_set_fast_threshold", ctx);
     check(stvo_orb_set_score_type(orb, Config::orbScore()), "stvo_orb_set_score_type", ctx);  // src/stereoFrame.cpp:112-114
@@ -114,7 +148,7 @@ FrameFeatures StereoFrameHandler::detectStereoFeatures(const GrayImage& img_l, c
     std::vector<int32_t> oct((size_t)2 * K);
     std::vector<uint8_t> desc((size_t)2 * K * 32);
     int32_t n[2] = {0, 0}, nt[2] = {0, 0};
-    check(stvo_orb_detect_levels(orb, pair.data(), kp.data(), resp.data(), ang.data(), oct.data(), desc.data(), n, nt), "stvo_orb_detect_levels", ctx);
+    check(stvo_orb_detect_levels(orb, pair_points, kp.data(), resp.data(), ang.data(), oct.data(), desc.data(), n, nt), "stvo_orb_detect_levels", ctx);
     for (int s = 0; s < 2; ++s) {
         if (nt[s] > n[s])  // more key-points qualified than the front-end's per-image capacity: not silently
             std::fprintf(stderr, "[StVO-HIP] detectStereoFeatures: %d of %d key-points of the %s image dropped at the capacity of %d\n",
@@ -128,7 +162,6 @@ FrameFeatures StereoFrameHandler::detectStereoFeatures(const GrayImage& img_l, c
             dm.push_back_row(desc.data() + k * 32);
         }
     }
-    return feat;
 }
 
 // StereoFrame::detectStereoLineSegments (src/stereoFrame.cpp:191-203) -> detectLineFeatures (:207-303) for both images of the
@@ -206,6 +239,15 @@ void StereoFrameHandler::initialize(const GrayImage& img_l, const GrayImage& img
 }
 
 void StereoFrameHandler::insertStereoPair(const GrayImage& img_l, const GrayImage& img_r, const int idx_) {
+    insertStereoPair(detectStereoFeatures(img_l, img_r), idx_);
+}
+
+void StereoFrameHandler::initialize(const Image& img_l, const Image& img_r, const int idx_) {
+    orb_fast_th = Config::orbFastTh();
+    initialize(detectStereoFeatures(img_l, img_r), idx_);
+}
+
+void StereoFrameHandler::insertStereoPair(const Image& img_l, const Image& img_r, const int idx_) {
     insertStereoPair(detectStereoFeatures(img_l, img_r), idx_);
 }
 

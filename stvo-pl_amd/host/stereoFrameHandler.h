@@ -28,7 +28,16 @@ public:
     void initialize(const GrayImage& img_l, const GrayImage& img_r, const int idx_);
     void insertStereoPair(const GrayImage& img_l, const GrayImage& img_r, const int idx_);
     void detectStereoLines(const uint8_t* pair, int cols, int rows, FrameFeatures& feat);
+    void detectOnPlanes(const uint8_t* pair_points, const uint8_t* pair_lines, FrameFeatures& feat);
     FrameFeatures detectStereoFeatures(const GrayImage& img_l, const GrayImage& img_r);
+    // Colour frames as the reference's loop takes them (8-bit B, G, R or B, G, R, A; one channel forwards to the overloads above):
+    // the grey images its consumers make for themselves are made on the GPU (stvo_color_to_gray) — COLOR_BGR2GRAY for cv::ORB,
+    // LSD and LBD; with use_fld_lines the key-lines and their descriptors read CV_RGB2GRAY of the same bytes instead
+    // (src/stereoFrame.cpp:249-258,303).
+    void initialize(const Image& img_l, const Image& img_r, const int idx_);
+    void insertStereoPair(const Image& img_l, const Image& img_r, const int idx_);
+    FrameFeatures detectStereoFeatures(const Image& img_l, const Image& img_r);
+    int gray_weights = STVO_GRAY_Q14;  // cvtColor's integer weights: STVO_GRAY_Q14 (OpenCV 3.0 - 3.4.1) or STVO_GRAY_Q15 (later)
     void updateFrame();
 
     void f2fTracking();

@@ -66,4 +66,14 @@ struct GrayImage {
     bool empty() const { return data == nullptr || rows <= 0 || cols <= 0; }
 };
 
+// cv::Mat as Dataset::nextFrame reads it (CV_LOAD_IMAGE_UNCHANGED): 8-bit, 1 channel (grey), 3 (B, G, R) or 4 (B, G, R, A)
+// interleaved, rows x cols x channels bytes, `step` bytes from row to row
+struct Image {
+    const uint8_t* data = nullptr;
+    int rows = 0, cols = 0, channels = 1;
+    size_t step = 0;  // 0: rows are contiguous (step == cols * channels)
+    bool empty() const { return data == nullptr || rows <= 0 || cols <= 0; }
+    GrayImage gray() const { return GrayImage{data, rows, cols, step}; }  // channels == 1 only
+};
+
 }  // namespace StVO

@@ -31,7 +31,9 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_rectify_images_dev", "stvo_orb_set_fast_thresholds", "stvo_orb_set_fast_thresholds_dev", "stvo_fast_adapt_dev",
            "stvo_seq_adapt_fast_dev", "stvo_traj_init_dev", "stvo_traj_update_dev", "stvo_seq_set_trajectory", "stvo_seq_read_trajectory",
            "stvo_seq_trajectory_state_dev", "stvo_seq_read_trajectory_state", "stvo_seq_control_next_step", "stvo_seq_restart_fast_dev",
-           "stvo_seq_set_tracks", "stvo_seq_read_tracks", "stvo_seq_tracks_dev", "stvo_seq_keyframe_headers", "stvo_seq_read_keyframe"]
+           "stvo_seq_set_tracks", "stvo_seq_read_tracks", "stvo_seq_tracks_dev", "stvo_seq_keyframe_headers", "stvo_seq_read_keyframe",
+           "stvo_color_to_gray", "stvo_color_to_gray_dev", "stvo_rectify_color_images", "stvo_rectify_color_images_dev",
+           "stvo_rectify_color_to_gray_dev"]
 
 SEQ_NSTAGE = 5  # include/stvo_hip.h: STVO_SEQ_NSTAGE
 SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_check", "pose")
@@ -267,6 +269,11 @@ def load():
     L.stvo_rectify_camera.argtypes = [C.c_void_p, C.POINTER(RectCamera)]
     L.stvo_rectify_images.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
     L.stvo_rectify_images_dev.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    L.stvo_color_to_gray.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3
+    L.stvo_color_to_gray_dev.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3
+    L.stvo_rectify_color_images.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+    L.stvo_rectify_color_images_dev.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+    L.stvo_rectify_color_to_gray_dev.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 6
     L.stvo_seq_push.argtypes = [C.c_void_p, C.POINTER(FrameFeatures), C.c_void_p, i32p]
     L.stvo_seq_upload.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameFeatures)]
     L.stvo_seq_upload_dev.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameFeatures)]
@@ -1045,6 +1052,35 @@ def rectify_compute(calib, maps=True):
     return (camera_dict(rc), m1, m2) if maps else camera_dict(rc)
 
 
+GRAY_WEIGHTS = {"q14": 0, "q15": 1}  # include/stvo_hip.h: STVO_GRAY_*
+GRAY_ORDERS = {"bgr": 0, "rgb": 1}    # STVO_ORDER_*
+
+
+def color_to_gray(ctx, img, order="bgr", weights="q14", swapped=False):
+    """Host colour images uint8 [n, rows, cols, ch] (or [rows, cols, ch]), ch = 3 (B, G, R) or 4 (B, G, R, A) -> the grey plane(s)
+    uint8 [n, rows, cols] of cvtColor's integer form (stvo_color_to_gray, synchronous).  swapped: also the plane with the red and
+    blue weights exchanged, from the same launch: returns (plane, swapped plane)."""
+    img = np.ascontiguousarray(img, np.uint8)
+    single = img.ndim == 3
+    if single:
+        img = img[None]
+    if img.ndim != 4:
+        raise ValueError("color_to_gray: images must be [n, rows, cols, channels]")
+    n, rows, cols, ch = img.shape
+    a = np.empty((n, rows, cols), np.uint8)
+    b = np.empty((n, rows, cols), np.uint8) if swapped else None
+    ctx._chk(ctx.lib.stvo_color_to_gray(ctx.h, n, rows, cols, ch, GRAY_ORDERS[order], GRAY_WEIGHTS[weights], _ptr(img), _ptr(a),
+                                        _ptr(b) if swapped else None))
+    if single:
+        a, b = a[0], (b[0] if swapped else None)
+    return (a, b) if swapped else a
+
+
+def color_to_gray_dev(ctx, n, rows, cols, ch, src, gray, gray_swapped=None, order="bgr", weights="q14"):
+    """Device pointers; asynchronous on the context's stream (stvo_color_to_gray_dev)."""
+    ctx._chk(ctx.lib.stvo_color_to_gray_dev(ctx.h, n, rows, cols, ch, GRAY_ORDERS[order], GRAY_WEIGHTS[weights], src, gray, gray_swapped))
+
+
 class Rectifier:
     """The GPU rectifier for up to B stereo pairs of one size (stvo_rectify_*): calib = RectCalib (read_dataset_params) or
     maps = (map1 int16 [2, rows, cols, 2], map2 uint16 [2, rows, cols]), left side first."""
@@ -1087,3 +1123,23 @@ class Rectifier:
     def rectify_dev(self, n, src_l, src_r, dst_l, dst_r):
         """Device pointers (n images each, rows * cols bytes apart); asynchronous on the context's stream."""
         self.ctx._chk(self.ctx.lib.stvo_rectify_images_dev(self.h, n, src_l, src_r, dst_l, dst_r))
+
+    def rectify_color(self, left, right):
+        """Host colour images uint8 [n, rows, cols, ch] each (n <= B, ch = 3 or 4) -> (left, right) rectified with all their
+        channels, synchronous."""
+        left, right = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
+        if left.ndim != 4 or left.shape[1:3] != (self.rows, self.cols) or right.shape != left.shape:
+            raise ValueError("Rectifier.rectify_color: left and right must both be [n, rows, cols, channels] of the rectifier's size")
+        out_l, out_r = np.empty_like(left), np.empty_like(right)
+        self.ctx._chk(self.ctx.lib.stvo_rectify_color_images(self.h, len(left), left.shape[3], _ptr(left), _ptr(right), _ptr(out_l), _ptr(out_r)))
+        return out_l, out_r
+
+    def rectify_color_dev(self, n, ch, src_l, src_r, dst_l, dst_r):
+        """Device pointers (n images each, rows * cols * ch bytes apart); asynchronous on the context's stream."""
+        self.ctx._chk(self.ctx.lib.stvo_rectify_color_images_dev(self.h, n, ch, src_l, src_r, dst_l, dst_r))
+
+    def rectify_color_to_gray_dev(self, n, ch, src_l, src_r, gray_l, gray_r, swapped_l=None, swapped_r=None, order="bgr", weights="q14"):
+        """Raw colour pairs -> the grey planes of the rectified colour images, one kernel (device pointers, asynchronous); swapped_*:
+        the planes of the other channel order, both or neither."""
+        self.ctx._chk(self.ctx.lib.stvo_rectify_color_to_gray_dev(self.h, n, ch, GRAY_ORDERS[order], GRAY_WEIGHTS[weights], src_l, src_r,
+                                                                  gray_l, gray_r, swapped_l, swapped_r))

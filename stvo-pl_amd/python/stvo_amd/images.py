@@ -6,7 +6,9 @@ Replaces, per frame and stream: StereoFrame::detectStereoPoints + matchStereoPoi
 StereoFrameHandler::f2fTracking + optimizePose (src/stereoFrameHandler.cpp:106-392); with lsd = stvo_lsd_params also
 detectStereoLineSegments + matchStereoLines (:191-243, :309-398): LSD detector, top-N cut, LBD descriptors (stvo_lsd_* / stvo_lbd_*);
 with fld = stvo_fld_params the FLD detector of use_fld_lines instead (:244-303, stvo_fld_*);
-with rectify = capi.Rectifier also the rectification of the raw pairs that Dataset::nextFrame does first (src/dataset.cpp:147-157)."""
+with rectify = capi.Rectifier also the rectification of the raw pairs that Dataset::nextFrame does first (src/dataset.cpp:147-157);
+with channels = 3 / 4 the frames are interleaved colour (B, G, R[, A]) as Dataset::nextFrame reads them, and the grey images every
+consumer of the reference makes for itself are made on the device (stvo_color_to_gray_dev / stvo_rectify_color_to_gray_dev)."""
 import ctypes as C
 
 import numpy as np
@@ -19,7 +21,7 @@ from .capi import FrameFeatures
 class ImagePipeline:
     def __init__(self, ctx, B, cam, mp, op, max_kp=2048, nfeatures=2000, fast_threshold=20, edge_threshold=19, device="cuda:0", nlevels=1,
                  scale_factor=1.2, lsd=None, max_kl=128, rectify=None, fld=None, orb_score=1, adaptive_fast=None,
-                 trajectory=None, trajectory_log=1, tracks=0, keyframe_sets=False):
+                 trajectory=None, trajectory_log=1, tracks=0, keyframe_sets=False, channels=1, gray_weights="q14"):
         """cam: one camera dict (width / height = image size) for all B streams.  nlevels / scale_factor: Config::orbNLevels /
         orbScaleFactor (the key-point octaves travel with the key-points: sigma2 = 1 / scale^(2 level)).  orb_score: Config::orbScore
         (1 FAST_SCORE, 0 HARRIS_SCORE ranking of the key-points).  lsd: capi.lsd_params(...)
@@ -38,7 +40,19 @@ class ImagePipeline:
         before, no launch and no allocation added.
         tracks: >= 1 turns on the feature tracks per stream (Sequences.set_tracks: which feature of the last key-frame every current
         stereo feature observes), read_tracks() returns the records of the last `tracks` steps; keyframe_sets: every stream also keeps
-        the stereo set of its last key-frame (keyframe_headers / read_keyframe).  0: off, no launch and no allocation added."""
+        the stereo set of its last key-frame (keyframe_headers / read_keyframe).  0: off, no launch and no allocation added.
+        channels: 1, or 3 / 4 for interleaved colour frames uint8 [rows, cols, channels] (B, G, R[, A]; alpha ignored): self.color
+        holds the 2 B colour frames, enqueue first makes the grey plane self.img from them (COLOR_BGR2GRAY in cvtColor's integer
+        form gray_weights, "q14" of OpenCV 3.0 - 3.4.1 or "q15" of the later releases) — with a rectifier in the same kernel as the
+        remap of the colour channels, as the reference rectifies the colour image and converts afterwards — and ORB reads it.  The
+        line detector and LBD read it too, except with fld: the reference's FLD branch converts with CV_RGB2GRAY, so they read
+        self.gray_b, the plane with the red and blue weights swapped, written by the same launch.  1: grey frames as before, no
+        launch and no allocation added."""
+        if channels not in (1, 3, 4):
+            raise ValueError("ImagePipeline: channels is 1 (grey), 3 (B, G, R) or 4 (B, G, R, A)")
+        if gray_weights not in capi.GRAY_WEIGHTS:
+            raise ValueError("ImagePipeline: gray_weights is 'q14' or 'q15'")
+        self.channels, self.gray_weights = channels, gray_weights
         self.ctx, self.B, self.K, self.M = ctx, B, max_kp, max_kl
         self.cols, self.rows = cam["width"], cam["height"]
         self.rectify = rectify
@@ -65,7 +79,12 @@ class ImagePipeline:
             self.seq.set_tracks(log_steps=self.tracks, keyframe_sets=self.keyframe_sets)
         dev = torch.device(device)
         self.img = torch.zeros((2 * B, self.rows, self.cols), dtype=torch.uint8, device=dev)
-        self.rect_img = torch.zeros((2 * B, self.rows, self.cols), dtype=torch.uint8, device=dev) if rectify is not None else None
+        self.rect_img = torch.zeros((2 * B, self.rows, self.cols), dtype=torch.uint8, device=dev) if rectify is not None and channels == 1 else None
+        self.color = self.gray_b = None  # colour frames in; the swapped-weight plane of the FLD branch
+        if channels != 1:
+            self.color = torch.zeros((2 * B, self.rows, self.cols, channels), dtype=torch.uint8, device=dev)
+            if self.fld is not None:
+                self.gray_b = torch.zeros((2 * B, self.rows, self.cols), dtype=torch.uint8, device=dev)
         self.kp = torch.zeros((2 * B, max_kp, 2), dtype=torch.float32, device=dev)
         self.resp = torch.zeros((2 * B, max_kp), dtype=torch.float32, device=dev)
         self.ang = torch.zeros((2 * B, max_kp), dtype=torch.float32, device=dev)
@@ -105,14 +124,20 @@ class ImagePipeline:
         self.slot = 0
 
     def set_images(self, left, right):
-        """left / right: uint8 [B, rows, cols] (numpy or torch); copied into the resident image buffer."""
+        """left / right: uint8 [B, rows, cols] (numpy or torch), with channels 3 / 4 [B, rows, cols, channels]; copied into the
+        resident image buffer."""
         B = self.B
+        if self.channels != 1:
+            self.color[:B].copy_(torch.as_tensor(left).reshape(B, self.rows, self.cols, self.channels), non_blocking=True)
+            self.color[B:].copy_(torch.as_tensor(right).reshape(B, self.rows, self.cols, self.channels), non_blocking=True)
+            return
         self.img[:B].copy_(torch.as_tensor(left).reshape(B, self.rows, self.cols), non_blocking=True)
         self.img[B:].copy_(torch.as_tensor(right).reshape(B, self.rows, self.cols), non_blocking=True)
 
     def enqueue(self, img_ptr=None, control=None):
         """Detection + description of the 2 B resident images (or of the uint8 [2 B, rows, cols] device buffer at img_ptr: B left,
-        then B right), ingestion, one pipeline step — all asynchronous.  With a rectifier the images are raw and are rectified first.
+        then B right; with channels 3 / 4 the colour buffer [2 B, rows, cols, channels]), ingestion, one pipeline step — all
+        asynchronous.  With a rectifier the images are raw and are rectified first.
         control: None, or B words capi.STREAM_RUN / STREAM_RESTART / STREAM_PARK for this step (Sequences.control_next_step): staged
         first, so that with adaptive_fast the restarted streams are detected at fast_threshold again (initialize sets orb_fast_th
         before it detects); the rule at the end of the step leaves the thresholds of restarted and parked streams alone."""
@@ -120,8 +145,19 @@ class ImagePipeline:
             self.seq.control_next_step(control)
             if self.adaptive_fast is not None:
                 self.seq.restart_fast_dev(self.fast_th, self.fast_threshold)
-        ip = img_ptr if img_ptr is not None else self.img.data_ptr()
-        if self.rectify is not None:
+        ip = img_ptr if img_ptr is not None else (self.img if self.channels == 1 else self.color).data_ptr()
+        lp = None  # what the line detector and LBD read where it is not what ORB reads
+        if self.channels != 1:
+            side = self.B * self.rows * self.cols
+            ga = self.img.data_ptr()
+            gb = self.gray_b.data_ptr() if self.gray_b is not None else None
+            if self.rectify is not None:
+                self.rectify.rectify_color_to_gray_dev(self.B, self.channels, ip, ip + side * self.channels, ga, ga + side, gb,
+                                                       gb + side if gb is not None else None, weights=self.gray_weights)
+            else:
+                capi.color_to_gray_dev(self.ctx, 2 * self.B, self.rows, self.cols, self.channels, ip, ga, gb, weights=self.gray_weights)
+            ip, lp = ga, gb
+        elif self.rectify is not None:
             side = self.B * self.rows * self.cols
             rp = self.rect_img.data_ptr()
             self.rectify.rectify_dev(self.B, ip, ip + side, rp, rp + side)
@@ -129,8 +165,9 @@ class ImagePipeline:
         self.orb.detect_dev(ip, self.kp.data_ptr(), self.resp.data_ptr(), self.ang.data_ptr(), self.desc.data_ptr(),
                             self.n.data_ptr(), octave=self.oct.data_ptr())
         if self.lines is not None:
-            self.lines.detect_dev(ip, self.kl.data_ptr(), None, self.nl.data_ptr())
-            self.lbd.compute_dev(ip, self.kl.data_ptr(), self.nl.data_ptr(), self.ldesc.data_ptr())
+            lp = ip if lp is None else lp
+            self.lines.detect_dev(lp, self.kl.data_ptr(), None, self.nl.data_ptr())
+            self.lbd.compute_dev(lp, self.kl.data_ptr(), self.nl.data_ptr(), self.ldesc.data_ptr())
             self.ctx._chk(self.ctx.lib.stvo_keylines_xy_dev(self.ctx.h, 2 * self.B, self.M, self.kl.data_ptr(), self.nl.data_ptr(), self.kl_xy.data_ptr()))
         self.seq.upload_dev(self.slot, self.ff)
         self.seq.step_dev(self.slot)

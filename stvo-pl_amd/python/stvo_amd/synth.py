@@ -352,14 +352,19 @@ def write_sequence(path, frames, cam):
 
 
 def write_image_sequence(path, pairs, cam):
-    """Stereo IMAGE hand-over file read by stvo-pl_amd/app/imagesStVO_synth.cpp ("STVOIMG1"): pairs = [(left, right), ...] uint8."""
+    """Stereo IMAGE hand-over file read by stvo-pl_amd/app/imagesStVO_synth.cpp: pairs = [(left, right), ...] uint8.  Grey images
+    [rows, cols] give "STVOIMG1"; colour images [rows, cols, channels] give "STVOIMG2", the same header followed by an int32
+    channels field, the pixels interleaved."""
     import struct
+    shape = np.shape(pairs[0][0])
     with open(path, "wb") as f:
-        f.write(b"STVOIMG1")
+        f.write(b"STVOIMG2" if len(shape) == 3 else b"STVOIMG1")
         f.write(struct.pack("<iii", len(pairs), cam["width"], cam["height"]))
         f.write(struct.pack("<5d", cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["b"]))
+        if len(shape) == 3:
+            f.write(struct.pack("<i", shape[2]))
         for left, right in pairs:
-            assert left.shape == (cam["height"], cam["width"]) and right.shape == left.shape
+            assert left.shape == shape and left.shape[:2] == (cam["height"], cam["width"]) and right.shape == left.shape
             f.write(np.ascontiguousarray(left, np.uint8).tobytes()); f.write(np.ascontiguousarray(right, np.uint8).tobytes())
 
 
