@@ -174,7 +174,7 @@ __device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) {
 // GridStructure::get for a one-row window (src/gridStructure.cpp:65-76) when the right features are numbered in CSR order:
 // the cells x - w_lo .. x + w_hi of row y are contiguous in the CSR, so the candidates of left feature i1 are the scan
 // positions [lo, hi) and the share of the wave that owns positions wbase .. wbase + 63 is one run of mask bits.
-// (lo, hi) come from the kernel that built the CSR (point_cells_kernel, seq_pipeline.hip): one coalesced 8-byte load per lane.
+// (lo, hi) come from the kernel that built the CSR (point_cells_kernel, stereo_assoc_kernels.hip): one coalesced 8-byte load per lane.
 __device__ __forceinline__ unsigned long long range_mask(const GridArgs& a, int i1, int wbase) {
     const int2 r = reinterpret_cast<const int2*>(a.range1)[i1 < a.n1 ? i1 : 0];
     const int b0 = max(r.x, wbase) - wbase, b1 = min(r.y, wbase + 64) - wbase;

@@ -12,6 +12,7 @@
 #include "../../include/stvo_hip.h"
 #include "debug_switches.h"
 #include "point_tail.h"
+#include "seq_layout.h"
 
 namespace stvo {
 
@@ -313,6 +314,15 @@ void launch_grid_batch(hipStream_t s, const GridBatch& g, bool lines, hipEvent_t
 bool grid_points_fused_ok(const GridBatch& g);
 void launch_grid_range_debug(hipStream_t s, const GridBatch& g);  // test hook, see stvo_seq_debug_grid
 
+// ---- the stereo association kernels of the device-resident pipeline (stereo_assoc_kernels.hip), one workgroup per frame of d.B ----
+struct SeqDev;  // seq_state.h
+void launch_point_cells(hipStream_t s, const SeqDev& d, bool lean);
+void launch_point_tail(hipStream_t s, const SeqDev& d);
+void launch_line_cells(hipStream_t s, const SeqDev& d);
+void launch_line_tail(hipStream_t s, const SeqDev& d);
+void launch_line_stereo_fused(hipStream_t s, const SeqDev& d, int lds_bytes, int Mk, int mutual, double ratio);
+bool line_stereo_fused_lds_opt_in(int lds_bytes);  // lds_opt_in for line_stereo_fused_kernel<256>
+
 // StereoFrameHandler::updateFrame's adaptive FAST rule for B streams, one lane per stream (fast_adapt_kernel.hip): th[b] moves by what
 // results[b] says.  `results` may be device memory or the pinned block a zero-copy step writes its results to.
 // ctl ([B] device, or nullptr = exactly the launch above all): the control words of the step the results come from (stvo_seq_control_next_step);
@@ -339,15 +349,7 @@ void launch_stream_ctl_post(hipStream_t s, int B, const int32_t* ctl, stvo_pose_
 void launch_fast_restart(hipStream_t s, int B, const int32_t* ctl, int32_t* th, int th0);
 
 // Feature tracks and key-frame sets per stream (track_kernel.hip around track_update.h), one workgroup per stream, one launch per step.
-// The arrays of one stereo set of the pipeline, [B][K] / [B][M] rows each (seq_pipeline.hip: stvo_seq::Set).
-struct StereoSetPtrs {
-    float4* rc;
-    uint8_t* desc;
-    int32_t* n;
-    double *spl, *epl, *sP, *eP, *le, *s2l, *s2lm;
-    uint8_t* ldesc;
-    int32_t* nl;
-};
+// (StereoSetPtrs, the arrays of one stereo set of the pipeline: seq_layout.h)
 struct TrackArgs {
     int B, K, M;         // K <= STVO_POSE_MAX_POINTS, M <= STVO_POSE_MAX_LINES: the winners of a stream fit the kernel's LDS
     int first;           // the pipeline's first step: every stream starts a sequence; nothing below up to `ctl` is read

@@ -1,7 +1,7 @@
 // point_cells.h — the grid of the key-points of ONE frame (/root/reference/src/stereoFrame.cpp:129-139; GridStructure as CSR): the
 // right key-points numbered in cell order (= the matcher's scan order), their cells, the cell starts, and the left key-points
 // counting-sorted by cell on a grid GRID_LW columns wide.  One workgroup of T threads per frame.
-// Shared by point_cells_kernel (seq_pipeline.hip: its own launch, 256 threads) and by the one-workgroup point matcher
+// Shared by point_cells_kernel (stereo_assoc_kernels.hip: its own launch, 256 threads) and by the one-workgroup point matcher
 // (grid_kernels.hip), which runs it as its FIRST phase when every workgroup of the launch has exactly one frame — single-stream
 // operation: one dependent launch and ~8 us less in the chain of a frame.
 #pragma once

@@ -1,6 +1,6 @@
 // point_tail.h — the tail of the stereo association of the key-points (src/stereoFrame.cpp:155-172): epipolar / disparity filters on
 // FLOAT differences, the stereo point's record, the kept left descriptor rows — one matched left key-point at a time.
-// Shared by point_tail_kernel (seq_pipeline.hip) and the one-workgroup point matcher (grid_kernels.hip), which runs it as the
+// Shared by point_tail_kernel (stereo_assoc_kernels.hip) and the one-workgroup point matcher (grid_kernels.hip), which runs it as the
 // last phase of a frame; the ordered compaction (ascending left index, :161-172) is the caller's.
 #pragma once
 

@@ -1028,7 +1028,7 @@ PM_HD double line_overlap(double sox, double soy, double eox, double eoy, double
 PM_HD double smin(double a, double b) { return b < a ? b : a; }
 PM_HD double smax(double a, double b) { return a < b ? b : a; }
 
-// Stereo association of a line pair, shared by line_tail_kernel (seq_pipeline.hip) and the host mirror (host/stereoFrame.cpp).
+// Stereo association of a line pair, shared by line_tail_kernel (stereo_assoc_kernels.hip) and the host mirror (host/stereoFrame.cpp).
 // Fraction of the left segment's row span [min(y_s, y_e), max(y_s, y_e)] that the right segment's rows cover
 // (StereoFrame::lineSegmentOverlapStereo, src/stereoFrame.cpp:473-508): 1 for a left segment flatter than horiz_th, and the
 // reference normalises by  max(left rows) - min(right rows)  (not by the left span) and clips at 1.

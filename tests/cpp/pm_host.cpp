@@ -55,7 +55,7 @@ int pmh_spd_cert(const double* C) { return pm::spd_unit_certificate(C); }
 double pmh_line_overlap(const double* so, const double* eo, const double* sp, const double* ep) {
     return pm::line_overlap(so[0], so[1], eo[0], eo[1], sp[0], sp[1], ep[0], ep[1]);
 }
-// the two helpers of the stereo line tail (line_tail_frame in seq_pipeline.hip, host/stereoFrame.cpp)
+// the two helpers of the stereo line tail (line_tail_frame in stereo_assoc_kernels.hip, host/stereoFrame.cpp)
 double pmh_stereo_row_overlap(double yl_s, double yl_e, double yr_s, double yr_e, double horiz_th) {
     return pm::stereo_row_overlap(yl_s, yl_e, yr_s, yr_e, horiz_th);
 }

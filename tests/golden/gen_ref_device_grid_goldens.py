@@ -1,5 +1,5 @@
 """Generates tests/golden/ref_device_grid_goldens.npz from the REFERENCE's own grid + Bresenham code, for the GPU test
-that checks the DEVICE-side grid builder / rasteriser / window gather (csrc/seq_pipeline.hip point_cells_kernel,
+that checks the DEVICE-side grid builder / rasteriser / window gather (csrc/stereo_assoc_kernels.hip point_cells_kernel,
 line_cells_kernel; csrc/grid_kernels.hip grid_cover) directly against reference outputs — not through the oracle.
 
 Runs only in the development container: needs oracle/_ref/libstvo_ref.so, which oracle/Makefile builds from

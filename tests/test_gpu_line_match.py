@@ -1,4 +1,4 @@
-"""The two key-line matchers of the device pipeline at their edges: line_stereo_fused_kernel (seq_pipeline.hip; the stereo association
+"""The two key-line matchers of the device pipeline at their edges: line_stereo_fused_kernel (stereo_assoc_kernels.hip; the stereo association
 of the key-lines in one workgroup per frame) and match_small_kernel (match_kernels.hip; the frame-to-frame match of one pair in
 one workgroup), and the general kernels that take their place on the other routes.  The case frames are those of
 tests/line_match_cases.py, which tests/test_line_match_host.py has shown to be fair and to hit their edges on the CPU.  Every

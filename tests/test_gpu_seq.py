@@ -185,6 +185,48 @@ def test_seq_rotating_slots_equal_push(oracle):
         ctx.close()
 
 
+def test_seq_upload_routes_agree_in_extra_slots():
+    """stvo_seq_upload (pinned staging block + copy) and stvo_seq_upload_dev (seq_ingest_kernel) write a raw frame slot through the two
+    views of one layout (seq_layout.h: raw_frame): the same features fed through either route into slots 2 and 3 of
+    stvo_seq_set_slots(4) give identical stereo sets (stvo_seq_debug_stereo, every record) and bit-identical poses.  B = 2, K = M = 64."""
+    import ctypes as C
+
+    import torch
+    from stvo_amd import capi
+    cam = synth.KITTI_CAM
+    seqs = [synth.make_stereo_sequence(4200 + b, n_frames=4, n_pts=53 - 7 * b, n_lines=50 - 9 * b, cam=cam) for b in range(2)]   # 64 (= K) and 55 key-points, 60 and 49 key-lines
+    mp = match_params("kitti"); op = opt_params("kitti")
+    ctx = capi.Context(device_id=0, max_rows=64, max_batch=2)
+    host = capi.Sequences(ctx, 2, 64, 64, cam, mp, op)
+    dev = capi.Sequences(ctx, 2, 64, 64, cam, mp, op)
+    try:
+        assert tuple(host.strides()) == (64, 64)
+        host.set_slots(4); dev.set_slots(4)
+        for k in range(4):
+            frames = [s[k] for s in seqs]
+            slot = 2 + (k & 1)
+            host.upload(slot, frames)
+            ff, arrays = dev._pack(frames)
+            on_dev = {name: torch.from_numpy(a).cuda() for name, a in arrays.items()}
+            for name, t in on_dev.items():
+                setattr(ff, name, C.c_void_p(t.data_ptr()))
+            torch.cuda.synchronize()
+            dev.upload_dev(slot, ff)
+            host.step_dev(slot); dev.step_dev(slot)
+            rh, ch = host.read()
+            rd, cd = dev.read()
+            assert ch[:, 0].min() > 0 and (k == 0 or rh["n_matched_pt"].min() > 0)   # the comparison is not one of empty sets
+            assert np.array_equal(ch, cd) and rh.tobytes() == rd.tobytes()
+            for b in range(2):
+                sh, sd = host.debug_stereo(b), dev.debug_stereo(b)
+                assert sh["n"] == sd["n"] == ch[b, 0] and sh["nl"] == sd["nl"] == ch[b, 1]
+                for name in sh:
+                    assert np.array_equal(np.asarray(sh[name]), np.asarray(sd[name])), (k, b, name)
+    finally:
+        host.close(); dev.close()
+        ctx.close()
+
+
 def test_seq_fetch_by_products(oracle):
     """stvo_seq_enable_fetch / fetch_matches / fetch_inliers (what the handler mirror rebuilds its host lists from): the raw
     stereo matches equal the oracle's grid matcher on the same frame, and the f2f matches / inlier flags are consistent

@@ -1,5 +1,5 @@
 """What the tails of the stereo association WRITE on the device, record by record: fused_tail (grid_kernels.hip, the last phase of the
-one-workgroup point matchers), point_tail_kernel, line_tail_kernel and the tail of line_stereo_fused_kernel (seq_pipeline.hip), read
+one-workgroup point matchers), point_tail_kernel, line_tail_kernel and the tail of line_stereo_fused_kernel (stereo_assoc_kernels.hip), read
 back through the stvo_seq_debug_stereo test hook and compared with the oracle and with the extended-precision statement
 (tests/np_stereo_tail.py) on the case frames of tests/stereo_tail_cases.py, which tests/test_stereo_tail_host.py has proved on
 the CPU.  Every case frame is one stream of a Sequences object and one push runs the whole set; it is the FIRST push, which only
