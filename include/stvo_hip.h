@@ -427,6 +427,60 @@ int stvo_seq_keyframe_headers(stvo_seq* seq, stvo_kf_header* hdr /* [B] host */)
 int stvo_seq_read_keyframe(stvo_seq* seq, int b, stvo_kf_header* hdr, int32_t cap_pts, float* rc, uint8_t* desc, int32_t cap_lines,
                            double* spl, double* epl, double* sP, double* eP, double* le, double* s2l, double* s2lm, uint8_t* ldesc);
 
+/* ---- export and import single streams (snapshots) ------------------------------------------------------------------------- */
+
+/* Everything one stream carries from one step to the next, as ONE position-independent blob (no pointers: it may be written to a file
+ * and read by another process, another pipeline, another stream index): rows [0, n) / [0, nl) of every array of the stereo set the last
+ * step built and the counts; with the motion model the seed of the next step; with the trajectory its stvo_traj_state (the ring is a log,
+ * not state); with the tracks the [K] + [M] records the NEXT step propagates from; with key-frame sets the key-frame header and rows
+ * [0, hdr.n_pts) / [0, hdr.n_lines) of the set.  The FAST threshold is the caller's array and travels with the caller.
+ * The blob is cut at the EXPORTING pipeline's capacities (K, M = stvo_seq_strides) and feature flags: stvo_seq_snapshot_layout gives the
+ * 256-aligned offset of every section (-1: the feature is off, nothing is cut), a function of (K, M, flags) alone.  The header section
+ * (256 bytes) holds a magic and a format version, bytes, K, M, flags, n, nl, the key-frame header (its `frame` names a step of the
+ * EXPORTING pipeline and is carried verbatim), the stream's stvo_cam and image size, and the pipeline's stvo_match_params and
+ * stvo_opt_params byte for byte.  Every byte that is no valid row and no header field is zero: two exports of the same state are
+ * byte-identical. */
+#define STVO_SNAP_MOTION 1   /* stvo_seq_set_motion_model */
+#define STVO_SNAP_TRAJ 2     /* stvo_seq_set_trajectory */
+#define STVO_SNAP_TRAJ_KF 4  /* ... with keyframes (needs STVO_SNAP_TRAJ) */
+#define STVO_SNAP_TRACKS 8   /* stvo_seq_set_tracks */
+#define STVO_SNAP_KF_SETS 16 /* ... with keyframe_sets (needs STVO_SNAP_TRACKS) */
+typedef struct stvo_snapshot_layout {
+    int64_t bytes; /* of one blob */
+    int64_t off_header, off_rc, off_desc, off_spl, off_epl, off_sP, off_eP, off_le, off_s2l, off_s2lm, off_ldesc, off_motion, off_traj,
+        off_tracks_p, off_tracks_l, off_kf_rc, off_kf_desc, off_kf_spl, off_kf_epl, off_kf_sP, off_kf_eP, off_kf_le, off_kf_s2l,
+        off_kf_s2lm, off_kf_ldesc;
+    int32_t K, M, flags, reserved;
+} stvo_snapshot_layout;
+/* Host only, no device.  K, M <= 0 or an illegal flag set: STVO_ERR_INVALID_ARG. */
+int stvo_seq_snapshot_layout(int K, int M, int flags, stvo_snapshot_layout* out);
+/* The capacities, the feature flags and the blob size of this pipeline (each pointer may be NULL). */
+int stvo_seq_snapshot_info(const stvo_seq* seq, int32_t* K, int32_t* M, int32_t* flags, int64_t* bytes_per_stream);
+/* Blob i (at i * bytes_per_stream) = the state of stream streams_host[i].  Reads only; legal whenever no step is half-enqueued, before
+ * the first step included (an empty set and initial states).  An index outside [0, B) or a NULL pointer: STVO_ERR_INVALID_ARG; an
+ * index named twice is exported twice.  _dev: blobs_dev is device memory, 16-byte aligned; ONE kernel launch on the context's stream,
+ * behind the last step's launches and whatever the caller chained there, no host synchronisation (the stream list travels through
+ * pinned staging that is not reused before its copy has completed).  The host form copies the blobs out and synchronises. */
+int stvo_seq_export_streams_dev(stvo_seq* seq, int n, const int32_t* streams_host, void* blobs_dev);
+int stvo_seq_export_streams(stvo_seq* seq, int n, const int32_t* streams_host, void* blobs_host);
+/* Stream streams_host[i] holds exactly the state in blob i (at i * blob_stride; a multiple of 16, at least the blob's `bytes`): its
+ * next RUN step tracks the frame in the slot against the imported stereo set with the imported seed, trajectory state, track state and
+ * key-frame set, as if the stream had lived here all along (n_frames, n_keyframes, serial continue).  Streams not named keep their state
+ * bit for bit.  Rows of the target at or beyond the imported counts are not written, except the track state, whose rows beyond the counts
+ * become zero.  Every refusal is decided on the host before anything is enqueued and leaves the pipeline unchanged:
+ *   bad magic / version / bytes, flags != this pipeline's features, camera or image size != the target stream's, stvo_match_params /
+ *   stvo_opt_params != this pipeline's (byte for byte), an index out of range or named twice, blobs of more than four different
+ *   (K, M) in one call                                                                                     STVO_ERR_INVALID_ARG
+ *   n > K, nl > M, hdr.n_pts > K or hdr.n_lines > M of THIS pipeline (the blob's own K, M may differ)       STVO_ERR_CAPACITY
+ * _dev: the n headers are fetched with one small copy, so the call synchronises the context's stream once; then one kernel launch.
+ * Before the first step (the restore case; after stvo_seq_set_motion_model / set_trajectory / set_tracks, which stay "only before the
+ * first step" and are refused after an import as they are after a step): the pipeline then counts as stepped — its next step tracks,
+ * the streams not imported hold an empty stereo set and initial states (what PARK on an empty frame leaves), and the caller starts
+ * sequences on them with RESTART.  The step after an import is enqueued as a step with a control is: it gives up the key-line stage and
+ * the grid ahead and the event-free fork; a pipeline that never imports enqueues every step exactly as before. */
+int stvo_seq_import_streams_dev(stvo_seq* seq, int n, const int32_t* streams_host, const void* blobs_dev, int64_t blob_stride);
+int stvo_seq_import_streams(stvo_seq* seq, int n, const int32_t* streams_host, const void* blobs_host, int64_t blob_stride);
+
 /* ---- LBD line descriptor (first half) ------------------------------------------------------- */
 
 /* Replaces  BinaryDescriptor::createBinaryDescriptor()->compute(img, lines, ldesc)  as called by StereoFrame::detectLineFeatures

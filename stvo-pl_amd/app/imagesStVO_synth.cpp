@@ -104,10 +104,10 @@ TrackLine follow_tracks(const std::vector<int32_t>& m12, const Features& curr, c
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::cerr << "usage: imagesStVO_synth <sequence.bin> <results.bin> [--preset kitti|euroc|default] [-c cfg] "
-                     "[--mode m] [-n frames] [--device-pipeline] [--keyframes] [--tracks]\n";
+                     "[--mode m] [-n frames] [--device-pipeline] [--keyframes] [--tracks] [--save-state file] [--load-state file]\n";
         return -1;
     }
-    std::string preset = "kitti", cfg, dataset_params;
+    std::string preset = "kitti", cfg, dataset_params, save_state, load_state;
     int mode = 0, max_frames = 0, frame_offset = 0, frame_step = 1;
     bool keyframes = false;
     bool device_pipeline = false, no_lines = false, tracks = false;
@@ -121,6 +121,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--keyframes")) keyframes = true;
         else if (!std::strcmp(argv[i], "--no-lines")) no_lines = true;
         else if (!std::strcmp(argv[i], "--tracks")) tracks = true;
+        else if (!std::strcmp(argv[i], "--save-state") && i + 1 < argc) save_state = argv[++i];
+        else if (!std::strcmp(argv[i], "--load-state") && i + 1 < argc) load_state = argv[++i];
         else if (!std::strcmp(argv[i], "--dataset-params") && i + 1 < argc) dataset_params = argv[++i];
         else if (!std::strcmp(argv[i], "--gray-weights") && i + 1 < argc) gray_weights = std::strcmp(argv[++i], "q15") ? STVO_GRAY_Q14 : STVO_GRAY_Q15;
         else if (!std::strcmp(argv[i], "-o") && i + 1 < argc) frame_offset = std::atoi(argv[++i]);  // imagesStVO.cpp:158-159
@@ -149,6 +151,10 @@ int main(int argc, char** argv) {
     }
     if (image_file && device_pipeline) {
         std::cerr << "--device-pipeline takes feature files; image files go through the handler" << std::endl;
+        return -1;
+    }
+    if ((!save_state.empty() || !load_state.empty()) && !device_pipeline) {
+        std::cerr << "--save-state / --load-state move the stream of the device pipeline: they go with --device-pipeline" << std::endl;
         return -1;
     }
     if (frame_offset < 0) frame_offset = 0;
@@ -195,8 +201,9 @@ int main(int argc, char** argv) {
         mp.ls_min_disp_ratio = Config::lsMinDispRatio(); mp.orb_scale_factor = Config::orbScaleFactor();
         mp.lsd_scale = Config::lsdScale();
         mp.min_ratio_12_p_d = Config::minRatio12P();
-        if (frame_offset != 0 || frame_step != 1) {
-            std::cerr << "--device-pipeline takes the sequence as it is: -o / -s belong to the handler path" << std::endl;
+        // (-o with --load-state: the run continues a stream saved behind frame -o - 1 of this file, and its first frame is tracked)
+        if ((frame_offset != 0 && load_state.empty()) || frame_step != 1) {
+            std::cerr << "--device-pipeline takes the sequence as it is: -o / -s belong to the handler path (-o alone goes with --load-state)" << std::endl;
             return -1;
         }
         stvo_opt_params op{};
@@ -229,15 +236,35 @@ int main(int argc, char** argv) {
             tr_pts.resize((size_t)trK);
             tr_lines.resize((size_t)trM);
         }
+        // --load-state: the stream as --save-state left it (stvo_seq_import_streams checks that it was saved under this camera, image
+        // size and configuration), in front of the first processed frame, which is then a tracked frame and no `initialize`
+        if (!load_state.empty()) {
+            std::ifstream sf(load_state, std::ios::binary | std::ios::ate);
+            const std::streamoff size = sf ? (std::streamoff)sf.tellg() : 0;
+            std::vector<char> blob((size_t)(size > 0 ? size : 0));
+            if (size > 0) sf.seekg(0);
+            if (size < 256 || (size & 15) || !sf.read(blob.data(), size)) {
+                std::cerr << "--load-state: cannot read " << load_state << std::endl;
+                return -4;
+            }
+            const int32_t stream0 = 0;
+            const int rc = stvo_seq_import_streams(seq, 1, &stream0, blob.data(), (int64_t)size);
+            if (rc != STVO_OK) {
+                std::cerr << "--load-state: " << load_state << " does not fit this run (" << stvo_error_string(rc)
+                          << "): it was saved under another camera, image size, preset or set of options" << std::endl;
+                return -4;
+            }
+        }
         double t_sum = 0.0;
         std::vector<double> t_all;
-        for (int k = 0; k < n_frames; ++k) {
+        for (int k = -frame_offset; k < n_frames; ++k) {
             FrameFeatures feat;
             int32_t n[4];
             if (!rd(in, n, 4) || !read_points(in, n[0], feat.points_l, feat.pdesc_l) ||
                 !read_points(in, n[1], feat.points_r, feat.pdesc_r) || !read_lines(in, n[2], feat.lines_l, feat.ldesc_l) ||
                 !read_lines(in, n[3], feat.lines_r, feat.ldesc_r))
                 return -1;
+            if (k < 0) continue;  // a frame in front of the offset
             std::vector<float> kpl(2 * n[0] + 2), kpr(2 * n[1] + 2), kll(4 * n[2] + 4), klr(4 * n[3] + 4);
             std::vector<int32_t> ol(n[0] + 1), oll(n[2] + 1);
             for (int i = 0; i < n[0]; ++i) { kpl[2 * i] = feat.points_l[i].x; kpl[2 * i + 1] = feat.points_l[i].y; ol[i] = feat.points_l[i].octave; }
@@ -260,7 +287,7 @@ int main(int argc, char** argv) {
                 return -3;
             }
             const double t1 = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
-            if (k == 0) continue;
+            if (k == 0 && load_state.empty()) continue;
             stvo_traj_record tr{};
             int32_t n_tr = 0;
             if (stvo_seq_read_trajectory(seq, 1, &tr, &n_tr) != STVO_OK || n_tr != 1) {  // (the stream is idle after the push: no second wait)
@@ -269,9 +296,10 @@ int main(int argc, char** argv) {
             }
             t_sum += t1;
             t_all.push_back(t1);
-            std::printf("Frame: %d\tRes.: %.8f \t Proc. time: %.3f ms\t \t Points: %d (%d) \t Lines:  %d (%d) \n", k, r.err, t1,
+            const int frame_no = frame_offset + k;  // the frame's number in the file
+            std::printf("Frame: %d\tRes.: %.8f \t Proc. time: %.3f ms\t \t Points: %d (%d) \t Lines:  %d (%d) \n", frame_no, r.err, t1,
                         r.n_matched_pt, r.n_inliers_pt, r.n_matched_ls, r.n_inliers_ls);
-            const int32_t ints[12] = {k, r.status, r.path, r.iters[0], r.iters[1], r.n_matched_pt, r.n_inliers_pt, r.n_matched_ls,
+            const int32_t ints[12] = {frame_no, r.status, r.path, r.iters[0], r.iters[1], r.n_matched_pt, r.n_inliers_pt, r.n_matched_ls,
                                       r.n_inliers_ls, cnt[0], cnt[1], 0};
             wr(out, ints, 12);
             wr(out, r.T, 16);
@@ -291,14 +319,26 @@ int main(int argc, char** argv) {
                 TrackLine lp, ll;
                 for (int i = 0; i < tc[0]; ++i) lp.add(tr_pts[i].kf != 0, tr_pts[i].inlier == 1, tr_pts[i].idx);
                 for (int i = 0; i < tc[1]; ++i) ll.add(tr_lines[i].kf != 0, tr_lines[i].inlier == 1, tr_lines[i].idx);
-                print_tracks(k, lp, ll);
+                print_tracks(frame_no, lp, ll);
             }
         }
-        if (n_frames > 1) {
+        // --save-state: everything the stream carries into the next frame, as one file
+        if (!save_state.empty()) {
+            int64_t bytes = 0;
+            const int32_t stream0 = 0;
+            std::vector<char> blob;
+            if (stvo_seq_snapshot_info(seq, nullptr, nullptr, nullptr, &bytes) == STVO_OK) blob.resize((size_t)bytes);
+            std::ofstream sf(save_state, std::ios::binary);
+            if (blob.empty() || stvo_seq_export_streams(seq, 1, &stream0, blob.data()) != STVO_OK || !sf.write(blob.data(), bytes)) {
+                std::cerr << "--save-state: cannot write " << save_state << ": " << stvo_ctx_last_error(ctx) << std::endl;
+                return -4;
+            }
+        }
+        if (!t_all.empty()) {
             // the median is the steady-state figure: the first frames of a process pay for code-object loading and allocations
             std::sort(t_all.begin(), t_all.end());
             std::printf("[imagesStVO_synth --device-pipeline] %d frame pairs, mean Proc. time %.3f ms, median %.3f ms (single stream, incl. H2D/D2H)\n",
-                        n_frames - 1, t_sum / (n_frames - 1), t_all[t_all.size() / 2]);
+                        (int)t_all.size(), t_sum / (double)t_all.size(), t_all[t_all.size() / 2]);
         }
         stvo_seq_destroy(seq);
         stvo_ctx_destroy(ctx);

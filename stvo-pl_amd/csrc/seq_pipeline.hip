@@ -105,6 +105,8 @@ int stvo_seq_create_multi(stvo_ctx* ctx, int B, int max_keypoints, int max_keyli
         return STVO_ERR_INVALID_ARG;
     }
     const size_t nb = (size_t)B;
+    s->cams_host.assign(cams, cams + B);  // what a snapshot's header says of a stream (seq_snapshot.hip)
+    for (int b = 0; b < B; ++b) s->img_size_host.insert(s->img_size_host.end(), {img_cols[b], img_rows[b]});
     s->raw_span = stvo::raw_frame_span(B, K, M);
     s->dev_bytes = stvo::seq_layout(*s, nullptr);
     bool ok = hip_ok(ctx, hipMalloc((void**)&s->dev, s->dev_bytes), "hipMalloc seq") && zero_device(ctx, s->dev, s->dev_bytes, "hipMemset seq");
@@ -181,11 +183,12 @@ int stvo_seq_destroy(stvo_seq* s) {
     }
     // (d_ctl and ctl_stage: one allocation for both copies each)
     for (void* p : {(void*)s->d_prof, (void*)s->d_motion_T, (void*)s->d_traj_state, (void*)s->d_traj_ring, (void*)s->d_tracks, (void*)s->d_kf,
-                    (void*)s->d_ctl[0], (void*)s->dev, (void*)s->extra_raw})
+                    (void*)s->d_ctl[0], (void*)s->dev, (void*)s->extra_raw, (void*)s->d_snap_img, (void*)s->d_snap_streams, (void*)s->snap_buf})
         if (p) (void)hipFree(p);
-    for (void* p : {(void*)s->ctl_stage[0], (void*)s->fetch_host, (void*)s->raw_host[0], (void*)s->raw_host[1], (void*)s->out_host})
+    // (snap_stage: one allocation for both blocks)
+    for (void* p : {(void*)s->ctl_stage[0], (void*)s->snap_stage[0], (void*)s->fetch_host, (void*)s->raw_host[0], (void*)s->raw_host[1], (void*)s->out_host})
         if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {s->ev_ctl[0], s->ev_ctl[1], s->ev_fork, s->ev_join, s->ev_cells, s->ev_upload, s->ev_stage[0], s->ev_stage[1], s->ev_fetch})
+    for (hipEvent_t e : {s->ev_snap[0], s->ev_snap[1], s->ev_ctl[0], s->ev_ctl[1], s->ev_fork, s->ev_join, s->ev_cells, s->ev_upload, s->ev_stage[0], s->ev_stage[1], s->ev_fetch})
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->tev) (void)hipEventDestroy(e);
     delete s;
@@ -365,6 +368,7 @@ void gather_step_facts(const stvo_seq* s, int slot, const stvo::StepFlags& fl, b
     f.lines_now = fl.lines_now; f.lines_prev = fl.lines_prev; f.track = fl.track;
     f.frame_idx = s->frame_idx;
     f.has_control = fl.ctl != nullptr;
+    f.after_import = s->imported;
     f.raw_split = s->raw_split[slot]; f.raw_max_lines = s->raw_max_lines[slot];
     f.set_lines_cap_prev = s->set_lines_cap[s->prev_set()]; f.set_lines_cap_cur = s->set_lines_cap[s->cur];
     f.st_dirty = s->st_dirty; f.fetch = s->fetch; f.zero_copy = s->zero_copy;
@@ -634,6 +638,7 @@ int stvo_seq_step_dev(stvo_seq* s, int slot) {
     s->fetch_value = pub.fetch_value;
     std::memcpy(s->last_schedule, plan.schedule, sizeof(s->last_schedule));
     s->st_dirty = true;
+    s->imported = false;
     s->set_lines[s->cur] = fl.lines_now;
     s->last_lines = fl.lines_now;
     s->last_slot = slot;

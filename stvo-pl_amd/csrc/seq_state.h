@@ -107,6 +107,23 @@ struct stvo_seq {
     int32_t* track_counts(size_t ring_row) const {
         return reinterpret_cast<int32_t*>(d_tracks + (size_t)(2 + track_log_steps) * track_row_bytes()) + ring_row * (size_t)B * 2;
     }
+    // export / import of single streams (stvo_seq_export_streams / stvo_seq_import_streams; seq_snapshot.hip).  The calibration and image
+    // size of every stream as the pipeline was created with them; everything else exists from the first call on, each its own allocation:
+    // the image sizes and the stream list of a call on the device (every reader and the copy that fills the list run on the context's
+    // stream), two pinned staging blocks for the list used alternately, each with an event behind the copy that read it, and the device
+    // buffer the host forms stage their blobs in.
+    std::vector<stvo_cam> cams_host;
+    std::vector<int32_t> img_size_host;     // [B][2] cols, rows
+    int32_t* d_snap_img = nullptr;          // [B][2]
+    int32_t* d_snap_streams = nullptr;      // [snap_streams_cap][2]
+    int32_t* snap_stage[2] = {nullptr, nullptr};
+    int snap_streams_cap = 0;
+    hipEvent_t ev_snap[2] = {nullptr, nullptr};
+    bool snap_stage_busy[2] = {false, false};
+    int snap_stage_next = 0;
+    char* snap_buf = nullptr;
+    size_t snap_buf_bytes = 0;
+    bool imported = false;                  // streams were imported since the last step (StepFacts::after_import)
     long long* d_prof = nullptr;   // STVO_POSE_PROF (developer aid): [B][16] phase ticks of the last pose launch, printed by stvo_seq_read
     char* dev = nullptr;     // one allocation, cut by stvo::seq_layout below
     size_t dev_bytes = 0;

@@ -47,6 +47,13 @@ struct StepFacts {
     // the step tracks AND carries a per-stream control (stvo_seq_control_next_step): a kernel at the very start of the step, on the point
     // stream, empties the previous stereo set of the streams that restart or are parked.  false (every other step): every plan as before.
     bool has_control = false;
+    // streams were imported since the last step (stvo_seq_import_streams): the unpack kernel, on the point stream behind
+    // optimizePose(k - 1), wrote rows and counts of the previous stereo set — key-line rows and counts included, which the line stream's f2f
+    // match of this step reads.  The same hazard as a control's, so the same answer: the line stream does nothing in this step before it
+    // has waited for the step's OWN fork event (no grid and no key-line stage ahead, no event-free fork).  Nothing else of the plan reads
+    // it: the step's results depend on no stage-ahead work and on no StepHistory, and the step behind it may run ahead again.
+    // false (every step of a pipeline that never imports): every plan as before.
+    bool after_import = false;
     DebugSwitches sw = switches_unset();
 };
 
@@ -128,7 +135,8 @@ inline StepPlan plan_step(const StepFacts& f, const StepHistory& h, LdsFits&& ld
     // for has been enqueued on the point stream since the last synchronisation — the step forks without an event
     // (a step with a control forks WITH an event: the line stream's f2f match reads the key-line count the control kernel cleared on the
     // point stream)
-    const bool fork_free = p.par && f.raw_split && !f.st_dirty && !f.has_control;
+    const bool own_fork = f.has_control || f.after_import;  // the line stream starts behind this step's own fork event
+    const bool fork_free = p.par && f.raw_split && !f.st_dirty && !own_fork;
     p.fork_at_start = p.par && !p.mid_fork && !fork_free;
     p.line_forked = p.par && (p.mid_fork || !fork_free);
     p.zero_nl = !f.lines_now && f.has_points;
@@ -158,7 +166,7 @@ inline StepPlan plan_step(const StepFacts& f, const StepHistory& h, LdsFits&& ld
         // step's OWN fork event, recorded behind the control kernel.  The next step may run ahead again: the event it waits for is this
         // step's, and nothing its key-line kernels touch is written by the control kernels.
         p.cells_ahead = p.mid_fork && p.lean_cells && !p.fused_cells && (!tev || p.light) && f.cells_differ && h.sl_forked_frame == last &&
-                        f.sw.cells_ahead != 0 && !f.has_control;
+                        f.sw.cells_ahead != 0 && !own_fork;
         // key-line stage ahead (stvo_seq::m12l_alt has the whole argument): the line stream waits for the PREVIOUS step's fork event — in
         // front of the cells kernel, whose output copy the matcher of two steps ago read — and not for this step's.  Safe only while the
         // second copy of the key-line match indices is in use (alt_ok) and after a step that recorded the fork event (fork_rec_frame).

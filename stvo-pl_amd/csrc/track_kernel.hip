@@ -3,6 +3,7 @@
 // at a key-frame copies the stream's current stereo set into its key-frame set.  The winner of every current feature (the largest
 // previous index that names it) is found in LDS; global memory sees plain vector stores only, rows at or beyond a stream's count are
 // not written, and the loops run over the counts, not the capacities.
+#include "copy_words.h"
 #include "ctx_internal.h"
 #include "track_update.h"
 
@@ -13,21 +14,6 @@ constexpr int TRACK_BLOCK = 256;
 
 static_assert(sizeof(stvo_track) == sizeof(unsigned long long), "a track record is stored as one 8-byte word");
 static_assert(sizeof(stvo_kf_header) == sizeof(int4), "the key-frame header is stored as one 16-byte word");
-
-template <typename W>
-__device__ __forceinline__ void copy_words(const void* __restrict__ src, void* __restrict__ dst, size_t first_word, int n_words, int tid) {
-    const W* s = reinterpret_cast<const W*>(src) + first_word;
-    W* d = reinterpret_cast<W*>(dst) + first_word;
-    int i = tid;
-    for (; i + 3 * TRACK_BLOCK < n_words; i += 4 * TRACK_BLOCK) {  // four loads in flight per lane: the copy is a latency chain otherwise
-        const W w0 = s[i], w1 = s[i + TRACK_BLOCK], w2 = s[i + 2 * TRACK_BLOCK], w3 = s[i + 3 * TRACK_BLOCK];
-        d[i] = w0;
-        d[i + TRACK_BLOCK] = w1;
-        d[i + 2 * TRACK_BLOCK] = w2;
-        d[i + 3 * TRACK_BLOCK] = w3;
-    }
-    for (; i < n_words; i += TRACK_BLOCK) d[i] = s[i];
-}
 
 __device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
@@ -57,16 +43,16 @@ __global__ __launch_bounds__(TRACK_BLOCK) void track_update_kernel(TrackArgs a) 
     if (tid == 0) *reinterpret_cast<int2*>(a.rec_counts + 2 * (size_t)b) = make_int2(n, nl);
     if (!a.kf_hdr || !reset) return;
     // the key-frame set: rows [0, n) of every array, byte for byte, then the header
-    copy_words<uint4>(a.cur.rc, a.kf.rc, op, n, tid);
-    copy_words<uint4>(a.cur.desc, a.kf.desc, op * 2, n * 2, tid);
-    copy_words<u64>(a.cur.spl, a.kf.spl, ol * 2, nl * 2, tid);
-    copy_words<u64>(a.cur.epl, a.kf.epl, ol * 2, nl * 2, tid);
-    copy_words<u64>(a.cur.sP, a.kf.sP, ol * 3, nl * 3, tid);
-    copy_words<u64>(a.cur.eP, a.kf.eP, ol * 3, nl * 3, tid);
-    copy_words<u64>(a.cur.le, a.kf.le, ol * 3, nl * 3, tid);
-    copy_words<u64>(a.cur.s2l, a.kf.s2l, ol, nl, tid);
-    copy_words<u64>(a.cur.s2lm, a.kf.s2lm, ol, nl, tid);
-    copy_words<uint4>(a.cur.ldesc, a.kf.ldesc, ol * 2, nl * 2, tid);
+    copy_words<uint4, TRACK_BLOCK>(a.cur.rc, a.kf.rc, op, n, tid);
+    copy_words<uint4, TRACK_BLOCK>(a.cur.desc, a.kf.desc, op * 2, n * 2, tid);
+    copy_words<u64, TRACK_BLOCK>(a.cur.spl, a.kf.spl, ol * 2, nl * 2, tid);
+    copy_words<u64, TRACK_BLOCK>(a.cur.epl, a.kf.epl, ol * 2, nl * 2, tid);
+    copy_words<u64, TRACK_BLOCK>(a.cur.sP, a.kf.sP, ol * 3, nl * 3, tid);
+    copy_words<u64, TRACK_BLOCK>(a.cur.eP, a.kf.eP, ol * 3, nl * 3, tid);
+    copy_words<u64, TRACK_BLOCK>(a.cur.le, a.kf.le, ol * 3, nl * 3, tid);
+    copy_words<u64, TRACK_BLOCK>(a.cur.s2l, a.kf.s2l, ol, nl, tid);
+    copy_words<u64, TRACK_BLOCK>(a.cur.s2lm, a.kf.s2lm, ol, nl, tid);
+    copy_words<uint4, TRACK_BLOCK>(a.cur.ldesc, a.kf.ldesc, ol * 2, nl * 2, tid);
     __threadfence();
     __syncthreads();
     if (tid == 0) {

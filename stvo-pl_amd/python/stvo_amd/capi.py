@@ -33,7 +33,8 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_seq_trajectory_state_dev", "stvo_seq_read_trajectory_state", "stvo_seq_control_next_step", "stvo_seq_restart_fast_dev",
            "stvo_seq_set_tracks", "stvo_seq_read_tracks", "stvo_seq_tracks_dev", "stvo_seq_keyframe_headers", "stvo_seq_read_keyframe",
            "stvo_color_to_gray", "stvo_color_to_gray_dev", "stvo_rectify_color_images", "stvo_rectify_color_images_dev",
-           "stvo_rectify_color_to_gray_dev"]
+           "stvo_rectify_color_to_gray_dev", "stvo_seq_snapshot_layout", "stvo_seq_snapshot_info", "stvo_seq_export_streams_dev",
+           "stvo_seq_export_streams", "stvo_seq_import_streams_dev", "stvo_seq_import_streams"]
 
 SEQ_NSTAGE = 5  # include/stvo_hip.h: STVO_SEQ_NSTAGE
 SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_check", "pose")
@@ -41,6 +42,20 @@ SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_
 SEQ_SCHEDULE_FIELDS = ("pose_kernel", "pose_waves", "fused_cells", "cells_ahead", "lines_ahead", "gate", "mid_fork", "line_fused")
 SCHED_POSE_LATENCY, SCHED_POSE_BATCH = 1, 2
 STREAM_RUN, STREAM_RESTART, STREAM_PARK = 0, 1, 2  # include/stvo_hip.h: STVO_STREAM_* (Sequences.control_next_step)
+SNAP_MOTION, SNAP_TRAJ, SNAP_TRAJ_KF, SNAP_TRACKS, SNAP_KF_SETS = 1, 2, 4, 8, 16  # include/stvo_hip.h: STVO_SNAP_*
+# the sections of a snapshot blob in the order they are cut (csrc/stream_snapshot.h): name, dtype of a row, "K" / "M" rows or one record
+_SET_SECTIONS = (("rc", ("<f4", (4,)), "K"), ("desc", ("u1", (32,)), "K"), ("spl", ("<f8", (2,)), "M"), ("epl", ("<f8", (2,)), "M"),
+                 ("sP", ("<f8", (3,)), "M"), ("eP", ("<f8", (3,)), "M"), ("le", ("<f8", (3,)), "M"), ("s2l", "<f8", "M"), ("s2lm", "<f8", "M"),
+                 ("ldesc", ("u1", (32,)), "M"))
+SNAP_SECTIONS = (("header", None, 1),) + _SET_SECTIONS + (("motion", ("<f8", (16,)), 1), ("traj", TRAJ_STATE_DTYPE, 1),
+                                                           ("tracks_p", TRACK_DTYPE, "K"), ("tracks_l", TRACK_DTYPE, "M")) + \
+    tuple(("kf_" + n, d, r) for n, d, r in _SET_SECTIONS)
+_CAM_DTYPE = np.dtype([(n, "<f8") for n in ("fx", "fy", "cx", "cy", "b")])
+SNAP_HEADER_DTYPE = np.dtype([("magic", "<u4"), ("version", "<u4"), ("bytes", "<i8"), ("K", "<i4"), ("M", "<i4"), ("flags", "<i4"), ("n", "<i4"),
+                              ("nl", "<i4"), ("reserved", "<i4"), ("kf", KF_HEADER_DTYPE), ("cam", _CAM_DTYPE), ("cols", "<i4"), ("rows", "<i4"),
+                              ("mp", "u1", (C.sizeof(MatchParams),)), ("op", "u1", (C.sizeof(OptParams),))])
+assert SNAP_HEADER_DTYPE.itemsize == 256
+SNAP_MAGIC, SNAP_VERSION = 0x53567453, 1
 
 u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
@@ -71,6 +86,45 @@ class FrameFeatures(C.Structure):
 
 class StvoError(RuntimeError):
     pass
+
+
+class SnapshotLayout(C.Structure):  # stvo_snapshot_layout
+    _fields_ = [("bytes", C.c_int64)] + [("off_" + n, C.c_int64) for n, _, _ in SNAP_SECTIONS] + \
+               [("K", C.c_int32), ("M", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+def snapshot_layout(K, M, flags):
+    """{"bytes", "K", "M", "flags", "off": {section name: offset or -1}} of a snapshot blob cut at capacities K, M with the feature
+    flags SNAP_* (stvo_seq_snapshot_layout: host only, no device)."""
+    lay = SnapshotLayout()
+    rc = load().stvo_seq_snapshot_layout(K, M, flags, C.byref(lay))
+    if rc != 0:
+        raise StvoError(f"stvo_seq_snapshot_layout({K}, {M}, {flags}): {rc}")
+    return dict(bytes=lay.bytes, K=lay.K, M=lay.M, flags=lay.flags, off={n: getattr(lay, "off_" + n) for n, _, _ in SNAP_SECTIONS})
+
+
+def snapshot_views(blob):
+    """Numpy views into ONE blob (uint8 [bytes]): "header" (a SNAP_HEADER_DTYPE record) and, for every section that is cut, its valid
+    rows — [n] / [nl] rows of the stereo set and the track state, [kf.n_pts] / [kf.n_lines] of the key-frame set, one record of the seed
+    and of the trajectory state.  "live" is a bool mask of the bytes these views cover (every other byte of a blob is zero)."""
+    blob = np.ascontiguousarray(blob, np.uint8).reshape(-1)
+    h = blob[:256].view(SNAP_HEADER_DTYPE)[0]
+    lay = snapshot_layout(int(h["K"]), int(h["M"]), int(h["flags"]))
+    assert lay["bytes"] == int(h["bytes"]) == blob.size, (lay["bytes"], int(h["bytes"]), blob.size)
+    out = dict(header=h, layout=lay)
+    live = np.zeros(blob.size, bool)
+    live[:256] = True
+    for name, dt, rows in SNAP_SECTIONS[1:]:
+        off = lay["off"][name]
+        if off < 0:
+            continue
+        dt = np.dtype(dt)
+        kf = name.startswith("kf_")
+        cnt = 1 if rows == 1 else int((h["kf"]["n_pts"] if kf else h["n"]) if rows == "K" else (h["kf"]["n_lines"] if kf else h["nl"]))
+        out[name] = blob[off:off + cnt * dt.itemsize].view(dt.base).reshape((cnt,) + dt.shape)
+        live[off:off + cnt * dt.itemsize] = True
+    out["live"] = live
+    return out
 
 
 class FastAdapt(C.Structure):  # stvo_fast_adapt
@@ -237,6 +291,12 @@ def load():
     L.stvo_seq_read_keyframe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int32, f32p, u8p, C.c_int32, f64p, f64p, f64p, f64p, f64p,
                                          f64p, f64p, u8p]
     L.stvo_seq_restart_fast_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.stvo_seq_snapshot_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(SnapshotLayout)]
+    L.stvo_seq_snapshot_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.stvo_seq_export_streams_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.stvo_seq_export_streams.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.stvo_seq_import_streams_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
+    L.stvo_seq_import_streams.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
     L.stvo_orb_detect_levels.argtypes = [C.c_void_p, u8p, f32p, f32p, f32p, i32p, u8p, i32p, i32p]
     L.stvo_orb_detect_levels_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 8
     L.stvo_lbd_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -916,6 +976,40 @@ class Sequences:
         return dict(n=n, rc=rc[:n].copy(), desc=desc[:n].copy(), nl=nl, spl=spl[:nl].copy(), epl=epl[:nl].copy(), sP=sP[:nl].copy(),
                     eP=eP[:nl].copy(), le=le[:nl].copy(), s2l=s2l[:nl].copy(), s2lm=s2lm[:nl].copy(), ldesc=ldesc[:nl].copy(),
                     frame=int(hdr["frame"][0]), serial=int(hdr["serial"][0]))
+
+    def snapshot_info(self):
+        """{"K", "M", "flags" (SNAP_*), "bytes" of one stream's blob} of this pipeline (stvo_seq_snapshot_info)."""
+        k, m, f, b = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        self.ctx._chk(self.ctx.lib.stvo_seq_snapshot_info(self.h, C.byref(k), C.byref(m), C.byref(f), C.byref(b)))
+        return dict(K=k.value, M=m.value, flags=f.value, bytes=b.value)
+
+    @staticmethod
+    def _streams(streams):
+        return np.ascontiguousarray(np.asarray(streams).reshape(-1), dtype=np.int32)
+
+    def export_streams(self, streams):
+        """uint8 [n, bytes]: blob i = everything stream streams[i] carries into the next step (stvo_seq_export_streams); synchronises."""
+        st = self._streams(streams)
+        out = np.zeros((st.size, self.snapshot_info()["bytes"]), np.uint8)
+        self.ctx._chk(self.ctx.lib.stvo_seq_export_streams(self.h, st.size, _ptr(st), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def export_streams_dev(self, streams, blob_ptr):
+        """The same into device memory at blob_ptr (n * bytes, 16-byte aligned), enqueued on the context's stream; no synchronisation."""
+        st = self._streams(streams)
+        self.ctx._chk(self.ctx.lib.stvo_seq_export_streams_dev(self.h, st.size, _ptr(st), C.c_void_p(blob_ptr)))
+
+    def import_streams(self, streams, blobs):
+        """Stream streams[i] holds the state of blobs[i] (uint8 [n, stride], as export_streams returns them, of this or another pipeline);
+        refusals raise StvoError and change nothing (stvo_seq_import_streams)."""
+        st = self._streams(streams)
+        blobs = np.ascontiguousarray(blobs, np.uint8).reshape(st.size, -1)
+        self.ctx._chk(self.ctx.lib.stvo_seq_import_streams(self.h, st.size, _ptr(st), blobs.ctypes.data_as(C.c_void_p), blobs.shape[1]))
+
+    def import_streams_dev(self, streams, blob_ptr, blob_stride):
+        """The same from device memory (blob i at blob_ptr + i * blob_stride); synchronises once for the headers, then enqueues."""
+        st = self._streams(streams)
+        self.ctx._chk(self.ctx.lib.stvo_seq_import_streams_dev(self.h, st.size, _ptr(st), C.c_void_p(blob_ptr), int(blob_stride)))
 
     def read(self):
         res = np.zeros(self.B, dtype=POSE_RESULT_DTYPE)

@@ -202,6 +202,30 @@ class ImagePipeline:
     def read_keyframe(self, b):
         return self.seq.read_keyframe(b)
 
+    def export_streams(self, streams):
+        """(blobs uint8 [n, bytes], thresholds int32 [n] or None): everything the named streams carry into the next pair
+        (Sequences.export_streams) and, with adaptive_fast, the FAST threshold their next detection reads — the caller's array, so it
+        travels beside the blob.  Synchronises."""
+        blobs = self.seq.export_streams(streams)   # (synchronises the context's stream: the rule behind the last step has run)
+        th = None
+        if self.fast_th is not None:
+            th = self.fast_th.cpu().numpy()[np.asarray(streams, np.int64).reshape(-1)].astype(np.int32)
+        return blobs, th
+
+    def import_streams(self, streams, blobs, fast_thresholds=None):
+        """The named streams continue from `blobs` (Sequences.import_streams: of this or another pipeline with the same features,
+        camera and parameters); with adaptive_fast, fast_thresholds [n] become their thresholds (None: fast_threshold, as for a
+        restarted stream).  The thresholds are written between two synchronisations of the context's stream and of torch's, which
+        orders the write behind the rule of the last step and in front of the next detection."""
+        self.seq.import_streams(streams, blobs)    # (synchronises the context's stream)
+        if self.fast_th is not None:
+            idx = torch.as_tensor(np.asarray(streams, np.int64).reshape(-1), device=self.fast_th.device)
+            th = np.full(idx.numel(), self.fast_threshold, np.int32) if fast_thresholds is None else np.asarray(fast_thresholds, np.int32).reshape(-1)
+            if th.size != idx.numel():
+                raise ValueError("ImagePipeline.import_streams: one threshold per stream")
+            self.fast_th[idx] = torch.as_tensor(th, device=self.fast_th.device)
+            torch.cuda.current_stream(self.fast_th.device).synchronize()
+
     def fast_thresholds(self):
         """Host copy of the per-stream FAST thresholds the NEXT detection will read (synchronises); tests and tools."""
         if self.fast_th is None:
