@@ -27,7 +27,7 @@
 //     of a query is two VGPRs per lane and the final cross-lane merge is a single swap of the wave halves.
 //   * bit -> K element mapping: K step kk covers descriptor words 2 kk (lower wave half) and 2 kk + 1 (upper); dword d of a
 //     lane's fragment holds bits d, d + 4, ..., d + 28 of its word as nibbles: ((w << (3 - d)) & 0x88888888) | 0x66666666 —
-//     shift + and-or per eight elements.  Any mapping works as long as both operands use the same one (a sum over k).
+//     and + shift-or per eight elements in the forward scan (expand_fp4_lshl_or).  Any mapping works as long as both operands use the same one (a sum over k).
 #include <type_traits>
 
 #include "kernels.h"
@@ -61,6 +61,19 @@ __device__ __forceinline__ v4i expand_fp4(uint32_t w) {
     r.w = (int)((w & 0x88888888u) | 0x66666666u);
     return r;
 }
+// The same nibbles for the forward scan's tile loop, where every vector operation counts: written as above the compiler emits
+// shift + and + or per dword (11 operations; gfx950's VOP3 takes no literal, so no v_and_or_b32 forms).  Masking FIRST leaves
+// (w & (0x11111111 << d)) << (3 - d) | 0x66666666 = one v_and_b32 with a literal and one v_lshl_or_b32 whose shift is an inline
+// constant and whose third operand is a scalar register: 8 operations.
+__device__ __forceinline__ v4i expand_fp4_lshl_or(uint32_t w) {
+    const uint32_t base = 0x66666666u;
+    v4i r;
+    asm("v_lshl_or_b32 %0, %1, 3, %2" : "=v"(r.x) : "v"(w & 0x11111111u), "s"(base));
+    asm("v_lshl_or_b32 %0, %1, 2, %2" : "=v"(r.y) : "v"(w & 0x22222222u), "s"(base));
+    asm("v_lshl_or_b32 %0, %1, 1, %2" : "=v"(r.z) : "v"(w & 0x44444444u), "s"(base));
+    r.w = (int)((w & 0x88888888u) | base);
+    return r;
+}
 __device__ __forceinline__ float med3_f32(float a, float b, float c) {
     float r;
     asm("v_med3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
@@ -81,7 +94,7 @@ __device__ __forceinline__ float min3_f32(float a, float b, float c) {
     asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
-constexpr float MF_NO_KEY_F = 1.0e30f;      // the float form's sentinel: rebasing by -32 never changes it
+constexpr float MF_NO_KEY_F = 1.0e30f;      // the float form's sentinel: rebasing by -32 / -64 never changes it
 constexpr float MF_NO_KEY_MIN_F = 1.0e29f;
 constexpr int MF_SCALE_2_4 = 127 + 4;       // E8M0 block scale 2^4 on both operands: (+-4 * 16)^2 = 4096
 
@@ -121,10 +134,15 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
     const int L = blockIdx.x;
     const int xcd = L & 7, k = L >> 3;
     int fb = k / per_frame, local = k % per_frame;
-    if (MODE == 0 && ndir == 1 && tiles > 1) {
-        // forward scan: the LAST query tile of a frame is the partial one (its workgroups are the shortest) — all of them go to the
-        // end of the launch, so that the final, partly filled dispatch round consists of short workgroups (1024 frames of ~1650
-        // rows: 6144 full workgroups = 8.0 rounds of 768 slots, then the 1024 partial ones; 0.551 -> 0.499 ms)
+    // Forward scan, which workgroup takes which query tile — decided from the frame's OWN row count, the host knows none:
+    // a frame has tiles - 1 slots in the MAIN section of the launch and one in the END section (all frames' end slots behind
+    // all main slots).  With full = nq / ROWS, main slot j takes tile j if j < min(full, tiles - 1) and leaves otherwise; the
+    // end slot takes tile min(full, tiles - 1) if it has rows: the ragged tile, or the last full one of a frame that fills its
+    // capacity.  The main section then holds full tiles only and the launch ends on the short workgroups at every capacity and
+    // row count (1647 rows in slots of 2048: main slots 0 - 5 scan, slot 6 leaves, the end slot scans the 111 rows of tile 6).
+    const bool remap = MODE == 0 && ndir == 1 && tiles > 1;
+    bool end_slot = false;
+    if (remap) {
         const int groups = (int)(gridDim.x >> 3) / per_frame;  // frames per XCD
         const int full_pf = (tiles - 1) * nseg, full = full_pf * groups;
         if (k < full) {
@@ -133,24 +151,25 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
         } else {
             fb = (k - full) / nseg;
             local = full_pf + (k - full) % nseg;
+            end_slot = true;
         }
     }
     const int b = fb * 8 + xcd;
     if (b >= B) return;
     const int seg = local % nseg;
     const int dir = dir0 + (local / nseg) / tiles;
-    const int tile = (local / nseg) % tiles;
+    const int slot = (local / nseg) % tiles;
     const size_t frame_off = (size_t)b * row_stride;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, col = lane & 31, hf = lane >> 5;
-    const int q_base = tile * ROWS;
     const uint32_t* __restrict__ Q = reinterpret_cast<const uint32_t*>((dir == 0 ? d1 : d2) + frame_off * STVO_DESC_BYTES);
-    // The query rows of the forward scan do not depend on the frame's row counts: fetch them while n1 / n2 are still on
-    // their way (rows past the count are inside the frame's slot, are scanned like any other row and never stored).
+    // A slot that knows its tile before the counts arrive fetches its query rows while n1 / n2 are still on their way (rows
+    // past the count are inside the frame's slot, are scanned like any other row and never stored).  An end slot learns its
+    // tile from the count and fetches behind it; one that leaves requests nothing.
     uint4 qw[QB][2];
-    if (!GATHER) {
+    if (!GATHER && !end_slot) {
 #pragma unroll
         for (int qb = 0; qb < QB; ++qb) {
-            const int qi = min(q_base + (wv * QB + qb) * 32 + col, row_stride - 1);
+            const int qi = min(slot * ROWS + (wv * QB + qb) * 32 + col, row_stride - 1);
             qw[qb][0] = reinterpret_cast<const uint4*>(Q)[2 * qi];
             qw[qb][1] = reinterpret_cast<const uint4*>(Q)[2 * qi + 1];
         }
@@ -162,21 +181,32 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
     const int seg_len = (((nt_all + nseg - 1) / nseg) + MF_TILE - 1) & ~(MF_TILE - 1);
     const int j0 = min(seg * seg_len, nt_all);
     const int nt = min(j0 + seg_len, nt_all);
-    if (claim_init && seg == 0 && dir == dir0)
-        for (int c = q_base + tid; c < min(q_base + ROWS, row_stride); c += MF_BLOCK) claim_init[frame_off + c] = 0xFFFFFFFFu;
+    if (claim_init && seg == 0 && dir == dir0)  // (by SLOT: rows 0 .. row_stride - 1 exactly once per frame, whichever tile the slot scans)
+        for (int c = slot * ROWS + tid; c < min((slot + 1) * ROWS, row_stride); c += MF_BLOCK) claim_init[frame_off + c] = 0xFFFFFFFFu;
+    int tile = slot;
+    if (remap) {
+        const int last = min(nq / ROWS, tiles - 1);
+        if (end_slot) tile = last;
+        else if (slot >= last) return;  // workgroup-uniform
+    }
+    const int q_base = tile * ROWS;
     if (q_base >= nq) return;  // workgroup-uniform
     const uint32_t* __restrict__ T = reinterpret_cast<const uint32_t*>((dir == 0 ? d2 : d1) + frame_off * STVO_DESC_BYTES);
     uint2* __restrict__ out = (dir == 0 ? knn12 : knn21) + (size_t)seg * B * row_stride + frame_off;
 
-    // query fragments: block qb of this wave = rows q_base + (wv * QB + qb) * 32 + col, kept for the whole scan
-    const bool wave_active = q_base + wv * QB * 32 < nq;
+    // A tile of at most ROWS / 2 rows (workgroup-uniform; under the remap only an end slot's) is scanned with ONE block per wave,
+    // rows q_base + 32 wv + col: all four waves work instead of two of them holding their registers idle through the scan.
+    const bool one_block = QB == 2 && nq - q_base <= ROWS / 2;
+    auto block_row = [&](int qb) { return q_base + (one_block ? wv : wv * QB + qb) * 32 + col; };
+    // query fragments: block qb of this wave, kept for the whole scan
+    const bool wave_active = block_row(0) - col < nq;
     v4i qf[QB][KSTEPS];
     auto query_row = [&](int qb) {  // recomputed for the final store rather than kept live across the scan
-        const int q = q_base + (wv * QB + qb) * 32 + col;
+        const int q = block_row(qb);
         const int qc = q < nq ? q : nq - 1;  // tail lanes scan a valid row and discard the result
         return GATHER ? qsel[frame_off + (qsel_from_back ? row_stride - 1 - qc : qc)] : qc;
     };
-    if (GATHER) {
+    if (GATHER || end_slot || one_block) {  // (the early fetch of a one-block tile outside the remap took the two-block rows)
 #pragma unroll
         for (int qb = 0; qb < QB; ++qb) {
             const int qi = query_row(qb);
@@ -195,12 +225,14 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
         qf[qb][3] = expand_fp4(~(up ? w[7] : w[6]));
     }
     // The train index enters through the C operand of the first matrix instruction of a tile: accumulator register r of
-    // this lane belongs to tile row (r & 3) + 8 (r >> 2) + 4 hf.  Keys are therefore TILE-RELATIVE (index - first row of
-    // the tile) and the running (best, second) are rebased by -32 per tile: 2 VALU ops per tile and query block instead
-    // of a ninth matrix instruction per block.
+    // this lane belongs to tile row (r & 3) + 8 (r >> 2) + 4 hf.  Keys are therefore relative to the first row of their PAIR
+    // of tiles (the second tile of a pair takes cidx + 32) and the running (best, second) are rebased by -64 per pair: 1 VALU
+    // op per tile and query block instead of a ninth matrix instruction per block (16 more registers: 168, the cap of three
+    // waves per SIMD, no scratch).
     acc_t cidx;
 #pragma unroll
     for (int r = 0; r < 16; ++r) cidx[r] = (key_t)((r & 3) + 8 * (r >> 2) + 4 * hf);
+    acc_t cidx2 = cidx + (key_t)MF_TILE;  // the second tile of a pair
 
     const key_t no_key = MF_NO_KEY_F;
     key_t best[QB], second[QB];
@@ -210,14 +242,19 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
     // staging role of this thread: word xk of train row xr of the tile
     const int xr = tid & 31, xk = tid >> 5;
     const int ntiles = (nt - j0 + MF_TILE - 1) / MF_TILE;
+    // A thread's word of tile t lies t KB behind its word of tile 0: a 32-bit byte offset against the frame's (scalar) base, one
+    // addition per fetch; only the segment's last tile can hold rows past its end, and only there a lane tests its row.
+    const uint32_t voff0 = (uint32_t)((j0 + xr) * 8 + xk) * 4u;
+    const int nfull = (nt - j0) / MF_TILE;
     auto fetch = [&](int t) -> uint32_t {
         const int j = j0 + t * MF_TILE + xr;
-        if (j >= nt) return 0u;
-        const int row = TGATHER ? tsel[frame_off + j] : j;
-        return T[(size_t)row * 8 + xk];
+        if (TGATHER) return j < nt ? T[(size_t)tsel[frame_off + j] * 8 + xk] : 0u;
+        const uint32_t* p = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(T) + (voff0 + (uint32_t)t * (MF_TILE * STVO_DESC_BYTES)));
+        if (t < nfull) return *p;
+        return j < nt ? *p : 0u;
     };
     auto stage = [&](int t, uint32_t w) {
-        s_tile[t & (NBUF - 1)][xk * 32 + xr] = expand_fp4(w);  // word xk = K step xk / 2, wave half xk & 1
+        s_tile[t & (NBUF - 1)][xk * 32 + xr] = expand_fp4_lshl_or(w);  // word xk = K step xk / 2, wave half xk & 1
     };
 #pragma unroll
     for (int i = 0; i < MF_TPB; ++i)
@@ -226,12 +263,13 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
     // Software pipeline, depth one tile: step t issues the matrix instructions of tile t and, in their shadow, folds the
     // accumulators of tile t - 1 into (best, second) — a v_mfma occupies the matrix pipe for 8 passes while the wave's
     // VALU slots stay free.  Only the last tile of a segment can be ragged and it is folded after the loop (masked).
-    auto rebase = [&]() {  // (best, second) relative to the next tile; the no-key sentinel stays far above any key
+    auto rebase = [&](int nb) {  // (best, second) relative to the next PAIR of tiles; the no-key sentinel stays far above any key
 #pragma unroll
-        for (int qb = 0; qb < QB; ++qb) {
-            best[qb] -= (key_t)MF_TILE;
-            second[qb] -= (key_t)MF_TILE;
-        }
+        for (int qb = 0; qb < QB; ++qb)
+            if (qb < nb) {
+                best[qb] -= (key_t)(2 * MF_TILE);
+                second[qb] -= (key_t)(2 * MF_TILE);
+            }
     };
     auto fold = [&](int qb, key_t key) {
         second[qb] = med3_f32(best[qb], second[qb], key);
@@ -241,19 +279,26 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
         const v8i a8 = {tf.x, tf.y, tf.z, tf.w, 0, 0, 0, 0}, b8 = {q.x, q.y, q.z, q.w, 0, 0, 0, 0};  // (FP4 reads four dwords)
         return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, MF_SCALE_2_4, 0, MF_SCALE_2_4);
     };
-    auto mma_fold = [&](acc_t (&cur)[QB], acc_t (&prev)[QB], int t) {
+    // NB blocks of this wave take part: QB, or 1 in the one-block form of a small tile — a compile-time constant per copy of the
+    // scan (below), so that either copy is straight-line code for the instruction groups at the end of a K step.
+    // FOLD: 0 = the first tile of a scan (nothing to fold yet), 1 = the tile behind it, 2 = every later tile.
+    // ODD: the second tile of a pair — its keys are relative to the pair's first row (C operand cidx + 32), and in front of its folds,
+    // which take the pair's first tile, (best, second) move from the previous pair's frame to this one.
+    auto mma_fold = [&](auto nb_c, auto fold_c, auto odd_c, acc_t (&cur)[QB], acc_t (&prev)[QB], int t) {
+        constexpr int NB = decltype(nb_c)::value, FOLD = decltype(fold_c)::value;
+        constexpr bool ODD = decltype(odd_c)::value;
+        constexpr bool fold_prev = FOLD > 0;  // tile t - 1 is a full tile here
         if (wave_active) {
             const v4i* frag = s_tile[t & (NBUF - 1)];
-            const bool fold_prev = t > 0;  // tile t - 1 is a full tile here
-            if (fold_prev) rebase();
-            key_t node[QB][5];
+            if (ODD && FOLD == 2) rebase(NB);  // (in the first pair they hold no key yet)
+            key_t node[NB][5];
             v4i tf = frag[lane];
 #pragma unroll
             for (int kk = 0; kk < KSTEPS; ++kk) {
                 v4i tf_ahead = tf;
                 if (kk < KSTEPS - 1) tf_ahead = frag[(kk + 1) * 64 + lane];  // one K step ahead of its use
 #pragma unroll
-                for (int qb = 0; qb < QB; ++qb) cur[qb] = mma(tf, qf[qb][kk], kk == 0 ? cidx : cur[qb]);
+                for (int qb = 0; qb < NB; ++qb) cur[qb] = mma(tf, qf[qb][kk], kk == 0 ? (ODD ? cidx2 : cidx) : cur[qb]);
                 if (fold_prev) {
                     // The fold as a TOURNAMENT of three-input nodes (round 5, last change).  The 16 keys of the previous tile and the
                     // running best are the 17 leaves of a tree of eight nodes; a node forms the smallest of its three inputs (v_min3,
@@ -270,11 +315,16 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
                     // of its destination.  With QB >= 2 the distance is structural — behind the last matrix instruction of a block's
                     // previous tile come its share of the fold, the other blocks' matrix instructions and folds, the rebasing and this
                     // tile's first matrix instruction (>= 14 counted conservatively; the ISA check fails the CPU suite below 12).  With one
-                    // block per wave (developer switch) only five fold operations and the rebasing lie between: an explicit fence, tied to
-                    // the registers, as in the reverse kernel.
-                    if (QB == 1 && kk == 0) asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 2" : "+v"(prev[0]));
+                    // block per wave (the one-block form of a small tile, and the developer switch) only five fold operations and the
+                    // rebasing lie between: an explicit fence, tied to the registers, as in the reverse kernel.  The same fence stands in
+                    // the SECOND tile of a scan: the first one folds nothing, its matrix instructions stand back to back.
+                    if ((NB == 1 || FOLD == 1) && kk == 0) {
+                        asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 2" : "+v"(prev[0]));
 #pragma unroll
-                    for (int qb = 0; qb < QB; ++qb) {
+                        for (int qb = 1; qb < NB; ++qb) asm volatile("" : "+v"(prev[qb]));  // (behind the fence: volatile asm keeps its order)
+                    }
+#pragma unroll
+                    for (int qb = 0; qb < NB; ++qb) {
                         const acc_t& p = prev[qb];
                         key_t(&a)[5] = node[qb];
                         if (kk == 0) {
@@ -299,7 +349,7 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
                 }
                 if (kk < KSTEPS - 1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);       // 1 LDS read (the next step's fragment)
 #pragma unroll
-                for (int qb = 0; qb < QB; ++qb) {  // (one instruction, then its share of the fold: with FP4 operands a matrix instruction
+                for (int qb = 0; qb < NB; ++qb) {  // (one instruction, then its share of the fold: with FP4 operands a matrix instruction
                                                    //  lasts about as long as the 8 fold operations of one block take to issue — 0.418 ->
                                                    //  0.401 ms per 1024 frames against QB instructions followed by all of the fold)
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                         // one matrix instruction
@@ -307,6 +357,9 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
                 }
                 tf = tf_ahead;
             }
+            // A tile is a scheduling region of its own: the instruction groups above hold only as long as no fold of the NEXT tile (an
+            // inline-asm read of the accumulators written just above) can be drawn into this tile's slots when two tiles share a basic block.
+            __builtin_amdgcn_sched_barrier(0);
         }
     };
     acc_t accA[QB], accB[QB];
@@ -331,43 +384,50 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
         w_near[i] = 0;
         if (MF_TPB + i < ntiles) w_near[i] = fetch(MF_TPB + i);
     }
-    for (; t + MF_TPB <= ntiles; t += MF_TPB) {
-        uint32_t w_far[MF_TPB];
+    // The scan exists twice, chosen per workgroup: QB blocks per wave, and ONE block per wave for a tile of at most ROWS / 2 rows.
+    // Both copies carry the same state through the loop (the one-block copy leaves the second block's registers alone).
+    auto scan = [&](auto nb_c) {
+        constexpr int NB = decltype(nb_c)::value;
+        auto group = [&](auto first_c) {  // MF_TPB tiles between two workgroup barriers; `first`: tiles 0 .. MF_TPB - 1
+            constexpr bool FIRST = decltype(first_c)::value;
+            uint32_t w_far[MF_TPB];
 #pragma unroll
-        for (int i = 0; i < MF_TPB; ++i) {
-            w_far[i] = 0;
-            if (t + 2 * MF_TPB + i < ntiles) w_far[i] = fetch(t + 2 * MF_TPB + i);
-        }
-#pragma unroll
-        for (int i = 0; i < MF_TPB; ++i) {
-            if ((i & 1) == 0) mma_fold(accA, accB, t + i);
-            else mma_fold(accB, accA, t + i);
-        }
-#pragma unroll
-        for (int i = 0; i < MF_TPB; ++i) {
-            if (t + MF_TPB + i < ntiles) stage(t + MF_TPB + i, w_near[i]);
-            w_near[i] = w_far[i];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < MF_TPB - 1; ++i)  // the last, partly filled group: its tiles are staged already (t is even here)
-        if (t + i < ntiles) {
-            if ((i & 1) == 0) mma_fold(accA, accB, t + i);
-            else mma_fold(accB, accA, t + i);
-        }
-    if (wave_active && ntiles > 0) {  // drain: the last tile, rows past the segment end carry no key
-        const int jt = j0 + (ntiles - 1) * MF_TILE;
-        const acc_t(&last)[QB] = (ntiles & 1) ? accA : accB;
-        rebase();
-#pragma unroll
-        for (int qb = 0; qb < QB; ++qb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int jr = jt + (r & 3) + 8 * (r >> 2) + 4 * hf;
-                fold(qb, jr < nt ? last[qb][r] : no_key);
+            for (int i = 0; i < MF_TPB; ++i) {
+                w_far[i] = 0;
+                if (t + 2 * MF_TPB + i < ntiles) w_far[i] = fetch(t + 2 * MF_TPB + i);
             }
-    }
+            static_assert(MF_TPB == 2, "the accumulator sets alternate tile by tile, two tiles per group");
+            mma_fold(nb_c, std::integral_constant<int, (FIRST ? 0 : 2)>{}, std::false_type{}, accA, accB, t);
+            mma_fold(nb_c, std::integral_constant<int, (FIRST ? 1 : 2)>{}, std::true_type{}, accB, accA, t + 1);
+#pragma unroll
+            for (int i = 0; i < MF_TPB; ++i) {
+                if (t + MF_TPB + i < ntiles) stage(t + MF_TPB + i, w_near[i]);
+                w_near[i] = w_far[i];
+            }
+            __syncthreads();
+            t += MF_TPB;
+        };
+        if (MF_TPB <= ntiles) group(std::true_type{});
+        while (t + MF_TPB <= ntiles) group(std::false_type{});
+        if (t < ntiles) {  // its tile is staged already (t is even here)
+            if (t == 0) mma_fold(nb_c, std::integral_constant<int, 0>{}, std::false_type{}, accA, accB, t);
+            else mma_fold(nb_c, std::integral_constant<int, 2>{}, std::false_type{}, accA, accB, t);
+        }
+        if (wave_active && ntiles > 0) {  // drain: the last tile, rows past the segment end carry no key
+            const int jt = j0 + (ntiles - 1) * MF_TILE;
+            const acc_t(&last)[QB] = (ntiles & 1) ? accA : accB;
+            if (ntiles & 1) rebase(NB);  // (the last tile opens a pair of its own)
+#pragma unroll
+            for (int qb = 0; qb < NB; ++qb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int jr = jt + (r & 3) + 8 * (r >> 2) + 4 * hf;
+                    fold(qb, jr < nt ? last[qb][r] : no_key);
+                }
+        }
+    };
+    if (one_block) scan(std::integral_constant<int, 1>{});
+    else scan(std::integral_constant<int, QB>{});
     if (!wave_active) return;
     // the two wave halves hold the same query columns over different train rows: merge, lower half writes
 #pragma unroll
@@ -379,9 +439,9 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
         const int hi = max(bi, ob);
         const int sec = min(min(si, os), hi);
         const int bst = min(bi, ob);
-        const int q = q_base + (wv * QB + qb) * 32 + col;
-        const int base = j0 + (ntiles - 1) * MF_TILE;  // the frame of the last rebasing
-        if (hf == 0 && q < nq) out[query_row(qb)] = make_uint2(key_to_knn(bst, base), key_to_knn(sec, base));
+        const int q = block_row(qb);
+        const int base = j0 + ((ntiles - 1) & ~1) * MF_TILE;  // the frame of the last rebasing: the first row of the last pair of tiles
+        if (hf == 0 && q < nq && (qb == 0 || !one_block)) out[query_row(qb)] = make_uint2(key_to_knn(bst, base), key_to_knn(sec, base));
     }
 }
 
