@@ -23,6 +23,7 @@
 
 #include "ctx_internal.h"
 #include "fast_atan2.h"
+#include "orb_rotate.h"
 
 #pragma clang fp contract(off)
 
@@ -802,25 +803,6 @@ __global__ __launch_bounds__(BL_T) void orb_blur_kernel(OrbDev o, BlurK kk) {
     }
 }
 
-// sine and cosine of a float angle in [0, 2 pi] in double precision (the routine of lsd_kernels.hip / oracle/stvo_lsd_oracle.c)
-__device__ __forceinline__ void orb_sincos(float xf, double& s, double& c) {
-    const double x = (double)xf;
-    const double PIO2_HI = 1.57079632679489655800e+00, PIO2_LO = 6.12323399573676603587e-17, TWO_OVER_PI = 6.36619772367581382433e-01;
-    const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
-                 S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
-    const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
-                 C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
-    const double k = __builtin_rint(x * TWO_OVER_PI);
-    double r = __builtin_fma(-k, PIO2_HI, x);
-    r = __builtin_fma(-k, PIO2_LO, r);
-    const double z = r * r;
-    const double sn = r + (z * r) * (S1 + z * (S2 + z * (S3 + z * (S4 + z * (S5 + z * S6)))));
-    const double cs = 1.0 - (0.5 * z - z * (z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6)))))));
-    const int q = (int)k & 3;
-    s = q == 0 ? sn : (q == 1 ? cs : (q == 2 ? -sn : -cs));
-    c = q == 0 ? cs : (q == 1 ? -sn : (q == 2 ? -cs : sn));
-}
-
 struct Umax {
     int u[ORB_HP + 2];
 };
@@ -948,12 +930,10 @@ __global__ __launch_bounds__(256) void orb_describe_kernel(OrbDev o, Umax um) {
 #pragma unroll
     for (int j = 0; j < BW_N; ++j) patch[l + 16 * j] = bw[j];  // (unconditional: the row is padded to 16 x BW_N words)
     // computeOrbDescriptors, WTA_K = 2: lane l evaluates tests 16 l .. 16 l + 15 = bytes 2 l, 2 l + 1 of the descriptor
-    const float rad = ang * (float)(3.14159265358979323846 / 180.0);
-    // (float)cos((double)rad), (float)sin((double)rad): one Cody-Waite + kernel-polynomial evaluation (within an ulp of the library's
-    // double results, i.e. the same floats except on rounding ties) instead of two library calls of ~100 instructions each
-    double sd, cd;
-    orb_sincos(rad, sd, cd);
-    const float a = (float)cd, sb = (float)sd;
+    // (float)cos, (float)sin of the float radians in double precision, like the oracle's library calls (orb_rotate.h: the same floats, which
+    // tests/cpp/orb_rotate_host_main.cpp holds for every float angle in [0, 360])
+    float a, sb;
+    orb_rotation(ang, a, sb);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -965,8 +945,8 @@ __global__ __launch_bounds__(256) void orb_describe_kernel(OrbDev o, Umax um) {
         const int w = pat[t];
         const float px0 = (float)(int8_t)(w & 0xFF), py0 = (float)(int8_t)((w >> 8) & 0xFF);
         const float px1 = (float)(int8_t)((w >> 16) & 0xFF), py1 = (float)(int8_t)((w >> 24) & 0xFF);
-        const int ix0 = __float2int_rn(px0 * a - py0 * sb), iy0 = __float2int_rn(px0 * sb + py0 * a);
-        const int ix1 = __float2int_rn(px1 * a - py1 * sb), iy1 = __float2int_rn(px1 * sb + py1 * a);
+        const int ix0 = ORB_ROTATE_X(px0, py0, a, sb), iy0 = ORB_ROTATE_Y(px0, py0, a, sb);
+        const int ix1 = ORB_ROTATE_X(px1, py1, a, sb), iy1 = ORB_ROTATE_Y(px1, py1, a, sb);
         const int t0 = bl[iy0 * (DESC_PW * 4) + ix0], t1 = bl[iy1 * (DESC_PW * 4) + ix1];
         bits |= (uint32_t)(t0 < t1) << t;
     }
