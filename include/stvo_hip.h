@@ -279,7 +279,9 @@ typedef struct stvo_orb stvo_orb;
 int stvo_orb_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keypoints, const stvo_orb_params* prm, stvo_orb** out);
 int stvo_orb_destroy(stvo_orb* orb);
 /* The 256 x 4 test pattern (x0, y0, x1, y1 per bit, |coordinate| <= 13).  The default is a seeded table; OpenCV's learned
- * table (bit_pattern_31_ of features2d/src/orb.cpp) is data this repository does not hold — pass it here to reproduce it. */
+ * table (bit_pattern_31_ of features2d/src/orb.cpp) is data this repository does not hold — pass it here to reproduce it.
+ * It is the pool of patch size 31: under another setting of stvo_orb_set_descriptor the effective pattern is derived from it again
+ * (wta_k 3 / 4 refuse a pool with fewer different points than a tuple holds), and at another patch size it is kept but not read. */
 int stvo_orb_set_pattern(stvo_orb* orb, const int8_t* pattern /*[1024]*/);
 /* The FAST threshold of the following calls: StereoFrameHandler::updateFrame adapts orb_fast_th frame by frame
  * (src/stereoFrameHandler.cpp:66-86) and passes it to detectStereoFeatures (:56 -> src/stereoFrame.cpp:59,104-118). */
@@ -300,6 +302,27 @@ int stvo_orb_set_fast_thresholds(stvo_orb* orb, const int32_t* th_host, int n_th
  * share) on that response — ties kept at both cuts, row-major order as above — and `response` is the Harris response.  n_total then
  * counts the key-points that pass the second cut.  Any other value: STVO_ERR_INVALID_ARG.  Applies to all four detect entry points. */
 int stvo_orb_set_score_type(stvo_orb* orb, int score_type);
+/* The descriptor of the following calls, cv::ORB::create's WTA_K = Config::orbWtaK() and patchSize = Config::orbPatchSize()
+ * (src/stereoFrame.cpp:112-114); the default is (2, 31).  Applies to all four detect entry points and to both rankings; FAST, the
+ * suppression, the rankings, the level budgets, the blur, the pyramid and the order of the key-points do not depend on either value, and
+ * key-points are filtered by edge_threshold alone, as in OpenCV.
+ *   patch_size P, 2 .. 63: the intensity-centroid angle is taken on the disc of half patch P / 2 (umax as for 15).  The pool of 512 test
+ *     points is the pattern of stvo_orb_set_pattern at P = 31 and OpenCV's makeRandomPattern (RNG(0x34985739), coordinates uniform in
+ *     -P / 2 .. P / 2) at every other P, where the learned table plays no part.
+ *   wta_k 2: 256 tests on the pool's points in pairs, as before.  wta_k 3 / 4: initializeOrbPattern — 128 tuples of 3 / 4 pairwise
+ *     different points drawn from the pool with RNG(0x12345678); the descriptor holds, four tuples per byte, the index of the tuple's
+ *     largest blurred intensity (ties go to the earlier point exactly as OpenCV's strict comparisons send them).  Still 32 bytes.
+ * Every pixel read lies inside the level image, so for P != 31 the setting needs edge_threshold >= ceil((P / 2) sqrt 2): P <= 27 at the
+ * shipped orb_edge_th 19, 44 for P = 63 (P = 31 keeps the reach 19 stvo_orb_create requires).  STVO_ERR_INVALID_ARG: wta_k outside
+ * 2 .. 4, patch_size < 2, the border rule; STVO_ERR_UNSUPPORTED: patch_size > 63.  A refused call changes nothing.  Synchronises the
+ * context's stream.  Parity with OpenCV itself is unpinned: the algorithm is restated, csrc/orb_pattern.h. */
+int stvo_orb_set_descriptor(stvo_orb* orb, int wta_k, int patch_size);
+/* HOST ONLY, no context: the effective point list of a setting — out[1024] = n_points (x, y) pairs (512 / 384 / 512 for wta_k 2 / 3 / 4),
+ * zero beyond them — and the verdicts of stvo_orb_set_descriptor except the border rule, which needs a detector.  pool: the 1024-byte
+ * pattern stvo_orb_set_pattern would be given (NULL: the seeded stand-in); it is read at patch_size 31 only, where a pool outside
+ * -13 .. 13, or with fewer different points than a tuple holds, is STVO_ERR_INVALID_ARG.  n_points may be NULL. */
+int stvo_orb_pattern(int wta_k, int patch_size, const int8_t* pool /*[1024] or NULL*/, int8_t* out /*[1024]*/, int32_t* n_points);
+/* The effective point list of the setting in force (stvo_orb_pattern's `out`): the pattern itself under (2, 31). */
 int stvo_orb_get_pattern(const stvo_orb* orb, int8_t* pattern /*[1024]*/);
 /* Host buffers in / out, synchronises.  images [B][rows][cols]; kp_xy [B][max_keypoints][2] = cv::KeyPoint::pt; response =
  * cv::KeyPoint::response (FAST score, or the Harris response under STVO_ORB_SCORE_HARRIS); angle in degrees = cv::KeyPoint::angle; desc [B][max_keypoints][32]; n_kp [B]. */

@@ -148,8 +148,9 @@ typedef struct stvo_frame_features {
 } stvo_frame_features;
 
 /* Parameters of the ORB point front-end = the cv::ORB::create arguments the reference passes (src/stereoFrame.cpp:112-114)
- * that vary between its configurations; fixed here: WTA_K 2 and patch size 31 (other values of orb_wta_k / orb_patch_size need
- * OpenCV's RNG-derived test pattern: not built).  The ranking, orb_score, is chosen with stvo_orb_set_score_type (default FAST_SCORE). */
+ * that vary between its configurations.  The ranking, orb_score, is chosen with stvo_orb_set_score_type (default FAST_SCORE); WTA_K and
+ * the patch size, orb_wta_k / orb_patch_size, with stvo_orb_set_descriptor (default 2 and 31; built: 2 / 3 / 4 and 2 .. 63, a patch size
+ * other than 31 under the border rule edge_threshold >= ceil((patch_size / 2) sqrt 2); patch sizes above 63 are not built). */
 #define STVO_ORB_MAX_LEVELS 8
 #define STVO_ORB_SCORE_HARRIS 0 /* cv::ORB::HARRIS_SCORE */
 #define STVO_ORB_SCORE_FAST 1   /* cv::ORB::FAST_SCORE   */

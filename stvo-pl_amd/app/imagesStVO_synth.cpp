@@ -398,8 +398,13 @@ int main(int argc, char** argv) {
         }
         const Image gl{img_l.data(), rows, cols, channels, (size_t)cols * channels}, gr{img_r.data(), rows, cols, channels, (size_t)cols * channels};
         if (frame_counter == 0) {
-            if (image_file) StVO->initialize(gl, gr, 0);  // initialize(img_l, img_r, 0), imagesStVO.cpp:90
-            else StVO->initialize(feat, 0);
+            try {  // (a configuration the front-ends refuse — e.g. an orb_patch_size the border does not admit — ends the run here)
+                if (image_file) StVO->initialize(gl, gr, 0);  // initialize(img_l, img_r, 0), imagesStVO.cpp:90
+                else StVO->initialize(feat, 0);
+            } catch (const std::exception& e) {
+                std::cerr << e.what() << std::endl;
+                return -2;
+            }
             kf_pt.assign(StVO->prev_frame->stereo_pt.size(), 1);  // initialize: the first frame is a key-frame
             kf_ls.assign(StVO->prev_frame->stereo_ls.size(), 1);
             continue;

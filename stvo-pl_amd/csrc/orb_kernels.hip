@@ -1,8 +1,9 @@
 // orb_kernels.hip — the ORB point front-end on gfx950: what the reference obtains from
 //     cv::ORB::create(...)->detectAndCompute(img, Mat(), points, pdesc, false)     (/root/reference/src/stereoFrame.cpp:104-118)
 // for orb_nlevels pyramid levels (config_kitti.yaml: 1; config_euroc.yaml / src/config.cpp:96-97: 4 at scale 1.2), FAST_SCORE
-// ranking (orb_score 1, the default) or HARRIS_SCORE ranking (orb_score 0: stvo_orb_set_score_type), WTA_K 2, patch 31 (other
-// values of orb_wta_k / orb_patch_size need OpenCV's RNG-derived test pattern and are not built).  Per level:
+// ranking (orb_score 1, the default) or HARRIS_SCORE ranking (orb_score 0: stvo_orb_set_score_type), WTA_K 2 and patch 31 by default,
+// orb_wta_k 2 / 3 / 4 and orb_patch_size 2 .. 63 with stvo_orb_set_descriptor (OpenCV's RNG-derived test patterns: csrc/orb_pattern.h;
+// a patch size other than 31 needs orb_edge_th >= ceil((P / 2) sqrt 2), and patch sizes above 63 are not built).  Per level:
 //   orb_fast_nms_kernel  FAST-9/16 score (cornerScore<16>) + 3x3 non-maximum suppression + border filter per 64 x 64 tile, all in
 //                        LDS: compass-point rejection, candidates compacted so that the full score runs on dense lanes;
 //                        survivors go to a per-image list + response histogram (no score map in global memory)
@@ -10,11 +11,14 @@
 //   orb_harris_kernel    (orb_score 0 only) HarrisResponses of the 2 n FAST-best key-points, 8 lanes per key-point; the ordering
 //                        kernel then cuts at the exact n-th largest response (radix select on the float keys, ties kept)
 //   orb_blur_kernel      GaussianBlur 7x7, sigma 2, 8-bit fixed point, BORDER_REFLECT_101
-//   orb_describe_kernel  intensity-centroid angle (ICAngles, fastAtan2) + rotated BRIEF, one wave per key-point
+//   orb_describe_kernel  intensity-centroid angle (ICAngles, fastAtan2) + rotated BRIEF, 16 lanes per key-point: (WTA_K 2, patch 31) only
+//   orb_describe_wta_kernel<WTA_K, reach>  the same for every other setting: any half patch, 2-bit fields for WTA_K 3 / 4, one wave per
+//                        key-point (six instances: WTA_K 2 / 3 / 4 x an LDS patch for reach <= 22 or <= 44)
 // around them (more than one level): orb_resize_kernel (level l from level l - 1, OpenCV's 8-bit bilinear resize in 11-bit fixed
 // point) and orb_concat_kernel (levels in order, coordinates x scale, octave = level).
 // OpenCV is third-party code that is not under /root/reference: the semantics are those of oracle/stvo_orb_oracle.c (a
-// restatement of OpenCV's algorithm, parity unpinned), against which these kernels are bit-exact (tests/test_gpu_orb.py).
+// restatement of OpenCV's algorithm, parity unpinned), against which these kernels are bit-exact (tests/test_gpu_orb.py); the settings
+// other than (2, 31) are pinned to the numpy statement tests/np_orb_wta.py in the same way (tests/test_gpu_orb_wta.py).
 // Integer / byte work throughout; the only floating point is the angle polynomial and the rotation of the test pattern, in
 // FP32 exactly as OpenCV evaluates them (no fused multiply-adds).
 #include <cmath>
@@ -23,6 +27,7 @@
 
 #include "ctx_internal.h"
 #include "fast_atan2.h"
+#include "orb_pattern.h"
 #include "orb_rotate.h"
 
 #pragma clang fp contract(off)
@@ -953,6 +958,137 @@ __global__ __launch_bounds__(256) void orb_describe_kernel(OrbDev o, Umax um) {
     if (valid) *reinterpret_cast<uint16_t*>(o.desc + kk * 32 + 2 * l) = (uint16_t)bits;
 }
 
+// Every descriptor setting other than (WTA_K 2, patch 31) — stvo_orb_set_descriptor — in place of orb_describe_kernel: ICAngles on the
+// disc of half patch h = P / 2, then the tests of the EFFECTIVE pattern (csrc/orb_pattern.h) on the blurred image, WTA_K 2 as above,
+// WTA_K 3 / 4 as the index of the largest of a tuple's 3 / 4 values in a 2-bit field (four tuples per byte).  ONE WAVE per key-point, four
+// key-points per workgroup, no workgroup barrier: a patch of up to 63 rows gives a row to every lane, 256 tests / 128 tuples give every
+// lane four bits of the descriptor, and at the largest patch (P = 63: 89 x 89 blurred bytes, reach 44) a workgroup holds 4 x 8188 bytes
+// of LDS — five workgroups fit the 160 KB of a CU.  RMAX is the largest reach an instance holds: 22 serves P <= 31 (2160 bytes per
+// key-point), 44 the rest.  The image patch (2 h + 1 rows) and the blurred patch (2 R + 1 rows, R = the reach of the setting) share the
+// buffer one after the other; rows are staged as unaligned words from the patch's first column on, so a word holds needed bytes from
+// its first byte and only the row's last word can look beyond the image buffer: it is read from the last word of the buffer and shifted.
+// Moments: a row's bytes are masked to the disc and summed with byte dot products into 32-bit sums (|m10| reaches 5.1e6 at h = 31).
+struct WtaArgs {
+    int h;                  // half patch
+    int R;                  // reach of the rotated pattern points: rows / columns y - R .. y + R of the blurred image are staged
+    const int8_t* pattern;  // the effective point list: 512 / 384 / 512 (x, y) pairs
+    const int8_t* umax;     // [h + 1]
+};
+constexpr int WTA_KP_PER_WG = 4;
+template <int WTA, int RMAX>
+__global__ __launch_bounds__(256) void orb_describe_wta_kernel(OrbDev o, WtaArgs wa) {
+    constexpr int PW = (2 * RMAX + 1 + 3) / 4, PH = 2 * RMAX + 1;  // words per row, rows
+    __shared__ uint32_t s_patch[WTA_KP_PER_WG][PH * PW];
+    const int xcd = blockIdx.x & 7, kq = blockIdx.x >> 3;  // (the XCD-aware grid of orb_describe_kernel)
+    const int bpi = (o.K + WTA_KP_PER_WG - 1) / WTA_KP_PER_WG;
+    const int b = (kq / bpi) * 8 + xcd, kb = kq % bpi;
+    if (b >= o.B) return;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int k = kb * WTA_KP_PER_WG + wave;
+    if (k >= o.n_kp[b]) return;  // wave-uniform; the kernel has no workgroup barrier
+    const int h = min(wa.h, RMAX), R = min(max(wa.R, h), RMAX);  // (validated on the host; the buffer is never left whatever arrives)
+    const size_t kk = (size_t)b * o.K + k;
+    const int x = (int)o.kp[2 * kk], y = (int)o.kp[2 * kk + 1];
+    const size_t base = (size_t)b * o.rows * o.cols;
+    const int off_hi = o.rows * o.cols - 4;
+    uint32_t* patch = s_patch[wave];
+    // rows y - r .. y + r, bytes x - r .. of `src` into the buffer: row i at word i * PW
+    auto stage = [&](const uint8_t* src, int r) {
+        const int nw = (2 * r + 1 + 3) / 4, n = (2 * r + 1) * nw;
+        const int org = (y - r) * o.cols + (x - r);
+        for (int i = lane; i < n; i += 64) {
+            const int row = i / nw, w = i - row * nw;
+            const int off = max(org + row * o.cols + 4 * w, 0);
+            const int over = min(max(off - off_hi, 0), 3);  // bytes by which the word would leave the buffer (the row's last word on the last rows)
+            patch[row * PW + w] = *reinterpret_cast<const u32_unaligned*>(src + min(off, off_hi)) >> (8 * over);
+        }
+    };
+    stage(o.img + base, h);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // ICAngles: lane r owns row r of the patch (dy = r - h); byte j of the row is column u = j - h
+    int m10 = 0, m01 = 0;
+    if (lane <= 2 * h) {
+        const int dy = lane - h, um = wa.umax[dy < 0 ? -dy : dy];
+        const uint32_t* row = patch + lane * PW;
+        const int nw = (2 * h + 1 + 3) / 4;
+        uint32_t s1 = 0u, su = 0u;
+        for (int w = 0; w < nw; ++w) {
+            uint32_t m = 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int u = 4 * w + j - h;
+                if ((u < 0 ? -u : u) <= um) m |= 0xFFu << (8 * j);
+            }
+            const uint32_t W = row[w] & m;
+            s1 = __builtin_amdgcn_udot4(W, 0x01010101u, s1, false);
+            su = __builtin_amdgcn_udot4(W, 0x03020100u + 0x04040404u * (uint32_t)w, su, false);  // weights u + h <= 63
+        }
+        m10 = (int)su - h * (int)s1;
+        m01 = dy * (int)s1;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        m10 += __shfl_xor(m10, off, 64);
+        m01 += __shfl_xor(m01, off, 64);
+    }
+    const float ang = fast_atan2_deg((float)m01, (float)m10);
+    if (lane == 0) o.angle[kk] = ang;
+    float a, sb;
+    orb_rotation(ang, a, sb);
+    // the blurred patch replaces the image patch (every lane is past its reads: the shuffles above synchronise the wave)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    stage(o.blur + base, R);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint8_t* bl = reinterpret_cast<const uint8_t*>(patch) + R * (PW * 4) + R;  // the key-point's own pixel
+    // lane l: tests 4 l .. 4 l + 3 (WTA_K 2) or tuples 2 l, 2 l + 1 (WTA_K 3 / 4) = bits 4 l .. 4 l + 3 of the descriptor
+    constexpr int NPT = WTA == 3 ? 6 : 8;  // points per lane: 12 / 16 bytes of the pattern
+    const uint32_t* pw = reinterpret_cast<const uint32_t*>(wa.pattern) + lane * (NPT / 2);
+    int t[NPT];
+#pragma unroll
+    for (int q = 0; q < NPT / 2; ++q) {
+        const uint32_t w = pw[q];
+        const float px0 = (float)(int8_t)(w & 0xFF), py0 = (float)(int8_t)((w >> 8) & 0xFF);
+        const float px1 = (float)(int8_t)((w >> 16) & 0xFF), py1 = (float)(int8_t)((w >> 24) & 0xFF);
+        // (clamped into the staged patch: a no-op for every pattern the host lets through)
+        const int ix0 = min(max(ORB_ROTATE_X(px0, py0, a, sb), -R), R), iy0 = min(max(ORB_ROTATE_Y(px0, py0, a, sb), -R), R);
+        const int ix1 = min(max(ORB_ROTATE_X(px1, py1, a, sb), -R), R), iy1 = min(max(ORB_ROTATE_Y(px1, py1, a, sb), -R), R);
+        t[2 * q] = bl[iy0 * (PW * 4) + ix0];
+        t[2 * q + 1] = bl[iy1 * (PW * 4) + ix1];
+    }
+    uint32_t nib = 0u;
+    if constexpr (WTA == 2) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) nib |= (uint32_t)(t[2 * j] < t[2 * j + 1]) << j;
+    } else if constexpr (WTA == 3) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int t0 = t[3 * j], t1 = t[3 * j + 1], t2 = t[3 * j + 2];
+            const uint32_t v = t2 > t1 ? (t2 > t0 ? 2u : 0u) : (uint32_t)(t1 > t0);
+            nib |= v << (2 * j);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            int t0 = t[4 * j], t2 = t[4 * j + 2];
+            const int t1 = t[4 * j + 1], t3 = t[4 * j + 3];
+            uint32_t va = 0u, vb = 2u;
+            if (t1 > t0) { t0 = t1; va = 1u; }
+            if (t3 > t2) { t2 = t3; vb = 3u; }
+            nib |= (t0 > t2 ? va : vb) << (2 * j);
+        }
+    }
+    // eight nibbles -> one word of the descriptor, written by every eighth lane
+    uint32_t word = nib | (__shfl_down(nib, 1, 64) << 4);
+    word |= __shfl_down(word, 2, 64) << 8;
+    word |= __shfl_down(word, 4, 64) << 16;
+    if ((lane & 7) == 0) *reinterpret_cast<uint32_t*>(o.desc + kk * 32 + (lane >> 1)) = word;
+}
+
 }  // namespace
 
 // the two 8-bit image operations other front-ends share (lsd_kernels.hip: the scaled image of the line detector)
@@ -993,8 +1129,13 @@ struct stvo_orb {
     char* dev = nullptr;  // every device array of the object, carved from one allocation
     char* io = nullptr;   // staging for the host-buffer entry point: images in, results out
     size_t io_bytes = 0;
-    int8_t pattern[1024];
+    int8_t pattern[1024];             // the pool of patch size 31 (stvo_orb_set_pattern; the stand-in by default)
     int8_t* d_pattern = nullptr;
+    // the descriptor setting (stvo_orb_set_descriptor).  (2, 31) runs orb_describe_kernel on d_pattern; every other setting runs
+    // orb_describe_wta_kernel on the effective pattern and the umax table of its half patch
+    int wta_k = 2, patch_size = 31;
+    int8_t effective[1024];           // what stvo_orb_get_pattern returns
+    int8_t* d_effective = nullptr;    // [1024] + umax [64], carved from dev
     int32_t* d_th_own = nullptr;  // [B] device copy behind stvo_orb_set_fast_thresholds (carved from dev)
     stvo::BlurK blur_k{};
     stvo::Umax umax{};
@@ -1002,18 +1143,8 @@ struct stvo_orb {
 
 namespace {
 
-void default_pattern(int8_t* pattern) {  // seeded stand-in for OpenCV's learned table (see stvo_orb_set_pattern)
-    uint32_t s = 31u;
-    for (int i = 0; i < 256; ++i) {
-        int v[4];
-        do {
-            for (int j = 0; j < 4; ++j) {
-                s = s * 1664525u + 1013904223u;
-                v[j] = (int)((s >> 16) % 27u) - 13;
-            }
-        } while (v[0] == v[2] && v[1] == v[3]);
-        for (int j = 0; j < 4; ++j) pattern[4 * i + j] = (int8_t)v[j];
-    }
+int pattern_verdict(int v) {
+    return v == stvo::ORB_PATTERN_OK ? STVO_OK : (v == stvo::ORB_PATTERN_UNSUPPORTED ? STVO_ERR_UNSUPPORTED : STVO_ERR_INVALID_ARG);
 }
 
 int cv_round_f(float v) { return (int)std::lrintf(v); }  // cvRound: half to even
@@ -1058,6 +1189,7 @@ int stvo_orb_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keypoints,
     auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
     size_t total = 1024;  // the pattern
     const size_t off_th = total; total += al((size_t)B * 4);
+    const size_t off_eff = total; total += al(1024 + 64);  // the effective pattern and umax of a descriptor setting other than (2, 31)
     size_t off_blur[STVO_ORB_MAX_LEVELS], off_hist[STVO_ORB_MAX_LEVELS], off_cand[STVO_ORB_MAX_LEVELS], off_hkey[STVO_ORB_MAX_LEVELS], off_nc[STVO_ORB_MAX_LEVELS],
         off_img[STVO_ORB_MAX_LEVELS], off_out[STVO_ORB_MAX_LEVELS];
     for (int l = 0; l < nlevels; ++l) {
@@ -1086,6 +1218,7 @@ int stvo_orb_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keypoints,
     }
     o->d_pattern = (int8_t*)o->dev;
     o->d_th_own = (int32_t*)(o->dev + off_th);
+    o->d_effective = (int8_t*)(o->dev + off_eff);
     for (int l = 0; l < nlevels; ++l) {
         stvo_orb::Level& L = o->lev[l];
         stvo::OrbDev& d = L.d;
@@ -1105,7 +1238,8 @@ int stvo_orb_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keypoints,
             L.n_tot = (int32_t*)q;
         }
     }
-    default_pattern(o->pattern);
+    stvo::orb_default_pool(o->pattern);
+    std::memcpy(o->effective, o->pattern, 1024);
     if (!upload_now(ctx, o->d_pattern, o->pattern, 1024, "hipMemcpy pattern")) {
         (void)hipFree(o->dev);
         delete o;
@@ -1119,14 +1253,7 @@ int stvo_orb_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keypoints,
             sum += k[i];
         }
         for (int i = 0; i < 7; ++i) o->blur_k.k[i] = (int)std::lrint((float)(k[i] / sum) * 256.0);
-        const int hp = stvo::ORB_HP;
-        const int vmax = (int)std::floor(hp * std::sqrt(2.0) / 2 + 1), vmin = (int)std::ceil(hp * std::sqrt(2.0) / 2);
-        for (int v = 0; v <= vmax; ++v) o->umax.u[v] = (int)std::lrint(std::sqrt((double)hp * hp - (double)v * v));
-        for (int v = hp, v0 = 0; v >= vmin; --v) {
-            while (o->umax.u[v0] == o->umax.u[v0 + 1]) ++v0;
-            o->umax.u[v] = v0;
-            ++v0;
-        }
+        stvo::orb_umax(stvo::ORB_HP, o->umax.u);
     }
     *out = o;
     return STVO_OK;
@@ -1146,11 +1273,55 @@ int stvo_orb_set_pattern(stvo_orb* o, const int8_t* pattern) {
     if (!o || !pattern) return STVO_ERR_INVALID_ARG;
     for (int i = 0; i < 1024; ++i)
         if (pattern[i] < -13 || pattern[i] > 13) return STVO_ERR_INVALID_ARG;  // rotated points must stay within the border
+    // the effective pattern of the setting in force is derived again (it depends on the pool only at patch size 31); a pool the
+    // setting cannot use — fewer different points than a tuple of WTA_K 3 / 4 holds — is refused and nothing changes
+    int8_t eff[1024];
+    if (o->patch_size == 31) {
+        const int v = pattern_verdict(stvo::orb_effective_pattern(o->wta_k, 31, pattern, eff, nullptr));
+        if (v != STVO_OK) return v;
+    } else {
+        std::memcpy(eff, o->effective, 1024);
+    }
     HIP_TRY(o->ctx, hipSetDevice(o->ctx->device));
     HIP_TRY(o->ctx, hipStreamSynchronize(o->ctx->stream));
     std::memcpy(o->pattern, pattern, 1024);
+    std::memcpy(o->effective, eff, 1024);
     if (!upload_now(o->ctx, o->d_pattern, o->pattern, 1024, "hipMemcpy pattern")) return STVO_ERR_HIP;
+    if (!upload_now(o->ctx, o->d_effective, o->effective, 1024, "hipMemcpy pattern")) return STVO_ERR_HIP;
     return STVO_OK;
+}
+
+int stvo_orb_set_descriptor(stvo_orb* o, int wta_k, int patch_size) {
+    if (!o) return STVO_ERR_INVALID_ARG;
+    if (wta_k == o->wta_k && patch_size == o->patch_size) return STVO_OK;  // in force already (stvo_orb_set_pattern keeps its tables current)
+    int8_t eff[1024];
+    const int v = pattern_verdict(stvo::orb_effective_pattern(wta_k, patch_size, o->pattern, eff, nullptr));
+    if (v != STVO_OK) return v;
+    // everything the kernels read lies inside the level image: key-points keep edge_threshold from its border, the moments reach the
+    // half patch and the rotated points the reach of the setting (19 at patch size 31, which stvo_orb_create has already required)
+    if (patch_size != 31 && o->prm.edge_threshold < stvo::orb_reach(patch_size)) return STVO_ERR_INVALID_ARG;
+    int8_t tab[1024 + 64];
+    std::memcpy(tab, eff, 1024);
+    {
+        int u[stvo::ORB_MAX_HALF_PATCH + 2];
+        stvo::orb_umax(stvo::orb_half_patch(patch_size), u);
+        for (int i = 0; i < 64; ++i) tab[1024 + i] = i <= stvo::orb_half_patch(patch_size) ? (int8_t)u[i] : 0;
+    }
+    HIP_TRY(o->ctx, hipSetDevice(o->ctx->device));
+    HIP_TRY(o->ctx, hipStreamSynchronize(o->ctx->stream));  // (detections already enqueued may still read the previous tables)
+    if (!upload_now(o->ctx, o->d_effective, tab, sizeof tab, "hipMemcpy pattern")) return STVO_ERR_HIP;
+    std::memcpy(o->effective, eff, 1024);
+    o->wta_k = wta_k;
+    o->patch_size = patch_size;
+    return STVO_OK;
+}
+
+int stvo_orb_pattern(int wta_k, int patch_size, const int8_t* pool, int8_t* out, int32_t* n_points) {
+    if (!out) return STVO_ERR_INVALID_ARG;
+    int n = 0;
+    const int v = pattern_verdict(stvo::orb_effective_pattern(wta_k, patch_size, pool, out, &n));
+    if (v == STVO_OK && n_points) *n_points = n;
+    return v;
 }
 
 int stvo_orb_set_fast_threshold(stvo_orb* o, int fast_threshold) {
@@ -1192,7 +1363,7 @@ int stvo_orb_set_score_type(stvo_orb* o, int score_type) {
 
 int stvo_orb_get_pattern(const stvo_orb* o, int8_t* pattern) {
     if (!o || !pattern) return STVO_ERR_INVALID_ARG;
-    std::memcpy(pattern, o->pattern, 1024);
+    std::memcpy(pattern, o->effective, 1024);
     return STVO_OK;
 }
 
@@ -1236,8 +1407,18 @@ int stvo_orb_detect_levels_dev(stvo_orb* o, const uint8_t* images, float* kp_xy,
         } else {
             hipLaunchKernelGGL(stvo::orb_order_kernel<false>, dim3(d.B), dim3(1024), 0, s, d);
         }
-        hipLaunchKernelGGL(stvo::orb_describe_kernel, dim3((unsigned)(((d.K + stvo::DESC_KP_PER_WG - 1) / stvo::DESC_KP_PER_WG) * ((d.B + 7) / 8) * 8)), dim3(256),
-                           0, s, d, o->umax);
+        if (o->wta_k == 2 && o->patch_size == 31) {
+            hipLaunchKernelGGL(stvo::orb_describe_kernel, dim3((unsigned)(((d.K + stvo::DESC_KP_PER_WG - 1) / stvo::DESC_KP_PER_WG) * ((d.B + 7) / 8) * 8)), dim3(256),
+                               0, s, d, o->umax);
+        } else {
+            const stvo::WtaArgs wa{stvo::orb_half_patch(o->patch_size), stvo::orb_reach(o->patch_size), o->d_effective, o->d_effective + 1024};
+            const dim3 grid((unsigned)(((d.K + stvo::WTA_KP_PER_WG - 1) / stvo::WTA_KP_PER_WG) * ((d.B + 7) / 8) * 8));
+            const bool big = wa.R > 22;  // the instance whose LDS patch holds the reach
+            auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, d, wa); };
+            if (o->wta_k == 2) big ? launch(stvo::orb_describe_wta_kernel<2, 44>) : launch(stvo::orb_describe_wta_kernel<2, 22>);
+            else if (o->wta_k == 3) big ? launch(stvo::orb_describe_wta_kernel<3, 44>) : launch(stvo::orb_describe_wta_kernel<3, 22>);
+            else big ? launch(stvo::orb_describe_wta_kernel<4, 44>) : launch(stvo::orb_describe_wta_kernel<4, 22>);
+        }
     }
     if (multi) {
         stvo::ConcatArgs c{};

@@ -34,7 +34,7 @@ public:
     STVO_CFG(int, matchingF2FWs, matching_f2f_ws)
     STVO_CFG(int, orbNFeatures, orb_nfeatures) STVO_CFG(double, orbScaleFactor, orb_scale_factor)
     STVO_CFG(int, orbNLevels, orb_nlevels) STVO_CFG(int, orbFastTh, orb_fast_th) STVO_CFG(int, orbEdgeTh, orb_edge_th)
-    STVO_CFG(int, orbScore, orb_score)
+    STVO_CFG(int, orbScore, orb_score) STVO_CFG(int, orbWtaK, orb_wta_k) STVO_CFG(int, orbPatchSize, orb_patch_size)
     STVO_CFG(int, lsdNFeatures, lsd_nfeatures) STVO_CFG(double, lsdScale, lsd_scale)
     STVO_CFG(int, lsdRefine, lsd_refine) STVO_CFG(double, lsdSigmaScale, lsd_sigma_scale) STVO_CFG(double, lsdQuant, lsd_quant)
     STVO_CFG(double, lsdAngTh, lsd_ang_th) STVO_CFG(double, lsdLogEps, lsd_log_eps) STVO_CFG(double, lsdDensityTh, lsd_density_th)
@@ -57,6 +57,7 @@ public:
     double orb_scale_factor;
     int orb_nlevels, orb_fast_th, orb_edge_th;
     int orb_score;  // 0 - HARRIS | 1 - FAST (cv::ORB's scoreType)
+    int orb_wta_k, orb_patch_size;  // cv::ORB's WTA_K (2, 3, 4) and patchSize (stvo_orb_set_descriptor)
     int lsd_nfeatures;
     double lsd_scale;
     int lsd_refine, lsd_n_bins;  // src/config.cpp:105-112

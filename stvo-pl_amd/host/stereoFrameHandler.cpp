@@ -144,6 +144,7 @@ void StereoFrameHandler::detectOnPlanes(const uint8_t* pair_points, const uint8_
     }
     check(stvo_orb_set_fast_threshold(orb, fast_th), "stvo_orb_set_fast_threshold", ctx);
     check(stvo_orb_set_score_type(orb, Config::orbScore()), "stvo_orb_set_score_type", ctx);  // src/stereoFrame.cpp:112-114
+    check(stvo_orb_set_descriptor(orb, Config::orbWtaK(), Config::orbPatchSize()), "stvo_orb_set_descriptor", ctx);  // (nothing to do while the setting stays)
     std::vector<float> kp((size_t)2 * K * 2), resp((size_t)2 * K), ang((size_t)2 * K);
     std::vector<int32_t> oct((size_t)2 * K);
     std::vector<uint8_t> desc((size_t)2 * K * 32);

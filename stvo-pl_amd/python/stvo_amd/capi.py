@@ -34,7 +34,8 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_seq_set_tracks", "stvo_seq_read_tracks", "stvo_seq_tracks_dev", "stvo_seq_keyframe_headers", "stvo_seq_read_keyframe",
            "stvo_color_to_gray", "stvo_color_to_gray_dev", "stvo_rectify_color_images", "stvo_rectify_color_images_dev",
            "stvo_rectify_color_to_gray_dev", "stvo_seq_snapshot_layout", "stvo_seq_snapshot_info", "stvo_seq_export_streams_dev",
-           "stvo_seq_export_streams", "stvo_seq_import_streams_dev", "stvo_seq_import_streams"]
+           "stvo_seq_export_streams", "stvo_seq_import_streams_dev", "stvo_seq_import_streams", "stvo_orb_set_descriptor",
+           "stvo_orb_pattern"]
 
 SEQ_NSTAGE = 5  # include/stvo_hip.h: STVO_SEQ_NSTAGE
 SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_check", "pose")
@@ -273,6 +274,8 @@ def load():
     L.stvo_orb_detect_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 6
     L.stvo_orb_set_fast_threshold.argtypes = [C.c_void_p, C.c_int]
     L.stvo_orb_set_score_type.argtypes = [C.c_void_p, C.c_int]
+    L.stvo_orb_set_descriptor.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.stvo_orb_pattern.argtypes = [C.c_int, C.c_int, C.c_void_p, i8p, C.POINTER(C.c_int32)]
     L.stvo_orb_set_fast_thresholds.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.stvo_orb_set_fast_thresholds_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.stvo_fast_adapt_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(FastAdapt), C.c_void_p]
@@ -511,18 +514,22 @@ class Orb:
     """The ORB point front-end for B images of one size (stvo_orb_*)."""
 
     def __init__(self, ctx, B, cols, rows, max_keypoints=2048, nfeatures=2000, fast_threshold=20, edge_threshold=19, nlevels=1,
-                 scale_factor=1.2, score=1):
-        """score: Config::orbScore() with OpenCV's values — 1 FAST_SCORE (the default), 0 HARRIS_SCORE."""
+                 scale_factor=1.2, score=1, wta_k=2, patch_size=31):
+        """score: Config::orbScore() with OpenCV's values — 1 FAST_SCORE (the default), 0 HARRIS_SCORE.  wta_k, patch_size:
+        Config::orbWtaK() (2, 3, 4) and Config::orbPatchSize() (2 .. 63; other than 31 it needs edge_threshold >= ceil(patch_size // 2 *
+        sqrt 2)): stvo_orb_set_descriptor."""
         self.ctx, self.B, self.cols, self.rows, self.K = ctx, B, cols, rows, max_keypoints
         self.h = C.c_void_p()
         prm = OrbParams(nfeatures, fast_threshold, edge_threshold, nlevels, scale_factor)
         ctx._chk(ctx.lib.stvo_orb_create(ctx.h, B, cols, rows, max_keypoints, C.byref(prm), C.byref(self.h)))
-        if score != 1:
-            try:
+        try:
+            if score != 1:
                 self.set_score_type(score)
-            except Exception:
-                self.close()
-                raise
+            if (wta_k, patch_size) != (2, 31):
+                self.set_descriptor(wta_k, patch_size)
+        except Exception:
+            self.close()
+            raise
 
     def close(self):
         if self.h:
@@ -530,9 +537,14 @@ class Orb:
             self.h = None
 
     def pattern(self):
+        """The effective point list of the setting in force as [256, 4] (x0, y0, x1, y1): 512 / 384 / 512 points for wta_k 2 / 3 / 4,
+        zero beyond them."""
         p = np.zeros(1024, np.int8)
         self.ctx._chk(self.ctx.lib.stvo_orb_get_pattern(self.h, p))
         return p.reshape(256, 4)
+
+    def set_descriptor(self, wta_k, patch_size):
+        self.ctx._chk(self.ctx.lib.stvo_orb_set_descriptor(self.h, wta_k, patch_size))
 
     def set_pattern(self, pattern):
         self.ctx._chk(self.ctx.lib.stvo_orb_set_pattern(self.h, np.ascontiguousarray(pattern, np.int8).reshape(-1)))
@@ -575,6 +587,21 @@ class Orb:
     def detect_dev(self, img, kp, resp, ang, desc, n, octave=None, n_total=None):
         """Device buffers (integers = device addresses): images in, key-points / descriptors out, on the context's stream."""
         self.ctx._chk(self.ctx.lib.stvo_orb_detect_levels_dev(self.h, img, kp, resp, ang, octave, desc, n, n_total))
+
+
+def orb_pattern(wta_k, patch_size, pool=None):
+    """stvo_orb_pattern (host only, no context): the effective point list [n_points, 2] int8 of a descriptor setting.  pool: the
+    1024-byte pattern of patch size 31 (None: the seeded stand-in).  Raises StvoError with the library's verdict."""
+    lib = load()
+    out, n = np.zeros(1024, np.int8), C.c_int32(0)
+    p = None if pool is None else np.ascontiguousarray(pool, np.int8).reshape(-1)
+    if p is not None and p.size != 1024:
+        raise ValueError("orb_pattern: the pool holds 1024 bytes")
+    rc = lib.stvo_orb_pattern(wta_k, patch_size, None if p is None else p.ctypes.data, out, C.byref(n))
+    if rc != 0:
+        raise StvoError(f"{lib.stvo_error_string(rc).decode()} ({rc}): stvo_orb_pattern({wta_k}, {patch_size})")
+    assert not out[2 * n.value:].any()
+    return out[:2 * n.value].reshape(-1, 2).copy()
 
 
 KEYLINE_DTYPE = np.dtype([("sx", "<f4"), ("sy", "<f4"), ("ex", "<f4"), ("ey", "<f4"), ("angle", "<f4"), ("num_pixels", "<i4")])  # stvo_keyline

@@ -21,10 +21,12 @@ from .capi import FrameFeatures
 class ImagePipeline:
     def __init__(self, ctx, B, cam, mp, op, max_kp=2048, nfeatures=2000, fast_threshold=20, edge_threshold=19, device="cuda:0", nlevels=1,
                  scale_factor=1.2, lsd=None, max_kl=128, rectify=None, fld=None, orb_score=1, adaptive_fast=None,
-                 trajectory=None, trajectory_log=1, tracks=0, keyframe_sets=False, channels=1, gray_weights="q14"):
+                 trajectory=None, trajectory_log=1, tracks=0, keyframe_sets=False, channels=1, gray_weights="q14", orb_wta_k=2,
+                 orb_patch_size=31):
         """cam: one camera dict (width / height = image size) for all B streams.  nlevels / scale_factor: Config::orbNLevels /
         orbScaleFactor (the key-point octaves travel with the key-points: sigma2 = 1 / scale^(2 level)).  orb_score: Config::orbScore
-        (1 FAST_SCORE, 0 HARRIS_SCORE ranking of the key-points).  lsd: capi.lsd_params(...)
+        (1 FAST_SCORE, 0 HARRIS_SCORE ranking of the key-points).  orb_wta_k / orb_patch_size: Config::orbWtaK / orbPatchSize
+        (capi.Orb: 2 .. 4 and 2 .. 63; the descriptor stays 32 bytes under the matchers' plain Hamming distance).  lsd: capi.lsd_params(...)
         for the key-line front-end (op.has_lines = 1, at most max_kl key-lines per image), None: key-points only (op.has_lines = 0).
         fld: capi.fld_params(...) instead of lsd, the FLD detector of use_fld_lines (src/stereoFrame.cpp:244-303); not both.
         rectify: a capi.Rectifier of the same context for at least B pairs of this size: enqueue first remaps the raw images into a
@@ -59,7 +61,7 @@ class ImagePipeline:
         if rectify is not None and (rectify.ctx is not ctx or rectify.B < B or rectify.cols != self.cols or rectify.rows != self.rows):
             raise ValueError("ImagePipeline: the rectifier must belong to the same context, hold B pairs and match the image size")
         self.orb = capi.Orb(ctx, 2 * B, self.cols, self.rows, max_kp, nfeatures, fast_threshold, edge_threshold, nlevels, scale_factor,
-                            score=orb_score)  # left images, then right
+                            score=orb_score, wta_k=orb_wta_k, patch_size=orb_patch_size)  # left images, then right
         if lsd is not None and fld is not None:
             raise ValueError("ImagePipeline: one line detector, lsd or fld")
         lp = lsd if lsd is not None else fld
