@@ -276,6 +276,18 @@ int check_gray(int n, int rows, int cols, int ch, const uint8_t* src, const uint
     return STVO_OK;
 }
 
+// The device block of ONE host-buffer call.  Whichever way the call ends, copies and kernels may still be using the block: the
+// context's stream is synchronised before it is freed.
+struct CallBlock {
+    stvo_ctx* ctx;
+    uint8_t* p = nullptr;
+    ~CallBlock() {
+        if (!p) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(p);
+    }
+};
+
 template <int CH, bool GRAY>
 void launch_rect_ch(stvo_rectify* r, int n, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l, uint8_t* dst_r, uint8_t* dstb_l,
                     uint8_t* dstb_r, const GrayWeights& w) {
@@ -336,23 +348,19 @@ int stvo_color_to_gray(stvo_ctx* ctx, int n, int rows, int cols, int channels, i
     if (!ctx || !gray_weights(order, weights, &w)) return STVO_ERR_INVALID_ARG;
     TRY(check_gray(n, rows, cols, channels, src, gray, gray_swapped, &npix));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // staging: the colour batch, then one or two planes (256-byte aligned each)
-    const size_t in_bytes = (npix * channels + 255) & ~(size_t)255, plane = (npix + 255) & ~(size_t)255;
-    uint8_t* io = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&io, in_bytes + 2 * plane));
-    uint8_t *da = io + in_bytes, *db = gray_swapped ? da + plane : nullptr;
-    int rc = STVO_ERR_HIP;
-    if (hip_ok(ctx, hipMemcpyAsync(io, src, npix * channels, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync colour images") &&
-        (rc = launch_gray(ctx, channels, io, da, db, npix, w)) == STVO_OK) {
-        rc = STVO_ERR_HIP;
-        if (hip_ok(ctx, hipMemcpyAsync(gray, da, npix, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync grey plane") &&
-            (!db || hip_ok(ctx, hipMemcpyAsync(gray_swapped, db, npix, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync grey plane")) &&
-            hip_ok(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
-            rc = STVO_OK;
-    }
-    if (rc != STVO_OK) (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(io);
-    return rc;
+    stvo::Carver size;
+    stvo::carve_gray_staging(size, npix, channels);
+    CallBlock io{ctx};
+    HIP_TRY(ctx, hipMalloc((void**)&io.p, size.off));
+    stvo::Carver c(io.p);
+    const stvo::GrayStaging S = stvo::carve_gray_staging(c, npix, channels);
+    uint8_t* db = gray_swapped ? S.swapped : nullptr;
+    HIP_TRY(ctx, hipMemcpyAsync(S.src, src, npix * channels, hipMemcpyHostToDevice, ctx->stream));
+    TRY(launch_gray(ctx, channels, S.src, S.gray, db, npix, w));
+    HIP_TRY(ctx, hipMemcpyAsync(gray, S.gray, npix, hipMemcpyDeviceToHost, ctx->stream));
+    if (db) HIP_TRY(ctx, hipMemcpyAsync(gray_swapped, db, npix, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return STVO_OK;
 }
 
 int stvo_rectify_color_images_dev(stvo_rectify* r, int n, int channels, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l,
@@ -367,23 +375,20 @@ int stvo_rectify_color_images(stvo_rectify* r, int n, int channels, const uint8_
     TRY(check_color_images(r, n, channels, src_l, src_r, dst_l, dst_r));
     stvo_ctx* ctx = r->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)n * r->cols * r->rows * channels, side = (bytes + 255) & ~(size_t)255;
-    uint8_t* io = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&io, 4 * side));
-    uint8_t *sl = io, *sr = io + side, *dl = io + 2 * side, *dr = io + 3 * side;
-    int rc = STVO_ERR_HIP;
-    if (hip_ok(ctx, hipMemcpyAsync(sl, src_l, bytes, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync colour images") &&
-        hip_ok(ctx, hipMemcpyAsync(sr, src_r, bytes, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync colour images") &&
-        (rc = launch_color_remap(r, n, channels, sl, sr, dl, dr)) == STVO_OK) {
-        rc = STVO_ERR_HIP;
-        if (hip_ok(ctx, hipMemcpyAsync(dst_l, dl, bytes, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync rectified images") &&
-            hip_ok(ctx, hipMemcpyAsync(dst_r, dr, bytes, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync rectified images") &&
-            hip_ok(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
-            rc = STVO_OK;
-    }
-    if (rc != STVO_OK) (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(io);
-    return rc;
+    const size_t bytes = (size_t)n * r->cols * r->rows * channels;
+    stvo::Carver size;
+    stvo::carve_color_rectify_staging(size, n, r->cols, r->rows, channels);
+    CallBlock io{ctx};
+    HIP_TRY(ctx, hipMalloc((void**)&io.p, size.off));
+    stvo::Carver c(io.p);
+    const stvo::StereoStaging S = stvo::carve_color_rectify_staging(c, n, r->cols, r->rows, channels);
+    HIP_TRY(ctx, hipMemcpyAsync(S.src_l, src_l, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(S.src_r, src_r, bytes, hipMemcpyHostToDevice, ctx->stream));
+    TRY(launch_color_remap(r, n, channels, S.src_l, S.src_r, S.dst_l, S.dst_r));
+    HIP_TRY(ctx, hipMemcpyAsync(dst_l, S.dst_l, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dst_r, S.dst_r, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return STVO_OK;
 }
 
 int stvo_rectify_color_to_gray_dev(stvo_rectify* r, int n, int channels, int order, int weights, const uint8_t* src_l, const uint8_t* src_r,

@@ -61,6 +61,25 @@ inline bool upload_now(stvo_ctx* ctx, void* dst, const void* src, size_t bytes, 
     return hip_ok(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream), what) && hip_ok(ctx, hipStreamSynchronize(ctx->stream), what);
 }
 
+// The grow-only device block of a host-buffer entry point (images in, results out): kept from call to call, replaced when a call needs
+// more.  The owner frees `p` when it is destroyed.
+struct Staging {
+    char* p = nullptr;
+    size_t bytes = 0;
+};
+inline int staging_reserve(stvo_ctx* ctx, Staging& s, size_t bytes) {
+    if (s.bytes >= bytes) return STVO_OK;
+    if (s.p) (void)hipFree(s.p);
+    s.p = nullptr;
+    s.bytes = 0;
+    if (!hip_ok(ctx, hipMalloc((void**)&s.p, bytes), "hipMalloc staging")) {
+        s.p = nullptr;
+        return STVO_ERR_HIP;
+    }
+    s.bytes = bytes;
+    return STVO_OK;
+}
+
 template <typename T>
 inline T* arena_alloc(stvo_ctx* ctx, size_t count) {
     size_t bytes = (count * sizeof(T) + 255) & ~size_t(255);

@@ -36,6 +36,7 @@
 
 #include "ctx_internal.h"
 #include "fast_atan2.h"
+#include "frontend_layout.h"
 #include "line_common.h"
 
 #pragma clang fp contract(off)
@@ -44,17 +45,9 @@ namespace stvo {
 namespace {
 
 constexpr double FLD_PI = 3.14159265358979323846;
-constexpr int FLD_UNIT_ROWS = 64;
-constexpr int FLD_UNIT = 64 * FLD_UNIT_ROWS;  // elements per wave of the counting sort
-constexpr int FLD_BINS = 1024;                 // 10-bit digits of the root (images up to 2^20 pixels)
 constexpr int FLD_WALK_T = 1024;
 constexpr int FLD_KL_T = 256;
-constexpr int FLD_SEG_CAP = 8192;              // segments per image in detection order (ranked); more are counted
 constexpr int FLD_SEG_BLOCKS = 8;              // workgroups per image of fld_segments_kernel (grid-stride over the chains)
-
-struct FldChain {
-    int32_t seed, off, n, nseg;  // seed raster index, first point in pts, points, segments kept
-};
 
 struct FldDev {
     int B, cols, rows, npx, nw, nunits;
@@ -713,41 +706,25 @@ int stvo_fld_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, 
     o->prm = *prm;
     stvo::FldDev& d = o->d;
     d.B = B; d.cols = cols; d.rows = rows; d.npx = cols * rows;
-    d.nw = (d.npx + 63) / 64 * 2;
-    d.nunits = (d.npx + stvo::FLD_UNIT - 1) / stvo::FLD_UNIT;
+    d.nw = stvo::fld_words(d.npx);
+    d.nunits = stvo::fld_units(d.npx);
     d.L = prm->length_threshold;
     d.low = (int)std::floor(prm->canny_th1 < 32767.0 ? prm->canny_th1 : 32767.0);
     d.dist_th = prm->distance_threshold;
     d.nfeatures = prm->nfeatures;
     d.K = max_keylines;
-    d.ch_cap = d.npx / (d.L + 1) + 1;  // a kept chain holds at least L + 1 pixels
-    d.sg_cap = d.npx / (d.L + 1) + 1;  // a chain of n points gives at most n / (L + 1) segments
-    const size_t npx = (size_t)d.npx, nb = (size_t)B, nw = (size_t)d.nw;
-    struct {
-        size_t off = 0;
-        size_t take(size_t bytes) {
-            const size_t o = off;
-            off += (bytes + 255) & ~size_t(255);
-            return o;
-        }
-    } c;
-    const size_t o_img = c.take(nb * npx), o_eb = c.take(nb * nw * 4), o_sb = c.take(nb * nw * 4), o_ws = c.take(nb * nw * 4),
-                 o_lab = c.take(nb * npx * 4), o_tmp = c.take(nb * npx * 4), o_list = c.take(nb * npx * 4),
-                 o_cnt = c.take(nb * d.nunits * stvo::FLD_BINS * 4), o_ne = c.take(nb * 4), o_pts = c.take(nb * npx * 4),
-                 o_at = c.take(nb * npx * 4), o_ch = c.take(nb * d.ch_cap * sizeof(stvo::FldChain)), o_nch = c.take(nb * 4),
-                 o_sg = c.take(nb * d.sg_cap * 16), o_ds = c.take(nb * stvo::FLD_SEG_CAP * 16), o_ns = c.take(nb * 4),
-                 o_err = c.take(nb * 4), o_lines = c.take(nb * d.K * sizeof(stvo_keyline)), o_resp = c.take(nb * d.K * 4),
-                 o_nl = c.take(nb * 4);
-    bool ok = hip_ok(ctx, hipMalloc((void**)&o->dev, c.off), "hipMalloc fld") && zero_device(ctx, o->dev, c.off, "hipMemset fld");
+    d.ch_cap = d.sg_cap = stvo::fld_store_cap(d.npx, d.L);
+    stvo::Carver size;
+    stvo::carve_fld_arena(size, B, cols, rows, d.L, d.K);
+    bool ok = hip_ok(ctx, hipMalloc((void**)&o->dev, size.off), "hipMalloc fld") && zero_device(ctx, o->dev, size.off, "hipMemset fld");
     if (ok) {
-        char* D = o->dev;
-        o->img = (uint8_t*)(D + o_img);
-        d.ebits = (uint32_t*)(D + o_eb); d.sbits = (uint32_t*)(D + o_sb); d.wsum = (uint32_t*)(D + o_ws);
-        d.lab = (int32_t*)(D + o_lab); d.tmp = (uint32_t*)(D + o_tmp); d.list = (uint32_t*)(D + o_list);
-        d.cnt = (uint32_t*)(D + o_cnt); d.n_edge = (int32_t*)(D + o_ne); d.pts = (uint32_t*)(D + o_pts);
-        d.ch_at = (int32_t*)(D + o_at); d.ch = (stvo::FldChain*)(D + o_ch); d.n_ch = (int32_t*)(D + o_nch);
-        d.sg = (float4*)(D + o_sg); d.dseg = (float4*)(D + o_ds); d.n_seg = (int32_t*)(D + o_ns); d.err = (int32_t*)(D + o_err);
-        o->lines = (stvo_keyline*)(D + o_lines); o->response = (float*)(D + o_resp); o->n_lines = (int32_t*)(D + o_nl);
+        stvo::Carver c(o->dev);
+        const stvo::FldArena a = stvo::carve_fld_arena(c, B, cols, rows, d.L, d.K);
+        o->img = a.img;
+        d.ebits = a.ebits; d.sbits = a.sbits; d.wsum = a.wsum; d.lab = a.lab; d.tmp = a.tmp; d.list = a.list;
+        d.cnt = a.cnt; d.n_edge = a.n_edge; d.pts = a.pts; d.ch_at = a.ch_at; d.ch = a.ch; d.n_ch = a.n_ch;
+        d.sg = a.sg; d.dseg = a.dseg; d.n_seg = a.n_seg; d.err = a.err;
+        o->lines = a.lines; o->response = a.response; o->n_lines = a.n_lines;
     }
     o->walk_lds = d.nw * 4;
     if (ok && o->walk_lds > 48 * 1024) ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::fld_walk_kernel), o->walk_lds);

@@ -18,6 +18,8 @@
 #include <new>
 
 #include "ctx_internal.h"
+#include "frontend_layout.h"
+#include "gaussian_q8.h"
 
 #pragma clang fp contract(off)
 
@@ -25,6 +27,7 @@ namespace stvo {
 namespace {
 
 constexpr int LBD_BANDS = 9, LBD_W = 7, LBD_ROWS = LBD_BANDS * LBD_W, LBD_DESC = LBD_BANDS * 8;
+static_assert(LBD_DESC == LBD_DESC_FLOATS, "the staging of stvo_lbd_compute holds LBD_DESC floats per key-line");
 
 struct LbdDev {
     int B, cols, rows, M;        // images, image size, key-line capacity per image
@@ -271,8 +274,7 @@ struct stvo_lbd {
     stvo_ctx* ctx = nullptr;
     stvo::LbdDev d{};
     char* dev = nullptr;  // blur | (dx, dy)
-    char* io = nullptr;   // staging of the host-buffer entry point
-    size_t io_bytes = 0;
+    Staging io;           // staging of the host-buffer entry point
 };
 
 extern "C" {
@@ -284,25 +286,18 @@ int stvo_lbd_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, 
     stvo_lbd* o = new (std::nothrow) stvo_lbd();
     if (!o) return STVO_ERR_HIP;
     o->ctx = ctx;
-    const size_t px = (size_t)B * rows * cols;
-    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
-    const size_t o_dxy = al(px), total = o_dxy + al(px * 4);
-    if (!hip_ok(ctx, hipMalloc((void**)&o->dev, total), "hipMalloc lbd")) {
+    stvo::Carver size;
+    stvo::carve_lbd_arena(size, B, cols, rows);
+    if (!hip_ok(ctx, hipMalloc((void**)&o->dev, size.off), "hipMalloc lbd")) {
         delete o;
         return STVO_ERR_HIP;
     }
+    stvo::Carver c(o->dev);
+    const stvo::LbdArena a = stvo::carve_lbd_arena(c, B, cols, rows);
     stvo::LbdDev& d = o->d;
     d.B = B; d.cols = cols; d.rows = rows; d.M = max_keylines;
-    d.blur = (uint8_t*)o->dev; d.dxy = (int32_t*)(o->dev + o_dxy);
-    {   // getGaussianKernel(5, 1) in 8-bit fixed point (binary_descriptor_custom.cpp:358)
-        double k[5], sum = 0.0;
-        for (int i = 0; i < 5; ++i) {
-            const double x = i - 2;
-            k[i] = std::exp(-x * x / (2.0 * 1.0 * 1.0));
-            sum += k[i];
-        }
-        for (int i = 0; i < 5; ++i) d.k5[i] = (int)std::lrint((float)(k[i] / sum) * 256.0);
-    }
+    d.blur = a.blur; d.dxy = a.dxy;
+    stvo::gaussian_q8(2, 1.0, d.k5);  // getGaussianKernel(5, 1) (binary_descriptor_custom.cpp:358)
     {   // the weight tables of BinaryDescriptor's constructor (:225-257), integer divisions included
         const int w = stvo::LBD_W;
         double u = (w * 3 - 1) / 2, sigma = (w * 2 + 1) / 2, inv = -1 / (2 * sigma * sigma);
@@ -327,7 +322,7 @@ int stvo_lbd_destroy(stvo_lbd* o) {
     (void)hipSetDevice(o->ctx->device);
     (void)hipStreamSynchronize(o->ctx->stream);
     if (o->dev) (void)hipFree(o->dev);
-    if (o->io) (void)hipFree(o->io);
+    if (o->io.p) (void)hipFree(o->io.p);
     delete o;
     return STVO_OK;
 }
@@ -356,25 +351,18 @@ int stvo_lbd_compute(stvo_lbd* o, const uint8_t* images, const stvo_keyline* lin
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const stvo::LbdDev& d = o->d;
     const size_t px = (size_t)d.B * d.rows * d.cols, nl = (size_t)d.B * d.M;
-    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
-    const size_t o_img = 0, o_ln = al(px), o_n = o_ln + al(nl * sizeof(stvo_keyline)), o_desc = o_n + al((size_t)d.B * 4), o_f = o_desc + al(nl * 32),
-                 total = o_f + al(nl * 72 * 4);
-    if (o->io_bytes < total) {
-        if (o->io) (void)hipFree(o->io);
-        o->io = nullptr;
-        o->io_bytes = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&o->io, total));
-        o->io_bytes = total;
-    }
-    char* D = o->io;
-    HIP_TRY(ctx, hipMemcpyAsync(D + o_img, images, px, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(D + o_ln, lines, nl * sizeof(stvo_keyline), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(D + o_n, n_lines, (size_t)d.B * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(D + o_desc, 0, total - o_desc, ctx->stream));
-    TRY(stvo_lbd_compute_dev(o, (const uint8_t*)(D + o_img), (const stvo_keyline*)(D + o_ln), (const int32_t*)(D + o_n), (uint8_t*)(D + o_desc),
-                             desc_float ? (float*)(D + o_f) : nullptr));
-    HIP_TRY(ctx, hipMemcpyAsync(desc, D + o_desc, nl * 32, hipMemcpyDeviceToHost, ctx->stream));
-    if (desc_float) HIP_TRY(ctx, hipMemcpyAsync(desc_float, D + o_f, nl * 72 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    stvo::Carver size;
+    stvo::carve_lbd_staging(size, d.B, d.cols, d.rows, d.M);
+    TRY(staging_reserve(ctx, o->io, size.off));
+    stvo::Carver c(o->io.p);
+    const stvo::LbdStaging S = stvo::carve_lbd_staging(c, d.B, d.cols, d.rows, d.M);
+    HIP_TRY(ctx, hipMemcpyAsync(S.img, images, px, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(S.lines, lines, nl * sizeof(stvo_keyline), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(S.n, n_lines, (size_t)d.B * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(S.desc, 0, (size_t)(o->io.p + c.off - (char*)S.desc), ctx->stream));
+    TRY(stvo_lbd_compute_dev(o, S.img, S.lines, S.n, S.desc, desc_float ? S.desc_f : nullptr));
+    HIP_TRY(ctx, hipMemcpyAsync(desc, S.desc, nl * 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (desc_float) HIP_TRY(ctx, hipMemcpyAsync(desc_float, S.desc_f, nl * stvo::LBD_DESC_FLOATS * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return STVO_OK;
 }

@@ -42,6 +42,8 @@
 
 #include "ctx_internal.h"
 #include "fast_atan2.h"
+#include "frontend_layout.h"
+#include "gaussian_q8.h"
 #include "line_common.h"
 
 #pragma clang fp contract(off)
@@ -57,14 +59,6 @@ constexpr uint32_t LSD_NOKEY = 0xFFFFFFFFu;
 constexpr int LSD_IDX_BITS = 20;  // pixel index inside a sort key: scaled images up to 2^20 pixels
 constexpr int LSD_ROWS = 16;      // image rows per workgroup of the per-pixel kernels
 
-// A pixel as the region growing sees it.  Three arrays (angle, (cos, sin), flag) were three divergent 64-lane gathers per sub-group
-// and round, and the batches are bound by exactly that — the address path of a CU shared by its sixteen waves (SQ counters, round 6:
-// the vector port of a SIMD is 29 % taken at four images per SIMD, a round takes 3.3 x as long as alone).
-struct LsdPx {
-    float ang;     // level-line angle in degrees, < 0: undefined
-    float c, s;    // cos / sin of float(angle in radians) as floats: what the pixel adds to a region's direction sums
-    int32_t used;  // 0 / 1: taken by a region (the only field written after lsd_gradient_kernel)
-};
 typedef float lsd_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ LsdPx px_ld(const LsdPx* p) {  // one 16-byte load
     const lsd_f4 v = *reinterpret_cast<const lsd_f4*>(p);
@@ -148,8 +142,6 @@ __global__ __launch_bounds__(256) void lsd_gradient_kernel(LsdDev d) {
 //   lsd_scatter_kernel  the unit again, row by row: a pixel's rank = the bin's running position + the lower lanes of its row with the same
 //                       bin (the lanes with equal bins matched bit by bit with ballots) — stable by construction, no atomics on the way.
 // The bin is (int)(norm (n_bins - 1) / max norm), norm = sqrt(k / 4) in double precision from the integer k both times.
-constexpr int LSD_UNIT_ROWS = 64;
-constexpr int LSD_UNIT = 64 * LSD_UNIT_ROWS;
 constexpr int LSD_MAX_BINS = 2048;
 __device__ __forceinline__ double lsd_bin_coef(const LsdDev& d, int b) {
     const int km = d.kmax[b];
@@ -993,8 +985,6 @@ __device__ __forceinline__ long long readfirstlane64(long long v) {
     const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
     return (long long)(((unsigned long long)hi << 32) | lo);
 }
-constexpr int LSD_WAVES_MAX_B = 128; // up to 16 images per XCD, each with a committer's workgroup + at least one speculating workgroup (~40 B of scratch per pixel
-                                     // and speculating workgroup); beyond that one wave per image and the batch as the parallelism
 
 // loads that bypass the vector L1 (sc1: served by the XCD's L2) — data another CU of the same XCD stores during the launch
 __device__ __forceinline__ int ld_l2(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -1026,8 +1016,6 @@ __device__ __forceinline__ void lds_st(int* p, int v) { __hip_atomic_store(p, v,
 // search, so any placement gives the same segments, only later.
 constexpr int LSD_XW = 4;          // waves per workgroup: one per SIMD
 constexpr int LSD_X_MAXW = 125;    // waves per image at most (7 bits of a table entry; 31 speculating workgroups of an XCD's 32 CUs)
-constexpr int LSD_CTL = 512;       // control words per image, zeroed per call
-constexpr size_t LSD_XCD_MAX_PX = 3u << 18;  // the committer's bitmap (96 KB) + the feeder's ring + the per-wave scratch fit the 160 KB of a CU
 constexpr int LSD_FEED_PX = 8192;   // words of the feeder's record ring (LDS)
 constexpr int LSD_FEED_Q = 256;     // records in it at most
 constexpr int LSD_FEED_MAXW = 2048; // a record's pixels at most (a quarter of the ring; larger regions go through the table)
@@ -1729,7 +1717,7 @@ struct stvo_lsd {
     int32_t* n_lines = nullptr;
     double* dbg = nullptr;
     char* wdev = nullptr;
-    size_t stamp_bytes = 0, pend_bytes = 0;
+    size_t stamp_bytes = 0, pend_ctl_bytes = 0;  // what a call clears of the scratch below (frontend_layout.h: LsdXcdArena)
     stvo::LsdXcd xx{};        // scratch of lsd_grow_xcd_kernel (small batches, the default), or null
     int xcd_lds = 0;          // its dynamic LDS: the committer's bitmap — and at least 84 KB, so that a CU holds ONE of its workgroups (a wave per SIMD)
 };
@@ -1775,7 +1763,7 @@ int lsd_enqueue(stvo_lsd* o, const uint8_t* images, stvo_keyline* lines, float* 
         hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<true, false>), dim3(d.B), dim3(64), 0, s, d, o->prm.density_th);
     } else if (o->wdev) {  // small batches: a committing wave + speculating workgroups on the CUs of one XCD per image (lsd_grow_xcd_kernel)
         HIP_TRY(ctx, hipMemsetAsync(o->xx.stamp, 0, o->stamp_bytes, s));
-        HIP_TRY(ctx, hipMemsetAsync(o->xx.pend, 0, o->pend_bytes + (size_t)d.B * stvo::LSD_CTL * 4, s));  // (the control words lie behind the table)
+        HIP_TRY(ctx, hipMemsetAsync(o->xx.pend, 0, o->pend_ctl_bytes, s));  // (the control words lie behind the table)
         const dim3 xg(8 * ((d.B + 7) / 8) * (1 + o->xx.nsb)), xb(stvo::LSD_XW * 64);
         if (prof) hipLaunchKernelGGL(stvo::lsd_grow_xcd_kernel<true>, xg, xb, o->xcd_lds, s, d, o->xx);
         else hipLaunchKernelGGL(stvo::lsd_grow_xcd_kernel<false>, xg, xb, o->xcd_lds, s, d, o->xx);
@@ -1807,7 +1795,7 @@ int stvo_lsd_geometry(const stvo_lsd_params* prm, int cols, int rows, int32_t* s
     if (prm->n_bins > stvo::LSD_MAX_BINS) return STVO_ERR_UNSUPPORTED;
     int w = cols, h = rows, hk = 0;
     double sigma = 0.0;
-    int32_t kw[STVO_LSD_MAX_TAPS] = {256};  // radius 0: the identity
+    int32_t kw[STVO_LSD_MAX_TAPS] = {0};
     if (prm->scale != 1) {
         if (!(prm->sigma_scale >= 0)) return STVO_ERR_INVALID_ARG;  // (a negative or NaN sigma has no kernel size)
         sigma = prm->scale < 1 ? prm->sigma_scale / prm->scale : prm->sigma_scale;
@@ -1816,15 +1804,6 @@ int stvo_lsd_geometry(const stvo_lsd_params* prm, int cols, int rows, int32_t* s
         // 7 x 7 kernel of the ORB front-end, the others on lsd_blur_resize_kernel
         if (!(hd <= STVO_LSD_MAX_RADIUS)) return STVO_ERR_UNSUPPORTED;
         hk = (int)hd;
-        if (hk > 0) {  // orc_lsd_kernel7 with 7 -> 1 + 2 hk (sigma = 0 has hk = 0 and no Gaussian to evaluate)
-            double k[STVO_LSD_MAX_TAPS], sum = 0.0;
-            for (int i = 0; i <= 2 * hk; ++i) {
-                const double x = i - hk;
-                k[i] = std::exp(-x * x / (2.0 * sigma * sigma));
-                sum += k[i];
-            }
-            for (int i = 0; i <= 2 * hk; ++i) kw[i] = (int32_t)std::lrint((float)(k[i] / sum) * 256.0);
-        }
         const double wd = std::rint((double)cols * prm->scale), hd2 = std::rint((double)rows * prm->scale);  // resize(..., Size(), scale, scale): cvRound
         if (!(wd >= 1 && hd2 >= 1)) return STVO_ERR_INVALID_ARG;  // nothing is left of the image
         if (wd >= 65536 || hd2 >= 32768) return STVO_ERR_CAPACITY;
@@ -1832,6 +1811,7 @@ int stvo_lsd_geometry(const stvo_lsd_params* prm, int cols, int rows, int32_t* s
         h = (int)hd2;
     }
     if ((long long)w * h > (1ll << stvo::LSD_IDX_BITS) || w >= 65536 || h >= 32768) return STVO_ERR_CAPACITY;
+    stvo::gaussian_q8(hk, sigma, kw);  // orc_lsd_kernel7 with 7 -> 1 + 2 hk (radius 0, where sigma may be 0: the identity)
     if (scaled_cols) *scaled_cols = w;
     if (scaled_rows) *scaled_rows = h;
     if (sigma_out) *sigma_out = sigma;
@@ -1872,28 +1852,17 @@ int stvo_lsd_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, 
     d.nfeatures = prm->nfeatures;
     d.K = max_keylines;
     d.seg_cap = 8192;  // segments per image the wrapper ranks (its LDS: 8 bytes each); more are counted, not stored
-    const size_t npx = (size_t)d.w * d.h, nb = (size_t)B;
-    struct {
-        size_t off = 0;
-        size_t take(size_t bytes) {
-            const size_t o = off;
-            off += (bytes + 255) & ~size_t(255);
-            return o;
-        }
-    } c;
-    const size_t o_blur = c.take(radius == 3 ? nb * cols * rows : 0) /* (the fused kernel keeps the blurred bytes in LDS) */, o_scaled = c.take(nb * npx), o_img = c.take(nb * cols * rows), o_px = c.take(nb * npx * sizeof(stvo::LsdPx)),
-                 o_k32 = c.take(nb * npx * 4), o_cnt = c.take(nb * ((npx + stvo::LSD_UNIT - 1) / stvo::LSD_UNIT) * (size_t)d.n_bins * 4),
-                 o_order = c.take(nb * npx * 4), o_reg = c.take(nb * npx * 4), o_kmax = c.take(nb * 4), o_seg = c.take(nb * d.seg_cap * 16),
-                 o_nseg = c.take(nb * 4), o_lines = c.take(nb * d.K * sizeof(stvo_keyline)),
-                 o_resp = c.take(nb * d.K * 4), o_nl = c.take(nb * 4), o_np = c.take(nb * 4);
-    bool ok = hip_ok(ctx, hipMalloc((void**)&o->dev, c.off), "hipMalloc lsd") && zero_device(ctx, o->dev, c.off, "hipMemset lsd");
+    const size_t npx = (size_t)d.w * d.h;
+    stvo::Carver size;
+    stvo::carve_lsd_arena(size, B, cols, rows, d.w, d.h, d.n_bins, d.seg_cap, d.K, radius == 3);
+    bool ok = hip_ok(ctx, hipMalloc((void**)&o->dev, size.off), "hipMalloc lsd") && zero_device(ctx, o->dev, size.off, "hipMemset lsd");
     if (ok) {
-        char* D = o->dev;
-        o->blur = (uint8_t*)(D + o_blur); o->scaled = (uint8_t*)(D + o_scaled); o->img = (uint8_t*)(D + o_img);
-        d.px = (stvo::LsdPx*)(D + o_px); d.k32 = (int32_t*)(D + o_k32); d.cnt = (uint32_t*)(D + o_cnt);
-        d.order = (uint32_t*)(D + o_order); d.reg = (int32_t*)(D + o_reg); d.kmax = (int32_t*)(D + o_kmax);
-        d.seg = (float4*)(D + o_seg); d.n_seg = (int32_t*)(D + o_nseg); d.n_pass = (int32_t*)(D + o_np);
-        o->lines = (stvo_keyline*)(D + o_lines); o->response = (float*)(D + o_resp); o->n_lines = (int32_t*)(D + o_nl);
+        stvo::Carver c(o->dev);
+        const stvo::LsdArena a = stvo::carve_lsd_arena(c, B, cols, rows, d.w, d.h, d.n_bins, d.seg_cap, d.K, radius == 3);
+        o->blur = a.blur; o->scaled = a.scaled; o->img = a.img;
+        d.px = a.px; d.k32 = a.k32; d.cnt = a.cnt; d.order = a.order; d.reg = a.reg; d.kmax = a.kmax;
+        d.seg = a.seg; d.n_seg = a.n_seg; d.n_pass = a.n_pass;
+        o->lines = a.lines; o->response = a.response; o->n_lines = a.n_lines;
     }
     if (ok && (size_t)4 * d.n_bins * 4 > 48 * 1024) {
         ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_hist_kernel), 4 * d.n_bins * 4) &&
@@ -1901,30 +1870,31 @@ int stvo_lsd_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, 
     }
     if (ok && (size_t)d.seg_cap * 8 > 48 * 1024)
         ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_keylines_kernel), d.seg_cap * 8);
-    if (ok && prm->refine == 0 && stvo::dbg().lsd_waves != 0 && B <= stvo::LSD_WAVES_MAX_B && npx <= stvo::LSD_XCD_MAX_PX) {  // small batches (STVO_LSD_WAVES=0: one wave per image there too)
+    if (ok && stvo::dbg().lsd_waves != 0 && stvo::lsd_xcd_route(prm->refine, B, npx)) {  // small batches (STVO_LSD_WAVES=0: one wave per image there too)
         // an XCD has 32 CUs and a CU holds one of the kernel's workgroups: images per XCD x (1 + speculating workgroups) <= 32
         const int per_xcd = (B + 7) / 8;
         int nsb = stvo::dbg().lsd_xcd_blocks == stvo::DBG_UNSET ? (32 / per_xcd - 1 < 16 ? 32 / per_xcd - 1 : 16) : stvo::dbg().lsd_xcd_blocks;  // STVO_LSD_XCD_BLOCKS
         nsb = nsb < 0 ? 0 : (nsb > (stvo::LSD_X_MAXW - 1) / stvo::LSD_XW ? (stvo::LSD_X_MAXW - 1) / stvo::LSD_XW : nsb);
         const size_t nw = 1 + (size_t)nsb * stvo::LSD_XW;
-        decltype(c) cw;
-        const size_t w_stamp = cw.take(nb * nw * npx * 4), w_list = cw.take(nb * nw * npx * 4), w_pend = cw.take(nb * npx * 8 + nb * stvo::LSD_CTL * 4);
+        stvo::Carver wsize;
+        stvo::carve_lsd_xcd_arena(wsize, B, npx, nw);
         o->xcd_lds = (int)(((((npx + 31) / 32) + 3) & ~size_t(3)) * 4) + stvo::LSD_FEED_PX * 4 + stvo::LSD_FEED_Q * 32;
         if (o->xcd_lds < 84 * 1024) o->xcd_lds = 84 * 1024;
         ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_grow_xcd_kernel<false>), o->xcd_lds) &&
              stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_grow_xcd_kernel<true>), o->xcd_lds) &&
-             hip_ok(ctx, hipMalloc((void**)&o->wdev, cw.off), "hipMalloc lsd xcd");
+             hip_ok(ctx, hipMalloc((void**)&o->wdev, wsize.off), "hipMalloc lsd xcd");
         if (ok) {
-            o->xx.stamp = (int32_t*)(o->wdev + w_stamp); o->xx.wlist = (int32_t*)(o->wdev + w_list);
-            o->xx.pend = (long long*)(o->wdev + w_pend); o->xx.ctl = (int32_t*)(o->wdev + w_pend + nb * npx * 8);
+            stvo::Carver cw(o->wdev);
+            const stvo::LsdXcdArena a = stvo::carve_lsd_xcd_arena(cw, B, npx, nw);
+            o->xx.stamp = a.stamp; o->xx.wlist = a.wlist; o->xx.pend = a.pend; o->xx.ctl = a.ctl;
+            o->stamp_bytes = a.stamp_bytes;
+            o->pend_ctl_bytes = a.pend_ctl_bytes;
             o->xx.nsb = nsb;
             const auto& g = stvo::dbg();
             o->xx.feed_ahead = g.lsd_feed_ahead == stvo::DBG_UNSET ? stvo::LSD_FEED_AHEAD : g.lsd_feed_ahead;
             o->xx.sep = g.lsd_sep == stvo::DBG_UNSET ? stvo::LSD_SEP : g.lsd_sep;
             o->xx.ahead = g.lsd_ahead == stvo::DBG_UNSET ? stvo::LSD_AHEAD : g.lsd_ahead;
             o->xx.multi = g.lsd_multi == 0 ? 0 : 1;
-            o->stamp_bytes = nb * nw * npx * 4;
-            o->pend_bytes = nb * npx * 8;
         }
     }
     if (!ok) {

@@ -27,6 +27,8 @@
 
 #include "ctx_internal.h"
 #include "fast_atan2.h"
+#include "frontend_layout.h"
+#include "gaussian_q8.h"
 #include "orb_pattern.h"
 #include "orb_rotate.h"
 
@@ -1127,8 +1129,7 @@ struct stvo_orb {
         bool active = true;    // a level without budget, or smaller than the border, yields nothing
     } lev[STVO_ORB_MAX_LEVELS];
     char* dev = nullptr;  // every device array of the object, carved from one allocation
-    char* io = nullptr;   // staging for the host-buffer entry point: images in, results out
-    size_t io_bytes = 0;
+    Staging io;           // staging for the host-buffer entry point: images in, results out
     int8_t pattern[1024];             // the pool of patch size 31 (stvo_orb_set_pattern; the stand-in by default)
     int8_t* d_pattern = nullptr;
     // the descriptor setting (stvo_orb_set_descriptor).  (2, 31) runs orb_describe_kernel on d_pattern; every other setting runs
@@ -1186,85 +1187,56 @@ int stvo_orb_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keypoints,
         nf[nlevels - 1] = prm->nfeatures - sum > 0 ? prm->nfeatures - sum : 0;
         if (nlevels == 1) nf[0] = prm->nfeatures;
     }
-    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
-    size_t total = 1024;  // the pattern
-    const size_t off_th = total; total += al((size_t)B * 4);
-    const size_t off_eff = total; total += al(1024 + 64);  // the effective pattern and umax of a descriptor setting other than (2, 31)
-    size_t off_blur[STVO_ORB_MAX_LEVELS], off_hist[STVO_ORB_MAX_LEVELS], off_cand[STVO_ORB_MAX_LEVELS], off_hkey[STVO_ORB_MAX_LEVELS], off_nc[STVO_ORB_MAX_LEVELS],
-        off_img[STVO_ORB_MAX_LEVELS], off_out[STVO_ORB_MAX_LEVELS];
+    int lcols[STVO_ORB_MAX_LEVELS], lrows[STVO_ORB_MAX_LEVELS];
     for (int l = 0; l < nlevels; ++l) {
         stvo_orb::Level& L = o->lev[l];
         L.scale = l ? (float)std::pow(prm->scale_factor, (double)l) : 1.f;
         stvo::OrbDev& d = L.d;
         d.B = B; d.K = max_keypoints;
-        d.cols = l ? cv_round_f((float)cols / L.scale) : cols;
-        d.rows = l ? cv_round_f((float)rows / L.scale) : rows;
+        d.cols = lcols[l] = l ? cv_round_f((float)cols / L.scale) : cols;
+        d.rows = lrows[l] = l ? cv_round_f((float)rows / L.scale) : rows;
         d.nfeatures = nf[l]; d.fast_th = prm->fast_threshold; d.edge_th = prm->edge_threshold;
-        d.cand_cap = d.rows * d.cols / 4 + 64;
+        d.cand_cap = stvo::orb_cand_cap(d.cols, d.rows);
         L.active = nf[l] > 0 && 2 * prm->edge_threshold < d.cols && 2 * prm->edge_threshold < d.rows && d.cols >= 16 && d.rows >= 16;
-        const size_t px = (size_t)B * d.rows * d.cols, nk = (size_t)B * max_keypoints;
-        off_blur[l] = total; total += al(px);
-        off_hist[l] = total; total += al((size_t)B * 256 * 4);
-        off_cand[l] = total; total += al((size_t)B * d.cand_cap * 4);
-        off_hkey[l] = total; total += al((size_t)B * d.cand_cap * 4);  // (either score type may be chosen later: stvo_orb_set_score_type)
-        off_nc[l] = total; total += al((size_t)B * 4);
-        off_img[l] = total; if (l) total += al(px);
-        off_out[l] = total; if (nlevels > 1) total += al(nk * 8) + 2 * al(nk * 4) + al(nk * 32) + 2 * al((size_t)B * 4);
     }
-    if (!hip_ok(ctx, hipMalloc((void**)&o->dev, total), "hipMalloc orb") || !zero_device(ctx, o->dev, total, "hipMemset orb")) {
-        if (o->dev) (void)hipFree(o->dev);
-        delete o;
+    stvo::Carver size;
+    stvo::carve_orb_arena(size, B, max_keypoints, nlevels, lcols, lrows);
+    if (!hip_ok(ctx, hipMalloc((void**)&o->dev, size.off), "hipMalloc orb") || !zero_device(ctx, o->dev, size.off, "hipMemset orb")) {
+        stvo_orb_destroy(o);
         return STVO_ERR_HIP;
     }
-    o->d_pattern = (int8_t*)o->dev;
-    o->d_th_own = (int32_t*)(o->dev + off_th);
-    o->d_effective = (int8_t*)(o->dev + off_eff);
-    for (int l = 0; l < nlevels; ++l) {
-        stvo_orb::Level& L = o->lev[l];
-        stvo::OrbDev& d = L.d;
-        const size_t nk = (size_t)B * max_keypoints;
-        d.blur = (uint8_t*)(o->dev + off_blur[l]);
-        d.hist = (int32_t*)(o->dev + off_hist[l]); d.cand = (uint32_t*)(o->dev + off_cand[l]); d.n_cand = (int32_t*)(o->dev + off_nc[l]);
-        d.hkey = (uint32_t*)(o->dev + off_hkey[l]);
-        d.pattern = o->d_pattern;
-        if (l) L.img = (uint8_t*)(o->dev + off_img[l]);
-        if (nlevels > 1) {
-            char* q = o->dev + off_out[l];
-            L.kp = (float*)q; q += al(nk * 8);
-            L.resp = (float*)q; q += al(nk * 4);
-            L.ang = (float*)q; q += al(nk * 4);
-            L.desc = (uint8_t*)q; q += al(nk * 32);
-            L.n = (int32_t*)q; q += al((size_t)B * 4);
-            L.n_tot = (int32_t*)q;
-        }
-    }
+    stvo::Carver c(o->dev);
+    const stvo::OrbArena a = stvo::carve_orb_arena(c, B, max_keypoints, nlevels, lcols, lrows);
+    o->d_pattern = a.pattern; o->d_th_own = a.th_own; o->d_effective = a.effective;
     stvo::orb_default_pool(o->pattern);
     std::memcpy(o->effective, o->pattern, 1024);
     if (!upload_now(ctx, o->d_pattern, o->pattern, 1024, "hipMemcpy pattern")) {
-        (void)hipFree(o->dev);
-        delete o;
+        stvo_orb_destroy(o);
         return STVO_ERR_HIP;
     }
-    {   // getGaussianKernel(7, 2) in 8-bit fixed point; umax of ICAngles
-        double k[7], sum = 0.0;
-        for (int i = 0; i < 7; ++i) {
-            const double x = i - 3;
-            k[i] = std::exp(-x * x / (2.0 * 2.0 * 2.0));
-            sum += k[i];
-        }
-        for (int i = 0; i < 7; ++i) o->blur_k.k[i] = (int)std::lrint((float)(k[i] / sum) * 256.0);
-        stvo::orb_umax(stvo::ORB_HP, o->umax.u);
+    for (int l = 0; l < nlevels; ++l) {
+        stvo_orb::Level& L = o->lev[l];
+        const stvo::OrbLevelBufs& q = a.lev[l];
+        stvo::OrbDev& d = L.d;
+        d.blur = q.blur; d.hist = q.hist; d.cand = q.cand; d.hkey = q.hkey; d.n_cand = q.n_cand;
+        d.pattern = o->d_pattern;
+        L.img = q.img;
+        L.kp = q.kp; L.resp = q.resp; L.ang = q.ang; L.desc = q.desc; L.n = q.n; L.n_tot = q.n_tot;
     }
+    stvo::gaussian_q8(3, 2.0, o->blur_k.k);  // getGaussianKernel(7, 2)
+    stvo::orb_umax(stvo::ORB_HP, o->umax.u);  // umax of ICAngles
     *out = o;
     return STVO_OK;
 }
 
 int stvo_orb_destroy(stvo_orb* o) {
     if (!o) return STVO_OK;
-    (void)hipSetDevice(o->ctx->device);
-    (void)hipStreamSynchronize(o->ctx->stream);
+    if (o->ctx) {
+        (void)hipSetDevice(o->ctx->device);
+        (void)hipStreamSynchronize(o->ctx->stream);
+    }
     if (o->dev) (void)hipFree(o->dev);
-    if (o->io) (void)hipFree(o->io);
+    if (o->io.p) (void)hipFree(o->io.p);
     delete o;
     return STVO_OK;
 }
@@ -1447,28 +1419,21 @@ int stvo_orb_detect_levels(stvo_orb* o, const uint8_t* images, float* kp_xy, flo
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const stvo::OrbDev& d = o->lev[0].d;
     const size_t px = (size_t)d.B * d.rows * d.cols, nk = (size_t)d.B * d.K;
-    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
-    const size_t o_img = 0, o_kp = al(px), o_resp = o_kp + al(nk * 8), o_ang = o_resp + al(nk * 4), o_oct = o_ang + al(nk * 4),
-                 o_desc = o_oct + al(nk * 4), o_n = o_desc + al(nk * 32), o_nt = o_n + al((size_t)d.B * 4), total = o_nt + al((size_t)d.B * 4);
-    if (o->io_bytes < total) {
-        if (o->io) (void)hipFree(o->io);
-        o->io = nullptr;
-        o->io_bytes = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&o->io, total));
-        o->io_bytes = total;
-    }
-    char* D = o->io;
-    HIP_TRY(ctx, hipMemcpyAsync(D + o_img, images, px, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(D + o_kp, 0, total - o_kp, ctx->stream));
-    TRY(stvo_orb_detect_levels_dev(o, (const uint8_t*)(D + o_img), (float*)(D + o_kp), (float*)(D + o_resp), (float*)(D + o_ang),
-                                   (int32_t*)(D + o_oct), (uint8_t*)(D + o_desc), (int32_t*)(D + o_n), (int32_t*)(D + o_nt)));
-    HIP_TRY(ctx, hipMemcpyAsync(kp_xy, D + o_kp, nk * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(response, D + o_resp, nk * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(angle, D + o_ang, nk * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (octave) HIP_TRY(ctx, hipMemcpyAsync(octave, D + o_oct, nk * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(desc, D + o_desc, nk * 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(n_kp, D + o_n, (size_t)d.B * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_total) HIP_TRY(ctx, hipMemcpyAsync(n_total, D + o_nt, (size_t)d.B * 4, hipMemcpyDeviceToHost, ctx->stream));
+    stvo::Carver size;
+    stvo::carve_orb_staging(size, d.B, d.cols, d.rows, d.K);
+    TRY(staging_reserve(ctx, o->io, size.off));
+    stvo::Carver c(o->io.p);
+    const stvo::OrbStaging S = stvo::carve_orb_staging(c, d.B, d.cols, d.rows, d.K);
+    HIP_TRY(ctx, hipMemcpyAsync(S.img, images, px, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(S.kp, 0, (size_t)(o->io.p + c.off - (char*)S.kp), ctx->stream));
+    TRY(stvo_orb_detect_levels_dev(o, S.img, S.kp, S.resp, S.ang, S.oct, S.desc, S.n, S.n_total));
+    HIP_TRY(ctx, hipMemcpyAsync(kp_xy, S.kp, nk * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(response, S.resp, nk * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(angle, S.ang, nk * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (octave) HIP_TRY(ctx, hipMemcpyAsync(octave, S.oct, nk * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(desc, S.desc, nk * 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(n_kp, S.n, (size_t)d.B * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_total) HIP_TRY(ctx, hipMemcpyAsync(n_total, S.n_total, (size_t)d.B * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return STVO_OK;
 }

@@ -6,13 +6,14 @@
 #include <cstdint>
 
 #include "ctx_internal.h"
+#include "frontend_layout.h"
 
 struct stvo_rectify {
     stvo_ctx* ctx = nullptr;
     int B = 0, cols = 0, rows = 0, nquads = 0;
     stvo_rect_camera cam{};
     char* dev = nullptr;  // [side][nquads] int4 map1, then [side][nquads] uint2 map2 (dist = 1 only)
-    uint8_t* io = nullptr;  // staging of the host-buffer entry point: 2 B source images, 2 B destinations (lazy)
+    stvo_detail::Staging io;  // staging of the host-buffer entry point: 2 B source images, 2 B destinations (lazy)
     int4* map1q(int side) const { return reinterpret_cast<int4*>(dev) + (size_t)side * nquads; }
     uint2* map2q(int side) const { return reinterpret_cast<uint2*>(dev + (size_t)2 * nquads * sizeof(int4)) + (size_t)side * nquads; }
 };

@@ -196,7 +196,7 @@ int stvo_rectify_destroy(stvo_rectify* r) {
     (void)hipSetDevice(r->ctx->device);
     (void)hipStreamSynchronize(r->ctx->stream);
     if (r->dev) (void)hipFree(r->dev);
-    if (r->io) (void)hipFree(r->io);
+    if (r->io.p) (void)hipFree(r->io.p);
     delete r;
     return STVO_OK;
 }
@@ -217,19 +217,17 @@ int stvo_rectify_images(stvo_rectify* r, int n, const uint8_t* src_l, const uint
     TRY(check_images(r, n, src_l, src_r, dst_l, dst_r));
     stvo_ctx* ctx = r->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t img = (size_t)r->cols * r->rows, side = (size_t)r->B * img, bytes = (size_t)n * img;
-    if (!r->io) {
-        if (!hip_ok(ctx, hipMalloc((void**)&r->io, 4 * side), "hipMalloc rectify staging")) {
-            r->io = nullptr;
-            return STVO_ERR_HIP;
-        }
-    }
-    uint8_t *sl = r->io, *sr = r->io + side, *dl = r->io + 2 * side, *dr = r->io + 3 * side;
-    HIP_TRY(ctx, hipMemcpyAsync(sl, src_l, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(sr, src_r, bytes, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch_remap(r, n, sl, sr, dl, dr));
-    HIP_TRY(ctx, hipMemcpyAsync(dst_l, dl, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(dst_r, dr, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t bytes = (size_t)n * r->cols * r->rows;
+    stvo::Carver size;
+    stvo::carve_rectify_staging(size, r->B, r->cols, r->rows);
+    TRY(staging_reserve(ctx, r->io, size.off));
+    stvo::Carver c(r->io.p);
+    const stvo::StereoStaging S = stvo::carve_rectify_staging(c, r->B, r->cols, r->rows);
+    HIP_TRY(ctx, hipMemcpyAsync(S.src_l, src_l, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(S.src_r, src_r, bytes, hipMemcpyHostToDevice, ctx->stream));
+    TRY(launch_remap(r, n, S.src_l, S.src_r, S.dst_l, S.dst_r));
+    HIP_TRY(ctx, hipMemcpyAsync(dst_l, S.dst_l, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dst_r, S.dst_r, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return STVO_OK;
 }

@@ -1,36 +1,14 @@
 // seq_layout.h — the memory layouts of the device-resident pipeline, each stated ONCE: the raw frame slot, a stereo set, the block of
-// match indices and inlier masks the host mirrors, and the carver all of them are cut with.  Host-pure (g++ alone compiles it; under
+// match indices and inlier masks the host mirrors, all cut with the carver of carver.h.  Host-pure (g++ alone compiles it; under
 // hipcc the vector types are HIP's): tests/cpp/seq_layout_host.cpp runs every layout here without a device.
 #pragma once
 
-#include <cstddef>
-#include <cstdint>
 #include <type_traits>
 
 #include "../../include/stvo_types.h"
-
-#if defined(__HIPCC__) || defined(__HIP_PLATFORM_AMD__)
-#include <hip/hip_runtime.h>
-#else
-struct alignas(16) float4 { float x, y, z, w; };
-#endif
+#include "carver.h"
 
 namespace stvo {
-
-// Cuts one allocation into buffers of 256-byte-aligned sizes.  take<T>(count) is where a buffer is named: it returns the pointer to store.
-// A layout function runs twice — on a null base, where only `off` (the bytes the allocation needs) matters and the pointers it stores
-// are bare offsets, and on the allocation.  A conditional buffer is `cond ? c.take<T>(n) : nullptr`: nothing is cut for it.
-struct Carver {
-    uintptr_t base = 0;
-    size_t off = 0;  // bytes cut so far: what the next take returns, and at the end the size of the allocation
-    explicit Carver(const void* b = nullptr) : base(reinterpret_cast<uintptr_t>(b)) {}
-    template <typename T>
-    T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(base + off);
-        off += (count * sizeof(T) + 255) & ~size_t(255);
-        return p;
-    }
-};
 
 // ---- a raw frame slot: the features of one frame of all B sequences as uploaded, K / M rows per image ------------------------------
 // One field list, two views: the kernels of a step read a slot (RawFrameView), the two upload routes write one (RawFrame).

@@ -30,7 +30,7 @@ def load():
         return _lib
     so = os.path.join(HERE, "cpp", "libseq_layout_host.so")
     csrc = os.path.join(HERE, "..", "stvo-pl_amd", "csrc")
-    deps = [SRC] + [os.path.join(csrc, h) for h in ("seq_layout.h", "seq_state.h", "kernels.h", "ctx_internal.h", "step_plan.h")] + \
+    deps = [SRC] + [os.path.join(csrc, h) for h in ("carver.h", "seq_layout.h", "seq_state.h", "kernels.h", "ctx_internal.h", "step_plan.h")] + \
         [os.path.join(HERE, "..", "include", h) for h in ("stvo_hip.h", "stvo_types.h")]
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O1"] + FLAGS + ["-fPIC", "-shared", "-o", so, SRC])

@@ -59,7 +59,7 @@ def expect(imgs, m1, m2):
 
 
 @pytest.mark.parametrize("name,ns", [("euroc_params.yaml", (1, 3, 64)), ("perceptin_params.yaml", (1, 3)), ("kitti_distorted", (1, 3)),
-                                     ("odd", (1, 3, 64))])
+                                     ("odd", (1, 3, 64)), ("odd", (64, 2))])  # (64, 2): fewer pairs than B after a full staging block
 def test_remap_parity(hip, name, ns):
     c = kitti_distorted() if name == "kitti_distorted" else odd_calib() if name == "odd" else calib_of(name)
     cam, m1, m2 = capi.rectify_compute(c)

@@ -70,6 +70,39 @@ def test_geometry_radius_3_is_the_oracles_kernel(oracle):
         assert g["radius"] == 3 and np.array_equal(g["weights"], k7)
 
 
+@pytest.mark.parametrize("scale,sigma_scale,radius", st.PAIRS)
+def test_gaussian_q8_against_the_statement(scale, sigma_scale, radius):
+    """the one routine ORB, LBD and stvo_lsd_geometry take their blur weights from (csrc/gaussian_q8.h), on the host"""
+    import frontend_layout_host_lib as flh
+    sigma, h, w = st.weights(scale, sigma_scale)
+    assert h == radius
+    got = flh.gaussian_q8(radius, sigma)
+    assert got.dtype == np.int32 and np.array_equal(got, w)
+
+
+def test_gaussian_q8_is_the_kernel_of_the_orb_and_lbd_blurs(oracle):
+    """(3, 2.0): the weights inside np_orb.gaussian_blur7; (2, 1.0): the five inside orc_gaussian_blur5.  Both keep their weights to
+    themselves, so each is held against the statement's filter run on gaussian_q8's weights: a steep random image, where a weight one
+    off moves whole regions of the result — and the expression itself, restated."""
+    import frontend_layout_host_lib as flh
+    import np_orb
+    w7, w5 = flh.gaussian_q8(3, 2.0), flh.gaussian_q8(2, 1.0)
+    for w, h, sigma in ((w7, 3, 2.0), (w5, 2, 1.0)):
+        k = np.exp(-(np.arange(1 + 2 * h) - float(h)) ** 2 / (2.0 * sigma * sigma))
+        assert np.array_equal(w, np.rint((k / k.sum()).astype(np.float32).astype(np.float64) * 256.0).astype(np.int32))
+    img = np.random.default_rng(5).integers(0, 256, (45, 61), dtype=np.uint8)
+    assert np.array_equal(st.blur(img, w7), np_orb.gaussian_blur7(img))
+    assert np.array_equal(st.blur(img, w5), oracle.gaussian_blur5(img))
+    for i in range(7):  # (the comparison would notice: every weight one off changes the image)
+        off = w7.copy()
+        off[i] += 1
+        assert not np.array_equal(st.blur(img, off), np_orb.gaussian_blur7(img))
+    for i in range(5):
+        off = w5.copy()
+        off[i] += 1
+        assert not np.array_equal(st.blur(img, off), oracle.gaussian_blur5(img))
+
+
 def test_geometry_refuses_what_create_refuses():
     from stvo_amd import capi
     from stvo_amd.capi import StvoError
