@@ -18,7 +18,10 @@ struct stvo_ctx {
     uint2* knn12 = nullptr;
     uint2* knn21 = nullptr;
     size_t knn_capacity = 0;  // elements in each of knn12 / knn21
-    int32_t *cand = nullptr, *need = nullptr, *qsel = nullptr, *nsel = nullptr;  // lazy reverse pass
+    int32_t *cand = nullptr, *qsel = nullptr, *nsel = nullptr;  // lazy reverse pass (match_scratch.h)
+    uint32_t* claim = nullptr;
+    // the matcher's scratch as launch_match takes it
+    stvo::MatchScratch match_scratch() const { return stvo::MatchScratch{knn12, knn21, cand, claim, qsel, nsel, knn_capacity}; }
     // bump arena for the host-buffer entry points
     char* arena = nullptr;
     char* arena_host = nullptr;  // pinned mirror of the arena: uploads are gathered here and sent as ONE H2D copy

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "ctx_internal.h"
+#include "hamming_ops.h"
 #include "point_cells.h"
 
 namespace stvo {
@@ -163,12 +164,6 @@ __global__ __launch_bounds__(256) void grid_cover_kernel(GridBatch g) {
     }
     if (USE_LDS)
         for (int w = 0; w < a.words64; ++w) gcol[(size_t)w * a.n1p] = s_col[w * 256 + threadIdx.x];  // padding columns: zeros
-}
-
-__device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) {
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
 }
 
 // GridStructure::get for a one-row window (src/gridStructure.cpp:65-76) when the right features are numbered in CSR order:

@@ -11,6 +11,7 @@
 
 #include "../../include/stvo_hip.h"
 #include "debug_switches.h"
+#include "match_scratch.h"
 #include "point_tail.h"
 #include "seq_layout.h"
 
@@ -34,22 +35,6 @@ inline bool lds_opt_in(const void* kernel, int bytes) {
     return ok;
 }
 
-constexpr int KNN_MIN_NSEG = 2, KNN_MAX_NSEG = 16;  // train-range segments per query tile in K1
-// Segments per query tile: 1 for very big batches, 2 for big ones (short dispatch rounds), up to 16 for a single frame pair so
-// that one 2000 x 2000 problem still spreads over a few hundred workgroups (single-stream latency).
-// `capacity` = elements of the context's knn scratch arrays: nseg * B * max_n must fit.
-inline int knn_pick_nseg(int B, int max_n, size_t capacity) {
-    const int tiles = (max_n + 255) / 256;
-    int nseg = (2048 + B * tiles - 1) / (B * tiles > 0 ? B * tiles : 1);
-    nseg = nseg < KNN_MIN_NSEG ? KNN_MIN_NSEG : (nseg > KNN_MAX_NSEG ? KNN_MAX_NSEG : nseg);
-    if ((long long)B * tiles >= 4096) nseg = 1;  // >= 5 dispatch rounds even unsegmented: a workgroup's fixed cost is paid once per query tile
-                                                 // (1024 frames: K1m 0.562 -> 0.551 ms, reverse check 0.054 -> 0.050 ms)
-    if (dbg().knn_nseg != DBG_UNSET && dbg().knn_nseg > 0) nseg = dbg().knn_nseg;  // developer override
-    const size_t per_seg = (size_t)(B > 0 ? B : 1) * (size_t)(max_n > 0 ? max_n : 1);
-    while (nseg > 1 && (size_t)nseg * per_seg > capacity) --nseg;
-    return nseg;
-}
-
 // CUs of the current device (persistent-workgroup launches size their grids with it), cached per device
 inline int device_cu_count() {
     static std::mutex mu;
@@ -65,55 +50,57 @@ inline int device_cu_count() {
     return n;
 }
 
-// ---- K1 / K2: brute-force Hamming 2-NN, ratio test, mutual check ----------------------------
-// knn: [nseg][B][row_stride] packed (best_key, second_key) per train segment,
-// key = (distance << 16) | train_index; consumers merge the segments.
-void launch_hamming_knn2(hipStream_t s, int B, int row_stride, int max_n, const uint8_t* d1, const int32_t* n1,
-                         const uint8_t* d2, const int32_t* n2, uint2* knn12, uint2* knn21, int both_directions,
-                         int lds_pad_bytes = 0, int dir0 = 0, const int32_t* qsel = nullptr,
-                         const int32_t* nsel = nullptr, int nseg = KNN_MIN_NSEG, uint32_t* claim_init = nullptr);
-// K1m: the same scan with the distances taken from the matrix cores (match_mfma.hip); qb = query blocks of 32 rows per
-// wave (1, 2 or 4; a workgroup covers 128 * qb query rows).  Train indices must fit 13 bits (max_n <= 8192).
-// the reverse check of the claimed columns in one launch (match_mfma.hip): light columns against S, heavy columns against all rows,
-// the train side of a unit resident in LDS; `slots` workgroups per frame pair share the frame's units; m12[claimant] = -1 for every
-// listed column whose claim another row blocks
-constexpr int REV_MAX_SEG = 8;
-__host__ __device__ inline int rev_segments(int train_rows) {  // train segments of a column list with this many train rows
-    const int s = (train_rows + 255) / 256;
-    return s < 1 ? 1 : (s > REV_MAX_SEG ? REV_MAX_SEG : s);
-}
-void launch_hamming_knn2_mfma_reverse(hipStream_t s, int B, int row_stride, const uint8_t* d1, const int32_t* n1, const uint8_t* d2, const int32_t* qsel,
-                                      const int32_t* nsel, const int32_t* tsel, const uint32_t* claim, float nnr, int32_t* m12, int slots);
-void launch_hamming_knn2_mfma(hipStream_t s, int B, int row_stride, int max_n, const uint8_t* d1, const int32_t* n1,
-                              const uint8_t* d2, const int32_t* n2, uint2* knn12, uint2* knn21, int both_directions,
-                              int dir0, const int32_t* qsel, const int32_t* nsel, int nseg, uint32_t* claim_init, int qb,
-                              int qsel_from_back = 0, const int32_t* tsel = nullptr, const int32_t* ntsel = nullptr);
-int knn_mfma_qb(int max_n);  // query blocks per wave of K1m for this problem size, 0 = VALU kernels
-// mutual matching with a lazy reverse pass: only the columns claimed by an accepted forward match are examined
-// (match_kernels.hip) — on the matrix-core path by a per-frame plan + one launch of sparse reverse scans, on the VALU path
-// (> 8192 rows, STVO_KNN_MFMA=0) by a range query with early exit
-struct LazyScratch {
-    uint2* knn12;
-    uint2* knn21;   // VALU path: reused as int32 blocked[B][row_stride].  Matrix-core path: tsel[] (B * row_stride int32) in the last
-                    // B * row_stride / 2 entries
-    int32_t* cand;  // [B][row_stride] forward ratio-tested best (VALU path)
-    int32_t* need;  // [B][row_stride] per-column claim (d0 << 16 | claimant), 0xFFFFFFFF = unclaimed
-    int32_t* qsel;  // [B][row_stride] compacted flagged columns
-    int32_t* nsel;  // [5][B]: claimed columns; light, heavy, |S|, tau of the matrix-core reverse check (reverse_plan_kernel)
-    size_t knn_capacity;  // elements of knn12 / knn21
+// ---- the brute-force descriptor matcher: StVO::match of B frame pairs (match_kernels.hip, match_mfma.hip) ----------------------
+// cv::BFMatcher(NORM_HAMMING).knnMatch(., ., 2) + the ratio test of StVO::matchNNR + the mutual check of StVO::match.  The scratch
+// it works in, and what a problem needs of it: match_scratch.h.  Two paths, chosen once per launch_match from the row count: the
+// matrix cores (K1m, row_stride <= 8192) or the VALU kernels (beyond, and under STVO_KNN_MFMA=0).
+struct MatchProblem {
+    int B, row_stride;  // frame pairs; rows per frame of d1, d2 and m12
+    const uint8_t* d1;  // [B][row_stride][32] descriptors of the previous frames, n1[b] rows valid
+    const int32_t* n1;  // [B]
+    const uint8_t* d2;  // the current frames
+    const int32_t* n2;
+    float nnr;          // ratio of the test, <= 1
 };
-void launch_match_mutual_lazy(hipStream_t s, int B, int row_stride, const uint8_t* d1, const int32_t* n1,
-                              const uint8_t* d2, const int32_t* n2, float nnr, const LazyScratch& w, int32_t* m12,
-                              int lds_pad_bytes, hipEvent_t wait_before_m12_write, hipEvent_t* timing_events = nullptr);
-// the verification pass alone, on the claims left by the last launch_match_mutual_lazy (timing tools)
-void launch_hamming_verify(hipStream_t s, int B, int row_stride, const uint8_t* d1, const int32_t* n1, const uint8_t* d2,
-                           float nnr, const LazyScratch& w, int lds_pad_bytes, int nseg, int32_t* m12);
+enum class MatchForm {  // (the vocabulary of step_plan.h: MatchRoute; its SMALL is launch_match_small below)
+    ONE_WAY,    // forward scan, ratio test (nnr_mutual_kernel): no mutual check
+    BOTH_DIRS,  // both directions as full scans in one launch, ratio tests + mutual check (nnr_mutual_kernel)
+    LAZY,       // mutual check by a reverse pass over the claimed columns only.  Matrix cores: forward scan, forward_plan_kernel,
+                // hamming_knn2_mfma_reverse_kernel.  VALU: forward scan, nnr_forward_kernel, compact_need_kernel, hamming_verify_kernel,
+                // nnr_reverse_check_kernel
+};
+struct MatchOptions {  // every default is "none"
+    int lds_pad_bytes = 0;                   // VALU scans only: dynamic LDS that caps the resident workgroups per CU (stvo_ctx_set_overlap)
+    hipEvent_t wait_before_m12 = nullptr;    // awaited on the stream before the first kernel that writes m12
+    hipEvent_t* timing_events = nullptr;     // LAZY only: [0], [1] recorded around the forward scan, [2], [3] (either may be null) around the reverse pass
+    int nseg_cap = 0;                        // > 0: at most this many train segments per query tile (MatchPlan::nseg_cap)
+};
+// m12[b][i] = the match of row i of frame pair b, or -1; everything on stream s, in the order named at MatchForm
+void launch_match(hipStream_t s, const MatchProblem& p, MatchForm form, const MatchScratch& w, int32_t* m12, const MatchOptions& o = MatchOptions());
+// single launches of the above, for timing tools (stvo_time_stage_dev): the forward scan; both directions as full scans; the reverse
+// scans of the LAZY form on the claims the last launch_match left in w (they clear the same entries of m12 again)
+void launch_forward_scan_alone(hipStream_t s, const MatchProblem& p, const MatchScratch& w, int lds_pad_bytes);
+void launch_both_dirs_scan_alone(hipStream_t s, const MatchProblem& p, const MatchScratch& w, int lds_pad_bytes);
+void launch_reverse_check_alone(hipStream_t s, const MatchProblem& p, const MatchScratch& w, int lds_pad_bytes, int32_t* m12);
+// between match_kernels.hip and match_mfma.hip: one top-2 scan (out: knn12, and knn21 with both_directions; [nseg][B][row_stride] each)
+struct KnnScan {
+    const MatchProblem& p;
+    int nseg;
+    bool both_directions;
+    uint2 *knn12, *knn21;
+    uint32_t* claim_init;  // or nullptr: [B][row_stride] reset to "unclaimed" on the way (VALU path of LAZY)
+};
+// K1m hamming_knn2_mfma_kernel<qb, 0>: qb = query blocks of 32 rows per wave (1, 2 or 4; a workgroup covers 128 * qb query rows).
+// Train indices must fit 13 bits (row_stride <= 8192).
+void launch_hamming_knn2_mfma(hipStream_t s, const KnnScan& a, int qb);
+// hamming_knn2_mfma_reverse_kernel: the reverse check of the claimed columns in one launch — light columns against S (v.tsel), heavy
+// columns against all rows; `slots` workgroups per frame pair share the frame's units; m12[claimant] = -1 for every listed column
+// whose claim another row blocks
+void launch_hamming_knn2_mfma_reverse(hipStream_t s, const MatchProblem& p, const MatchViews& v, int32_t* m12, int slots);
 // StVO::match of B frame pairs with at most 512 rows per set (key-lines): one workgroup per frame pair, both sets in LDS
 bool match_small_ok(int row_stride);
 void launch_match_small(hipStream_t s, int B, int row_stride, const uint8_t* d1, const int32_t* n1, const uint8_t* d2,
                         const int32_t* n2, float nnr, int mutual, int32_t* m12, int cap = 0 /* rows per set the LDS is sized for; 0: row_stride */);
-void launch_nnr_mutual(hipStream_t s, int B, int row_stride, const uint2* knn12, const uint2* knn21, const int32_t* n1,
-                       const int32_t* n2, float nnr, int mutual, int32_t* m12, int nseg = KNN_MIN_NSEG);
 void launch_valu_probe(hipStream_t s, int blocks, int iters, uint32_t* sink);
 // 16-byte-granular copy kernel; either side may be pinned host memory.  For the few hundred KB a single-stream call
 // moves it has ~5 us less latency than the DMA engine behind hipMemcpyAsync (6 us vs 11 us on top of an empty launch,

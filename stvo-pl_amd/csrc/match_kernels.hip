@@ -1,8 +1,25 @@
-// match_kernels.hip — K1 `hamming_knn2` and K2 `nnr_mutual` for gfx950 (CDNA4, wave64).
+// match_kernels.hip — the brute-force descriptor matcher for gfx950 (CDNA4, wave64): StVO::match of B frame pairs.
 //
-// K1 replaces cv::BFMatcher(NORM_HAMMING).knnMatch(desc1, desc2, ., 2) as called from
-// StVO::matchNNR (/root/reference/src/matching.cpp:47-48), in both directions (:69-74).
-// K2 replaces the float ratio test (:53-58) and the mutual check of StVO::match (:80-86).
+// cv::BFMatcher(NORM_HAMMING).knnMatch(desc1, desc2, ., 2) as called from StVO::matchNNR (the reference's src/matching.cpp:47-48),
+// the float ratio test (:53-58) and the mutual check of StVO::match (:69-74, :80-86).  The host surface is launch_match (kernels.h):
+// it picks the train segments, decides ONCE between the matrix cores (match_mfma.hip) and the VALU kernels below, and launches one
+// of three forms.  The scratch all of them work in: match_scratch.h.
+//
+//   kernel                    launched by                               what it does
+//   hamming_knn2_kernel       launch_scan, VALU path (> 8192 rows,      K1: top-2 scan of one or both directions
+//                             STVO_KNN_MFMA=0), every form
+//   (hamming_knn2_mfma_kernel launch_scan, matrix-core path             K1m: the same scan, match_mfma.hip)
+//   nnr_mutual_kernel         launch_match: ONE_WAY, BOTH_DIRS          K2: ratio test, mutual check against the reverse top-2
+//   forward_plan_kernel       launch_match: LAZY, matrix-core path      ratio test, column claims, verdicts the forward top-2 decides,
+//                                                                       the light / heavy column lists and the row list S
+//   (hamming_knn2_mfma_reverse_kernel  launch_reverse_scans, behind it  the reverse check of those lists, match_mfma.hip)
+//   nnr_forward_kernel        launch_match: LAZY, VALU path             ratio test + column claims
+//   compact_need_kernel       launch_match: LAZY, VALU path             the claimed columns as a list
+//   hamming_verify_kernel     launch_reverse_scans, VALU path           K1v: is any other row within the claim's threshold?
+//   nnr_reverse_check_kernel  launch_match: LAZY, VALU path             m12 from claims and verdicts
+//   match_small_kernel        launch_match_small (the planner's SMALL)  a whole frame pair of <= 512 rows in one workgroup
+//   valu_probe_kernel         launch_valu_probe (stvo_valu_peak_probe)  integer-VALU roof with K1's instruction mix
+//   copy16_kernel             launch_copy16                             16-byte-granular copies, either side may be pinned memory
 //
 // K1 mapping (integer-VALU bound):
 //   * lane  = one QUERY row: its 256-bit descriptor lives in 8 VGPRs for the whole scan
@@ -15,6 +32,7 @@
 //     The packed key makes `min` pick the LOWEST train index among equal distances, which is
 //     knnMatch's tie order (strict '<' insertion over ascending train index).
 //   * grid = (query tiles of 256 rows, 2 directions, B frame pairs); no inter-workgroup traffic.
+#include "hamming_ops.h"
 #include "kernels.h"
 
 #include <stdlib.h>
@@ -27,24 +45,11 @@ __device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c)
     return r;
 }
 
-// popcount-accumulate: D = popcount(x) + acc in ONE VALU op.  Written as inline asm because the
-// compiler otherwise re-associates the 8-term sum into bcnt(x,0) + v_add3 trees (22 instead of
-// 19 VALU ops per pair).
-__device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) {
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
 // key = (d << 16) | j with the wave-uniform train index taken from an SGPR (one VALU op; the
 // compiler's own lowering of (d << 16) | (j + u) is shift + v_or3 = two).
 __device__ __forceinline__ uint32_t pack_key(uint32_t d, uint32_t j_uniform) {
     uint32_t r;
     asm("v_lshl_or_b32 %0, %1, 16, %2" : "=v"(r) : "v"(d), "s"(j_uniform));
-    return r;
-}
-__device__ __forceinline__ uint32_t bcnt0(uint32_t x) {
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, 0" : "=v"(r) : "v"(x));
     return r;
 }
 
@@ -77,20 +82,16 @@ __device__ __forceinline__ uint2 merged_knn(const uint2* __restrict__ knn, size_
     return r;
 }
 
-// qsel / nsel (optional): scan only the listed query rows of this direction (not used by the product path any more:
-// the mutual check is hamming_verify below); qsel = nullptr scans every row.
 // nseg: the train range of every query tile is split into nseg segments scanned by different workgroups
 // (partial top-2 per segment, merged by the consumers).  One wave then works for ~N/nseg rows instead of N,
 // which keeps the dispatch rounds short: with 2000 rows a whole-range wave lasts ~0.5 ms and any grid that
 // is not a multiple of the 8192 resident waves wastes up to one such round.
-__global__ __launch_bounds__(KNN_BLOCK) void hamming_knn2_kernel(int B, int tiles, int ndir, int dir0, int nseg, int row_stride,
+__global__ __launch_bounds__(KNN_BLOCK) void hamming_knn2_kernel(int B, int tiles, int ndir, int nseg, int row_stride,
                                                                  const uint8_t* __restrict__ d1,
                                                                  const int32_t* __restrict__ n1,
                                                                  const uint8_t* __restrict__ d2,
                                                                  const int32_t* __restrict__ n2,
                                                                  uint2* __restrict__ knn12, uint2* __restrict__ knn21,
-                                                                 const int32_t* __restrict__ qsel,
-                                                                 const int32_t* __restrict__ nsel,
                                                                  uint32_t* __restrict__ claim_init) {
     // XCD-aware block -> (frame pair, direction, tile) mapping.  Workgroups are dispatched round-robin
     // over the 8 XCDs (workgroup L runs on XCD L % 8, each XCD has a private 4 MiB L2).  With the
@@ -104,10 +105,10 @@ __global__ __launch_bounds__(KNN_BLOCK) void hamming_knn2_kernel(int B, int tile
     if (b >= B) return;
     const int local = k % per_frame;
     const int seg = local % nseg;
-    const int dir = dir0 + (local / nseg) / tiles;
+    const int dir = (local / nseg) / tiles;
     const int tile = (local / nseg) % tiles;
     const int na = n1[b], nb = n2[b];
-    const int nq = qsel ? nsel[b] : (dir == 0 ? na : nb);
+    const int nq = dir == 0 ? na : nb;
     const int nt_all = dir == 0 ? nb : na;
     // this workgroup's train rows [j0, nt): equal segments rounded up to the 4-row trip
     const int seg_len = (((nt_all + nseg - 1) / nseg) + 3) & ~3;
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void hamming_knn2_kernel(int B, int tile
     const size_t frame_off = (size_t)b * row_stride;
     // lazy mutual matching: the per-column claims consumed by nnr_forward_kernel are reset here (segment 0 covers
     // every column index once) instead of by a separate memset launch
-    if (claim_init && seg == 0 && dir == dir0 && q_base + (int)threadIdx.x < row_stride)
+    if (claim_init && seg == 0 && dir == 0 && q_base + (int)threadIdx.x < row_stride)
         claim_init[frame_off + q_base + threadIdx.x] = 0xFFFFFFFFu;
     if (q_base + (int)(threadIdx.x & ~63u) >= nq) return;  // wave-uniform: no barriers in this kernel
     const uint8_t* Q = (dir == 0 ? d1 : d2) + frame_off * STVO_DESC_BYTES;
@@ -126,9 +127,8 @@ __global__ __launch_bounds__(KNN_BLOCK) void hamming_knn2_kernel(int B, int tile
 
     const int q = q_base + threadIdx.x;
     const int qc = q < nq ? q : nq - 1;  // tail lanes scan a valid row and discard the result
-    const int qi = qsel ? qsel[frame_off + qc] : qc;
-    const uint4 q0 = reinterpret_cast<const uint4*>(Q)[2 * qi];
-    const uint4 q1 = reinterpret_cast<const uint4*>(Q)[2 * qi + 1];
+    const uint4 q0 = reinterpret_cast<const uint4*>(Q)[2 * qc];
+    const uint4 q1 = reinterpret_cast<const uint4*>(Q)[2 * qc + 1];
 
     uint32_t best = 0xFFFFFFFFu, second = 0xFFFFFFFFu;
     uint32_t second_d = 0xFFFFu;  // == second >> 16, refreshed only when the top-2 changes
@@ -158,34 +158,33 @@ __global__ __launch_bounds__(KNN_BLOCK) void hamming_knn2_kernel(int B, int tile
         for (int u = 0; u < 4; ++u) update(d[u], (uint32_t)(j + u));
     }
     for (; j < nt; ++j) update(hamming256(q0, q1, T + 8 * j), (uint32_t)j);
-    if (q < nq) out[qi] = make_uint2(best, second);
+    if (q < nq) out[q] = make_uint2(best, second);
 }
 
 // Query blocks per wave of the matrix-core scan (match_mfma.hip), 0 = use the VALU scan: train indices must fit the
 // 13 index bits of its keys.  STVO_KNN_MFMA=0 selects the VALU kernels (K1 + K1v) for comparison runs.
-int knn_mfma_qb(int max_n) {
+static int knn_mfma_qb(int row_stride) {
     const int qb = dbg().knn_mfma != DBG_UNSET ? dbg().knn_mfma : 2;
-    return max_n <= 8192 ? qb : 0;
+    return row_stride <= 8192 ? qb : 0;
 }
+static int pick_nseg(const MatchProblem& p, const MatchScratch& w) { return knn_pick_nseg(p.B, p.row_stride, w.knn_capacity, dbg().knn_nseg); }
 
-void launch_hamming_knn2(hipStream_t s, int B, int row_stride, int max_n, const uint8_t* d1, const int32_t* n1,
-                         const uint8_t* d2, const int32_t* n2, uint2* knn12, uint2* knn21, int both_directions,
-                         int lds_pad_bytes, int dir0, const int32_t* qsel, const int32_t* nsel, int nseg, uint32_t* claim_init) {
-    if (B <= 0 || max_n <= 0) return;
-    const int mfma_qb = knn_mfma_qb(max_n);
+// one top-2 scan on the path the caller decided (mfma_qb from knn_mfma_qb)
+static void launch_scan(hipStream_t s, const KnnScan& a, int mfma_qb, int lds_pad_bytes) {
+    const MatchProblem& p = a.p;
+    if (p.B <= 0 || p.row_stride <= 0) return;
     if (mfma_qb > 0) {
         // (lds_pad_bytes is not applied: co-residency with the pose kernel does not pay for this kernel)
-        launch_hamming_knn2_mfma(s, B, row_stride, max_n, d1, n1, d2, n2, knn12, knn21, both_directions, dir0, qsel, nsel, nseg,
-                                 claim_init, mfma_qb);
+        launch_hamming_knn2_mfma(s, a, mfma_qb);
         return;
     }
-    const int tiles = (max_n + KNN_BLOCK - 1) / KNN_BLOCK, ndir = both_directions ? 2 : 1;
-    const int groups = (B + 7) / 8;  // frame pairs are dealt to the 8 XCDs in groups of 8
-    dim3 grid((unsigned)(groups * 8 * tiles * ndir * nseg));
+    const int tiles = (p.row_stride + KNN_BLOCK - 1) / KNN_BLOCK, ndir = a.both_directions ? 2 : 1;
+    const int groups = (p.B + 7) / 8;  // frame pairs are dealt to the 8 XCDs in groups of 8
+    dim3 grid((unsigned)(groups * 8 * tiles * ndir * a.nseg));
     // lds_pad_bytes > 0 only caps the number of resident workgroups per CU (the kernel uses no LDS), leaving
     // wave slots and VGPRs for a concurrently running pose kernel (stvo_ctx_set_overlap)
-    hipLaunchKernelGGL(hamming_knn2_kernel, grid, dim3(KNN_BLOCK), (size_t)lds_pad_bytes, s, B, tiles, ndir, dir0,
-                       nseg, row_stride, d1, n1, d2, n2, knn12, knn21, qsel, nsel, claim_init);
+    hipLaunchKernelGGL(hamming_knn2_kernel, grid, dim3(KNN_BLOCK), (size_t)lds_pad_bytes, s, p.B, tiles, ndir, a.nseg, p.row_stride, p.d1,
+                       p.n1, p.d2, p.n2, a.knn12, a.knn21, a.claim_init);
 }
 
 // K2: m12[i] = j  iff  float(d0) < float(d1) * nnr  (12 direction)  and, when `mutual`, the 21
@@ -218,11 +217,9 @@ __global__ __launch_bounds__(256) void nnr_mutual_kernel(int nseg, int row_strid
     m12[off + i] = m;
 }
 
-void launch_nnr_mutual(hipStream_t s, int B, int row_stride, const uint2* knn12, const uint2* knn21, const int32_t* n1,
-                       const int32_t* n2, float nnr, int mutual, int32_t* m12, int nseg) {
-    if (B <= 0 || row_stride <= 0) return;
-    dim3 grid((row_stride + 255) / 256, B);
-    hipLaunchKernelGGL(nnr_mutual_kernel, grid, dim3(256), 0, s, nseg, row_stride, knn12, knn21, n1, n2, nnr, mutual, m12);
+static void launch_nnr_mutual(hipStream_t s, const MatchProblem& p, const MatchScratch& w, int nseg, bool mutual, int32_t* m12) {
+    dim3 grid((p.row_stride + 255) / 256, p.B);
+    hipLaunchKernelGGL(nnr_mutual_kernel, grid, dim3(256), 0, s, nseg, p.row_stride, w.knn12, w.knn21, p.n1, p.n2, p.nnr, mutual ? 1 : 0, m12);
 }
 
 // ---- lazy mutual matching -----------------------------------------------------------------------
@@ -353,11 +350,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void hamming_verify_kernel(int B, int ti
     const uint4 q1 = reinterpret_cast<const uint4*>(d2 + frame_off * STVO_DESC_BYTES)[2 * qi + 1];
     const uint32_t c = claim[frame_off + qi];
     const uint32_t istar = c & 0xFFFFu;
-    uint32_t thr = c >> 16;  // d0
-    {
-        const float f0 = (float)thr;
-        while (thr < 256u && !(f0 < (float)(thr + 1u) * nnr)) ++thr;  // largest distance that still blocks
-    }
+    const uint32_t thr = block_threshold(c >> 16, nnr);  // (c >> 16 = d0)
     bool blk = false;
     // 4 prev rows (128 B, two s_load_dwordx16) per step
     auto step4 = [&](const uint32_t* __restrict__ t, int jb) {
@@ -438,12 +431,6 @@ __global__ __launch_bounds__(1024) void nnr_reverse_check_kernel(int row_stride,
 // a per-frame cut tau splits the claimed columns into LIGHT (T_j <= tau: scanned against S = { second <= tau }, a
 // superset of every S_j) and HEAVY (T_j > tau: scanned against all rows); tau minimises the number of distance
 // evaluations (C - L(tau)) * N1 + L(tau) * |S(tau)| from two 257-bin histograms, tau = -1 being "everything heavy".
-__device__ __forceinline__ uint32_t block_threshold(uint32_t d0, float nnr) {
-    const float f0 = (float)d0;
-    uint32_t thr = d0;
-    while (thr < 256u && !(f0 < (float)(thr + 1u) * nnr)) ++thr;  // largest distance that still blocks
-    return thr;
-}
 
 // One workgroup per frame pair does everything between the forward scan and the reverse scans:
 //   1. merges the per-segment top-2 of every row, applies the forward ratio test (StVO::matchNNR, matching.cpp:53-58) and
@@ -581,74 +568,70 @@ __global__ __launch_bounds__(PLAN_BLOCK) void forward_plan_kernel(int B, int nse
     }
 }
 
-// scratch of the matrix-core reverse check: the last B * row_stride int32 of knn21 hold tsel[] (the reverse top-2 array of the non-lazy
-// path is not needed here)
-struct ReversePlan {
-    int32_t* tsel;
-};
+// ---- the host surface (kernels.h) ---------------------------------------------------------------------------------------------
 constexpr int KNN_REV_SLOTS = 4;  // workgroups per frame pair sharing the frame's reverse-check units (match_mfma.hip)
-static ReversePlan reverse_plan(const LazyScratch& w, int B, int row_stride) {
-    const size_t per = (size_t)B * row_stride;
-    ReversePlan p;
-    p.tsel = reinterpret_cast<int32_t*>(w.knn21 + (w.knn_capacity - per)) + per;  // (the place it had beside the flags of round 5's first form)
-    return p;
-}
 
-// light columns against the rows of S (positions in tsel), heavy columns against every row — one launch; m12 loses the claimants whose
-// column some scanned row blocks
-static void launch_reverse_scans(hipStream_t s, int B, int row_stride, const uint8_t* d1, const int32_t* n1, const uint8_t* d2, float nnr,
-                                 const LazyScratch& w, const ReversePlan& rp, int32_t* m12) {
-    launch_hamming_knn2_mfma_reverse(s, B, row_stride, d1, n1, d2, w.qsel, w.nsel, rp.tsel, reinterpret_cast<const uint32_t*>(w.need), nnr, m12,
-                                     KNN_REV_SLOTS);
-}
-
-void launch_hamming_verify(hipStream_t s, int B, int row_stride, const uint8_t* d1, const int32_t* n1, const uint8_t* d2,
-                           float nnr, const LazyScratch& w, int lds_pad_bytes, int nseg, int32_t* m12) {
-    if (B <= 0 || row_stride <= 0) return;
-    const int mfma_qb = knn_mfma_qb(row_stride);
-    if (mfma_qb > 0) {  // the reverse scans on the lists left by the last forward_plan_kernel (they clear the same entries of m12 again)
-        launch_reverse_scans(s, B, row_stride, d1, n1, d2, nnr, w, reverse_plan(w, B, row_stride), m12);
+// The reverse pass of the LAZY form over the claims and lists in v.  Matrix cores: light columns against the rows of S (positions in
+// tsel), heavy columns against every row — one launch; m12 loses the claimants whose column some scanned row blocks.  VALU: K1v
+// writes its verdicts to v.blocked.
+static void launch_reverse_scans(hipStream_t s, const MatchProblem& p, const MatchViews& v, int mfma_qb, int nseg, int lds_pad_bytes, int32_t* m12) {
+    if (mfma_qb > 0) {
+        launch_hamming_knn2_mfma_reverse(s, p, v, m12, KNN_REV_SLOTS);
         return;
     }
-    const int tiles = (row_stride + KNN_BLOCK - 1) / KNN_BLOCK, groups = (B + 7) / 8;
-    hipLaunchKernelGGL(hamming_verify_kernel, dim3((unsigned)(groups * 8 * tiles * nseg)), dim3(KNN_BLOCK),
-                       (size_t)lds_pad_bytes, s, B, tiles, nseg, row_stride, d1, n1, d2,
-                       reinterpret_cast<const uint32_t*>(w.need), w.qsel, w.nsel, nnr, reinterpret_cast<int32_t*>(w.knn21));
+    const int tiles = (p.row_stride + KNN_BLOCK - 1) / KNN_BLOCK, groups = (p.B + 7) / 8;
+    hipLaunchKernelGGL(hamming_verify_kernel, dim3((unsigned)(groups * 8 * tiles * nseg)), dim3(KNN_BLOCK), (size_t)lds_pad_bytes, s, p.B, tiles,
+                       nseg, p.row_stride, p.d1, p.n1, p.d2, v.claim, v.qsel, v.nsel, p.nnr, v.blocked);
 }
 
-void launch_match_mutual_lazy(hipStream_t s, int B, int row_stride, const uint8_t* d1, const int32_t* n1,
-                              const uint8_t* d2, const int32_t* n2, float nnr, const LazyScratch& w, int32_t* m12,
-                              int lds_pad_bytes, hipEvent_t wait_before_m12_write, hipEvent_t* tev) {
-    if (B <= 0 || row_stride <= 0) return;
-    const dim3 grid2((row_stride + 255) / 256, B);
-    const int nseg = knn_pick_nseg(B, row_stride, w.knn_capacity);
-    uint32_t* claim = reinterpret_cast<uint32_t*>(w.need);
-    int32_t* blocked = reinterpret_cast<int32_t*>(w.knn21);  // the reverse top-2 array is not needed any more
+void launch_match(hipStream_t s, const MatchProblem& p, MatchForm form, const MatchScratch& w, int32_t* m12, const MatchOptions& o) {
+    if (p.B <= 0 || p.row_stride <= 0) return;
+    const int mfma_qb = knn_mfma_qb(p.row_stride);  // matrix cores or VALU kernels: decided here, for every launch below
+    int nseg = pick_nseg(p, w);
+    if (o.nseg_cap > 0 && nseg > o.nseg_cap) nseg = o.nseg_cap;
+    if (form != MatchForm::LAZY) {
+        const bool both = form == MatchForm::BOTH_DIRS;
+        launch_scan(s, KnnScan{p, nseg, both, w.knn12, w.knn21, nullptr}, mfma_qb, o.lds_pad_bytes);
+        if (o.wait_before_m12) (void)hipStreamWaitEvent(s, o.wait_before_m12, 0);
+        launch_nnr_mutual(s, p, w, nseg, both, m12);
+        return;
+    }
+    const MatchViews v = match_views(w, p.B, p.row_stride);
+    hipEvent_t* tev = o.timing_events;
     if (tev) (void)hipEventRecord(tev[0], s);
     // (the VALU path resets the column claims inside K1; forward_plan_kernel of the matrix-core path builds them in LDS)
-    launch_hamming_knn2(s, B, row_stride, row_stride, d1, n1, d2, n2, w.knn12, w.knn21, 0, lds_pad_bytes, 0, nullptr,
-                        nullptr, nseg, knn_mfma_qb(row_stride) > 0 ? nullptr : claim);
+    launch_scan(s, KnnScan{p, nseg, false, w.knn12, w.knn21, mfma_qb > 0 ? nullptr : v.claim}, mfma_qb, o.lds_pad_bytes);
     if (tev) (void)hipEventRecord(tev[1], s);
-    const int mfma_qb = knn_mfma_qb(row_stride);
     if (mfma_qb > 0) {
-        // Two launches behind the forward scan (three until the end of round 5: a last pass turned claim[] and per-column flags into
-        // m12): the plan writes m12 as far as the forward top-2 decides it, the reverse scans clear the claimants they find blocked.
-        const ReversePlan rp = reverse_plan(w, B, row_stride);
-        if (wait_before_m12_write) (void)hipStreamWaitEvent(s, wait_before_m12_write, 0);
+        // Two launches behind the forward scan: the plan writes m12 as far as the forward top-2 decides it, the reverse scans clear the
+        // claimants they find blocked.
+        if (o.wait_before_m12) (void)hipStreamWaitEvent(s, o.wait_before_m12, 0);
         if (tev && tev[2]) (void)hipEventRecord(tev[2], s);
-        hipLaunchKernelGGL(forward_plan_kernel, dim3(B), dim3(PLAN_BLOCK), (size_t)row_stride * 7, s, B, nseg, row_stride, w.knn12,
-                           n1, n2, nnr, m12, claim, w.qsel, rp.tsel, w.nsel);
-        launch_reverse_scans(s, B, row_stride, d1, n1, d2, nnr, w, rp, m12);
+        hipLaunchKernelGGL(forward_plan_kernel, dim3(p.B), dim3(PLAN_BLOCK), (size_t)p.row_stride * 7, s, p.B, nseg, p.row_stride, v.knn12, p.n1,
+                           p.n2, p.nnr, m12, v.claim, v.qsel, v.tsel, v.nsel);
+        launch_reverse_scans(s, p, v, mfma_qb, nseg, o.lds_pad_bytes, m12);
         if (tev && tev[3]) (void)hipEventRecord(tev[3], s);
         return;
     }
-    hipLaunchKernelGGL(nnr_forward_kernel, grid2, dim3(256), 0, s, nseg, row_stride, w.knn12, n1, n2, nnr, w.cand, claim);
-    hipLaunchKernelGGL(compact_need_kernel, dim3(B), dim3(256), 0, s, row_stride, claim, n2, w.qsel, w.nsel, blocked);
+    const dim3 grid2((p.row_stride + 255) / 256, p.B);
+    hipLaunchKernelGGL(nnr_forward_kernel, grid2, dim3(256), 0, s, nseg, p.row_stride, v.knn12, p.n1, p.n2, p.nnr, v.cand, v.claim);
+    hipLaunchKernelGGL(compact_need_kernel, dim3(p.B), dim3(256), 0, s, p.row_stride, v.claim, p.n2, v.qsel, v.nsel, v.blocked);
     if (tev && tev[2]) (void)hipEventRecord(tev[2], s);
-    launch_hamming_verify(s, B, row_stride, d1, n1, d2, nnr, w, lds_pad_bytes, nseg, m12);
+    launch_reverse_scans(s, p, v, mfma_qb, nseg, o.lds_pad_bytes, m12);
     if (tev && tev[3]) (void)hipEventRecord(tev[3], s);
-    if (wait_before_m12_write) (void)hipStreamWaitEvent(s, wait_before_m12_write, 0);
-    hipLaunchKernelGGL(nnr_reverse_check_kernel, dim3(B), dim3(1024), 0, s, row_stride, claim, blocked, n1, m12);
+    if (o.wait_before_m12) (void)hipStreamWaitEvent(s, o.wait_before_m12, 0);
+    hipLaunchKernelGGL(nnr_reverse_check_kernel, dim3(p.B), dim3(1024), 0, s, p.row_stride, v.claim, v.blocked, p.n1, m12);
+}
+
+void launch_forward_scan_alone(hipStream_t s, const MatchProblem& p, const MatchScratch& w, int lds_pad_bytes) {
+    launch_scan(s, KnnScan{p, pick_nseg(p, w), false, w.knn12, w.knn21, nullptr}, knn_mfma_qb(p.row_stride), lds_pad_bytes);
+}
+void launch_both_dirs_scan_alone(hipStream_t s, const MatchProblem& p, const MatchScratch& w, int lds_pad_bytes) {
+    launch_scan(s, KnnScan{p, pick_nseg(p, w), true, w.knn12, w.knn21, nullptr}, knn_mfma_qb(p.row_stride), lds_pad_bytes);
+}
+void launch_reverse_check_alone(hipStream_t s, const MatchProblem& p, const MatchScratch& w, int lds_pad_bytes, int32_t* m12) {
+    if (p.B <= 0 || p.row_stride <= 0) return;
+    launch_reverse_scans(s, p, match_views(w, p.B, p.row_stride), knn_mfma_qb(p.row_stride), pick_nseg(p, w), lds_pad_bytes, m12);
 }
 
 // Integer-VALU roof probe: the same instruction mix as K1's inner loop (xor, bcnt-accumulate,

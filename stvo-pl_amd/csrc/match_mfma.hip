@@ -105,10 +105,7 @@ __device__ __forceinline__ uint32_t key_to_knn(int key, int base) {
     return ((u >> MF_KEY_SHIFT) << 16) | (u & ((1u << MF_KEY_SHIFT) - 1u));
 }
 
-// MODE 0: every row of the direction's query side against every row of its train side (the forward scan).
-// MODE 1: the query rows listed in qsel (front of the per-frame list, or its back when qsel_from_back) against every train row.
-// MODE 2: as 1, and the train rows are the ones listed in tsel; the indices in the keys are then positions in tsel.
-// (the reverse check of the claimed columns, match_kernels.hip; separate instantiations also keep the uses apart in traces)
+// Every row of the direction's query side against every row of its train side.
 template <int QB, int MODE>
 __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void hamming_knn2_mfma_kernel(int B, int tiles, int ndir, int dir0, int nseg, int row_stride,
                                                                       const uint8_t* __restrict__ d1,
@@ -116,12 +113,9 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
                                                                       const uint8_t* __restrict__ d2,
                                                                       const int32_t* __restrict__ n2,
                                                                       uint2* __restrict__ knn12, uint2* __restrict__ knn21,
-                                                                      const int32_t* __restrict__ qsel,
-                                                                      const int32_t* __restrict__ nsel,
-                                                                      uint32_t* __restrict__ claim_init, int qsel_from_back,
-                                                                      const int32_t* __restrict__ tsel,
-                                                                      const int32_t* __restrict__ ntsel) {
-    constexpr bool GATHER = MODE >= 1, TGATHER = MODE == 2;
+                                                                      uint32_t* __restrict__ claim_init) {
+    // the second template argument is part of the name traces and the committed counter files know this kernel by (<QB, 0>)
+    static_assert(MODE == 0, "only the forward scan exists");
     constexpr int ROWS = 4 * QB * 32;  // query rows per workgroup
     constexpr int KSTEPS = 4;  // matrix instructions (K = 64) per 32 x 32 tile of 256-bit distances
     using key_t = float;
@@ -140,7 +134,7 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
     // end slot takes tile min(full, tiles - 1) if it has rows: the ragged tile, or the last full one of a frame that fills its
     // capacity.  The main section then holds full tiles only and the launch ends on the short workgroups at every capacity and
     // row count (1647 rows in slots of 2048: main slots 0 - 5 scan, slot 6 leaves, the end slot scans the 111 rows of tile 6).
-    const bool remap = MODE == 0 && ndir == 1 && tiles > 1;
+    const bool remap = ndir == 1 && tiles > 1;
     bool end_slot = false;
     if (remap) {
         const int groups = (int)(gridDim.x >> 3) / per_frame;  // frames per XCD
@@ -166,7 +160,7 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
     // past the count are inside the frame's slot, are scanned like any other row and never stored).  An end slot learns its
     // tile from the count and fetches behind it; one that leaves requests nothing.
     uint4 qw[QB][2];
-    if (!GATHER && !end_slot) {
+    if (!end_slot) {
 #pragma unroll
         for (int qb = 0; qb < QB; ++qb) {
             const int qi = min(slot * ROWS + (wv * QB + qb) * 32 + col, row_stride - 1);
@@ -175,9 +169,8 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
         }
     }
     const int na = n1[b], nb = n2[b];
-    const int nq = GATHER ? nsel[b] : (dir == 0 ? na : nb);
-    const int nt_all = TGATHER ? ntsel[b] : (dir == 0 ? nb : na);
-    if (TGATHER && nt_all == 0) return;  // an empty row list: the consumer does not read this frame's results (nsel[3][b] == 0)
+    const int nq = dir == 0 ? na : nb;
+    const int nt_all = dir == 0 ? nb : na;
     const int seg_len = (((nt_all + nseg - 1) / nseg) + MF_TILE - 1) & ~(MF_TILE - 1);
     const int j0 = min(seg * seg_len, nt_all);
     const int nt = min(j0 + seg_len, nt_all);
@@ -203,10 +196,9 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
     v4i qf[QB][KSTEPS];
     auto query_row = [&](int qb) {  // recomputed for the final store rather than kept live across the scan
         const int q = block_row(qb);
-        const int qc = q < nq ? q : nq - 1;  // tail lanes scan a valid row and discard the result
-        return GATHER ? qsel[frame_off + (qsel_from_back ? row_stride - 1 - qc : qc)] : qc;
+        return q < nq ? q : nq - 1;  // tail lanes scan a valid row and discard the result
     };
-    if (GATHER || end_slot || one_block) {  // (the early fetch of a one-block tile outside the remap took the two-block rows)
+    if (end_slot || one_block) {  // (the early fetch of a one-block tile outside the remap took the two-block rows)
 #pragma unroll
         for (int qb = 0; qb < QB; ++qb) {
             const int qi = query_row(qb);
@@ -248,7 +240,6 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
     const int nfull = (nt - j0) / MF_TILE;
     auto fetch = [&](int t) -> uint32_t {
         const int j = j0 + t * MF_TILE + xr;
-        if (TGATHER) return j < nt ? T[(size_t)tsel[frame_off + j] * 8 + xk] : 0u;
         const uint32_t* p = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(T) + (voff0 + (uint32_t)t * (MF_TILE * STVO_DESC_BYTES)));
         if (t < nfull) return *p;
         return j < nt ? *p : 0u;
@@ -461,6 +452,11 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
 // Result: m12[claimant] = -1 for every listed column whose claim some other row blocks (each train range decides for itself: the
 // question is a union over ranges; forward_plan_kernel wrote m12[claimant] = column before) — no top-2 array leaves the kernel.
 constexpr int REV_CHUNK_TILES = 8, REV_CHUNK = REV_CHUNK_TILES * MF_TILE;
+constexpr int REV_MAX_SEG = 8;
+__host__ __device__ inline int rev_segments(int train_rows) {  // train segments of a column list with this many train rows
+    const int s = (train_rows + 255) / 256;
+    return s < 1 ? 1 : (s > REV_MAX_SEG ? REV_MAX_SEG : s);
+}
 
 __global__ __launch_bounds__(MF_BLOCK, 4) void hamming_knn2_mfma_reverse_kernel(int B, int slots, int row_stride, const uint8_t* __restrict__ d1,
                                                                                 const int32_t* __restrict__ n1, const uint8_t* __restrict__ d2,
@@ -479,7 +475,8 @@ __global__ __launch_bounds__(MF_BLOCK, 4) void hamming_knn2_mfma_reverse_kernel(
     const int na = n1[b];
     const int nl = nsel[(size_t)B + b], nh = nsel[2 * (size_t)B + b], ns = nsel[3 * (size_t)B + b];
     if ((ns == 0 || nl == 0) && nh == 0) return;  // (an empty S: nothing can block a light column any more)
-    {   // match_kernels.hip: block_threshold — the largest d' for which float(d0) < float(d') * nnr is false
+    {   // block_threshold (match_scratch.h) for every d0, its loop written out: calling the function here changes the register
+        // allocation of this whole kernel
         const float f0 = (float)threadIdx.x;
         uint32_t thr = threadIdx.x;
         while (thr < 256u && !(f0 < (float)(thr + 1u) * nnr)) ++thr;
@@ -662,40 +659,32 @@ __global__ __launch_bounds__(MF_BLOCK, 4) void hamming_knn2_mfma_reverse_kernel(
     }
 }
 
-void launch_hamming_knn2_mfma_reverse(hipStream_t s, int B, int row_stride, const uint8_t* d1, const int32_t* n1, const uint8_t* d2, const int32_t* qsel,
-                                      const int32_t* nsel, const int32_t* tsel, const uint32_t* claim, float nnr, int32_t* m12, int slots) {
-    if (B <= 0 || row_stride <= 0) return;
-    const dim3 grid((unsigned)(((B + 7) / 8) * 8 * slots));
-    hipLaunchKernelGGL(hamming_knn2_mfma_reverse_kernel, grid, dim3(MF_BLOCK), 0, s, B, slots, row_stride, d1, n1, d2, qsel, nsel, tsel, claim, nnr, m12);
+void launch_hamming_knn2_mfma_reverse(hipStream_t s, const MatchProblem& p, const MatchViews& v, int32_t* m12, int slots) {
+    if (p.B <= 0 || p.row_stride <= 0) return;
+    const dim3 grid((unsigned)(((p.B + 7) / 8) * 8 * slots));
+    hipLaunchKernelGGL(hamming_knn2_mfma_reverse_kernel, grid, dim3(MF_BLOCK), 0, s, p.B, slots, p.row_stride, p.d1, p.n1, p.d2, v.qsel, v.nsel, v.tsel,
+                       v.claim, p.nnr, m12);
 }
 
-int mfma_rows_per_block(int qb) { return 4 * qb * 32; }
-
-template <int QB, int MODE>
-static void launch_mf(dim3 grid, hipStream_t s, int B, int tiles, int ndir, int dir0, int nseg, int row_stride, const uint8_t* d1,
-                      const int32_t* n1, const uint8_t* d2, const int32_t* n2, uint2* knn12, uint2* knn21, const int32_t* qsel,
-                      const int32_t* nsel, uint32_t* claim_init, int qsel_from_back, const int32_t* tsel, const int32_t* ntsel) {
-    hipLaunchKernelGGL((hamming_knn2_mfma_kernel<QB, MODE>), grid, dim3(MF_BLOCK), 0, s, B, tiles, ndir, dir0, nseg, row_stride, d1, n1, d2, n2,
-                       knn12, knn21, qsel, nsel, claim_init, qsel_from_back, tsel, ntsel);
+template <int QB>
+static void launch_mf(hipStream_t s, const KnnScan& a) {
+    const MatchProblem& p = a.p;
+    constexpr int rows = 4 * QB * 32;  // query rows per workgroup
+    const int tiles = (p.row_stride + rows - 1) / rows, ndir = a.both_directions ? 2 : 1;
+    const int groups = (p.B + 7) / 8;
+    const dim3 grid((unsigned)(groups * 8 * tiles * ndir * a.nseg));
+    // dir0, the first direction of the launch, stays a kernel argument although it is always the forward one: as a constant it
+    // takes an instruction out of the scan, and this kernel's instruction stream is held fixed
+    const int first_direction = 0;
+    hipLaunchKernelGGL((hamming_knn2_mfma_kernel<QB, 0>), grid, dim3(MF_BLOCK), 0, s, p.B, tiles, ndir, first_direction, a.nseg, p.row_stride, p.d1, p.n1, p.d2, p.n2,
+                       a.knn12, a.knn21, a.claim_init);
 }
 
-void launch_hamming_knn2_mfma(hipStream_t s, int B, int row_stride, int max_n, const uint8_t* d1, const int32_t* n1,
-                              const uint8_t* d2, const int32_t* n2, uint2* knn12, uint2* knn21, int both_directions,
-                              int dir0, const int32_t* qsel, const int32_t* nsel, int nseg, uint32_t* claim_init, int qb,
-                              int qsel_from_back, const int32_t* tsel, const int32_t* ntsel) {
-    if (B <= 0 || max_n <= 0) return;
-    const int rows = mfma_rows_per_block(qb);
-    const int tiles = (max_n + rows - 1) / rows, ndir = both_directions ? 2 : 1;
-    const int groups = (B + 7) / 8;
-    const dim3 grid((unsigned)(groups * 8 * tiles * ndir * nseg));
-#define STVO_MF_ARGS grid, s, B, tiles, ndir, dir0, nseg, row_stride, d1, n1, d2, n2, knn12, knn21, qsel, nsel, claim_init, qsel_from_back, tsel, ntsel
-    // (MODE 1 / 2 — listed query rows / listed train rows — served the reverse check until round 5, which has its own kernel above;
-    //  no caller passes a list any more and only the forward form is instantiated)
-    if (qsel || tsel) return;
-    if (qb == 1) launch_mf<1, 0>(STVO_MF_ARGS);
-    else if (qb == 2) launch_mf<2, 0>(STVO_MF_ARGS);
-    else launch_mf<4, 0>(STVO_MF_ARGS);
-#undef STVO_MF_ARGS
+void launch_hamming_knn2_mfma(hipStream_t s, const KnnScan& a, int qb) {
+    if (a.p.B <= 0 || a.p.row_stride <= 0) return;
+    if (qb == 1) launch_mf<1>(s, a);
+    else if (qb == 2) launch_mf<2>(s, a);
+    else launch_mf<4>(s, a);
 }
 
 }  // namespace stvo

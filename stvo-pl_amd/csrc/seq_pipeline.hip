@@ -84,13 +84,13 @@ int stvo_seq_create_multi(stvo_ctx* ctx, int B, int max_keypoints, int max_keyli
     for (int b = 0; b < B; ++b)
         if (img_cols[b] <= 0 || img_rows[b] <= 0) return STVO_ERR_INVALID_ARG;
     if (max_keypoints > STVO_POSE_MAX_POINTS || max_keylines > STVO_POSE_MAX_LINES) return STVO_ERR_CAPACITY;
-    // the pipeline runs the context's matching scratch (cand / need / qsel: max_rows x max_batch ints, nsel: [5][max_batch])
+    // the pipeline runs the context's matching scratch (cand / claim / qsel: max_rows x max_batch ints, nsel: [5][max_batch])
     // with K = max_keypoints rounded up to 64 as row stride: validate the ROUNDED figures
     const int K = (max_keypoints + 63) & ~63;
     const int M = max_keylines > 0 ? ((max_keylines + 63) & ~63) : 64;
     if (B > ctx->max_batch || K > ctx->max_rows || (size_t)B * (size_t)K > (size_t)ctx->max_batch * (size_t)ctx->max_rows)
         return STVO_ERR_CAPACITY;
-    if ((size_t)2 * B * K > ctx->knn_capacity) return STVO_ERR_CAPACITY;  // forward top-2 + reverse-check scratch (reverse_plan)
+    if (!stvo::match_scratch_fits(B, K, ctx->knn_capacity)) return STVO_ERR_CAPACITY;  // forward top-2 + reverse-check scratch (match_scratch.h)
     if (!(mp->min_ratio_12_p <= 1.0f) || !(mp->min_ratio_12_l <= 1.0f)) return STVO_ERR_INVALID_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     stvo_seq* s = new (std::nothrow) stvo_seq();
@@ -109,6 +109,10 @@ int stvo_seq_create_multi(stvo_ctx* ctx, int B, int max_keypoints, int max_keyli
     for (int b = 0; b < B; ++b) s->img_size_host.insert(s->img_size_host.end(), {img_cols[b], img_rows[b]});
     s->raw_span = stvo::raw_frame_span(B, K, M);
     s->dev_bytes = stvo::seq_layout(*s, nullptr);
+    if (!stvo::match_scratch_fits(B, M, s->lazy_l.knn_capacity)) {  // the key-line scratch, as the context's for the key-points above
+        delete s;
+        return STVO_ERR_CAPACITY;
+    }
     bool ok = hip_ok(ctx, hipMalloc((void**)&s->dev, s->dev_bytes), "hipMalloc seq") && zero_device(ctx, s->dev, s->dev_bytes, "hipMemset seq");
     for (char*& h : s->raw_host) ok = ok && hip_ok(ctx, hipHostMalloc((void**)&h, s->raw_span.bytes, hipHostMallocDefault), "hipHostMalloc seq");
     ok = ok && hip_ok(ctx, hipHostMalloc((void**)&s->out_host, nb * (sizeof(stvo_pose_result) + 16), hipHostMallocDefault), "hipHostMalloc seq out") &&
@@ -462,29 +466,27 @@ int StepEnq::line_stage() const {
 // ---- f2fTracking: prev stereo sets vs curr stereo sets, then the line stream joins (or signals) and the match indices leave for the host
 int StepEnq::f2f_and_join() const {
     const int B = s->B;
-    auto match_set = [&](const stvo::MatchPlan& m, hipStream_t q, const stvo::LazyScratch& ws, int stride, const uint8_t* da, const int32_t* na,
+    auto match_set = [&](const stvo::MatchPlan& m, hipStream_t q, const stvo::MatchScratch& ws, int stride, const uint8_t* da, const int32_t* na,
                          const uint8_t* db, const int32_t* nb, float nnr, int32_t* m12, hipEvent_t* mev) {
         if (m.route == stvo::MatchRoute::SMALL) {
             stvo::launch_match_small(q, B, stride, da, na, db, nb, nnr, s->mp.best_lr_matches, m12, m.small_cap);
-        } else if (m.route == stvo::MatchRoute::BOTH_DIRS) {
-            const int nseg = std::min(m.nseg_cap, stvo::knn_pick_nseg(B, stride, ws.knn_capacity));
-            stvo::launch_hamming_knn2(q, B, stride, stride, da, na, db, nb, ws.knn12, ws.knn21, 1, 0, 0, nullptr, nullptr, nseg);
-            stvo::launch_nnr_mutual(q, B, stride, ws.knn12, ws.knn21, na, nb, nnr, 1, m12, nseg);
-        } else if (m.route == stvo::MatchRoute::LAZY) {
-            stvo::launch_match_mutual_lazy(q, B, stride, da, na, db, nb, nnr, ws, m12, 0, nullptr, mev);
-        } else {
-            const int nseg = stvo::knn_pick_nseg(B, stride, ws.knn_capacity);
-            stvo::launch_hamming_knn2(q, B, stride, stride, da, na, db, nb, ws.knn12, ws.knn21, 0, 0, 0, nullptr, nullptr, nseg);
-            stvo::launch_nnr_mutual(q, B, stride, ws.knn12, ws.knn21, na, nb, nnr, 0, m12, nseg);
+            return;
         }
+        const stvo::MatchForm form = m.route == stvo::MatchRoute::BOTH_DIRS ? stvo::MatchForm::BOTH_DIRS
+                                     : m.route == stvo::MatchRoute::LAZY    ? stvo::MatchForm::LAZY
+                                                                            : stvo::MatchForm::ONE_WAY;
+        stvo::MatchOptions o;
+        o.timing_events = mev;
+        o.nseg_cap = m.nseg_cap;
+        stvo::launch_match(q, stvo::MatchProblem{B, stride, da, na, db, nb, nnr}, form, ws, m12, o);
     };
     if (p.track) {
-        const stvo::LazyScratch w{ctx->knn12, ctx->knn21, ctx->cand, ctx->need, ctx->qsel, ctx->nsel, ctx->knn_capacity};
+        const stvo::MatchScratch w = ctx->match_scratch();
         hipEvent_t mev_light[4] = {tev ? tev[4] : nullptr, tev ? tev[5] : nullptr, nullptr, nullptr};  // (light: no pair around plan + reverse scans)
         if (p.point_stage)
             match_set(p.match_points, st, w, s->K, ps.desc, ps.n, cs.desc, cs.n, s->mp.min_ratio_12_p, s->fb.m12p, tev ? (p.light ? mev_light : tev + 4) : nullptr);
         if (p.match_lines_run)
-            match_set(p.match_lines, sl, s->lazy_l, s->M, ps.ldesc, ps.nl, cs.ldesc, cs.nl, s->mp.min_ratio_12_l, m12l_use, nullptr);
+            match_set(p.match_lines, sl, s->lazy_l.match_scratch(), s->M, ps.ldesc, ps.nl, cs.ldesc, cs.nl, s->mp.min_ratio_12_l, m12l_use, nullptr);
         if (p.clear_m12l) HIP_TRY(ctx, hipMemsetAsync(m12l_use, 0xFF, (size_t)B * s->M * sizeof(int32_t), st));
     }
     if (p.join_signal) {

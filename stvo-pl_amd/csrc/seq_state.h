@@ -198,7 +198,16 @@ struct stvo_seq {
     } cells_buf[2] = {};
     unsigned long long *cover_l = nullptr, *top2_l = nullptr;
     int32_t* owner2_l = nullptr;
-    stvo::LazyScratch lazy_l{};
+    // the matcher's scratch for the key-lines, as the layout below cuts it (the context owns the key-points').  `need` holds the column
+    // claims — MatchScratch::claim; the buffer keeps the name the pipeline's buffer list knows it by (tests/cpp/seq_layout_host.cpp)
+    struct KeylineMatchBufs {
+        uint2 *knn12, *knn21;
+        int32_t* cand;
+        uint32_t* need;
+        int32_t *qsel, *nsel;
+        size_t knn_capacity;
+        stvo::MatchScratch match_scratch() const { return stvo::MatchScratch{knn12, knn21, cand, need, qsel, nsel, knn_capacity}; }
+    } lazy_l{};
     // optional by-products for callers that mirror the reference's host-side feature lists (StereoFrameHandler):
     // the four match-index arrays are copied to pinned memory right after the f2f stage (ev_fetch), i.e. while the
     // pose kernel still runs; the inlier masks follow the pose kernel.  fetch_host mirrors `fb`, offset for offset.
@@ -267,10 +276,10 @@ inline size_t seq_layout(stvo_seq& s, char* base) {
     const bool alt_l = B >= 64;  // second copy of the key-line match indices (key-line stage ahead: batches only)
     s.m12l_alt = alt_l ? i32(nM) : nullptr;
     s.cover_l = c.take<u64>(nb * (size_t)(M / 64) * M); s.top2_l = c.take<u64>(nM); s.owner2_l = i32(nM);
-    LazyScratch& w = s.lazy_l;
-    w.knn_capacity = nM * 4;  // line f2f: up to 4 train segments
+    stvo_seq::KeylineMatchBufs& w = s.lazy_l;
+    w.knn_capacity = nM * 4;  // line f2f: up to 4 train segments; stvo_seq_create_multi holds it against match_scratch_fits
     w.knn12 = c.take<uint2>(w.knn_capacity); w.knn21 = c.take<uint2>(w.knn_capacity);
-    w.cand = i32(nM); w.need = i32(nM); w.qsel = i32(nM); w.nsel = i32(nb * 5);
+    w.cand = i32(nM); w.need = c.take<uint32_t>(nM); w.qsel = i32(nM); w.nsel = i32(nb * 5);
     for (StereoSetPtrs& q : s.set) q = carve_stereo_set(c, B, K, M, true);
     return c.off;
 }

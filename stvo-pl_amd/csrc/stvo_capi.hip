@@ -109,7 +109,7 @@ int stvo_ctx_create(int device_id, int max_rows, int max_batch, stvo_ctx** out) 
     ok = ok && hip_ok(ctx, hipMalloc((void**)&ctx->knn12, knn_seg_elems * sizeof(uint2)), "hipMalloc knn12") &&
          hip_ok(ctx, hipMalloc((void**)&ctx->knn21, knn_seg_elems * sizeof(uint2)), "hipMalloc knn21") &&
          hip_ok(ctx, hipMalloc((void**)&ctx->cand, knn_elems * sizeof(int32_t)), "hipMalloc cand") &&
-         hip_ok(ctx, hipMalloc((void**)&ctx->need, knn_elems * sizeof(int32_t)), "hipMalloc need") &&
+         hip_ok(ctx, hipMalloc((void**)&ctx->claim, knn_elems * sizeof(uint32_t)), "hipMalloc claim") &&
          hip_ok(ctx, hipMalloc((void**)&ctx->qsel, knn_elems * sizeof(int32_t)), "hipMalloc qsel") &&
          hip_ok(ctx, hipMalloc((void**)&ctx->nsel, (size_t)max_batch * 5 * sizeof(int32_t)), "hipMalloc nsel") &&
          hip_ok(ctx, hipMalloc((void**)&ctx->arena, ctx->arena_size), "hipMalloc arena") &&
@@ -130,7 +130,7 @@ int stvo_ctx_destroy(stvo_ctx* ctx) {
     if (ctx->knn12) (void)hipFree(ctx->knn12);
     if (ctx->knn21) (void)hipFree(ctx->knn21);
     if (ctx->cand) (void)hipFree(ctx->cand);
-    if (ctx->need) (void)hipFree(ctx->need);
+    if (ctx->claim) (void)hipFree(ctx->claim);
     if (ctx->qsel) (void)hipFree(ctx->qsel);
     if (ctx->nsel) (void)hipFree(ctx->nsel);
     if (ctx->arena) (void)hipFree(ctx->arena);
@@ -195,6 +195,9 @@ int stvo_ctx_set_overlap(stvo_ctx* ctx, int enable) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// the ABI's `mutual` flag as a form of launch_match: the mutual check always by the lazy reverse pass
+static stvo::MatchForm match_form(int mutual) { return mutual ? stvo::MatchForm::LAZY : stvo::MatchForm::ONE_WAY; }
+
 int stvo_match_nnr_mutual(stvo_ctx* ctx, const uint8_t* d1, int n1, const uint8_t* d2, int n2, float nnr, int mutual,
                           int32_t* m12, int32_t* n_matches) {
     if (!ctx || n1 < 0 || n2 < 0 || (n1 > 0 && (!d1 || !m12)) || (n2 > 0 && !d2)) return STVO_ERR_INVALID_ARG;
@@ -214,15 +217,7 @@ int stvo_match_nnr_mutual(stvo_ctx* ctx, const uint8_t* d1, int n1, const uint8_
     TRY(upload(ctx, &dn2, &n2, 1));
     TRY(flush_uploads(ctx));
     TRY(upload(ctx, &dm12, (const int32_t*)nullptr, (size_t)stride));
-    if (mutual) {
-        const stvo::LazyScratch w{ctx->knn12, ctx->knn21, ctx->cand, ctx->need, ctx->qsel, ctx->nsel, ctx->knn_capacity};
-        stvo::launch_match_mutual_lazy(ctx->stream, 1, stride, dd1, dn1, dd2, dn2, nnr, w, dm12, 0, nullptr);
-    } else {
-        const int nseg = stvo::knn_pick_nseg(1, stride, ctx->knn_capacity);
-        stvo::launch_hamming_knn2(ctx->stream, 1, stride, stride, dd1, dn1, dd2, dn2, ctx->knn12, ctx->knn21, 0, 0, 0,
-                                  nullptr, nullptr, nseg);
-        stvo::launch_nnr_mutual(ctx->stream, 1, stride, ctx->knn12, ctx->knn21, dn1, dn2, nnr, 0, dm12, nseg);
-    }
+    stvo::launch_match(ctx->stream, stvo::MatchProblem{1, stride, dd1, dn1, dd2, dn2, nnr}, match_form(mutual), ctx->match_scratch(), dm12);
     TRY(check_launch(ctx));
     TRY(download_begin(ctx, dm12, (size_t)n1 * sizeof(int32_t)));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -239,21 +234,13 @@ int stvo_match_nnr_mutual_batched_dev(stvo_ctx* ctx, int B, int row_stride, cons
                                       const uint8_t* d2, const int32_t* n2, float nnr, int mutual, int32_t* m12) {
     if (!ctx || B < 0 || row_stride <= 0 || !d1 || !d2 || !n1 || !n2 || !m12 || !(nnr <= 1.0f))
         return STVO_ERR_INVALID_ARG;
-    // per-problem scratch (nsel: [5][max_batch]) and per-row scratch (cand / need / qsel: max_batch x max_rows; the knn
-    // arrays hold the forward top-2 plus the reverse-check lists: 2 x B x row_stride) are sized by the context
+    // per-problem scratch (nsel: [5][max_batch]) and per-row scratch (cand / claim / qsel: max_batch x max_rows) are sized by the
+    // context; what the knn arrays must hold: match_scratch.h
     if (B > ctx->max_batch || (size_t)B * row_stride > (size_t)ctx->max_batch * ctx->max_rows || row_stride > STVO_MAX_ROWS_LIMIT ||
-        (size_t)2 * B * row_stride > ctx->knn_capacity)
+        !stvo::match_scratch_fits(B, row_stride, ctx->knn_capacity))
         return STVO_ERR_CAPACITY;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (mutual) {
-        const stvo::LazyScratch w{ctx->knn12, ctx->knn21, ctx->cand, ctx->need, ctx->qsel, ctx->nsel, ctx->knn_capacity};
-        stvo::launch_match_mutual_lazy(ctx->stream, B, row_stride, d1, n1, d2, n2, nnr, w, m12, 0, nullptr);
-    } else {
-        const int nseg = stvo::knn_pick_nseg(B, row_stride, ctx->knn_capacity);
-        stvo::launch_hamming_knn2(ctx->stream, B, row_stride, row_stride, d1, n1, d2, n2, ctx->knn12, ctx->knn21, 0, 0, 0,
-                                  nullptr, nullptr, nseg);
-        stvo::launch_nnr_mutual(ctx->stream, B, row_stride, ctx->knn12, ctx->knn21, n1, n2, nnr, 0, m12, nseg);
-    }
+    stvo::launch_match(ctx->stream, stvo::MatchProblem{B, row_stride, d1, n1, d2, n2, nnr}, match_form(mutual), ctx->match_scratch(), m12);
     return check_launch(ctx);
 }
 
@@ -417,7 +404,7 @@ int check_batch(stvo_ctx* ctx, const stvo_track_batch_dev* b, bool need_desc) {
     if (b->max_pts > STVO_POSE_MAX_POINTS || b->max_lines > STVO_POSE_MAX_LINES) return STVO_ERR_CAPACITY;
     const size_t rows = (size_t)(b->max_pts > b->max_lines ? b->max_pts : b->max_lines);
     if (b->B > ctx->max_batch || (size_t)b->B * rows > (size_t)ctx->max_batch * (size_t)ctx->max_rows ||
-        (size_t)2 * b->B * rows > ctx->knn_capacity)
+        !stvo::match_scratch_fits(b->B, (int)rows, ctx->knn_capacity))
         return STVO_ERR_CAPACITY;
     return STVO_OK;
 }
@@ -435,11 +422,12 @@ int stvo_track_batched_dev(stvo_ctx* ctx, const stvo_track_batch_dev* b, const s
     // kernel); K2 rewrites m12, which the previous pose kernel may still be reading => K2 waits for it.
     const int pad = ctx->overlap ? kOverlapLdsPad : 0;
     hipEvent_t prev_pose = (ctx->overlap && ctx->pose_pending) ? ctx->ev_pose_done : nullptr;
-    const stvo::LazyScratch w{ctx->knn12, ctx->knn21, ctx->cand, ctx->need, ctx->qsel, ctx->nsel, ctx->knn_capacity};
     auto match_set = [&](int stride, const uint8_t* da, const int32_t* na, const uint8_t* db, const int32_t* nb,
                          float nnr, int32_t* m12) {
+        stvo::MatchOptions o;
+        o.lds_pad_bytes = pad;
+        o.wait_before_m12 = prev_pose;
         if (mutual) {
-            hipEvent_t* tev = nullptr;
             if (ctx->timing && da == b->prev_pdesc) {  // time the point-descriptor launches only
                 while (ctx->ev_pool.size() < ctx->ev_used + 4) {
                     hipEvent_t e;
@@ -447,18 +435,12 @@ int stvo_track_batched_dev(stvo_ctx* ctx, const stvo_track_batch_dev* b, const s
                     ctx->ev_pool.push_back(e);
                 }
                 if (ctx->ev_pool.size() >= ctx->ev_used + 4) {
-                    tev = ctx->ev_pool.data() + ctx->ev_used;
+                    o.timing_events = ctx->ev_pool.data() + ctx->ev_used;
                     ctx->ev_used += 4;
                 }
             }
-            stvo::launch_match_mutual_lazy(ctx->stream, b->B, stride, da, na, db, nb, nnr, w, m12, pad, prev_pose, tev);
-        } else {
-            const int nseg = stvo::knn_pick_nseg(b->B, stride, ctx->knn_capacity);
-            stvo::launch_hamming_knn2(ctx->stream, b->B, stride, stride, da, na, db, nb, ctx->knn12, ctx->knn21, 0, pad, 0,
-                                      nullptr, nullptr, nseg);
-            if (prev_pose) (void)hipStreamWaitEvent(ctx->stream, prev_pose, 0);
-            stvo::launch_nnr_mutual(ctx->stream, b->B, stride, ctx->knn12, ctx->knn21, na, nb, nnr, 0, m12, nseg);
         }
+        stvo::launch_match(ctx->stream, stvo::MatchProblem{b->B, stride, da, na, db, nb, nnr}, match_form(mutual), ctx->match_scratch(), m12, o);
     };
     // matchF2FPoints (:131-153)
     if (params->has_points)
@@ -508,20 +490,17 @@ int stvo_time_stage_dev(stvo_ctx* ctx, const stvo_track_batch_dev* b, const stvo
     stvo::PoseArgs a{};
     fill_pose_args(b, cam, params, false, &a);
     HIP_TRY(ctx, hipEventRecord(e0, ctx->stream));
-    const stvo::LazyScratch lw{ctx->knn12, ctx->knn21, ctx->cand, ctx->need, ctx->qsel, ctx->nsel, ctx->knn_capacity};
+    const stvo::MatchProblem points{b->B, b->max_pts, b->prev_pdesc, b->n_prev_pts, b->curr_pdesc, b->n_curr_pts, nnr};
+    const stvo::MatchScratch w = ctx->match_scratch();
     for (int it = 0; it < iters; ++it) {
         const int pad = ctx->overlap ? kOverlapLdsPad : 0;
-        const int nseg = stvo::knn_pick_nseg(b->B, b->max_pts, ctx->knn_capacity);
-        if (stage == 0 || stage == 2) {  // hamming_knn2: the forward top-2 scan of every prev row
-            stvo::launch_hamming_knn2(ctx->stream, b->B, b->max_pts, b->max_pts, b->prev_pdesc, b->n_prev_pts,
-                                      b->curr_pdesc, b->n_curr_pts, ctx->knn12, ctx->knn21, 0, pad, 0, nullptr, nullptr, nseg);
-        } else if (stage == 3) {  // hamming_verify on the claims of the LAST stvo_track_batched_dev call
-            stvo::launch_hamming_verify(ctx->stream, b->B, b->max_pts, b->prev_pdesc, b->n_prev_pts, b->curr_pdesc, nnr, lw,
-                                        pad, nseg, b->m12_pts);
-        } else if (stage == 4) {  // developer probe: both directions as full top-2 scans (the pre-lazy formulation)
-            stvo::launch_hamming_knn2(ctx->stream, b->B, b->max_pts, b->max_pts, b->prev_pdesc, b->n_prev_pts,
-                                      b->curr_pdesc, b->n_curr_pts, ctx->knn12, ctx->knn21, 1, pad, 0, nullptr, nullptr, nseg);
-        } else
+        if (stage == 0 || stage == 2)  // hamming_knn2: the forward top-2 scan of every prev row
+            stvo::launch_forward_scan_alone(ctx->stream, points, w, pad);
+        else if (stage == 3)  // the reverse scans on the claims of the LAST stvo_track_batched_dev call
+            stvo::launch_reverse_check_alone(ctx->stream, points, w, pad, b->m12_pts);
+        else if (stage == 4)  // developer probe: both directions as full top-2 scans (the pre-lazy formulation)
+            stvo::launch_both_dirs_scan_alone(ctx->stream, points, w, pad);
+        else
             stvo::launch_pose(ctx->stream, a);
     }
     HIP_TRY(ctx, hipEventRecord(e1, ctx->stream));
