@@ -40,6 +40,45 @@
 #include "point_cells.h"
 
 namespace stvo {
+// What the kernels take by value: the three parts of a GridMatch (kernels.h, where every field is described) side by side in ONE flat
+// struct, in the field order the kernels were tuned with.  The compiler merges the scalar loads of neighbouring kernel arguments, so
+// the order decides the instruction streams: handed the nested GridMatch itself, every kernel here moved by a few instructions
+// (profiles/grid_surface_disassembly.txt).  Only kernel_args() below fills it; it keeps the name traces know the kernels' argument by.
+struct GridBatch {
+    int B, stride1, stride2, xy_width, items_stride, words64, n1p;
+    const int32_t* cell_xy1;
+    const uint8_t* d1;
+    const int32_t *n1, *cell_start, *cell_items;
+    const uint8_t* d2;
+    const int32_t* n2;
+    const double* dir2;
+    stvo_grid_window w;
+    double ratio, line_sim_th;
+    int mutual;
+    unsigned long long* cover;
+    const int32_t *rank, *perm;
+    unsigned long long* top2;
+    int32_t *owner2, *m12;
+    int fused_cells;
+    const int32_t *range1, *cell2;
+    const uint32_t* lstart;
+    const int32_t* lperm;
+    uint32_t* elig;
+    int32_t *elig_cnt, *ovf, *misfit;
+    int lean_cells, has_tail;
+    PointTail tail;
+    PointCells cells;
+};
+static GridBatch kernel_args(const GridMatch& m) {
+    const GridProblem& p = m.p;
+    const GridScratch& s = m.s;
+    const PointRoute& r = m.r;
+    return GridBatch{p.B,     p.stride1, p.stride2, p.xy_width, p.items_stride, p.words64, p.n1p,   p.cell_xy1,    p.d1,     p.n1,   p.cell_start,
+                     p.cell_items, p.d2, p.n2,      p.dir2,     p.w,            p.ratio,   p.line_sim_th, p.mutual, s.cover,  p.rank, p.perm,
+                     s.top2,  s.owner2,  p.m12,     r.fused_cells, r.range1,    r.cell2,   r.lstart, r.lperm,      s.elig,   s.elig_cnt, s.ovf,
+                     s.misfit, r.lean_cells, r.has_tail, r.tail, r.cells};
+}
+
 namespace {
 
 #ifndef GRID_ROWS_PER_TRIP
@@ -178,12 +217,13 @@ __device__ __forceinline__ unsigned long long range_mask(const GridArgs& a, int 
     return any ? run : 0ull;
 }
 
-// TEST HOOK (stvo_seq_debug_grid): materialises the masks the range formulation feeds the scan into the bit-matrix layout
-__global__ __launch_bounds__(256) void grid_range_debug_kernel(GridBatch g) {
-    const GridArgs a = frame_view(g, blockIdx.y);
+// TEST HOOK (stvo_seq_debug_grid): materialises the masks the range formulation feeds the scan of frame b into the bit-matrix layout;
+// g.cover is the matrix of that ONE frame
+__global__ __launch_bounds__(256) void grid_range_debug_kernel(GridBatch g, const int b) {
+    const GridArgs a = frame_view(g, b);
     const int i1 = blockIdx.x * 256 + threadIdx.x;
     if (i1 >= a.n1p) return;
-    for (int w = 0; w < a.words64; ++w) a.cover[(size_t)w * a.n1p + i1] = range_mask(a, i1, w * 64);
+    for (int w = 0; w < a.words64; ++w) g.cover[(size_t)w * a.n1p + i1] = range_mask(a, i1, w * 64);
 }
 
 template <bool LINES, int PASS, bool RANGE>
@@ -929,70 +969,67 @@ __global__ __launch_bounds__(FUSED_T) void grid_points_fused_kernel(GridBatch g,
 
 }  // namespace
 
-bool grid_points_fused_ok(const GridBatch& g) {
-    const bool range = g.range_points && g.range1 != nullptr;
+// the range form (kernels.h: PointRoute): points whose candidates are one run of scan positions each — no bit-matrix is built or read
+static bool grid_range_form(const GridMatch& m) { return !m.p.lines() && m.r.range1 != nullptr; }
+
+bool grid_points_fused_ok(const GridMatch& m) {
+    const GridProblem& p = m.p;
+    const PointRoute& r = m.r;
     // STVO_GRID_FUSED=0: the scan formulation for every batch
-    const bool fused = range && g.misfit && g.cell2 && g.lperm && g.lstart && g.stride1 <= FUSED_ROWS && g.stride2 <= FUSED_ROWS && g.w.w_lo >= 0 &&
-                       g.w.w_lo <= FUSED_LW - STVO_GRID_COLS && g.w.w_hi == 0 && g.w.h_lo == 0 && g.w.h_hi == 0 && dbg().grid_fused != 0;
+    const bool fused = grid_range_form(m) && m.s.misfit && r.cell2 && r.lperm && r.lstart && p.stride1 <= FUSED_ROWS && p.stride2 <= FUSED_ROWS &&
+                       p.w.w_lo >= 0 && p.w.w_lo <= FUSED_LW - STVO_GRID_COLS && p.w.w_hi == 0 && p.w.h_lo == 0 && p.w.h_hi == 0 && dbg().grid_fused != 0;
     return fused && lds_opt_in(reinterpret_cast<const void*>(grid_points_fused_kernel<false>), (int)FUSED_LDS) &&
            lds_opt_in(reinterpret_cast<const void*>(grid_points_fused_kernel<true>), (int)FUSED_LDS);
 }
 
-// cover (zeroed here) -> scan -> finalize for a batch of frame pairs
-void launch_grid_batch(hipStream_t s, const GridBatch& g, bool lines, hipEvent_t* scan_events) {
-    if (g.B <= 0 || g.stride1 <= 0 || g.stride2 <= 0) return;
-    const dim3 g1((g.stride1 + 255) / 256, g.B), g2((g.stride2 + 255) / 256, g.B), gc((g.n1p + 255) / 256, g.B), blk(256);
-    // LDS staging column per thread: words64 x 256 x 8 B per workgroup (64 KB at 2048 right features)
-    const size_t lds = (size_t)g.words64 * 256 * sizeof(unsigned long long);
-    const bool use_lds = lds <= ((size_t)64 << 10);
-    if (lines) {
-        if (use_lds)
-            hipLaunchKernelGGL((grid_cover_kernel<true, true>), gc, blk, lds, s, g);
+// [cover (zeroed here) ->] scan pass 1 -> elig -> scan pass 2, the events around the scans
+template <bool LINES, bool RANGE>
+static void launch_grid_scans(hipStream_t s, const GridBatch& g, hipEvent_t* scan_events) {
+    const dim3 g2((g.stride2 + 255) / 256, g.B), gc((g.n1p + 255) / 256, g.B), blk(256);
+    if (!RANGE) {
+        // LDS staging column per thread: words64 x 256 x 8 B per workgroup (64 KB at 2048 right features)
+        const size_t lds = (size_t)g.words64 * 256 * sizeof(unsigned long long);
+        if (lds <= ((size_t)64 << 10))
+            hipLaunchKernelGGL((grid_cover_kernel<LINES, true>), gc, blk, lds, s, g);
         else
-            hipLaunchKernelGGL((grid_cover_kernel<true, false>), gc, blk, 0, s, g);
-        if (scan_events && scan_events[0]) (void)hipEventRecord(scan_events[0], s);
-        hipLaunchKernelGGL((grid_scan_kernel<true, 1, false>), g2, blk, 0, s, g);
-        if (g.elig) hipLaunchKernelGGL(grid_elig_kernel, g2, blk, 0, s, g);
-        hipLaunchKernelGGL((grid_scan_kernel<true, 2, false>), g2, blk, 0, s, g);
-        if (scan_events) (void)hipEventRecord(scan_events[1], s);
-    } else {
-        const bool range = g.range_points && g.range1 != nullptr;
-        if (grid_points_fused_ok(g)) {
-            // STVO_GRID_FUSED_CAP: capacity for the keys of right features with more than 16 candidates (tests force the misfit path with -1)
-            int cap = dbg().grid_fused_cap != DBG_UNSET ? dbg().grid_fused_cap : FUSED_KEY_CAP;
-            if (cap > FUSED_KEY_CAP) cap = FUSED_KEY_CAP;  // negative: every frame misfits
-            const int fused_wgs = device_cu_count();  // one persistent workgroup per CU (its LDS and registers fill one)
-            if (scan_events && scan_events[0]) (void)hipEventRecord(scan_events[0], s);
-            if (g.fused_cells && g.B <= fused_wgs)
-                hipLaunchKernelGGL(grid_points_fused_kernel<true>, dim3(g.B), dim3(FUSED_T), FUSED_LDS, s, g, cap);
-            else
-                hipLaunchKernelGGL(grid_points_fused_kernel<false>, dim3(g.B < fused_wgs ? g.B : fused_wgs), dim3(FUSED_T), FUSED_LDS, s, g, cap);
-            if (scan_events) (void)hipEventRecord(scan_events[1], s);
-            return;
-        }
-        if (range) {
-            if (scan_events && scan_events[0]) (void)hipEventRecord(scan_events[0], s);
-            hipLaunchKernelGGL((grid_scan_kernel<false, 1, true>), g2, blk, 0, s, g);
-            if (g.elig) hipLaunchKernelGGL(grid_elig_kernel, g2, blk, 0, s, g);
-            hipLaunchKernelGGL((grid_scan_kernel<false, 2, true>), g2, blk, 0, s, g);
-        } else {
-            if (use_lds)
-                hipLaunchKernelGGL((grid_cover_kernel<false, true>), gc, blk, lds, s, g);
-            else
-                hipLaunchKernelGGL((grid_cover_kernel<false, false>), gc, blk, 0, s, g);
-            if (scan_events && scan_events[0]) (void)hipEventRecord(scan_events[0], s);
-            hipLaunchKernelGGL((grid_scan_kernel<false, 1, false>), g2, blk, 0, s, g);
-            if (g.elig) hipLaunchKernelGGL(grid_elig_kernel, g2, blk, 0, s, g);
-            hipLaunchKernelGGL((grid_scan_kernel<false, 2, false>), g2, blk, 0, s, g);
-        }
-        if (scan_events) (void)hipEventRecord(scan_events[1], s);
+            hipLaunchKernelGGL((grid_cover_kernel<LINES, false>), gc, blk, 0, s, g);
     }
-    hipLaunchKernelGGL(grid_finalize_kernel, g1, blk, 0, s, g);
+    if (scan_events && scan_events[0]) (void)hipEventRecord(scan_events[0], s);
+    hipLaunchKernelGGL((grid_scan_kernel<LINES, 1, RANGE>), g2, blk, 0, s, g);
+    if (g.elig) hipLaunchKernelGGL(grid_elig_kernel, g2, blk, 0, s, g);
+    hipLaunchKernelGGL((grid_scan_kernel<LINES, 2, RANGE>), g2, blk, 0, s, g);
+    if (scan_events) (void)hipEventRecord(scan_events[1], s);
 }
 
-// test hook: the candidate masks of the range formulation, written into g.cover in the bit-matrix layout
-void launch_grid_range_debug(hipStream_t s, const GridBatch& g) {
-    hipLaunchKernelGGL(grid_range_debug_kernel, dim3((g.n1p + 255) / 256, g.B), dim3(256), 0, s, g);
+// the one-workgroup-per-frame point matcher, or scans -> finalize, for a batch of frame pairs
+void launch_grid_batch(hipStream_t s, const GridMatch& m, hipEvent_t* scan_events) {
+    const GridBatch g = kernel_args(m);
+    if (g.B <= 0 || g.stride1 <= 0 || g.stride2 <= 0) return;
+    if (grid_points_fused_ok(m)) {
+        // STVO_GRID_FUSED_CAP: capacity for the keys of right features with more than 16 candidates (tests force the misfit path with -1)
+        int cap = dbg().grid_fused_cap != DBG_UNSET ? dbg().grid_fused_cap : FUSED_KEY_CAP;
+        if (cap > FUSED_KEY_CAP) cap = FUSED_KEY_CAP;  // negative: every frame misfits
+        const int fused_wgs = device_cu_count();  // one persistent workgroup per CU (its LDS and registers fill one)
+        if (scan_events && scan_events[0]) (void)hipEventRecord(scan_events[0], s);
+        if (g.fused_cells && g.B <= fused_wgs)
+            hipLaunchKernelGGL(grid_points_fused_kernel<true>, dim3(g.B), dim3(FUSED_T), FUSED_LDS, s, g, cap);
+        else
+            hipLaunchKernelGGL(grid_points_fused_kernel<false>, dim3(g.B < fused_wgs ? g.B : fused_wgs), dim3(FUSED_T), FUSED_LDS, s, g, cap);
+        if (scan_events) (void)hipEventRecord(scan_events[1], s);
+        return;
+    }
+    if (m.p.lines())
+        launch_grid_scans<true, false>(s, g, scan_events);
+    else if (grid_range_form(m))
+        launch_grid_scans<false, true>(s, g, scan_events);
+    else
+        launch_grid_scans<false, false>(s, g, scan_events);
+    hipLaunchKernelGGL(grid_finalize_kernel, dim3((g.stride1 + 255) / 256, g.B), dim3(256), 0, s, g);
+}
+
+// test hook: the candidate masks the range form gives frame b, written into m.s.cover (ONE frame's matrix) in the bit-matrix layout
+void launch_grid_range_debug(hipStream_t s, const GridMatch& m, int b) {
+    hipLaunchKernelGGL(grid_range_debug_kernel, dim3((m.p.n1p + 255) / 256), dim3(256), 0, s, kernel_args(m), b);
 }
 
 namespace {
@@ -1018,9 +1055,11 @@ int run_grid(stvo_ctx* ctx, const int32_t* cell_xy1, const uint8_t* d1, int n1, 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->arena_off = 0;
     ctx->upload_hi = 0;
-    GridBatch a;
-    std::memset(&a, 0, sizeof(a));
-    int32_t *dxy, *dstart, *ditems, *downer, *dm12, *dn1, *dn2;
+    GridMatch g;
+    std::memset(&g, 0, sizeof(g));
+    GridProblem& a = g.p;
+    GridScratch& sc = g.s;
+    int32_t *dxy, *dstart, *ditems, *dm12, *dn1, *dn2;
     uint8_t *dd1, *dd2;
     double* ddir = nullptr;
     TRY(upload(ctx, &dxy, cell_xy1, (size_t)n1 * (LINES ? 4 : 2)));
@@ -1031,13 +1070,6 @@ int run_grid(stvo_ctx* ctx, const int32_t* cell_xy1, const uint8_t* d1, int n1, 
     if (LINES) TRY(upload(ctx, &ddir, dir2, (size_t)n2 * 2));
     TRY(upload(ctx, &dn1, &n1, 1));
     TRY(upload(ctx, &dn2, &n2, 1));
-    a.B = 1;
-    a.stride1 = n1;
-    a.stride2 = n2;
-    a.xy_width = LINES ? 4 : 2;
-    a.items_stride = n_items;
-    a.words64 = (n2 + 63) / 64;
-    a.n1p = (n1 + 63) & ~63;
     // scan order of the right features = order of first appearance in the CSR grid (cell-major, i.e.
     // spatial); features that are in no cell come last (they are nobody's candidate anyway)
     std::vector<int32_t> rank((size_t)n2, -1), perm((size_t)n2);
@@ -1057,35 +1089,24 @@ int run_grid(stvo_ctx* ctx, const int32_t* cell_xy1, const uint8_t* d1, int n1, 
     int32_t *drank, *dperm;
     TRY(upload(ctx, &drank, rank.data(), (size_t)n2));
     TRY(upload(ctx, &dperm, perm.data(), (size_t)n2));
-    a.rank = drank;
-    a.perm = dperm;
     TRY(flush_uploads(ctx));
+    const GridScratchCounts cnt = grid_scratch_counts(1, n1, n2, true, false);
     if (mutual) {
-        a.elig = arena_alloc<uint32_t>(ctx, (size_t)GRID_ELIG * n2);
-        a.elig_cnt = arena_alloc<int32_t>(ctx, (size_t)n2);
-        a.ovf = arena_alloc<int32_t>(ctx, 1);
-        if (!a.elig || !a.elig_cnt || !a.ovf) return STVO_ERR_CAPACITY;
+        sc.elig = arena_alloc<uint32_t>(ctx, cnt.elig);
+        sc.elig_cnt = arena_alloc<int32_t>(ctx, cnt.elig_cnt);
+        sc.ovf = arena_alloc<int32_t>(ctx, cnt.ovf);
+        if (!sc.elig || !sc.elig_cnt || !sc.ovf) return STVO_ERR_CAPACITY;
     }
-    a.cover = arena_alloc<unsigned long long>(ctx, (size_t)a.n1p * a.words64);
-    a.top2 = arena_alloc<unsigned long long>(ctx, (size_t)n1);
-    downer = arena_alloc<int32_t>(ctx, (size_t)n2);
+    sc.cover = arena_alloc<unsigned long long>(ctx, cnt.cover);
+    sc.top2 = arena_alloc<unsigned long long>(ctx, cnt.top2);
+    sc.owner2 = arena_alloc<int32_t>(ctx, cnt.owner2);
     dm12 = arena_alloc<int32_t>(ctx, (size_t)n1);
-    if (!a.cover || !a.top2 || !downer || !dm12) return STVO_ERR_CAPACITY;
-    a.cell_xy1 = dxy;
-    a.d1 = dd1;
-    a.n1 = dn1;
-    a.cell_start = dstart;
-    a.cell_items = ditems;
-    a.d2 = dd2;
-    a.n2 = dn2;
-    a.dir2 = ddir;
-    a.w = *w;
-    a.ratio = ratio;
-    a.line_sim_th = line_sim_th;
-    a.mutual = mutual;
-    a.owner2 = downer;
-    a.m12 = dm12;
-    launch_grid_batch(ctx->stream, a, LINES);
+    if (!sc.cover || !sc.top2 || !sc.owner2 || !dm12) return STVO_ERR_CAPACITY;
+    const GridMatrixDims md = grid_matrix_dims(n1, n2);
+    a.B = 1; a.stride1 = n1; a.stride2 = n2; a.xy_width = LINES ? 4 : 2; a.items_stride = n_items; a.words64 = md.words64; a.n1p = md.n1p;
+    a.cell_xy1 = dxy; a.d1 = dd1; a.n1 = dn1; a.cell_start = dstart; a.cell_items = ditems; a.d2 = dd2; a.n2 = dn2; a.dir2 = ddir;
+    a.w = *w; a.ratio = ratio; a.line_sim_th = line_sim_th; a.mutual = mutual; a.rank = drank; a.perm = dperm; a.m12 = dm12;
+    launch_grid_batch(ctx->stream, g);
     TRY(check_launch(ctx));
     TRY(download_begin(ctx, dm12, (size_t)n1 * sizeof(int32_t)));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

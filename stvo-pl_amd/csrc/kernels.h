@@ -11,6 +11,7 @@
 
 #include "../../include/stvo_hip.h"
 #include "debug_switches.h"
+#include "grid_scratch.h"
 #include "match_scratch.h"
 #include "point_tail.h"
 #include "seq_layout.h"
@@ -242,11 +243,13 @@ struct PointCells {
     int32_t* prank;              // [B][K]
 };
 
-struct GridBatch {
+// The grid matcher's arguments in three parts (GridMatch); grid_kernels.hip hands its kernels ONE flat by-value copy of them.
+// The problem: what both overloads of StVO::matchGrid take, batched, plus the scan order of the right features and the result.
+struct GridProblem {
     int B, stride1, stride2;   // frame pairs; rows per frame of the left / right feature arrays
     int xy_width;              // 2 (points: cx, cy) or 4 (lines: sx, sy, ex, ey)
     int items_stride;          // CSR items per frame
-    int words64, n1p;          // ceil(stride2 / 64); stride1 rounded up to 64
+    int words64, n1p;          // grid_matrix_dims(stride1, stride2), grid_scratch.h
     const int32_t* cell_xy1;   // [B][stride1][xy_width]
     const uint8_t* d1;         // [B][stride1][32]
     const int32_t* n1;         // [B]
@@ -258,48 +261,47 @@ struct GridBatch {
     stvo_grid_window w;
     double ratio, line_sim_th;
     int mutual;
-    unsigned long long* cover; // [B][words64][n1p] scratch
     const int32_t* rank;       // [B][stride2] right feature id -> scan position
     const int32_t* perm;       // [B][stride2] scan position -> right feature id
-    unsigned long long* top2;  // [B][stride1] scratch
-    int32_t* owner2;           // [B][stride2] scratch
     int32_t* m12;              // [B][stride1] out
-    // optional scratch of the single-scan formulation (mutual != 0): the ELIGIBLE (left feature, distance) pairs every right
-    // feature met in scan pass 1 — nullptr: two full scan passes
-    // range_points != 0 (points, window of one grid row, right features numbered in CSR order — the stvo_seq pipeline): the
-    // candidates of a left feature are ONE contiguous range of scan positions, cell_start[row][x - w_lo] .. cell_start[row][x +
-    // w_hi + 1); the scan derives its masks from cell_start and no candidate bit-matrix is built (cover may be nullptr);
-    // top2 / ovf must then be initialised by the caller (kTop2Empty = 0x00000000FFFFFFFF, 0)
-    int range_points;
-    const int32_t* range1;     // [B][stride1][2] (lo, hi) of every left feature when range_points != 0
+    bool lines() const { return xy_width == 4; }
+};
+// What the device-CSR point route of the pipeline adds (all null / 0 for lines and for the C-ABI points call).
+// range1 != nullptr — the RANGE FORM (points, window of one grid row, right features numbered in CSR order): the candidates of a left
+// feature are ONE contiguous range of scan positions, cell_start[row][x - w_lo] .. cell_start[row][x + w_hi + 1); the scan derives its
+// masks from it and no candidate bit-matrix is built (GridScratch::cover may be nullptr); top2 / ovf must then be initialised by the
+// caller (kTop2Empty = 0x00000000FFFFFFFF, 0).
+struct PointRoute {
+    const int32_t* range1;     // [B][stride1][2] (lo, hi) of every left feature
     const int32_t* cell2;      // [B][stride2] or nullptr: grid cell (y * 64 + x) of the right feature at each scan position, -1 outside the grid
     // left key-points counting-sorted by cell for the one-workgroup-per-frame point matcher (both or none), on a grid GRID_LW
     // columns wide (a left key-point up to w_lo columns right of the grid still has candidates)
     const uint32_t* lstart;    // [B][GRID_LSTART_STRIDE] exclusive cell starts, [GRID_LCELLS] = number of placed left key-points
     const int32_t* lperm;      // [B][stride1] position -> left feature
-    uint32_t* elig;            // [B][GRID_ELIG][stride2]  (i1 << 16 | d), slot-major
-    int32_t* elig_cnt;         // [B][stride2]
-    int32_t* ovf;              // [B] set when some right feature of the frame met more than GRID_ELIG eligible pairs
-    int32_t* misfit;           // [B] or nullptr: written by the one-workgroup-per-frame point matcher (1: frame left to the scan formulation)
-    // != 0: the caller left range1 / top2 / ovf uninitialised because grid_points_fused_ok() holds; the one-workgroup matcher
-    // derives them from cell_start / lstart / lperm for the frames it hands to the scan formulation
+    // ---- what the step planner decides (step_plan.h), each only with grid_points_fused_ok
+    // != 0: the caller left range1 / top2 / ovf uninitialised; the one-workgroup matcher derives them from cell_start / lstart / lperm
+    // for the frames it hands to the scan formulation
     int lean_cells;
-    // has_tail != 0 (only with grid_points_fused_ok): the one-workgroup matcher also runs the tail of the stereo association on the
-    // frame it just matched (filters, back-projection, ordered compaction, point_tail.h) — no point_tail_kernel launch, no second
-    // pass over the matches
+    // != 0: the one-workgroup matcher also runs the tail of the stereo association on the frame it just matched (filters,
+    // back-projection, ordered compaction, point_tail.h) — no point_tail_kernel launch, no second pass over the matches
     int has_tail;
-    PointTail tail;
-    // fused_cells != 0 (only with grid_points_fused_ok and B <= the number of workgroups of the launch, i.e. one frame per workgroup):
-    // the one-workgroup matcher builds the grid of its frame itself as its first phase — no point_cells_kernel launch
+    // != 0 (and B <= the number of workgroups of the launch, i.e. one frame per workgroup): the one-workgroup matcher builds the grid
+    // of its frame itself as its first phase — no point_cells_kernel launch
     int fused_cells;
+    PointTail tail;
     PointCells cells;
 };
-constexpr int GRID_ELIG = 16;
+struct GridMatch {
+    GridProblem p;
+    GridScratch s;  // grid_scratch.h
+    PointRoute r;
+};
 // scan_events (optional): [0] / [1] are recorded on `s` before / after the two grid_scan passes
-void launch_grid_batch(hipStream_t s, const GridBatch& g, bool lines, hipEvent_t* scan_events = nullptr);
-// true when launch_grid_batch(.., lines = false) will run the one-workgroup-per-frame point matcher for this batch
-bool grid_points_fused_ok(const GridBatch& g);
-void launch_grid_range_debug(hipStream_t s, const GridBatch& g);  // test hook, see stvo_seq_debug_grid
+void launch_grid_batch(hipStream_t s, const GridMatch& g, hipEvent_t* scan_events = nullptr);
+// true when launch_grid_batch will run the one-workgroup-per-frame point matcher for this batch
+bool grid_points_fused_ok(const GridMatch& g);
+// test hook, see stvo_seq_debug_grid: the masks the range form gives frame b, into g.s.cover = ONE frame's matrix
+void launch_grid_range_debug(hipStream_t s, const GridMatch& g, int b);
 
 // ---- the stereo association kernels of the device-resident pipeline (stereo_assoc_kernels.hip), one workgroup per frame of d.B ----
 struct SeqDev;  // seq_state.h

@@ -56,13 +56,13 @@ int stvo_seq_debug_grid(stvo_seq* s, int b, int lines, int32_t* cell_start, int3
     const stvo::SeqDev& d = s->d;
     stvo::SeqDev full = d;
     full.raw = s->raw_view(s->last_slot);
-    if (!lines && s->last_point_grid.lean_cells) {  // the step ran the lean cells kernel: produce the full set of grid arrays for the hook
+    if (!lines && s->last_point_lean) {  // the step ran the lean cells kernel: produce the full set of grid arrays for the hook
         stvo::launch_point_cells(ctx->stream, full, false);
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (lines && s->last_line_fused) {  // the step ran the fused line kernel: the general matcher's kernels produce the grid arrays
         stvo::launch_line_cells(ctx->stream, full);
-        stvo::launch_grid_batch(ctx->stream, s->last_line_grid, true);
+        stvo::launch_grid_batch(ctx->stream, stvo::line_grid_args(s, full));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     const int R = lines ? s->M : s->K, xyw = lines ? 4 : 2;
@@ -79,14 +79,23 @@ int stvo_seq_debug_grid(stvo_seq* s, int b, int lines, int32_t* cell_start, int3
     if (n_items) HIP_TRY(ctx, hipMemcpy(cell_items, (lines ? d.litems : d.pitems) + (size_t)b * items_stride, (size_t)n_items * 4, hipMemcpyDeviceToHost));
     if (nl) HIP_TRY(ctx, hipMemcpy(cells_left, (lines ? d.lxy_l : d.pxy_l) + (size_t)b * R * xyw, (size_t)nl * xyw * 4, hipMemcpyDeviceToHost));
     // candidate sets: bit p % 64 of cover[p / 64][i1] <=> right feature perm[p] is a candidate of left feature i1
-    if (!lines && s->last_point_grid.range_points) {  // the point scan derives its masks from ranges: materialise exactly those
-        stvo::launch_grid_range_debug(ctx->stream, s->last_point_grid);
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    const int words64 = R / 64;
-    std::vector<unsigned long long> cover((size_t)words64 * R);
+    const stvo::GridMatrixDims md = stvo::grid_matrix_dims(R, R);
+    const int words64 = md.words64;
+    std::vector<unsigned long long> cover(md.words());  // (no key-point stage: no candidates)
     std::vector<int32_t> perm((size_t)R);
-    HIP_TRY(ctx, hipMemcpy(cover.data(), (lines ? s->cover_l : s->cover) + (size_t)b * words64 * R, cover.size() * 8, hipMemcpyDeviceToHost));
+    if (lines) {
+        HIP_TRY(ctx, hipMemcpy(cover.data(), s->grid_l.cover + (size_t)b * cover.size(), cover.size() * 8, hipMemcpyDeviceToHost));
+    } else if (s->op.has_points) {
+        // the point matchers derive their masks from ranges and the pipeline keeps no key-point matrix: materialise exactly those masks
+        // for frame b, in a matrix that lives for this call
+        stvo::GridMatch g = stvo::point_grid_args(s, full);
+        HIP_TRY(ctx, hipMalloc((void**)&g.s.cover, cover.size() * 8));
+        stvo::launch_grid_range_debug(ctx->stream, g, b);
+        hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipMemcpy(cover.data(), g.s.cover, cover.size() * 8, hipMemcpyDeviceToHost);
+        (void)hipFree(g.s.cover);
+        HIP_TRY(ctx, e);
+    }
     HIP_TRY(ctx, hipMemcpy(perm.data(), (lines ? d.lperm : d.pperm) + (size_t)b * R, perm.size() * 4, hipMemcpyDeviceToHost));
     int tot = 0;
     std::vector<int32_t> row;
@@ -113,7 +122,7 @@ int stvo_seq_debug_grid(stvo_seq* s, int b, int lines, int32_t* cell_start, int3
 }
 
 // TEST HOOK.  Which way the stereo point matcher of the LAST step took each frame: out[b] = {misfit, ovf}, the two words the matcher keeps
-// side by side in govf (ovf[B] then misfit[B]).  Copies only: nothing is launched, no state of `s` changes.  A word that the route of
+// side by side (GridScratch: ovf[B] then misfit[B]).  Copies only: nothing is launched, no state of `s` changes.  A word that the route of
 // the step did not write for a frame is reported as 0, not as an earlier step left it: misfit belongs to the one-workgroup kernel
 // (lean_cells), ovf to a frame the scan formulation ran with best_lr_matches on (every frame of the scan route, the misfit frames of
 // the other).  Ask BEFORE stvo_seq_debug_grid: after a step of the one-workgroup route that hook runs the full cells kernel, which
@@ -125,9 +134,9 @@ int stvo_seq_debug_point_route(stvo_seq* s, int32_t* out) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(s->line_stream));
     const int B = s->B;
-    std::vector<int32_t> w((size_t)2 * B, 0);
-    if (s->op.has_points) HIP_TRY(ctx, hipMemcpy(w.data(), s->govf, w.size() * 4, hipMemcpyDeviceToHost));
-    const bool fused = s->op.has_points && s->last_point_grid.lean_cells != 0, lr = s->last_point_grid.ovf != nullptr;
+    std::vector<int32_t> w(stvo::grid_route_words(B), 0);  // ovf[B] then misfit[B], ONE buffer (grid_scratch.h)
+    if (s->op.has_points) HIP_TRY(ctx, hipMemcpy(w.data(), s->grid_p.ovf, w.size() * 4, hipMemcpyDeviceToHost));
+    const bool fused = s->op.has_points && s->last_point_lean, lr = s->last_mutual;
     for (int b = 0; b < B; ++b) {
         const int misfit = fused ? w[(size_t)B + b] : 0;
         const bool scanned = s->op.has_points && (!fused || misfit != 0);

@@ -74,6 +74,49 @@ void reset_slot_records(stvo_seq* s, size_t n) {
 
 }  // namespace
 
+namespace stvo {
+
+// What the two stereo matchers share: the problem of `rows` x `rows` features per frame, and the owner's scratch — its eligible-pair
+// arrays only with best_lr_matches (GridScratch::elig == nullptr: two full scan passes).
+static GridMatch grid_args(const stvo_seq* s, int rows, int xy_width, int items_stride, const GridScratch& scratch) {
+    GridMatch g;
+    std::memset(&g, 0, sizeof(g));
+    const GridMatrixDims md = grid_matrix_dims(rows, rows);
+    GridProblem& p = g.p;
+    p.B = s->B; p.stride1 = rows; p.stride2 = rows; p.xy_width = xy_width; p.items_stride = items_stride; p.words64 = md.words64; p.n1p = md.n1p;
+    p.w = stvo_grid_window{s->mp.matching_s_ws, 0, 0, 0};  // stereoFrame.cpp:141-143, :340-342
+    p.ratio = s->ratio_grid;  // minRatio12P for the key-lines too (sic, matching.cpp:241)
+    p.mutual = s->mp.best_lr_matches;
+    g.s = scratch;
+    if (!p.mutual) g.s.elig = nullptr, g.s.elig_cnt = nullptr, g.s.ovf = nullptr;
+    return g;
+}
+
+// The arguments of the stereo point matcher, up to what the plan decides (lean_cells, has_tail, fused_cells).
+GridMatch point_grid_args(const stvo_seq* s, const SeqDev& d) {
+    GridMatch g = grid_args(s, s->K, 2, s->K, s->grid_p);
+    GridProblem& p = g.p;
+    p.cell_xy1 = d.pxy_l; p.d1 = d.raw.desc_l; p.n1 = d.raw.n_kp_l; p.cell_start = d.pstart; p.cell_items = d.pitems;
+    p.d2 = d.raw.desc_r; p.n2 = d.raw.n_kp_r;
+    p.rank = d.prank; p.perm = d.pperm; p.m12 = s->fb.m12s_p;
+    // device CSR: right key-points are numbered in cell order, one grid row per window — the range form
+    g.r.range1 = d.prange; g.r.cell2 = d.pcell; g.r.lstart = d.plstart; g.r.lperm = d.plperm;
+    return g;
+}
+
+// ... and of the general matcher for the key-lines
+GridMatch line_grid_args(const stvo_seq* s, const SeqDev& d) {
+    GridMatch g = grid_args(s, s->M, 4, s->M * LENT, s->grid_l);
+    GridProblem& p = g.p;
+    p.cell_xy1 = d.lxy_l; p.d1 = d.raw.ldesc_l; p.n1 = d.raw.n_kl_l; p.cell_start = d.lstart; p.cell_items = d.litems;
+    p.d2 = d.raw.ldesc_r; p.n2 = d.raw.n_kl_r; p.dir2 = d.ldir;
+    p.line_sim_th = s->mp.line_sim_th;
+    p.rank = d.lrank; p.perm = d.lperm; p.m12 = s->fb.m12s_l;
+    return g;
+}
+
+}  // namespace stvo
+
 extern "C" {
 
 int stvo_seq_create_multi(stvo_ctx* ctx, int B, int max_keypoints, int max_keylines, const int32_t* img_cols,
@@ -339,34 +382,14 @@ struct StepEnq {
     void mark(int k, hipStream_t q) const {
         if (tev && !(p.light && k < 2)) (void)hipEventRecord(tev[k], q);
     }
-    int point_stage(stvo::GridBatch& g) const;
+    int point_stage(stvo::GridMatch& g) const;
     int line_stage() const;
     int f2f_and_join() const;
     int pose(StepPub& pub) const;
 };
 
-// The arguments of the stereo point matcher, up to what the plan decides (lean_cells, has_tail, fused_cells).
-stvo::GridBatch point_grid_args(const stvo_seq* s, const stvo::SeqDev& d) {
-    const int K = s->K;
-    stvo::GridBatch g;
-    std::memset(&g, 0, sizeof(g));
-    g.B = s->B; g.stride1 = K; g.stride2 = K; g.xy_width = 2; g.items_stride = K; g.words64 = K / 64; g.n1p = K;
-    g.cell_xy1 = d.pxy_l; g.d1 = d.raw.desc_l; g.n1 = d.raw.n_kp_l; g.cell_start = d.pstart; g.cell_items = d.pitems;
-    g.d2 = d.raw.desc_r; g.n2 = d.raw.n_kp_r; g.dir2 = nullptr;
-    g.w = stvo_grid_window{s->mp.matching_s_ws, 0, 0, 0};  // stereoFrame.cpp:141-143
-    g.ratio = s->ratio_grid; g.line_sim_th = 0.0; g.mutual = s->mp.best_lr_matches;
-    g.cover = s->cover; g.rank = d.prank; g.perm = d.pperm; g.top2 = s->top2; g.owner2 = s->owner2; g.m12 = s->fb.m12s_p;
-    if (g.mutual) { g.elig = s->elig; g.elig_cnt = s->elig_cnt; g.ovf = s->govf; }
-    g.misfit = s->govf + s->B;
-    g.range_points = 1;  // device CSR: right key-points are numbered in cell order, one grid row per window
-    g.range1 = d.prange;
-    g.cell2 = d.pcell;
-    g.lstart = d.plstart; g.lperm = d.plperm;
-    return g;
-}
-
 // Everything plan_step reads.  The launch helpers are asked what they were asked before, each only where it was asked before.
-void gather_step_facts(const stvo_seq* s, int slot, const stvo::StepFlags& fl, bool timing_events, const stvo::GridBatch& g, stvo::StepFacts& f) {
+void gather_step_facts(const stvo_seq* s, int slot, const stvo::StepFlags& fl, bool timing_events, const stvo::GridMatch& g, stvo::StepFacts& f) {
     f.B = s->B; f.K = s->K; f.M = s->M; f.cus = stvo::device_cu_count();
     f.has_points = s->op.has_points; f.has_lines = s->op.has_lines; f.best_lr_matches = s->mp.best_lr_matches;
     f.lines_now = fl.lines_now; f.lines_prev = fl.lines_prev; f.track = fl.track;
@@ -394,20 +417,21 @@ void gather_step_facts(const stvo_seq* s, int slot, const stvo::StepFlags& fl, b
 }
 
 // ---- stereo association of the key-points into set[cur]
-int StepEnq::point_stage(stvo::GridBatch& g) const {
+int StepEnq::point_stage(stvo::GridMatch& g) const {
     const int B = s->B;
     if (!p.point_stage) {
         HIP_TRY(ctx, hipMemsetAsync(cs.n, 0, (size_t)B * 4, st));
         return STVO_OK;
     }
     mark(0, st);
-    g.lean_cells = p.lean_cells;
-    g.has_tail = p.has_tail;
-    if (p.has_tail) g.tail = stvo::point_tail_args(d);
-    g.fused_cells = p.fused_cells;
+    stvo::PointRoute& r = g.r;
+    r.lean_cells = p.lean_cells;
+    r.has_tail = p.has_tail;
+    if (p.has_tail) r.tail = stvo::point_tail_args(d);
+    r.fused_cells = p.fused_cells;
     if (p.lines_ahead) HIP_TRY(ctx, hipStreamWaitEvent(sl, s->ev_fork, 0));  // the PREVIOUS step's fork event
     if (p.fused_cells)
-        g.cells = stvo::point_cells_args(d);
+        r.cells = stvo::point_cells_args(d);
     else if (p.lean_cells)
         stvo::launch_point_cells(p.cells_ahead ? sl : st, d, true);
     else
@@ -426,8 +450,9 @@ int StepEnq::point_stage(stvo::GridBatch& g) const {
         if (!p.lines_ahead) HIP_TRY(ctx, hipStreamWaitEvent(sl, s->ev_fork, 0));
         if (p.gate) stvo::launch_stream_gate(sl, s->d_pose_flag, s->pose_flag_value);
     }
-    s->last_point_grid = g;
-    stvo::launch_grid_batch(st, g, false, tev ? (p.light ? gev_light : tev + 2) : nullptr);
+    s->last_point_lean = p.lean_cells;
+    s->last_mutual = g.p.mutual != 0;
+    stvo::launch_grid_batch(st, g, tev ? (p.light ? gev_light : tev + 2) : nullptr);
     if (!p.has_tail) stvo::launch_point_tail(st, d);
     mark(1, st);
     return STVO_OK;
@@ -435,26 +460,15 @@ int StepEnq::point_stage(stvo::GridBatch& g) const {
 
 // ---- stereo association of the key-lines into set[cur]
 int StepEnq::line_stage() const {
-    const int B = s->B, M = s->M;
+    const int B = s->B;
     if (p.line_stage) {
-        stvo::GridBatch g;
-        std::memset(&g, 0, sizeof(g));
-        g.B = B; g.stride1 = M; g.stride2 = M; g.xy_width = 4; g.items_stride = M * stvo::LENT; g.words64 = M / 64; g.n1p = M;
-        g.cell_xy1 = d.lxy_l; g.d1 = d.raw.ldesc_l; g.n1 = d.raw.n_kl_l; g.cell_start = d.lstart; g.cell_items = d.litems;
-        g.d2 = d.raw.ldesc_r; g.n2 = d.raw.n_kl_r; g.dir2 = d.ldir;
-        g.w = stvo_grid_window{s->mp.matching_s_ws, 0, 0, 0};  // :340-342
-        g.ratio = s->ratio_grid /* sic, minRatio12P: matching.cpp:241 */; g.line_sim_th = s->mp.line_sim_th;
-        g.mutual = s->mp.best_lr_matches;
-        g.cover = s->cover_l; g.rank = d.lrank; g.perm = d.lperm; g.top2 = s->top2_l; g.owner2 = s->owner2_l; g.m12 = s->fb.m12s_l;
-        if (g.mutual) { g.elig = s->elig_l; g.elig_cnt = s->elig_cnt_l; g.ovf = s->govf_l; }
-        s->last_line_grid = g;
         s->set_lines_cap[s->cur] = p.Mk;
         s->last_line_fused = p.line_fused;
         if (p.line_fused) {
             stvo::launch_line_stereo_fused(sl, d, p.line_lds, p.Mk, (int)s->mp.best_lr_matches, s->ratio_grid);
         } else {
             stvo::launch_line_cells(sl, d);
-            stvo::launch_grid_batch(sl, g, true);
+            stvo::launch_grid_batch(sl, stvo::line_grid_args(s, d));
             stvo::launch_line_tail(sl, d);
         }
     } else if (p.clear_nl) {
@@ -555,7 +569,7 @@ int StepEnq::pose(StepPub& pub) const {
 // values it handed out.  Of the state of `s` it changes only: the counters the three flags' values are drawn from (pose_epoch, join_epoch,
 // fetch_epoch) — a value handed to a launch may reach the device even when a later launch of the step fails, so it is never handed out
 // twice (which is why the planner draws none); later steps wait only for what stvo_seq_step_dev commits —, the key-line capacity of the
-// set it builds (set_lines_cap[cur]), the stage-timing events it takes, and the test hooks (last_*_grid, last_line_fused).
+// set it builds (set_lines_cap[cur]), the stage-timing events it takes, and the test hooks' facts (last_point_lean, last_mutual, last_line_fused).
 // The stream operations are those of the step before the planner existed, in the same order.  The queries that enqueue nothing — the
 // LDS opt-ins behind grid_points_fused_ok and plan_step's lds_fits (hipGetDevice, and hipFuncSetAttribute the first time), the CU
 // count — are the same ones, made under the same conditions, but all in front of the first stream operation instead of between them.
@@ -583,8 +597,8 @@ int seq_enqueue_step(stvo_seq* s, int slot, const stvo::StepFlags& fl, stvo::Ste
     const size_t res_bytes = (size_t)s->B * sizeof(stvo_pose_result);
     d.host_n = s->zero_copy ? reinterpret_cast<int32_t*>(s->out_host + res_bytes) : nullptr;
     d.host_nl = s->zero_copy ? reinterpret_cast<int32_t*>(s->out_host + res_bytes + (size_t)s->B * 4) : nullptr;
-    stvo::GridBatch g;
-    if (s->op.has_points) g = point_grid_args(s, d);
+    stvo::GridMatch g;
+    if (s->op.has_points) g = stvo::point_grid_args(s, d);
     stvo::StepFacts facts;
     gather_step_facts(s, slot, fl, tev != nullptr, g, facts);
     // ---- plan

@@ -40,7 +40,7 @@ struct SeqDev {
     unsigned long long* top2_p;  // [B][K]
     int32_t* govf_p;             // [B]
     uint32_t* plstart;           // [B][GRID_LSTART_STRIDE] | left key-points counting-sorted by cell for the one-workgroup-per-frame
-    int32_t* plperm;             // [B][K]                  | matcher (GridBatch); nullptr when capacity or window exceed what it handles
+    int32_t* plperm;             // [B][K]                  | matcher (PointRoute); nullptr when capacity or window exceed what it handles
     int32_t* pcell;              // [B][K] grid cell (y * 64 + x) of the right key-point at each CSR position, -1: outside the grid
     int32_t* prange;             // [B][K][2] candidate range of every left key-point in CSR positions (GridStructure::get, one-row window)
 };
@@ -160,10 +160,9 @@ struct stvo_seq {
                                  // k + 1 (key-line stage ahead, below), which writes set (k + 1) mod 3, may run while the pose kernel of step k still reads sets k - 1 and k
     int cur = 0;
     int prev_set() const { return (cur + 2) % 3; }
-    unsigned long long *cover, *top2;
-    uint32_t *elig = nullptr, *elig_l = nullptr;         // eligible pairs of the grid scans (points / lines), see GridBatch
-    int32_t *elig_cnt = nullptr, *elig_cnt_l = nullptr, *govf = nullptr, *govf_l = nullptr;
-    int32_t *owner2, *counts;
+    // scratch of the grid matchers (grid_scratch.h): key-points — no bit-matrix, the pipeline's point routes never read one — and key-lines
+    stvo::GridScratch grid_p{}, grid_l{};
+    int32_t* counts;
     stvo::FetchBlock fb{};  // the stereo and f2f match indices and the inlier masks, back to back (seq_layout.h)
     // ---- key-line stage AHEAD (the default for batches, round 6; STVO_LINES_AHEAD=0 switches it off): the key-line kernels of step k + 1
     // (stereo association + f2f of ~100 rows per image: 1024 small workgroups each) do not depend on anything the point stream does in
@@ -196,8 +195,6 @@ struct stvo_seq {
         int32_t *pstart, *pperm, *pcell, *plperm;
         uint32_t* plstart;
     } cells_buf[2] = {};
-    unsigned long long *cover_l = nullptr, *top2_l = nullptr;
-    int32_t* owner2_l = nullptr;
     // the matcher's scratch for the key-lines, as the layout below cuts it (the context owns the key-points').  `need` holds the column
     // claims — MatchScratch::claim; the buffer keeps the name the pipeline's buffer list knows it by (tests/cpp/seq_layout_host.cpp)
     struct KeylineMatchBufs {
@@ -225,9 +222,10 @@ struct stvo_seq {
     bool set_lines[3] = {false, false, false};  // stereo set was built from a frame with key-lines
     bool last_lines = false;             // the last step ran the line stage
     int last_slot = 0;                   // raw slot of the last step
-    stvo::GridBatch last_point_grid{};   // arguments of the last point grid match (test hook)
-    stvo::GridBatch last_line_grid{};    // the general matcher's arguments for the key-lines of the last step (test hook)
-    bool last_line_fused = false;        // the last step ran line_stereo_fused_kernel: the hook rebuilds the grid arrays
+    // what the test hooks need of the last step's routes; they rebuild the matchers' arguments (point_grid_args / line_grid_args)
+    bool last_point_lean = false;        // its point stage ran the lean cells phase and the one-workgroup matcher (StepPlan::lean_cells)
+    bool last_mutual = false;            // its matchers ran with best_lr_matches (ovf is written)
+    bool last_line_fused = false;        // it ran line_stereo_fused_kernel: the hook rebuilds the grid arrays
     int32_t last_schedule[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // what the last enqueued step decided (stvo_seq_last_schedule)
     // inside the pinned mirror of `fb`: the array at byte offset `off` (FetchBlock::off_*), the flag word behind the block
     int32_t* fetch_mirror(size_t off) const { return reinterpret_cast<int32_t*>(fetch_host + off); }
@@ -243,7 +241,6 @@ namespace stvo {
 // this on a null base for the size (what it stores then are bare offsets, overwritten by the second run) and on the allocation.
 // Reads s.B, s.K, s.M, s.mp and s.raw_span.
 inline size_t seq_layout(stvo_seq& s, char* base) {
-    typedef unsigned long long u64;
     const int B = s.B, K = s.K, M = s.M, R = K > M ? K : M, ws = s.mp.matching_s_ws;
     const size_t nb = (size_t)B, nK = nb * K, nM = nb * M, n_cells = nb * (STVO_GRID_CELLS + 1), n_lstart = nb * GRID_LSTART_STRIDE;
     SeqDev& d = s.d;
@@ -266,16 +263,18 @@ inline size_t seq_layout(stvo_seq& s, char* base) {
     }
     // ... key-lines
     d.lxy_l = i32(nM * 4); d.lstart = i32(n_cells); d.litems = i32(nM * LENT); d.lrank = i32(nM); d.lperm = i32(nM); d.ldir = c.take<double>(nM * 2);
-    // scratch of the grid matchers (GridBatch): key-points (or either kind: R rows), key-lines
-    s.cover = c.take<u64>(nb * (size_t)(R / 64) * R); s.top2 = d.top2_p = c.take<u64>(nb * R); s.owner2 = i32(nb * R);
-    s.elig = c.take<uint32_t>(nK * GRID_ELIG); s.elig_cnt = i32(nK); s.govf = d.govf_p = i32(nb * 2);  // ovf[nb] + misfit[nb]
-    s.elig_l = c.take<uint32_t>(nM * GRID_ELIG); s.elig_cnt_l = i32(nM); s.govf_l = i32(nb);
+    // scratch of the grid matchers (grid_scratch.h).  Key-points: no bit-matrix, misfit behind ovf; top2 / owner2 keep the R rows they
+    // have always had.  Key-lines: the eligible-pair half here, the half with the bit-matrix behind the fetch block.
+    carve_grid_scratch(c, s.grid_p, B, R, R, false, true, GRID_SCRATCH_ROWS);
+    carve_grid_scratch(c, s.grid_p, B, K, K, false, true, GRID_SCRATCH_ELIG);
+    d.top2_p = s.grid_p.top2; d.govf_p = s.grid_p.ovf;
+    carve_grid_scratch(c, s.grid_l, B, M, M, true, false, GRID_SCRATCH_ELIG);
     s.fb = carve_fetch_block(c, B, K, M);
     d.m12s_p = s.fb.m12s_p; d.m12s_l = s.fb.m12s_l;
     s.results = c.take<stvo_pose_result>(nb); s.counts = i32(nb * 4);
     const bool alt_l = B >= 64;  // second copy of the key-line match indices (key-line stage ahead: batches only)
     s.m12l_alt = alt_l ? i32(nM) : nullptr;
-    s.cover_l = c.take<u64>(nb * (size_t)(M / 64) * M); s.top2_l = c.take<u64>(nM); s.owner2_l = i32(nM);
+    carve_grid_scratch(c, s.grid_l, B, M, M, true, false, GRID_SCRATCH_ROWS);
     stvo_seq::KeylineMatchBufs& w = s.lazy_l;
     w.knn_capacity = nM * 4;  // line f2f: up to 4 train segments; stvo_seq_create_multi holds it against match_scratch_fits
     w.knn12 = c.take<uint2>(w.knn_capacity); w.knn21 = c.take<uint2>(w.knn_capacity);
@@ -303,5 +302,10 @@ struct StepFlags {
     const int32_t* ctl;  // [B] device: the control words this step carries out (only a step that tracks does), or nullptr
 };
 int enqueue_track_update(stvo_seq* s, const StepPlan& plan, const StepFlags& fl);
+
+// The arguments of the two stereo grid matchers for the arrays in `d` (seq_pipeline.hip): the step's, and what the test hooks rebuild.
+// The point matcher's up to what the plan decides (PointRoute::lean_cells, has_tail, fused_cells).
+GridMatch point_grid_args(const stvo_seq* s, const SeqDev& d);
+GridMatch line_grid_args(const stvo_seq* s, const SeqDev& d);
 
 }  // namespace stvo

@@ -55,18 +55,21 @@ int slh_main(int B, int K, int M, int ws, long long* out) {
     for (const void* p : {(const void*)c1.pstart, (const void*)c1.pperm, (const void*)c1.pcell, (const void*)c1.plstart, (const void*)c1.plperm})
         out[n++] = second ? at(p) : -1;
     for (const void* p : {(const void*)d.lxy_l, (const void*)d.lstart, (const void*)d.litems, (const void*)d.lrank, (const void*)d.lperm, (const void*)d.ldir,
-                          (const void*)s.cover, (const void*)s.top2, (const void*)s.owner2, (const void*)s.elig, (const void*)s.elig_cnt, (const void*)s.govf,
-                          (const void*)s.elig_l, (const void*)s.elig_cnt_l, (const void*)s.govf_l, (const void*)s.fb.m12s_p, (const void*)s.fb.m12s_l,
+                          (const void*)s.grid_p.top2, (const void*)s.grid_p.owner2, (const void*)s.grid_p.elig, (const void*)s.grid_p.elig_cnt,
+                          (const void*)s.grid_p.ovf, (const void*)s.grid_l.elig, (const void*)s.grid_l.elig_cnt, (const void*)s.grid_l.ovf,
+                          (const void*)s.fb.m12s_p, (const void*)s.fb.m12s_l,
                           (const void*)s.fb.m12p, (const void*)s.fb.m12l, (const void*)s.fb.inlp, (const void*)s.fb.inll, (const void*)s.results,
                           (const void*)s.counts})
         out[n++] = at(p);
     out[n++] = at_opt(s.m12l_alt);
-    for (const void* p : {(const void*)s.cover_l, (const void*)s.top2_l, (const void*)s.owner2_l, (const void*)s.lazy_l.knn12, (const void*)s.lazy_l.knn21,
+    for (const void* p : {(const void*)s.grid_l.cover, (const void*)s.grid_l.top2, (const void*)s.grid_l.owner2, (const void*)s.lazy_l.knn12, (const void*)s.lazy_l.knn21,
                           (const void*)s.lazy_l.cand, (const void*)s.lazy_l.need, (const void*)s.lazy_l.qsel, (const void*)s.lazy_l.nsel})
         out[n++] = at(p);
     for (const stvo::StereoSetPtrs& q : s.set) n += put_set(q, out + n);
     // what SeqDev carries of the above is the same buffer
-    if (d.cams != s.d_cams || d.inv_wh != s.d_inv_wh || d.top2_p != s.top2 || d.govf_p != s.govf || d.m12s_p != s.fb.m12s_p || d.m12s_l != s.fb.m12s_l ||
+    // ... the key-points keep no bit-matrix, and misfit lies behind ovf in one buffer
+    if (s.grid_p.cover != nullptr || s.grid_p.misfit != s.grid_p.ovf + B || s.grid_l.misfit != nullptr) return -1;
+    if (d.cams != s.d_cams || d.inv_wh != s.d_inv_wh || d.top2_p != s.grid_p.top2 || d.govf_p != s.grid_p.ovf || d.m12s_p != s.fb.m12s_p || d.m12s_l != s.fb.m12s_l ||
         s.cells_buf[0].pstart != d.pstart || s.cells_buf[0].plperm != d.plperm || s.lazy_l.knn_capacity != (size_t)B * M * 4)
         return -1;
     for (size_t o : {s.fb.off_m12s_l, s.fb.off_m12p, s.fb.off_m12l, s.fb.off_inlp, s.fb.off_inll, s.fb.off_flag}) out[n++] = (long long)o;

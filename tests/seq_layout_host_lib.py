@@ -16,7 +16,7 @@ RAW = ("kp_l", "oct_l", "desc_l", "n_kp_l", "kp_r", "desc_r", "n_kp_r", "kl_l", 
 SET = ("rc", "desc", "n", "spl", "epl", "sP", "eP", "le", "s2l", "s2lm", "ldesc", "nl")
 MAIN = ("raw0", "raw1", "cams", "inv_wh", "qtab", "join_flag", "pose_flag", "pxy_l", "pstart", "pitems", "prank", "pperm", "prange", "pcell",
         "plstart", "plperm", "pstart2", "pperm2", "pcell2", "plstart2", "plperm2", "lxy_l", "lstart", "litems", "lrank", "lperm", "ldir",
-        "cover", "top2", "owner2", "elig", "elig_cnt", "govf", "elig_l", "elig_cnt_l", "govf_l", "m12s_p", "m12s_l", "m12p", "m12l", "inlp",
+        "top2", "owner2", "elig", "elig_cnt", "govf", "elig_l", "elig_cnt_l", "govf_l", "m12s_p", "m12s_l", "m12p", "m12l", "inlp",
         "inll", "results", "counts", "m12l_alt", "cover_l", "top2_l", "owner2_l", "knn12_l", "knn21_l", "cand_l", "need_l", "qsel_l",
         "nsel_l") + tuple("set%d.%s" % (t, k) for t in range(3) for k in SET)
 FETCH = ("off_m12s_l", "off_m12p", "off_m12l", "off_inlp", "off_inll", "off_flag", "m12_span", "inl_span")
@@ -30,7 +30,7 @@ def load():
         return _lib
     so = os.path.join(HERE, "cpp", "libseq_layout_host.so")
     csrc = os.path.join(HERE, "..", "stvo-pl_amd", "csrc")
-    deps = [SRC] + [os.path.join(csrc, h) for h in ("carver.h", "seq_layout.h", "seq_state.h", "kernels.h", "ctx_internal.h", "step_plan.h")] + \
+    deps = [SRC] + [os.path.join(csrc, h) for h in ("carver.h", "seq_layout.h", "seq_state.h", "grid_scratch.h", "kernels.h", "ctx_internal.h", "step_plan.h")] + \
         [os.path.join(HERE, "..", "include", h) for h in ("stvo_hip.h", "stvo_types.h")]
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O1"] + FLAGS + ["-fPIC", "-shared", "-o", so, SRC])
