@@ -296,6 +296,20 @@ int stvo_orb_set_fast_thresholds_dev(stvo_orb* orb, const int32_t* th_dev, int n
 /* The same from a HOST array (every entry 1 .. 254): the detector keeps a device copy of its own, uploaded on the context's stream;
  * synchronises.  th_host == NULL returns to the scalar. */
 int stvo_orb_set_fast_thresholds(stvo_orb* orb, const int32_t* th_host, int n_th);
+/* One image SIZE per image for the following calls: image i of the B images is sizes_host[i % n] = {cols, rows}; n must divide B, and
+ * with n = B / 2 the left image b and the right image B / 2 + b of a stereo detector share an entry.  The image buffer keeps the layout
+ * [B][rows][cols] of the size given at creation (the slot): image i occupies the top-left cols_i x rows_i of its slot and keeps the slot's
+ * row pitch; the bytes of the slot outside the image influence nothing.  What comes back for image i is, bit for bit, what a detector
+ * created at (cols_i, rows_i) returns for that crop — key-points, responses, angles, octaves, descriptors, n_kp, n_total — at every
+ * nlevels, under either ranking, every descriptor setting and together with per-image FAST thresholds: level sizes, resize ratios and the
+ * rule by which a level yields anything are formed per entry (a level smaller than the border yields nothing for the images of that entry
+ * while the other images' level runs).  All four detect entry points; the host-buffer ones take and return slot-shaped buffers as before.
+ * STVO_ERR_INVALID_ARG and nothing changes: n <= 0, n > B, B % n != 0, an entry larger than the slot, an entry stvo_orb_create would
+ * refuse as an image size (below 64, or 2 * edge_threshold >= a side).  sizes_host is read during the call; the table travels on the
+ * context's stream behind the detections already enqueued, through pinned staging that is not reused before its copy has completed: no
+ * synchronisation.  The device table is allocated at the first call; sizes_host == NULL: every image fills its slot again, on the very
+ * kernels of a detector that was never given a table. */
+int stvo_orb_set_image_sizes(stvo_orb* orb, const int32_t* sizes_host /* [n][2] = cols, rows */, int n);
 /* The ranking of the following calls, cv::ORB::create's scoreType = Config::orbScore() (src/stereoFrame.cpp:112-114), with OpenCV's
  * values: STVO_ORB_SCORE_FAST (1, the default) as described above; STVO_ORB_SCORE_HARRIS (0): per level retainBest(2 x the level's
  * share) on the FAST response, HarrisResponses (7 x 7 block, k 0.04) of the survivors on the level image, retainBest(the level's
@@ -412,6 +426,17 @@ int stvo_seq_control_next_step(stvo_seq* seq, const int32_t* ctl_host /* [B] */)
  * launched when nothing is staged.  stvo_seq_adapt_fast_dev behind a step that carried a control leaves the thresholds of its RESTART
  * and PARK streams alone (initialize has no updateFrame). */
 int stvo_seq_restart_fast_dev(stvo_seq* seq, int32_t* th_dev /* [B] */, int th0);
+/* The camera of the sequence a RESTART stream begins: the reference builds one PinholeStereoCamera per dataset (app/imagesStVO.cpp:66), and
+ * kitti00-02 / 03 / 04-10 differ in focal length, principal point, baseline and image size (hence in the grid scale 64 / cols, 48 / rows
+ * of src/stereoFrame.cpp:47-48).  Call it after stvo_seq_control_next_step for the same step: for every stream the STAGED control marks
+ * RESTART, the calibration, the grid scale and the image size of the stream become cams_host[b], img_cols[b], img_rows[b] before that
+ * step's first kernel reads them; entries of RUN and PARK streams are not read.  All three arrays [B], read during the call.
+ * STVO_ERR_INVALID_ARG and nothing changes: no control staged, no RESTART in it, a size <= 0 for a RESTART stream.  No synchronisation:
+ * pinned staging as for the control words, one small launch on the context's stream, device memory of its own.  A snapshot exported
+ * afterwards carries the new camera and stvo_seq_import_streams checks a blob against it.  A RESTART without this call keeps the
+ * stream's camera.  The cameras are taken when the call is made: a control withdrawn afterwards (an all-RUN
+ * stvo_seq_control_next_step) does not bring the old cameras back, and the next step is still ordered behind the update. */
+int stvo_seq_restart_cameras(stvo_seq* seq, const stvo_cam* cams_host /* [B] */, const int32_t* img_cols, const int32_t* img_rows);
 
 /* ---- feature tracks and key-frame sets per stream ------------------------------------------------------------------------- */
 

@@ -336,6 +336,13 @@ void launch_stream_ctl_post(hipStream_t s, int B, const int32_t* ctl, stvo_pose_
                             int32_t* inl_l, int M);
 // th[b] = th0 for the RESTART streams
 void launch_fast_restart(hipStream_t s, int B, const int32_t* ctl, int32_t* th, int th0);
+// the camera a RESTART stream takes with its new sequence (stvo_seq_restart_cameras): calibration, grid scale 64 / cols, 48 / rows, image size
+struct CamRestart {
+    stvo_cam cam;
+    double inv_w, inv_h;
+    int32_t cols, rows;
+};
+void launch_cam_restart(hipStream_t s, int B, const int32_t* ctl, const CamRestart* upd, stvo_cam* cams, double* inv_wh, int32_t* snap_img /* [B][2] or nullptr */);
 
 // Feature tracks and key-frame sets per stream (track_kernel.hip around track_update.h), one workgroup per stream, one launch per step.
 // (StereoSetPtrs, the arrays of one stereo set of the pipeline: seq_layout.h)

@@ -16,6 +16,8 @@
 //                        key-point (six instances: WTA_K 2 / 3 / 4 x an LDS patch for reach <= 22 or <= 44)
 // around them (more than one level): orb_resize_kernel (level l from level l - 1, OpenCV's 8-bit bilinear resize in 11-bit fixed
 // point) and orb_concat_kernel (levels in order, coordinates x scale, octave = level).
+// One image size per image (stvo_orb_set_image_sizes): the three kernels that see an image border — FAST + NMS, blur, resize — are templates on
+// MIXED; the MIXED instances read their image's row of a size table (csrc/orb_sizes.h), the others are the kernels as they were.
 // OpenCV is third-party code that is not under /root/reference: the semantics are those of oracle/stvo_orb_oracle.c (a
 // restatement of OpenCV's algorithm, parity unpinned), against which these kernels are bit-exact (tests/test_gpu_orb.py); the settings
 // other than (2, 31) are pinned to the numpy statement tests/np_orb_wta.py in the same way (tests/test_gpu_orb_wta.py).
@@ -31,6 +33,7 @@
 #include "gaussian_q8.h"
 #include "orb_pattern.h"
 #include "orb_rotate.h"
+#include "orb_sizes.h"
 
 #pragma clang fp contract(off)
 
@@ -58,7 +61,30 @@ struct OrbDev {
     uint8_t* desc;        // [B][K][32]
     int32_t* n_kp;        // [B]
     const int8_t* pattern;  // [256][4]
+    // one image size per image (stvo_orb_set_image_sizes; read by the MIXED kernel instances only): image i is the top-left
+    // cols x rows of row (i % n_sz) * sz_stride + level of the table, inside its slot of rows x cols above, whose pitch it keeps
+    const OrbLevelSize* sz;
+    int n_sz, sz_stride, level;
 };
+
+// The image a workgroup works on.  MIXED = false: the slot itself, the kernel argument.  MIXED = true: the image's row of the size table —
+// blockIdx.z is uniform, so this is one scalar load per workgroup, as the threshold below — clamped into the slot, which the host has
+// validated it to fit.  An image whose level is not active yields nothing, and a workgroup wholly outside its image has no work: both leave
+// before their first barrier.
+struct OrbGeom {
+    int cols, rows;
+    bool active;
+};
+template <bool MIXED>
+__device__ __forceinline__ OrbGeom orb_geom(const OrbDev& o, int b) {
+    if constexpr (MIXED) {
+        const OrbLevelSize* e = o.sz + (size_t)(b % o.n_sz) * o.sz_stride + o.level;
+        return OrbGeom{__builtin_amdgcn_readfirstlane(min(max(e->cols, 4), o.cols)), __builtin_amdgcn_readfirstlane(min(max(e->rows, 1), o.rows)),
+                       __builtin_amdgcn_readfirstlane(e->active) != 0};
+    } else {
+        return OrbGeom{o.cols, o.rows, true};
+    }
+}
 
 // circle offsets in OpenCV's order (dx, dy)
 __device__ __constant__ int8_t c_circle[16][2] = {{0, 3},  {1, 3},   {2, 2},   {3, 1},   {3, 0},  {3, -1}, {2, -2}, {1, -3},
@@ -160,6 +186,7 @@ __device__ __forceinline__ void append4(const bool (&flag)[4], int* counter, int
 //   4. non-maximum suppression walks that corner list (~3 % of the positions), not the tile; a corner that beats its 8
 //      neighbours and lies inside the border is appended to the image's candidate list and counted in the response histogram —
 //      no score / keep maps ever reach global memory.
+template <bool MIXED>
 __global__ __launch_bounds__(256) void orb_fast_nms_kernel(OrbDev o) {
     __shared__ uint32_t tile[IM_H][IM_PITCH];
     __shared__ uint32_t sc_w[SC_H][SC_PITCH / 4];
@@ -168,6 +195,9 @@ __global__ __launch_bounds__(256) void orb_fast_nms_kernel(OrbDev o) {
     __shared__ uint32_t s_kp[FT_W * FT_H / 4];  // key-points of this tile (a 3x3 maximum every 4 pixels at most)
     __shared__ int s_n, s_nc, s_nkp, s_base;
     const int b = blockIdx.z, x0 = blockIdx.x * FT_W, y0 = blockIdx.y * FT_H, tid = threadIdx.x, lane = tid & 63;
+    const OrbGeom geo = orb_geom<MIXED>(o, b);
+    const int cols = geo.cols, rows = geo.rows, pitch = o.cols;  // the image, and the row pitch of its slot
+    if (MIXED && (!geo.active || x0 >= cols || y0 >= rows)) return;
     const uint8_t* img = o.img + (size_t)b * o.rows * o.cols;
     const uint8_t* tile8 = reinterpret_cast<const uint8_t*>(&tile[0][0]);
     uint8_t* sc = reinterpret_cast<uint8_t*>(&sc_w[0][0]);
@@ -185,21 +215,21 @@ __global__ __launch_bounds__(256) void orb_fast_nms_kernel(OrbDev o) {
         for (int k = 0; k < ST_TRIPS; ++k) {
             const int i = min(tid + 256 * k, IM_H * IM_DW - 1);
             const int ty = i / IM_DW, td = i - ty * IM_DW;
-            const int gx = x0 - 5 + 4 * td, gy = min(max(y0 + ty - 4, 0), o.rows - 1);
-            wv[k] = *reinterpret_cast<const u32_unaligned*>(img + (size_t)gy * o.cols + min(max(gx, 0), o.cols - 4));
+            const int gx = x0 - 5 + 4 * td, gy = min(max(y0 + ty - 4, 0), rows - 1);
+            wv[k] = *reinterpret_cast<const u32_unaligned*>(img + (size_t)gy * pitch + min(max(gx, 0), cols - 4));
         }
 #pragma unroll
         for (int k = 0; k < ST_TRIPS; ++k) {
             const int i = tid + 256 * k;
             if (i < IM_H * IM_DW) {
                 const int ty = i / IM_DW, td = i - ty * IM_DW;
-                const int gx = x0 - 5 + 4 * td, gy = min(max(y0 + ty - 4, 0), o.rows - 1);
+                const int gx = x0 - 5 + 4 * td, gy = min(max(y0 + ty - 4, 0), rows - 1);
                 uint32_t w = wv[k];
-                if (gx < 0 || gx + 4 > o.cols) {  // image border: replicate (those pixels never pass the border test below, their values only have to exist)
-                    const uint8_t* row = img + (size_t)gy * o.cols;
+                if (gx < 0 || gx + 4 > cols) {  // image border: replicate (those pixels never pass the border test below, their values only have to exist)
+                    const uint8_t* row = img + (size_t)gy * pitch;
                     w = 0u;
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) w |= (uint32_t)row[min(max(gx + c, 0), o.cols - 1)] << (8 * c);
+                    for (int c = 0; c < 4; ++c) w |= (uint32_t)row[min(max(gx + c, 0), cols - 1)] << (8 * c);
                 }
                 tile[ty][td] = w;
             }
@@ -230,14 +260,14 @@ __global__ __launch_bounds__(256) void orb_fast_nms_kernel(OrbDev o) {
         Q[1] = __builtin_amdgcn_perm(ew01, ns01, 0x07060302u);
         Q[2] = __builtin_amdgcn_perm(ew23, ns23, 0x05040100u);
         Q[3] = __builtin_amdgcn_perm(ew23, ns23, 0x07060302u);
-        const bool row_ok = item && y >= 3 && y < o.rows - 3;
+        const bool row_ok = item && y >= 3 && y < rows - 3;
         const int xb = x0 + 4 * g - 1;  // image column of pixel 0
         bool cand[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const uint32_t V = __builtin_amdgcn_perm(C, C, 0x01010101u * (uint32_t)j);  // the centre in all four bytes
             const uint32_t sad = __builtin_amdgcn_sad_u8(Q[j], V, 0u);
-            cand[j] = row_ok && 4 * g + j < SC_W && xb + j >= 3 && xb + j < o.cols - 3 && sad >= sad_min;
+            cand[j] = row_ok && 4 * g + j < SC_W && xb + j >= 3 && xb + j < cols - 3 && sad >= sad_min;
         }
         int slot[4];
         append4(cand, &s_n, slot);
@@ -296,13 +326,13 @@ __global__ __launch_bounds__(256) void orb_fast_nms_kernel(OrbDev o) {
         const int x = x0 + sx - 1, y = y0 + sy - 1;
         bool kp = false;
         uint32_t s = 0u;
-        if (sy >= 1 && sy <= FT_H && sx >= 1 && sx <= FT_W && x < o.cols && y < o.rows) {  // inside the tile proper (the halo only serves as neighbours)
+        if (sy >= 1 && sy <= FT_H && sx >= 1 && sx <= FT_W && x < cols && y < rows) {  // inside the tile proper (the halo only serves as neighbours)
             const uint8_t* q = sc + sy * SC_PITCH + sx;
             s = q[0];
             const uint32_t m8 = max(max(max((uint32_t)q[-SC_PITCH - 1], (uint32_t)q[-SC_PITCH]), max((uint32_t)q[-SC_PITCH + 1], (uint32_t)q[-1])),
                                     max(max((uint32_t)q[1], (uint32_t)q[SC_PITCH - 1]), max((uint32_t)q[SC_PITCH], (uint32_t)q[SC_PITCH + 1])));
             // 3x3 strict maximum, then KeyPointsFilter::runByImageBorder
-            kp = s > m8 && x >= o.edge_th && x < o.cols - o.edge_th && y >= o.edge_th && y < o.rows - o.edge_th;
+            kp = s > m8 && x >= o.edge_th && x < cols - o.edge_th && y >= o.edge_th && y < rows - o.edge_th;
         }
         const unsigned long long bal = __ballot(kp);
         int base = 0;
@@ -633,32 +663,48 @@ struct ResizeArgs {
     double scale_x, scale_y;  // 1 / inv_scale as OpenCV forms them: inv_scale = dsize / ssize for a given dsize, = fx, fy for Size()
     const uint8_t* src;
     uint8_t* dst;
+    // MIXED only: the sizes above are the slots' (and the pitches of both buffers); image b is resized from row `level - 1` to row
+    // `level` of its entry of the size table, with that row's inverse scales
+    const OrbLevelSize* sz;
+    int n_sz, sz_stride, level;
 };
+template <bool MIXED>
 __global__ __launch_bounds__(256) void orb_resize_kernel(ResizeArgs r) {
     const int dx = blockIdx.x * 256 + threadIdx.x, dy = blockIdx.y, b = blockIdx.z;
-    if (dx >= r.dcols) return;
-    float fx = (float)(((double)dx + 0.5) * r.scale_x - 0.5);
+    int scols = r.scols, srows = r.srows, dcols = r.dcols;
+    double scale_x = r.scale_x, scale_y = r.scale_y;
+    if constexpr (MIXED) {  // (uniform over the workgroup: scalar loads)
+        const OrbLevelSize* e = r.sz + (size_t)(b % r.n_sz) * r.sz_stride + r.level;
+        scols = min(max(e[-1].cols, 1), r.scols);
+        srows = min(max(e[-1].rows, 1), r.srows);
+        dcols = min(e->cols, r.dcols);
+        scale_x = e->inv_sx;
+        scale_y = e->inv_sy;
+        if (dy >= e->rows) return;
+    }
+    if (dx >= dcols) return;
+    float fx = (float)(((double)dx + 0.5) * scale_x - 0.5);
     int sx = (int)floorf(fx);
     fx -= (float)sx;
     if (sx < 0) {
         fx = 0.f;
         sx = 0;
     }
-    if (sx >= r.scols - 1) {
+    if (sx >= scols - 1) {
         fx = 0.f;
-        sx = r.scols - 1;
+        sx = scols - 1;
     }
     const int a0 = (short)__float2int_rn((1.f - fx) * 2048.f), a1 = (short)__float2int_rn(fx * 2048.f);
-    float fy = (float)(((double)dy + 0.5) * r.scale_y - 0.5);
+    float fy = (float)(((double)dy + 0.5) * scale_y - 0.5);
     const int sy = (int)floorf(fy);
     fy -= (float)sy;
     const int b0 = (short)__float2int_rn((1.f - fy) * 2048.f), b1 = (short)__float2int_rn(fy * 2048.f);
     const uint8_t* img = r.src + (size_t)b * r.srows * r.scols;
-    const int y0 = min(max(sy, 0), r.srows - 1), y1 = min(max(sy + 1, 0), r.srows - 1);
+    const int y0 = min(max(sy, 0), srows - 1), y1 = min(max(sy + 1, 0), srows - 1);
     const uint8_t* r0 = img + (size_t)y0 * r.scols;
     const uint8_t* r1 = img + (size_t)y1 * r.scols;
     int S0, S1;
-    if (sx < r.scols - 1) {
+    if (sx < scols - 1) {
         S0 = (int)r0[sx] * a0 + (int)r0[sx + 1] * a1;
         S1 = (int)r1[sx] * a0 + (int)r1[sx + 1] * a1;
     } else {
@@ -735,9 +781,13 @@ struct BlurK {
 // is the integer one of the tile version (weights * 2^8 per pass, (s + 2^15) >> 16), so the sums may be taken in any order.
 constexpr int BL_R = 16, BL_T = 64;
 
+template <bool MIXED>
 __global__ __launch_bounds__(BL_T) void orb_blur_kernel(OrbDev o, BlurK kk) {
     const int b = blockIdx.z, x = (blockIdx.x * BL_T + threadIdx.x) * 4, y0 = blockIdx.y * BL_R;
-    if (x >= o.cols) return;
+    const OrbGeom geo = orb_geom<MIXED>(o, b);
+    const int cols = geo.cols, rows = geo.rows, pitch = o.cols;  // BORDER_REFLECT_101 at the image's own border; the row pitch of its slot
+    if (MIXED && (!geo.active || y0 >= rows)) return;
+    if (x >= cols) return;
     const uint8_t* img = o.img + (size_t)b * o.rows * o.cols;
     uint8_t* out = o.blur + (size_t)b * o.rows * o.cols;
     const uint32_t k03 = (uint32_t)kk.k[0] | ((uint32_t)kk.k[1] << 8) | ((uint32_t)kk.k[2] << 16) | ((uint32_t)kk.k[3] << 24);
@@ -754,10 +804,10 @@ __global__ __launch_bounds__(BL_T) void orb_blur_kernel(OrbDev o, BlurK kk) {
         int q[4], lo = 0x7FFFFFFF;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            q[i] = reflect101(x - 4 + 4 * wi + i, o.cols);
+            q[i] = reflect101(x - 4 + 4 * wi + i, cols);
             lo = min(lo, q[i]);
         }
-        lo = max(min(lo, o.cols - 4), 0);
+        lo = max(min(lo, cols - 4), 0);
         woff[wi] = lo;
         wsel[wi] = (uint32_t)(q[0] - lo) | ((uint32_t)(q[1] - lo) << 8) | ((uint32_t)(q[2] - lo) << 16) | ((uint32_t)(q[3] - lo) << 24);
     }
@@ -769,9 +819,9 @@ __global__ __launch_bounds__(BL_T) void orb_blur_kernel(OrbDev o, BlurK kk) {
 #pragma unroll
     for (int r = 0; r < BL_R + 6; ++r) {
         const int yo = y0 + r - 6;                  // output row completed by this input row
-        if (r >= 6 && yo >= o.rows) break;          // uniform over the workgroup
-        const int gy = reflect101(y0 + r - 3, o.rows);
-        const uint8_t* row = img + (size_t)gy * o.cols;
+        if (r >= 6 && yo >= rows) break;            // uniform over the workgroup
+        const int gy = reflect101(y0 + r - 3, rows);
+        const uint8_t* row = img + (size_t)gy * pitch;
         const uint32_t w0 = __builtin_amdgcn_perm(0u, *reinterpret_cast<const u32_unaligned*>(row + woff[0]), wsel[0]);
         const uint32_t w1 = __builtin_amdgcn_perm(0u, *reinterpret_cast<const u32_unaligned*>(row + woff[1]), wsel[1]);
         const uint32_t w2 = __builtin_amdgcn_perm(0u, *reinterpret_cast<const u32_unaligned*>(row + woff[2]), wsel[2]);
@@ -800,11 +850,11 @@ __global__ __launch_bounds__(BL_T) void orb_blur_kernel(OrbDev o, BlurK kk) {
                 for (int j = 0; j < 7; ++j) sv += __umul24((uint32_t)kk.k[j], h[j][i]);  // (weights <= 2^8, row sums <= 2^16: the 24-bit multiply-add is exact and full rate)
                 px |= min(sv >> 16, 255u) << (8 * i);
             }
-            uint8_t* dst = out + (size_t)yo * o.cols + x;
-            if (x + 4 <= o.cols) {
+            uint8_t* dst = out + (size_t)yo * pitch + x;
+            if (x + 4 <= cols) {
                 *reinterpret_cast<u32_unaligned*>(dst) = px;
             } else {
-                for (int i = 0; x + i < o.cols; ++i) dst[i] = (uint8_t)(px >> (8 * i));
+                for (int i = 0; x + i < cols; ++i) dst[i] = (uint8_t)(px >> (8 * i));
             }
         }
     }
@@ -1100,7 +1150,7 @@ void launch_blur7_u8(hipStream_t s, int B, int cols, int rows, const uint8_t* sr
     BlurK kk{};
     for (int i = 0; i < 7; ++i) kk.k[i] = k7[i];
     const dim3 tiles((cols + 4 * BL_T - 1) / (4 * BL_T), (rows + BL_R - 1) / BL_R, B);
-    hipLaunchKernelGGL(orb_blur_kernel, tiles, dim3(BL_T), 0, s, o, kk);
+    hipLaunchKernelGGL(orb_blur_kernel<false>, tiles, dim3(BL_T), 0, s, o, kk);
 }
 void launch_resize_linear_u8(hipStream_t s, int B, int scols, int srows, int dcols, int drows, const uint8_t* src, uint8_t* dst, double fx, double fy) {
     ResizeArgs r{};
@@ -1109,7 +1159,7 @@ void launch_resize_linear_u8(hipStream_t s, int B, int scols, int srows, int dco
     r.scale_x = 1.0 / (fx > 0 ? fx : (double)dcols / scols);
     r.scale_y = 1.0 / (fy > 0 ? fy : (double)drows / srows);
     r.src = src; r.dst = dst;
-    hipLaunchKernelGGL(orb_resize_kernel, dim3((dcols + 255) / 256, drows, B), dim3(256), 0, s, r);
+    hipLaunchKernelGGL(orb_resize_kernel<false>, dim3((dcols + 255) / 256, drows, B), dim3(256), 0, s, r);
 }
 }  // namespace stvo
 
@@ -1140,6 +1190,16 @@ struct stvo_orb {
     int32_t* d_th_own = nullptr;  // [B] device copy behind stvo_orb_set_fast_thresholds (carved from dev)
     stvo::BlurK blur_k{};
     stvo::Umax umax{};
+    // one image size per image (stvo_orb_set_image_sizes): nothing of it exists until the first call.  The device table is an allocation
+    // of its own ([B][nlevels] rows: the largest n); two pinned staging blocks are used alternately, each with the event of the copy
+    // that last read it
+    int nf[STVO_ORB_MAX_LEVELS] = {};       // the feature budget of every level
+    stvo::OrbLevelSize* d_sizes = nullptr;
+    int n_sizes = 0;                        // entries of the table in force; 0: every image fills its slot
+    stvo::OrbLevelSize* sizes_stage[2] = {nullptr, nullptr};
+    hipEvent_t ev_sizes[2] = {nullptr, nullptr};
+    bool sizes_busy[2] = {false, false};
+    int sizes_next = 0;
 };
 
 namespace {
@@ -1147,8 +1207,6 @@ namespace {
 int pattern_verdict(int v) {
     return v == stvo::ORB_PATTERN_OK ? STVO_OK : (v == stvo::ORB_PATTERN_UNSUPPORTED ? STVO_ERR_UNSUPPORTED : STVO_ERR_INVALID_ARG);
 }
-
-int cv_round_f(float v) { return (int)std::lrintf(v); }  // cvRound: half to even
 
 }  // namespace
 
@@ -1173,31 +1231,22 @@ int stvo_orb_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keypoints,
     o->ctx = ctx;
     o->prm = *prm;
     o->B = B; o->K = max_keypoints; o->nlevels = nlevels;
-    // level geometry and feature budgets exactly as ORB_Impl forms them (oracle/stvo_orb_oracle.c: orc_orb_levels)
-    int nf[STVO_ORB_MAX_LEVELS];
-    {
-        const float factor = (float)(1.0 / (nlevels > 1 ? prm->scale_factor : 1.2));
-        float nd = (float)prm->nfeatures * (1.f - factor) / (1.f - (float)std::pow((double)factor, (double)nlevels));
-        int sum = 0;
-        for (int l = 0; l < nlevels - 1; ++l) {
-            nf[l] = cv_round_f(nd);
-            sum += nf[l];
-            nd *= factor;
-        }
-        nf[nlevels - 1] = prm->nfeatures - sum > 0 ? prm->nfeatures - sum : 0;
-        if (nlevels == 1) nf[0] = prm->nfeatures;
-    }
+    // level geometry and feature budgets exactly as ORB_Impl forms them (orb_sizes.h)
+    int* nf = o->nf;
+    stvo::orb_level_budgets(prm->nfeatures, nlevels, prm->scale_factor, nf);
+    stvo::OrbLevelSize slot[STVO_ORB_MAX_LEVELS];
+    stvo::orb_level_sizes(cols, rows, nlevels, prm->scale_factor, prm->edge_threshold, nf, slot);
     int lcols[STVO_ORB_MAX_LEVELS], lrows[STVO_ORB_MAX_LEVELS];
     for (int l = 0; l < nlevels; ++l) {
         stvo_orb::Level& L = o->lev[l];
-        L.scale = l ? (float)std::pow(prm->scale_factor, (double)l) : 1.f;
+        L.scale = stvo::orb_level_scale(prm->scale_factor, l);
         stvo::OrbDev& d = L.d;
         d.B = B; d.K = max_keypoints;
-        d.cols = lcols[l] = l ? cv_round_f((float)cols / L.scale) : cols;
-        d.rows = lrows[l] = l ? cv_round_f((float)rows / L.scale) : rows;
+        d.cols = lcols[l] = slot[l].cols;
+        d.rows = lrows[l] = slot[l].rows;
         d.nfeatures = nf[l]; d.fast_th = prm->fast_threshold; d.edge_th = prm->edge_threshold;
         d.cand_cap = stvo::orb_cand_cap(d.cols, d.rows);
-        L.active = nf[l] > 0 && 2 * prm->edge_threshold < d.cols && 2 * prm->edge_threshold < d.rows && d.cols >= 16 && d.rows >= 16;
+        L.active = slot[l].active != 0;
     }
     stvo::Carver size;
     stvo::carve_orb_arena(size, B, max_keypoints, nlevels, lcols, lrows);
@@ -1237,6 +1286,10 @@ int stvo_orb_destroy(stvo_orb* o) {
     }
     if (o->dev) (void)hipFree(o->dev);
     if (o->io.p) (void)hipFree(o->io.p);
+    if (o->d_sizes) (void)hipFree(o->d_sizes);
+    if (o->sizes_stage[0]) (void)hipHostFree(o->sizes_stage[0]);  // (one allocation for both blocks)
+    for (hipEvent_t e : o->ev_sizes)
+        if (e) (void)hipEventDestroy(e);
     delete o;
     return STVO_OK;
 }
@@ -1326,6 +1379,44 @@ int stvo_orb_set_fast_thresholds(stvo_orb* o, const int32_t* th_host, int n_th) 
     return stvo_orb_set_fast_thresholds_dev(o, o->d_th_own, n_th);
 }
 
+// One image size per image (stvo_hip.h).  Validated before anything changes.  The table is formed on the host (orb_sizes.h) in a pinned
+// block and copied on the context's stream, so it arrives behind the detections already enqueued (which read the previous contents) and in
+// front of the next one; nothing waits for it.  A pinned block is written again only after the copy that last read it (two calls ago) has
+// completed — long since, unless nothing has synchronised in between.
+int stvo_orb_set_image_sizes(stvo_orb* o, const int32_t* sizes_host, int n) {
+    if (!o) return STVO_ERR_INVALID_ARG;
+    if (!sizes_host) {  // every image fills its slot again: the uniform kernel instances, which read no table
+        o->n_sizes = 0;
+        return STVO_OK;
+    }
+    const stvo::OrbDev& d0 = o->lev[0].d;
+    if (!stvo::orb_image_sizes_ok(sizes_host, n, o->B, d0.cols, d0.rows, o->prm.edge_threshold)) return STVO_ERR_INVALID_ARG;
+    stvo_ctx* ctx = o->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t span = ((size_t)o->B * o->nlevels * sizeof(stvo::OrbLevelSize) + 255) & ~size_t(255);
+    if (!o->d_sizes) HIP_TRY(ctx, hipMalloc((void**)&o->d_sizes, span));
+    if (!o->sizes_stage[0]) {
+        HIP_TRY(ctx, hipHostMalloc((void**)&o->sizes_stage[0], 2 * span, hipHostMallocDefault));
+        o->sizes_stage[1] = reinterpret_cast<stvo::OrbLevelSize*>(reinterpret_cast<char*>(o->sizes_stage[0]) + span);
+    }
+    for (auto& e : o->ev_sizes)
+        if (!e) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    const int hb = o->sizes_next;
+    if (o->sizes_busy[hb]) {
+        HIP_TRY(ctx, hipEventSynchronize(o->ev_sizes[hb]));
+        o->sizes_busy[hb] = false;
+    }
+    stvo::OrbLevelSize* tab = o->sizes_stage[hb];
+    for (int i = 0; i < n; ++i)
+        stvo::orb_level_sizes(sizes_host[2 * i], sizes_host[2 * i + 1], o->nlevels, o->prm.scale_factor, o->prm.edge_threshold, o->nf, tab + (size_t)i * o->nlevels);
+    HIP_TRY(ctx, hipMemcpyAsync(o->d_sizes, tab, (size_t)n * o->nlevels * sizeof(stvo::OrbLevelSize), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(o->ev_sizes[hb], ctx->stream));
+    o->sizes_busy[hb] = true;
+    o->sizes_next = hb ^ 1;
+    o->n_sizes = n;
+    return STVO_OK;
+}
+
 int stvo_orb_set_score_type(stvo_orb* o, int score_type) {
     if (!o || (score_type != STVO_ORB_SCORE_HARRIS && score_type != STVO_ORB_SCORE_FAST)) return STVO_ERR_INVALID_ARG;
     o->score_type = score_type;
@@ -1346,14 +1437,22 @@ int stvo_orb_detect_levels_dev(stvo_orb* o, const uint8_t* images, float* kp_xy,
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const bool multi = o->nlevels > 1;
+    // one size per image: the MIXED instances of the three kernels that see an image border (FAST + NMS, blur, resize) on the slots' launch
+    // grids; the others index with the slot's pitch and stay inside the image through the edge threshold.  A level the slot is too small
+    // for is too small for every entry (cvRound is monotone), so the slot's `active` below still skips it as a whole.
+    const bool mixed = o->n_sizes > 0;
     const uint8_t* prev = images;
     for (int l = 0; l < o->nlevels; ++l) {
         stvo_orb::Level& L = o->lev[l];
         stvo::OrbDev d = L.d;
+        d.sz = mixed ? o->d_sizes : nullptr; d.n_sz = o->n_sizes; d.sz_stride = o->nlevels; d.level = l;
         if (l) {  // resize(level l - 1): needed by the next level even when this one yields nothing
             const stvo::OrbDev& p = o->lev[l - 1].d;
-            stvo::ResizeArgs r{d.B, p.cols, p.rows, d.cols, d.rows, 1.0 / ((double)d.cols / p.cols), 1.0 / ((double)d.rows / p.rows), prev, L.img};
-            hipLaunchKernelGGL(stvo::orb_resize_kernel, dim3((d.cols + 255) / 256, d.rows, d.B), dim3(256), 0, s, r);
+            stvo::ResizeArgs r{d.B, p.cols, p.rows, d.cols, d.rows, 1.0 / ((double)d.cols / p.cols), 1.0 / ((double)d.rows / p.rows), prev, L.img,
+                               d.sz, d.n_sz, d.sz_stride, l};
+            const dim3 rgrid((d.cols + 255) / 256, d.rows, d.B);
+            if (mixed) hipLaunchKernelGGL(stvo::orb_resize_kernel<true>, rgrid, dim3(256), 0, s, r);
+            else hipLaunchKernelGGL(stvo::orb_resize_kernel<false>, rgrid, dim3(256), 0, s, r);
             d.img = L.img;
         } else {
             d.img = images;
@@ -1370,9 +1469,14 @@ int stvo_orb_detect_levels_dev(stvo_orb* o, const uint8_t* images, float* kp_xy,
             continue;
         }
         const dim3 tiles((d.cols + 4 * stvo::BL_T - 1) / (4 * stvo::BL_T), (d.rows + stvo::BL_R - 1) / stvo::BL_R, d.B), tb(stvo::BL_T);
-        hipLaunchKernelGGL(stvo::orb_fast_nms_kernel, dim3((d.cols + stvo::FT_W - 1) / stvo::FT_W, (d.rows + stvo::FT_H - 1) / stvo::FT_H, d.B),
-                           dim3(256), 0, s, d);
-        hipLaunchKernelGGL(stvo::orb_blur_kernel, tiles, tb, 0, s, d, o->blur_k);
+        const dim3 ftiles((d.cols + stvo::FT_W - 1) / stvo::FT_W, (d.rows + stvo::FT_H - 1) / stvo::FT_H, d.B);
+        if (mixed) {
+            hipLaunchKernelGGL(stvo::orb_fast_nms_kernel<true>, ftiles, dim3(256), 0, s, d);
+            hipLaunchKernelGGL(stvo::orb_blur_kernel<true>, tiles, tb, 0, s, d, o->blur_k);
+        } else {
+            hipLaunchKernelGGL(stvo::orb_fast_nms_kernel<false>, ftiles, dim3(256), 0, s, d);
+            hipLaunchKernelGGL(stvo::orb_blur_kernel<false>, tiles, tb, 0, s, d, o->blur_k);
+        }
         if (d.score_harris) {
             hipLaunchKernelGGL(stvo::orb_harris_kernel, dim3(stvo::HR_BLOCKS, d.B), dim3(256), 0, s, d);
             hipLaunchKernelGGL(stvo::orb_order_kernel<true>, dim3(d.B), dim3(1024), 0, s, d);

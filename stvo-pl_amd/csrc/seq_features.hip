@@ -290,4 +290,74 @@ int stvo_seq_restart_fast_dev(stvo_seq* s, int32_t* th_dev, int th0) {
     return check_launch(ctx);
 }
 
+// The camera of the sequence a RESTART stream begins (stvo_hip.h): for every stream the STAGED control marks RESTART, d_cams[b], d_inv_wh[b]
+// and what a snapshot header says of the stream become the given values, by one small kernel enqueued NOW on the context's stream (the
+// point stream), behind the copy of the control words it reads and in front of the step they belong to.
+// Why no reader sees a half-old camera.  The readers are the cells kernels (inv_wh), the stereo tails of key-points and key-lines (cams),
+// the pose kernel (cams) and the snapshot export (cams, image size).
+//   * Of step k - 1 and earlier: everything on the point stream — its pose kernel last — was enqueued there earlier, so it precedes this
+//     kernel in stream order; the key-line stream's work of step k - 1 was joined in FRONT of that pose kernel (the join event, or the flag
+//     the pose kernel waits for), so it has completed as well.  An export enqueued earlier runs on the context's stream too.
+//   * Of step k: a step with a control runs nothing ahead of its own fork event (step_plan.h: never the cells kernel or the key-line stage
+//     ahead, never the event-free fork), and that event is recorded on the point stream behind the control kernel of the step, which is
+//     enqueued behind this one.  So every kernel of step k on either stream follows this kernel.
+//   * A step that follows this call WITHOUT carrying the control — the pipeline's own first step (a control staged for it is consumed
+//     without effect, but the cameras given here are taken), or a step before which an all-RUN stvo_seq_control_next_step withdrew the
+//     control after the cameras were written — would be free to fork without an event or to run its cells kernel ahead on the key-line
+//     stream, beside this kernel.  The call therefore leaves cams_pending set until the next step is enqueued, which the planner reads as
+//     it reads an import (StepFacts::after_import -> own_fork): that step, too, does nothing on the key-line stream before its own fork
+//     event.  It also marks the point stream as holding work (st_dirty), so that an upload in between copies nothing ahead either.
+//   * Later steps may run ahead again: what they wait for is step k's fork event or a later one.
+// The host copies (cams_host, img_size_host: what stvo_seq_import_streams checks a blob against) change during the call, in host order.
+int stvo_seq_restart_cameras(stvo_seq* s, const stvo_cam* cams_host, const int32_t* img_cols, const int32_t* img_rows) {
+    if (!s || !cams_host || !img_cols || !img_rows || !s->ctl_staged) return STVO_ERR_INVALID_ARG;
+    const int32_t* ctl = s->ctl_stage[s->ctl_stage_next ^ 1];  // the words stvo_seq_control_next_step staged last (host copy)
+    bool any = false;
+    for (int b = 0; b < s->B; ++b) {
+        if (ctl[b] != STVO_STREAM_RESTART) continue;  // entries of RUN and PARK streams are not read
+        if (img_cols[b] <= 0 || img_rows[b] <= 0) return STVO_ERR_INVALID_ARG;
+        any = true;
+    }
+    if (!any) return STVO_ERR_INVALID_ARG;
+    stvo_ctx* ctx = s->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)s->B * sizeof(stvo::CamRestart), span = (bytes + 255) & ~size_t(255);
+    if (!s->d_cam_upd) HIP_TRY(ctx, hipMalloc((void**)&s->d_cam_upd, span));
+    if (!s->cam_stage[0]) {
+        HIP_TRY(ctx, hipHostMalloc((void**)&s->cam_stage[0], 2 * span, hipHostMallocDefault));
+        s->cam_stage[1] = reinterpret_cast<stvo::CamRestart*>(reinterpret_cast<char*>(s->cam_stage[0]) + span);
+    }
+    for (auto& e : s->ev_cam)
+        if (!e) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    const int hb = s->cam_stage_next;
+    if (s->cam_stage_busy[hb]) {  // the copy that last read this block (two calls ago)
+        HIP_TRY(ctx, hipEventSynchronize(s->ev_cam[hb]));
+        s->cam_stage_busy[hb] = false;
+    }
+    stvo::CamRestart* u = s->cam_stage[hb];
+    std::memset(u, 0, bytes);
+    for (int b = 0; b < s->B; ++b) {
+        if (ctl[b] != STVO_STREAM_RESTART) continue;
+        u[b].cam = cams_host[b];
+        u[b].inv_w = STVO_GRID_COLS / (double)img_cols[b];  // stereoFrame.cpp:47-48, as stvo_seq_create_multi forms them
+        u[b].inv_h = STVO_GRID_ROWS / (double)img_rows[b];
+        u[b].cols = img_cols[b];
+        u[b].rows = img_rows[b];
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(s->d_cam_upd, u, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev_cam[hb], ctx->stream));
+    s->cam_stage_busy[hb] = true;
+    s->cam_stage_next = hb ^ 1;
+    stvo::launch_cam_restart(ctx->stream, s->B, s->d_ctl[s->ctl_next], s->d_cam_upd, s->d_cams, s->d_inv_wh, s->d_snap_img);
+    s->st_dirty = true;
+    s->cams_pending = true;
+    for (int b = 0; b < s->B; ++b) {
+        if (ctl[b] != STVO_STREAM_RESTART) continue;
+        s->cams_host[b] = cams_host[b];
+        s->img_size_host[2 * b] = img_cols[b];
+        s->img_size_host[2 * b + 1] = img_rows[b];
+    }
+    return check_launch(ctx);
+}
+
 }  // extern "C"

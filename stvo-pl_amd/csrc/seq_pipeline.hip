@@ -230,12 +230,12 @@ int stvo_seq_destroy(stvo_seq* s) {
     }
     // (d_ctl and ctl_stage: one allocation for both copies each)
     for (void* p : {(void*)s->d_prof, (void*)s->d_motion_T, (void*)s->d_traj_state, (void*)s->d_traj_ring, (void*)s->d_tracks, (void*)s->d_kf,
-                    (void*)s->d_ctl[0], (void*)s->dev, (void*)s->extra_raw, (void*)s->d_snap_img, (void*)s->d_snap_streams, (void*)s->snap_buf})
+                    (void*)s->d_ctl[0], (void*)s->d_cam_upd, (void*)s->dev, (void*)s->extra_raw, (void*)s->d_snap_img, (void*)s->d_snap_streams, (void*)s->snap_buf})
         if (p) (void)hipFree(p);
     // (snap_stage: one allocation for both blocks)
-    for (void* p : {(void*)s->ctl_stage[0], (void*)s->snap_stage[0], (void*)s->fetch_host, (void*)s->raw_host[0], (void*)s->raw_host[1], (void*)s->out_host})
+    for (void* p : {(void*)s->ctl_stage[0], (void*)s->cam_stage[0], (void*)s->snap_stage[0], (void*)s->fetch_host, (void*)s->raw_host[0], (void*)s->raw_host[1], (void*)s->out_host})
         if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {s->ev_snap[0], s->ev_snap[1], s->ev_ctl[0], s->ev_ctl[1], s->ev_fork, s->ev_join, s->ev_cells, s->ev_upload, s->ev_stage[0], s->ev_stage[1], s->ev_fetch})
+    for (hipEvent_t e : {s->ev_snap[0], s->ev_snap[1], s->ev_ctl[0], s->ev_ctl[1], s->ev_cam[0], s->ev_cam[1], s->ev_fork, s->ev_join, s->ev_cells, s->ev_upload, s->ev_stage[0], s->ev_stage[1], s->ev_fetch})
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->tev) (void)hipEventDestroy(e);
     delete s;
@@ -395,7 +395,8 @@ void gather_step_facts(const stvo_seq* s, int slot, const stvo::StepFlags& fl, b
     f.lines_now = fl.lines_now; f.lines_prev = fl.lines_prev; f.track = fl.track;
     f.frame_idx = s->frame_idx;
     f.has_control = fl.ctl != nullptr;
-    f.after_import = s->imported;
+    // (imported streams, and cameras written by stvo_seq_restart_cameras: state the point stream holds that the step's line-stream work must follow)
+    f.after_import = s->imported || s->cams_pending;
     f.raw_split = s->raw_split[slot]; f.raw_max_lines = s->raw_max_lines[slot];
     f.set_lines_cap_prev = s->set_lines_cap[s->prev_set()]; f.set_lines_cap_cur = s->set_lines_cap[s->cur];
     f.st_dirty = s->st_dirty; f.fetch = s->fetch; f.zero_copy = s->zero_copy;
@@ -655,6 +656,7 @@ int stvo_seq_step_dev(stvo_seq* s, int slot) {
     std::memcpy(s->last_schedule, plan.schedule, sizeof(s->last_schedule));
     s->st_dirty = true;
     s->imported = false;
+    s->cams_pending = false;
     s->set_lines[s->cur] = fl.lines_now;
     s->last_lines = fl.lines_now;
     s->last_slot = slot;

@@ -91,6 +91,15 @@ struct stvo_seq {
     int ctl_stage_next = 0, ctl_next = 0;   // the staging block / device copy the next stvo_seq_control_next_step fills
     bool ctl_staged = false;                // d_ctl[ctl_next] holds a control for the next step
     const int32_t* last_ctl = nullptr;      // the control the last enqueued step carried out (device), or nullptr
+    // the cameras of restarting streams (stvo_seq_restart_cameras): nothing of it exists until the first call.  One device block [B] of its
+    // own — the copy that fills it and the kernel that reads it run on the context's stream — and two pinned staging blocks used
+    // alternately, each with an event behind the copy that read it
+    stvo::CamRestart* d_cam_upd = nullptr;
+    stvo::CamRestart* cam_stage[2] = {nullptr, nullptr};
+    hipEvent_t ev_cam[2] = {nullptr, nullptr};
+    bool cam_stage_busy[2] = {false, false};
+    int cam_stage_next = 0;
+    bool cams_pending = false;              // cameras were written on the point stream since the last step: that step forks with its own event
     // feature tracks and key-frame sets per stream (stvo_seq_set_tracks; track_kernel.hip): null = off.  d_tracks is one allocation of
     // 2 + track_log_steps rows of [B][K] point records followed by [B][M] key-line records — rows 0 / 1 the state (step k reads copy
     // (k + 1) & 1 and writes copy k & 1), row 2 + k % track_log_steps the record of step k — and behind them the ring's counts

@@ -8,7 +8,9 @@
 //   stream_ctl_post_kernel   behind the pose kernel, where the result was written (device memory or the pinned zero-copy block): the
 //                            stream's result record becomes all-zero bytes (what stvo_seq_read reports for a first frame), its motion-model
 //                            seed the identity (prev_frame->DT = I, :45) and its inlier rows -1;
-//   fast_restart_kernel      th[b] = th0 for the RESTART streams (:38 precedes the detection of :41-42).
+//   fast_restart_kernel      th[b] = th0 for the RESTART streams (:38 precedes the detection of :41-42);
+//   cam_restart_kernel       cams[b], inv_wh[b] (and the image size a snapshot header carries) of the RESTART streams become those of the
+//                            new sequence's dataset (app/imagesStVO.cpp:66 builds one PinholeStereoCamera per dataset), in front of the step.
 // One wave per stream, four streams per workgroup; a wave whose stream RUNs reads its control word and leaves.  No barrier, plain
 // vector stores.
 #include "ctx_internal.h"
@@ -54,6 +56,20 @@ __global__ __launch_bounds__(64) void fast_restart_kernel(int B, const int32_t* 
     if (ctl[b] == STVO_STREAM_RESTART) th[b] = th0;
 }
 
+__global__ __launch_bounds__(64) void cam_restart_kernel(int B, const int32_t* __restrict__ ctl, const CamRestart* __restrict__ upd,
+                                                         stvo_cam* __restrict__ cams, double* __restrict__ inv_wh, int32_t* __restrict__ snap_img) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B || ctl[b] != STVO_STREAM_RESTART) return;
+    const CamRestart u = upd[b];
+    cams[b] = u.cam;
+    inv_wh[2 * b] = u.inv_w;
+    inv_wh[2 * b + 1] = u.inv_h;
+    if (snap_img) {
+        snap_img[2 * b] = u.cols;
+        snap_img[2 * b + 1] = u.rows;
+    }
+}
+
 }  // namespace
 
 void launch_stream_ctl_pre(hipStream_t s, int B, const int32_t* ctl, int32_t* n_prev, int32_t* nl_prev, int32_t* m12p, int K, int32_t* m12l, int M) {
@@ -67,6 +83,10 @@ void launch_stream_ctl_post(hipStream_t s, int B, const int32_t* ctl, stvo_pose_
 
 void launch_fast_restart(hipStream_t s, int B, const int32_t* ctl, int32_t* th, int th0) {
     hipLaunchKernelGGL(fast_restart_kernel, dim3((B + 63) / 64), dim3(64), 0, s, B, ctl, th, th0);
+}
+
+void launch_cam_restart(hipStream_t s, int B, const int32_t* ctl, const CamRestart* upd, stvo_cam* cams, double* inv_wh, int32_t* snap_img) {
+    hipLaunchKernelGGL(cam_restart_kernel, dim3((B + 63) / 64), dim3(64), 0, s, B, ctl, upd, cams, inv_wh, snap_img);
 }
 
 }  // namespace stvo

@@ -35,7 +35,7 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_color_to_gray", "stvo_color_to_gray_dev", "stvo_rectify_color_images", "stvo_rectify_color_images_dev",
            "stvo_rectify_color_to_gray_dev", "stvo_seq_snapshot_layout", "stvo_seq_snapshot_info", "stvo_seq_export_streams_dev",
            "stvo_seq_export_streams", "stvo_seq_import_streams_dev", "stvo_seq_import_streams", "stvo_orb_set_descriptor",
-           "stvo_orb_pattern"]
+           "stvo_orb_pattern", "stvo_orb_set_image_sizes", "stvo_seq_restart_cameras"]
 
 SEQ_NSTAGE = 5  # include/stvo_hip.h: STVO_SEQ_NSTAGE
 SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_check", "pose")
@@ -278,6 +278,7 @@ def load():
     L.stvo_orb_pattern.argtypes = [C.c_int, C.c_int, C.c_void_p, i8p, C.POINTER(C.c_int32)]
     L.stvo_orb_set_fast_thresholds.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.stvo_orb_set_fast_thresholds_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.stvo_orb_set_image_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.stvo_fast_adapt_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(FastAdapt), C.c_void_p]
     L.stvo_seq_adapt_fast_dev.argtypes = [C.c_void_p, C.POINTER(FastAdapt), C.c_void_p]
     L.stvo_traj_init_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -294,6 +295,7 @@ def load():
     L.stvo_seq_read_keyframe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int32, f32p, u8p, C.c_int32, f64p, f64p, f64p, f64p, f64p,
                                          f64p, f64p, u8p]
     L.stvo_seq_restart_fast_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.stvo_seq_restart_cameras.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.stvo_seq_snapshot_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(SnapshotLayout)]
     L.stvo_seq_snapshot_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.stvo_seq_export_streams_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -569,6 +571,17 @@ class Orb:
             a = np.ascontiguousarray(th, np.int32).reshape(-1)
             self.ctx._chk(lib.stvo_orb_set_fast_thresholds(self.h, _ptr(a), a.size))
             self._th_keep = None
+
+    def set_image_sizes(self, sizes):
+        """One image size per image: sizes [n][2] = (cols, rows), image i takes sizes[i % n] (n divides B) and occupies the top-left of
+        its slot of the size given at creation, whose row pitch it keeps (stvo_orb_set_image_sizes).  None: every image fills its slot."""
+        if sizes is None:
+            self.ctx._chk(self.ctx.lib.stvo_orb_set_image_sizes(self.h, None, 0))
+            return
+        a = np.ascontiguousarray(sizes, np.int32)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("Orb.set_image_sizes: sizes is [n][2] = (cols, rows)")
+        self.ctx._chk(self.ctx.lib.stvo_orb_set_image_sizes(self.h, _ptr(a), a.shape[0]))
 
     def set_score_type(self, score):
         self.ctx._chk(self.ctx.lib.stvo_orb_set_score_type(self.h, score))
@@ -936,6 +949,17 @@ class Sequences:
         if str(th.dtype) != "torch.int32" or not th.is_cuda or not th.is_contiguous() or th.numel() != self.B:
             raise ValueError("Sequences.restart_fast_dev: th must be a contiguous int32 device tensor of B entries")
         self.ctx._chk(self.ctx.lib.stvo_seq_restart_fast_dev(self.h, th.data_ptr(), int(th0)))
+
+    def restart_cameras(self, cams):
+        """The cameras of the sequences the staged control's RESTART streams begin (stvo_seq_restart_cameras), after control_next_step for
+        the same step: cams = B entries, a camera dict (fx, fy, cx, cy, b, width, height) for every stream that restarts, None (or
+        anything) for the others, which are not read.  No synchronisation."""
+        if len(cams) != self.B:
+            raise ValueError("Sequences.restart_cameras: one entry per stream")
+        arr = (Cam * self.B)(*[Cam.from_dict(c) if c is not None else Cam() for c in cams])
+        cols = np.array([c["width"] if c is not None else 0 for c in cams], np.int32)
+        rows = np.array([c["height"] if c is not None else 0 for c in cams], np.int32)
+        self.ctx._chk(self.ctx.lib.stvo_seq_restart_cameras(self.h, C.cast(arr, C.c_void_p), _ptr(cols), _ptr(rows)))
 
     def set_trajectory(self, prm, log_steps=1):
         """Trajectory and key-frame decision per stream behind every tracked step (stvo_seq_set_trajectory): prm = traj_params(...) or

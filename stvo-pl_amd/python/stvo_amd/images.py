@@ -23,7 +23,12 @@ class ImagePipeline:
                  scale_factor=1.2, lsd=None, max_kl=128, rectify=None, fld=None, orb_score=1, adaptive_fast=None,
                  trajectory=None, trajectory_log=1, tracks=0, keyframe_sets=False, channels=1, gray_weights="q14", orb_wta_k=2,
                  orb_patch_size=31):
-        """cam: one camera dict (width / height = image size) for all B streams.  nlevels / scale_factor: Config::orbNLevels /
+        """cam: one camera dict (width / height = image size) for all B streams, or a list of B dicts, one camera AND image size per stream
+        (KITTI 00-02 / 03 / 04-10 side by side): the resident image buffer is then cut in slots of the largest width x the largest height,
+        stream b's images occupy the top-left of their slots (set_images takes a list of B arrays of each stream's own size), the
+        detector reads every image at its own size (Orb.set_image_sizes) and the pipeline is created with the B cameras; a stream that
+        RESTARTs may take another camera (enqueue / push_images: cams).  Key-points only: with a list, lsd, fld, rectify and channels
+        other than 1 raise ValueError (their detectors, the rectifier and the colour conversion hold one size each).  nlevels / scale_factor: Config::orbNLevels /
         orbScaleFactor (the key-point octaves travel with the key-points: sigma2 = 1 / scale^(2 level)).  orb_score: Config::orbScore
         (1 FAST_SCORE, 0 HARRIS_SCORE ranking of the key-points).  orb_wta_k / orb_patch_size: Config::orbWtaK / orbPatchSize
         (capi.Orb: 2 .. 4 and 2 .. 63; the descriptor stays 32 bytes under the matchers' plain Hamming distance).  lsd: capi.lsd_params(...)
@@ -56,12 +61,29 @@ class ImagePipeline:
             raise ValueError("ImagePipeline: gray_weights is 'q14' or 'q15'")
         self.channels, self.gray_weights = channels, gray_weights
         self.ctx, self.B, self.K, self.M = ctx, B, max_kp, max_kl
-        self.cols, self.rows = cam["width"], cam["height"]
+        self.cams = None  # one camera per stream: the B dicts in force (a RESTART may bring another)
+        if not isinstance(cam, dict):
+            cam = list(cam)
+            if len(cam) != B:
+                raise ValueError("ImagePipeline: cam is one dict or a list of B dicts")
+            for name, given in (("lsd", lsd is not None), ("fld", fld is not None), ("rectify", rectify is not None), ("channels", channels != 1)):
+                if given:
+                    raise ValueError(f"ImagePipeline: {name} is not available with one camera per stream (cam as a list): key-points only")
+            self.cams = cam
+            self.cols, self.rows = max(c["width"] for c in cam), max(c["height"] for c in cam)  # the slot
+        else:
+            self.cols, self.rows = cam["width"], cam["height"]
         self.rectify = rectify
         if rectify is not None and (rectify.ctx is not ctx or rectify.B < B or rectify.cols != self.cols or rectify.rows != self.rows):
             raise ValueError("ImagePipeline: the rectifier must belong to the same context, hold B pairs and match the image size")
         self.orb = capi.Orb(ctx, 2 * B, self.cols, self.rows, max_kp, nfeatures, fast_threshold, edge_threshold, nlevels, scale_factor,
                             score=orb_score, wta_k=orb_wta_k, patch_size=orb_patch_size)  # left images, then right
+        if self.cams is not None:  # n = B on 2 B images: left image b and right image B + b share entry b
+            try:
+                self.orb.set_image_sizes([(c["width"], c["height"]) for c in self.cams])
+            except Exception:
+                self.orb.close()
+                raise
         if lsd is not None and fld is not None:
             raise ValueError("ImagePipeline: one line detector, lsd or fld")
         lp = lsd if lsd is not None else fld
@@ -125,10 +147,33 @@ class ImagePipeline:
         self.ff = ff  # (without a line detector every line pointer stays NULL: no key-lines; oct_ll NULL: one octave)
         self.slot = 0
 
-    def set_images(self, left, right):
+    def _cams_after(self, control, cams):
+        """The B cameras in force once the RESTART streams of `control` have taken theirs from `cams` (B entries, None for the others)."""
+        if self.cams is None or control is None or len(cams) != self.B:
+            raise ValueError("ImagePipeline: cams takes one camera per stream (cam as a list), a control and B entries")
+        ctl = np.asarray(control).reshape(-1)
+        new = [c if c is not None and ctl[b] == capi.STREAM_RESTART else self.cams[b] for b, c in enumerate(cams)]
+        if any(c["width"] > self.cols or c["height"] > self.rows for c in new):
+            raise ValueError("ImagePipeline: a camera's images are larger than the slot the pipeline was built with")
+        return new
+
+    def set_images(self, left, right, cams=None):
         """left / right: uint8 [B, rows, cols] (numpy or torch), with channels 3 / 4 [B, rows, cols, channels]; copied into the
-        resident image buffer."""
+        resident image buffer.  With one camera per stream also two lists of B arrays [height_b, width_b] of each stream's own size:
+        each is placed top-left in its slot (what the slot holds beyond it is never read); cams: the B cameras whose sizes the images have,
+        where they are not yet the ones in force (push_images with a RESTART)."""
         B = self.B
+        cams = self.cams if cams is None else cams
+        if self.cams is not None and isinstance(left, (list, tuple)):
+            if len(left) != B or len(right) != B:
+                raise ValueError("ImagePipeline.set_images: one image per stream and side")
+            for side, imgs in ((0, left), (B, right)):
+                for b, im in enumerate(imgs):
+                    t = torch.as_tensor(im)
+                    if tuple(t.shape) != (cams[b]["height"], cams[b]["width"]):
+                        raise ValueError(f"ImagePipeline.set_images: stream {b} takes images of {cams[b]['width']} x {cams[b]['height']}")
+                    self.img[side + b, :t.shape[0], :t.shape[1]].copy_(t, non_blocking=True)
+            return
         if self.channels != 1:
             self.color[:B].copy_(torch.as_tensor(left).reshape(B, self.rows, self.cols, self.channels), non_blocking=True)
             self.color[B:].copy_(torch.as_tensor(right).reshape(B, self.rows, self.cols, self.channels), non_blocking=True)
@@ -136,15 +181,30 @@ class ImagePipeline:
         self.img[:B].copy_(torch.as_tensor(left).reshape(B, self.rows, self.cols), non_blocking=True)
         self.img[B:].copy_(torch.as_tensor(right).reshape(B, self.rows, self.cols), non_blocking=True)
 
-    def enqueue(self, img_ptr=None, control=None):
+    def enqueue(self, img_ptr=None, control=None, cams=None):
         """Detection + description of the 2 B resident images (or of the uint8 [2 B, rows, cols] device buffer at img_ptr: B left,
         then B right; with channels 3 / 4 the colour buffer [2 B, rows, cols, channels]), ingestion, one pipeline step — all
         asynchronous.  With a rectifier the images are raw and are rectified first.
         control: None, or B words capi.STREAM_RUN / STREAM_RESTART / STREAM_PARK for this step (Sequences.control_next_step): staged
         first, so that with adaptive_fast the restarted streams are detected at fast_threshold again (initialize sets orb_fast_th
-        before it detects); the rule at the end of the step leaves the thresholds of restarted and parked streams alone."""
+        before it detects); the rule at the end of the step leaves the thresholds of restarted and parked streams alone.
+        cams (one camera per stream only): None, or B entries — the camera dict of the sequence a RESTART stream begins, None for the
+        others: the pipeline (Sequences.restart_cameras) and the detector (Orb.set_image_sizes) take it before the detection."""
+        new = self._cams_after(control, cams) if cams is not None else None
         if control is not None:
             self.seq.control_next_step(control)
+            if new is not None and new != self.cams:
+                # the detector first: it validates every size, and what it has taken can be put back should the pipeline refuse —
+                # the two never disagree, and a refused call leaves no control staged
+                ctl = np.asarray(control).reshape(-1)
+                try:
+                    self.orb.set_image_sizes([(c["width"], c["height"]) for c in new])
+                    self.seq.restart_cameras([c if ctl[b] == capi.STREAM_RESTART else None for b, c in enumerate(new)])
+                except Exception:
+                    self.orb.set_image_sizes([(c["width"], c["height"]) for c in self.cams])
+                    self.seq.control_next_step(np.zeros(self.B, np.int32))
+                    raise
+                self.cams = new
             if self.adaptive_fast is not None:
                 self.seq.restart_fast_dev(self.fast_th, self.fast_threshold)
         ip = img_ptr if img_ptr is not None else (self.img if self.channels == 1 else self.color).data_ptr()
@@ -177,11 +237,12 @@ class ImagePipeline:
             self.seq.adapt_fast_dev(self.adaptive_fast, self.fast_th)
         self.slot ^= 1
 
-    def push_images(self, left, right, control=None):
-        """One frame of every stream: (pose results [B], counts [B, 4]) like Sequences.push.  control: as for enqueue."""
-        self.set_images(left, right)
+    def push_images(self, left, right, control=None, cams=None):
+        """One frame of every stream: (pose results [B], counts [B, 4]) like Sequences.push.  control, cams: as for enqueue (the images of
+        a stream that takes another camera have that camera's size)."""
+        self.set_images(left, right, cams=self._cams_after(control, cams) if cams is not None else None)
         torch.cuda.current_stream().synchronize()  # the copies above ran on torch's stream, the library uses its own
-        self.enqueue(control=control)
+        self.enqueue(control=control, cams=cams)
         return self.seq.read()
 
     def read_trajectory(self, n_last=1):

@@ -48,8 +48,20 @@ def empty_frame():
     return dict(kp_l=z2, oct_l=zi, desc_l=zd, kp_r=z2, desc_r=zd, kl_l=z4, oct_ll=zi, ldesc_l=zd, kl_r=z4, ldesc_r=zd)
 
 
-def run(dev, sequences, tracks=0, keyframe_sets=False):
+def initial_cameras(lengths, B, cams):
+    """The B camera dicts to create the pipeline of run(dev, sequences, cams=cams) with: cams[i] of the sequence the plan starts on each
+    stream in step 0, and — a stream that starts parked reads no camera before its first RESTART brings one — cams[0] for the others."""
+    steps = plan(lengths, B)
+    if not steps:
+        raise ValueError("ragged.initial_cameras: no sequence")
+    return [cams[c[0]] if c is not None else cams[0] for c in steps[0].consume]
+
+
+def run(dev, sequences, tracks=0, keyframe_sets=False, cams=None):
     """Drives dev (a fresh capi.Sequences of B streams) through plan([len(s) for s in sequences], dev.B), one push per step.
+    cams: None (every sequence has the camera its stream was created with), or one camera dict per sequence — dev is then created with
+    initial_cameras(lengths, B, cams), and every RESTART of the plan is followed by Sequences.restart_cameras with the camera of the
+    sequence that begins (a stream's sequences need not share a calibration or an image size).
     Returns (results, counts, records): per sequence a POSE_RESULT_DTYPE array [frames] (entry 0, the sequence's first frame, all-zero),
     an int32 array [frames, 4], and — with the trajectory on (Sequences.set_trajectory), else records is None — a TRAJ_RECORD_DTYPE
     array [frames - 1] of the tracked frames (its `frame` counts from 1 in every sequence).
@@ -68,6 +80,8 @@ def run(dev, sequences, tracks=0, keyframe_sets=False):
     for st in steps:
         if st.control.any():
             dev.control_next_step(st.control)
+            if cams is not None and (st.control == STREAM_RESTART).any():
+                dev.restart_cameras([cams[c[0]] if st.control[b] == STREAM_RESTART else None for b, c in enumerate(st.consume)])
         res, cnt = dev.push([sequences[c[0]][c[1]] if c is not None else idle for c in st.consume])
         rec = dev.read_trajectory(1) if traj else None
         if tracks:
