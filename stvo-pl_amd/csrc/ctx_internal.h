@@ -8,11 +8,19 @@
 
 #include "kernels.h"
 
+namespace stvo_detail {
+// A grow-only device block: kept from call to call, replaced when a call needs more (staging_reserve).  The owner frees `p` when it
+// is destroyed.  The host-buffer entry points stage their images and results in one; the context keeps the pose arenas in two.
+struct Staging {
+    char* p = nullptr;
+    size_t bytes = 0;
+};
+}  // namespace stvo_detail
+
 struct stvo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    bool stream_retained = false;  // this context holds a reference on the stream's pose-record arena (kernels.h)
     int max_rows = 0, max_batch = 0;
     // persistent scratch for the batched path
     uint2* knn12 = nullptr;
@@ -33,6 +41,9 @@ struct stvo_ctx {
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_match_done = nullptr, ev_pose_done = nullptr;
     bool pose_pending = false;
+    // the record arenas of the batch pose kernels (pose_scratch.h), one per stream this context launches them on: `stream` (whichever
+    // it is at the time: stvo_ctx_set_stream synchronises the old one) and aux_stream.  Grown by launch_pose_ctx, freed by stvo_ctx_destroy.
+    stvo_detail::Staging pose_arena, pose_arena_aux;
     // optional live kernel timing (bench): event pairs around every hamming_knn2 launch of the batched path
     int timing = 0;
     std::vector<hipEvent_t> ev_pool;  // start/stop pairs, grown on demand
@@ -64,12 +75,6 @@ inline bool upload_now(stvo_ctx* ctx, void* dst, const void* src, size_t bytes, 
     return hip_ok(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream), what) && hip_ok(ctx, hipStreamSynchronize(ctx->stream), what);
 }
 
-// The grow-only device block of a host-buffer entry point (images in, results out): kept from call to call, replaced when a call needs
-// more.  The owner frees `p` when it is destroyed.
-struct Staging {
-    char* p = nullptr;
-    size_t bytes = 0;
-};
 inline int staging_reserve(stvo_ctx* ctx, Staging& s, size_t bytes) {
     if (s.bytes >= bytes) return STVO_OK;
     if (s.p) (void)hipFree(s.p);
@@ -138,6 +143,20 @@ inline const T* host_mirror(stvo_ctx* ctx, const T* dev) {
         int _rc = (expr);        \
         if (_rc != STVO_OK) return _rc; \
     } while (0)
+
+// launch_pose on one of the context's two streams, with that stream's arena behind it.  The block is replaced only when a launch
+// needs more than it holds (a larger batch, the double form after the compact one); the launches that may still be using the old
+// one are all on `s`, which is synchronised first.
+inline int launch_pose_ctx(stvo_ctx* ctx, hipStream_t s, const stvo::PoseProblem& p, const stvo::PosePoints& r,
+                           const stvo::PoseOptions& o = stvo::PoseOptions()) {
+    Staging& a = s == ctx->stream ? ctx->pose_arena : ctx->pose_arena_aux;
+    const size_t need = stvo::pose_route(p.B, r.is_compact(), o.eval_out != nullptr).arena_bytes;
+    if (a.bytes < need) {
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        TRY(staging_reserve(ctx, a, need));
+    }
+    return stvo::launch_pose(s, p, r, a.p, a.bytes, o);
+}
 
 inline int check_launch(stvo_ctx* ctx) {
     HIP_TRY(ctx, hipGetLastError());

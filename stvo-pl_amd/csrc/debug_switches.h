@@ -18,7 +18,7 @@ struct DebugSwitches {
     int pose_los;        // STVO_POSE_LOS        0: the key-lines of pose_kernel.hip always with the worker waves (never the solver wave)
     int knn_mfma;        // STVO_KNN_MFMA        0: VALU matcher (K1 + K1v), else query blocks per wave of K1m
     int knn_nseg;        // STVO_KNN_NSEG        train segments per query tile
-    int seq_inline;      // STVO_SEQ_INLINE      0: events between the streams of a step for small batches too (kernels.h: PoseArgs::wait_flag)
+    int seq_inline;      // STVO_SEQ_INLINE      0: events between the streams of a step for small batches too (kernels.h: PoseSync::wait_flag)
     int line_fused;      // STVO_LINE_FUSED      0 / 1: general / one-workgroup stereo line matcher
     int match_small;     // STVO_MATCH_SMALL     0: the general f2f machinery for the key-line sets too
     int match_lazy;      // STVO_MATCH_LAZY      1: the lazy reverse check for small batches too

@@ -14,6 +14,7 @@
 #include "grid_scratch.h"
 #include "match_scratch.h"
 #include "point_tail.h"
+#include "pose_scratch.h"
 #include "seq_layout.h"
 
 namespace stvo {
@@ -109,15 +110,17 @@ void launch_valu_probe(hipStream_t s, int blocks, int iters, uint32_t* sink);
 void launch_copy16(hipStream_t s, const void* src, void* dst, size_t bytes);
 extern const double kValuProbeOpsPerThreadIter;
 
-// ---- K4-K6: pose optimisation, one workgroup per frame pair ------------------------------------
-struct PoseArgs {
-    int B, max_pts, max_lines;
-    const int32_t* n_prev_pts;
-    const double* prev_P;
-    const double* prev_s2p;
-    const double* curr_pl;
-    const int32_t* m12p;        // nullptr: identity association (records mode)
+// ---- K4-K6: pose optimisation, one workgroup per frame pair (pose_kernel.hip, pose_kernel2p.hip) ------------------------------
+// StereoFrameHandler::optimizePose of B frame pairs.  A launch is a problem, the stereo points in ONE of two record forms, and what
+// it may be given on top (PoseOptions); the route it takes and the arena it needs: pose_scratch.h.  The kernels are handed one flat
+// by-value copy of all of it (pose_args.h, private to the two pose files).
+// The problem: what optimizePose takes, batched.
+struct PoseProblem {
+    int B, max_pts, max_lines;  // frame pairs; rows per frame of the point / key-line arrays
+    const int32_t* n_prev_pts;  // [B], or nullptr: no points
+    const int32_t* m12p;        // [B][max_pts] match of prev point i, or nullptr: identity association (records mode)
     const int32_t* init_inl_p;  // nullptr: every matched record starts as inlier
+    // the key-line records
     const int32_t* n_prev_lines;
     const double* prev_sP;
     const double* prev_eP;
@@ -135,71 +138,80 @@ struct PoseArgs {
     stvo_pose_result* results;
     int32_t* inl_p_out;  // [B][max_pts] or nullptr
     int32_t* inl_l_out;
-    int eval_only;       // 1: a single optimizeFunctions evaluation at init_T
-    int eval_robust;
-    double* eval_out;    // [B][44]: H(36) g(6) e n
-    long long* prof_out; // optional [B][16] phase ticks (tools only)
-    // compact records of the device-resident pipeline (seq_pipeline.hip), or nullptr: a stereo point is {u, v, disparity as
-    // floats, pyramid level} — exactly what the reference's PointFeature is built from (src/stereoFrame.cpp:152-167: float
-    // key-point coordinates, a float difference, backProjection of the three) — so P, sigma2 and the observation are recomputed
-    // on chip instead of being stored and re-read as seven doubles.  prev_rc[i] gives P and sigma2 of prev point i, curr_rc[j]
-    // the observation; prev_P / prev_s2p / curr_pl are ignored then.
-    const float4* prev_rc;  // [B][max_pts]
-    const float4* curr_rc;  // [B][max_pts]
-    const double* q_tab;    // [STVO_POSE_QTAB] sqrt(sigma2) of pyramid level l (device memory; levels beyond the table are computed)
-    double level_scale;     // orbScaleFactor: sigma2 = 1 / scale^(2 level) (src/stereoFeatures.cpp:41-47)
-    // In-kernel ordering for single-stream operation (pose_inline_sync_ok; the latency kernel only), instead of events between
-    // streams — on this runtime every recorded / awaited event delays the next kernel of its stream by ~6 us:
-    //   wait_flag   the kernel starts by waiting until *wait_flag has reached wait_value (device memory, set by
-    //               launch_stream_signal behind the last kernel of another stream whose results this launch reads);
-    //   fetch_*     the solver wave of workgroup 0 copies fetch_n16 16-byte words (by-products the host wants while this kernel
-    //               runs) to pinned host memory and then publishes fetch_value in *fetch_flag (pinned, system scope).
-    const unsigned* wait_flag;
-    unsigned wait_value;
-    // lazy_eig != 0 (latency kernel only; the caller reads the results through stvo_seq_read): cov_eig is left to the reader, flagged in
-    // stvo_pose_result::path (pose_block.h: PATH_EIG_PENDING)
-    int lazy_eig;
-    // lines_on_solver != 0 (set by launch_pose for the latency kernel; STVO_POSE_LOS=0 clears it): frame pairs with at most 64 LPT
-    // key-lines have them evaluated by the solver wave (pose_kernel.hip)
-    int lines_on_solver;
-    const uint4* fetch_src;
-    uint4* fetch_dst;
-    unsigned fetch_n16;
-    unsigned* fetch_flag;
-    unsigned fetch_value;
-    // start_flag (batch kernel pose2c only; nullptr otherwise): the FIRST workgroup of the launch publishes start_value there when it
-    // starts — the launch is taking its CUs (1024 workgroups are placed within a few microseconds).  seq_pipeline.hip holds the next
+};
+// The stereo point records, [B][max_pts] each, in one of two forms (doubles() / compact() make one and leave the other empty):
+//   doubles   P, sigma2 of prev point i and the observation of curr point j, as the C-ABI's batches hold them;
+//   compact   of the device-resident pipeline (seq_pipeline.hip): a stereo point is {u, v, disparity as floats, pyramid level} —
+//             exactly what the reference's PointFeature is built from (src/stereoFrame.cpp:152-167: float key-point coordinates, a
+//             float difference, backProjection of the three) — so P, sigma2 and the observation are recomputed on chip instead of
+//             being stored and re-read as seven doubles.  prev_rc[i] gives P and sigma2 of prev point i, curr_rc[j] the observation.
+// Half a compact form (prev_rc without curr_rc / q_tab) is STVO_ERR_INVALID_ARG.
+struct PosePoints {
+    const double *prev_P = nullptr, *prev_s2p = nullptr, *curr_pl = nullptr;
+    const float4 *prev_rc = nullptr, *curr_rc = nullptr;
+    const double* q_tab = nullptr;  // [STVO_POSE_QTAB] sqrt(sigma2) of pyramid level l (device memory; levels beyond the table are computed)
+    double level_scale = 0.0;       // orbScaleFactor: sigma2 = 1 / scale^(2 level) (src/stereoFeatures.cpp:41-47)
+    bool is_compact() const { return prev_rc != nullptr; }
+    static PosePoints doubles(const double* prev_P, const double* prev_s2p, const double* curr_pl) {
+        PosePoints r;
+        r.prev_P = prev_P; r.prev_s2p = prev_s2p; r.curr_pl = curr_pl;
+        return r;
+    }
+    static PosePoints compact(const float4* prev_rc, const float4* curr_rc, const double* q_tab, double level_scale) {
+        PosePoints r;
+        r.prev_rc = prev_rc; r.curr_rc = curr_rc; r.q_tab = q_tab; r.level_scale = level_scale;
+        return r;
+    }
+};
+// In-kernel ordering for single-stream operation, instead of events between streams — on this runtime every recorded / awaited event
+// delays the next kernel of its stream by ~6 us.  Every device is absent by default; which of them a launch honours: PoseRoute.
+struct PoseSync {
+    // the kernel starts by waiting until *wait_flag has reached wait_value (device memory, set by launch_stream_signal behind the last
+    // kernel of another stream whose results this launch reads).  PoseRoute::inline_sync, else the launch is refused.
+    const unsigned* wait_flag = nullptr;
+    unsigned wait_value = 0;
+    // the solver wave of workgroup 0 copies fetch_n16 16-byte words (by-products the host wants while this kernel runs) to pinned host
+    // memory and then publishes fetch_value in *fetch_flag (pinned, system scope).  PoseRoute::inline_sync, else the launch is refused.
+    const uint4* fetch_src = nullptr;
+    uint4* fetch_dst = nullptr;
+    unsigned fetch_n16 = 0;
+    unsigned* fetch_flag = nullptr;
+    unsigned fetch_value = 0;
+    // the FIRST workgroup of the launch publishes start_value in *start_flag when it starts — the launch is taking its CUs (1024
+    // workgroups are placed within a few microseconds).  PoseRoute::start_flag, ignored otherwise.  seq_pipeline.hip holds the next
     // step's key-line kernels behind it (launch_stream_gate), so that their workgroups do not take the CUs first.  Not the LAST
     // workgroup: 1024 frame pairs fill every VGPR of the chip (2 waves x 256 registers per SIMD), so the SIMD that hosts the waiting
     // gate wave has room for one pose wave only — the last workgroup could not start before the gate left, and the gate waited for the
     // last workgroup: a circular wait that resolved only when the first frame pair of the launch finished, 160 us later (round 6: every
     // second pipeline of a process ran 0.864 instead of 0.793 ms per step that way, depending on where the gate wave had landed).
-    unsigned* start_flag;
-    unsigned start_value;
+    unsigned* start_flag = nullptr;
+    unsigned start_value = 0;
+    // != 0 (latency kernel only; the caller reads the results through stvo_seq_read): cov_eig is left to the reader, flagged in
+    // stvo_pose_result::path (PATH_EIG_PENDING)
+    int lazy_eig = 0;
 };
-// the batch kernel honours PoseArgs::start_flag for this launch (same selection as launch_pose)
-bool pose_start_flag_ok(const PoseArgs& a);
+struct PoseOptions {  // every default is "none"
+    PoseSync sync;
+    double* eval_out = nullptr;     // [B][44] H(36) g(6) e n: present = ONE optimizeFunctions evaluation at init_T instead of the optimisation
+    int eval_robust = 0;            // != 0: that evaluation is optimizeFunctionsRobust
+    long long* prof_out = nullptr;  // [B][16] phase ticks (tools only)
+};
+// One pose launch on `s`: the route pose_route names.  arena: device memory the batch kernels keep their records in while they run,
+// at least PoseRoute::arena_bytes (STVO_ERR_CAPACITY otherwise) and the caller's until the launch has completed; nothing is allocated here.
+int launch_pose(hipStream_t s, const PoseProblem& p, const PosePoints& r, void* arena, size_t arena_bytes, const PoseOptions& o = PoseOptions());
+// the route of a launch on the current device under the developer switches in force
+inline PoseRoute pose_route(int B, bool compact, bool eval) {
+    const DebugSwitches& sw = dbg();
+    return pose_route(B, compact, eval, pose_takes_batch_kernel(B, eval, sw) ? device_cu_count() : 0, sw);
+}
 // one thread that leaves when *flag has reached value, or after 3000 polls ~0.45 us apart, ~1.3-1.5 ms (a scheduling hint, never a
 // dependence)
 void launch_stream_gate(hipStream_t s, const unsigned* flag, unsigned value);
 constexpr int STVO_POSE_QTAB = 16;
 // internal flag in stvo_pose_result::path (never leaves the library): the eigenvalues of `cov` are still to be computed by the reader
 constexpr int PATH_EIG_PENDING = 1 << 30;
-// may launch_pose honour wait_flag / fetch_* for a batch of B frame pairs?  (few workgroups: the kernels they wait for always find CUs)
-bool pose_inline_sync_ok(int B);
 // *flag = value (release, device scope) once everything enqueued on `s` so far has completed
 void launch_stream_signal(hipStream_t s, unsigned* flag, unsigned value);
-// dispatch: pose_kernel.hip (the latency kernel) up to 256 frame pairs and for single evaluations, pose_kernel2p.hip beyond
-int launch_pose(hipStream_t s, const PoseArgs& a);
-int launch_pose2p(hipStream_t s, const PoseArgs& a);  // pose_kernel2p.hip: thread-private records, four frame pairs per CU
-// the two selections above as launch_pose / launch_pose2p make them, for callers that record the route a launch takes
-// (stvo_seq_last_schedule): does launch_pose hand this launch to launch_pose2p, and with how many waves per frame pair (2 or 4)?
-bool pose_batch_kernel_selected(const PoseArgs& a);
-int pose2p_waves_per_pair(int B);
-// the per-(device, stream) record arena of the batch kernel: every context that holds a stream retains it, the last release frees
-// it (the releasing caller has synchronised the stream and made its device current)
-void pose2p_retain_stream(hipStream_t s);
-void pose2p_release_stream(hipStream_t s);
 
 // ---- 8-bit image operations of the ORB front-end that the line detector reuses (orb_kernels.hip) ----
 // cv::GaussianBlur(7 x 7) in 8-bit fixed point with the integer kernel k7 (weights x 2^8), BORDER_REFLECT_101

@@ -20,7 +20,7 @@ struct PointTail {
     double max_dist_epip, min_disp;
     float4* rc;              // [B][K] out: the stereo point in compact form {u, v, disparity, level} — what PointFeature is built
                              // from (:152-167); P = backProjection(u, v, disparity) and sigma2 = 1 / scale^(2 level) are rebuilt
-                             // where they are used (the pose kernels, kernels.h: PoseArgs::prev_rc), not stored
+                             // where they are used (the pose kernels, kernels.h: PosePoints::compact), not stored
     uint8_t* desc;           // [B][K][32] out: pdesc_l rows
     int32_t* n;              // [B] out: stereo points of the frame
     int32_t* host_n;         // [B] or nullptr: the same count in host-visible memory

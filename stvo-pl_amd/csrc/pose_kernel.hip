@@ -21,7 +21,9 @@
 //     LDS, so the control flow is block-uniform and matches the reference iteration for iteration;
 //     the loops themselves are pose_block.h's optimize_pose_flow, shared with the batch kernels.
 #include <cstdlib>
+#include <cstring>
 
+#include "pose_args.h"
 #include "pose_block.h"
 
 namespace stvo {
@@ -472,7 +474,6 @@ __global__ __launch_bounds__(BLOCK + 64, 2) void pose_kernel(PoseArgs a) {  // 2
 constexpr int POSE_BLOCK_L = 448;
 constexpr int POSE_PPT = (STVO_POSE_MAX_POINTS + POSE_BLOCK_L - 1) / POSE_BLOCK_L;
 constexpr int POSE_LPT = (STVO_POSE_MAX_LINES + POSE_BLOCK_L - 1) / POSE_BLOCK_L;
-constexpr int POSE_LATENCY_MAX_B = 256;
 // dynamic LDS available to the records: 160 KB per CU minus the kernel's static LDS (PoseSh, partial sums, counters)
 constexpr size_t POSE_REC_MAX_BYTES = (size_t)160 * 1024 - 8 * 1024;
 static_assert((size_t)STVO_POSE_MAX_POINTS * 48 + (size_t)STVO_POSE_MAX_LINES * 112 <= POSE_REC_MAX_BYTES,
@@ -498,33 +499,49 @@ void launch_stream_signal(hipStream_t s, unsigned* flag, unsigned value) {
 void launch_stream_gate(hipStream_t s, const unsigned* flag, unsigned value) {
     hipLaunchKernelGGL(stream_gate_kernel, dim3(1), dim3(1), 0, s, flag, value);
 }
-bool pose_batch_kernel_selected(const PoseArgs& a) {  // launch_pose below hands the launch to launch_pose2p
-    const int which = dbg().pose_kernel;
-    return !a.eval_only && (which == 4 || (which != 1 && a.B > POSE_LATENCY_MAX_B));
+// the parts of the host surface (kernels.h) as the kernels' one flat argument
+static PoseArgs flat_pose_args(const PoseProblem& p, const PosePoints& r, const PoseOptions& o) {
+    PoseArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.B = p.B; a.max_pts = p.max_pts; a.max_lines = p.max_lines;
+    a.n_prev_pts = p.n_prev_pts; a.m12p = p.m12p; a.init_inl_p = p.init_inl_p;
+    a.prev_P = r.prev_P; a.prev_s2p = r.prev_s2p; a.curr_pl = r.curr_pl;
+    a.prev_rc = r.prev_rc; a.curr_rc = r.curr_rc; a.q_tab = r.q_tab; a.level_scale = r.level_scale;
+    a.n_prev_lines = p.n_prev_lines; a.prev_sP = p.prev_sP; a.prev_eP = p.prev_eP; a.prev_spl = p.prev_spl; a.prev_epl = p.prev_epl;
+    a.prev_s2l = p.prev_s2l; a.curr_le = p.curr_le; a.m12l = p.m12l; a.init_inl_l = p.init_inl_l;
+    a.init_T = p.init_T; a.next_T = p.next_T; a.cam = p.cam; a.cams = p.cams; a.prm = p.prm;
+    a.results = p.results; a.inl_p_out = p.inl_p_out; a.inl_l_out = p.inl_l_out;
+    a.eval_only = o.eval_out != nullptr; a.eval_robust = o.eval_robust; a.eval_out = o.eval_out; a.prof_out = o.prof_out;
+    const PoseSync& y = o.sync;
+    a.wait_flag = y.wait_flag; a.wait_value = y.wait_value; a.lazy_eig = y.lazy_eig;
+    a.fetch_src = y.fetch_src; a.fetch_dst = y.fetch_dst; a.fetch_n16 = y.fetch_n16; a.fetch_flag = y.fetch_flag; a.fetch_value = y.fetch_value;
+    a.start_flag = y.start_flag; a.start_value = y.start_value;
+    return a;
 }
-bool pose_start_flag_ok(const PoseArgs& a) {  // launch_pose below takes the batch kernel on compact records (pose2c_kernel)
-    return a.B > 0 && a.prev_rc != nullptr && pose_batch_kernel_selected(a);
-}
-bool pose_inline_sync_ok(int B) { return B >= 1 && B <= 16 && dbg().pose_kernel != 4; }
 
-int launch_pose(hipStream_t s, const PoseArgs& a) {
-    if (a.B <= 0) return STVO_OK;
-    if ((a.wait_flag || a.fetch_dst) && !pose_inline_sync_ok(a.B)) return STVO_ERR_INVALID_ARG;
+int launch_pose(hipStream_t s, const PoseProblem& p, const PosePoints& r, void* arena, size_t arena_bytes, const PoseOptions& o) {
+    if (p.B <= 0) return STVO_OK;
+    const PoseRoute route = pose_route(p.B, r.is_compact(), o.eval_out != nullptr);
+    if ((o.sync.wait_flag || o.sync.fetch_dst) && !route.inline_sync) return STVO_ERR_INVALID_ARG;
+    if (p.max_pts > STVO_POSE_MAX_POINTS || p.max_lines > STVO_POSE_MAX_LINES) return STVO_ERR_CAPACITY;
+    PoseArgs a = flat_pose_args(p, r, o);
     // Two formulations (round 4: the 128-VGPR / compacted-LDS kernel of round 2 and the owner + evaluator experiment of round 3
     // are gone — both measured slower than what is here, NOTES.md):
     //   * up to 256 frame pairs, and for single evaluations (stvo_normal_eq): this file's kernel — one workgroup per CU,
     //     seven worker waves + a solver wave, every record resident in LDS (121 us for one pair);
     //   * larger batches: pose_kernel2p.hip — thread-private records, two waves per pair at 256 VGPRs, four pairs per CU.
     // STVO_POSE_KERNEL = 1 / 4 (debug_switches.h) force either for every batch size: the parity tests run both everywhere.
-    if (pose_batch_kernel_selected(a)) return launch_pose2p(s, a);
-    if (a.max_pts > STVO_POSE_MAX_POINTS || a.max_lines > STVO_POSE_MAX_LINES) return STVO_ERR_CAPACITY;
+    if (route.batch) {
+        if (r.prev_rc && (!r.curr_rc || !r.q_tab)) return STVO_ERR_INVALID_ARG;
+        if (!arena || arena_bytes < route.arena_bytes) return STVO_ERR_CAPACITY;
+        return launch_pose2p(s, a, route.waves, static_cast<double2*>(arena));
+    }
     // more than the default 64 KB of dynamic LDS needs an explicit opt-in (done once)
     const void* kfn = reinterpret_cast<const void*>(&pose_kernel<POSE_BLOCK_L, POSE_PPT, POSE_LPT>);
     if (!lds_opt_in(kfn, (int)POSE_REC_MAX_BYTES)) return STVO_ERR_CAPACITY;
-    PoseArgs args = a;
-    args.lines_on_solver = dbg().pose_los != 0 ? 1 : 0;
-    const size_t rec_bytes = ((size_t)a.max_pts * 6 + (size_t)a.max_lines * 14) * sizeof(double);
-    hipLaunchKernelGGL((pose_kernel<POSE_BLOCK_L, POSE_PPT, POSE_LPT>), dim3(a.B), dim3(POSE_BLOCK_L + 64), rec_bytes, s, args);
+    a.lines_on_solver = dbg().pose_los != 0 ? 1 : 0;
+    const size_t rec_bytes = ((size_t)p.max_pts * 6 + (size_t)p.max_lines * 14) * sizeof(double);
+    hipLaunchKernelGGL((pose_kernel<POSE_BLOCK_L, POSE_PPT, POSE_LPT>), dim3(p.B), dim3(POSE_BLOCK_L + 64), rec_bytes, s, a);
     return STVO_OK;
 }
 

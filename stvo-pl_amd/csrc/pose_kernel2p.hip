@@ -7,7 +7,7 @@
 // its matched records 0, 1, ... in that order (the ORDINAL); record r of thread t lives in LDS planes [r][part][t] — 16-byte
 // parts of neighbouring threads are neighbours: conflict-free wide accesses, no cross-thread compaction, no barrier between
 // staging and use.  Two kernels, both on the state machine of pose_block.h (optimize_pose_flow):
-//   * pose2c_kernel (round 4) — COMPACT records, the device-resident pipeline's format (kernels.h: PoseArgs::prev_rc): a stereo
+//   * pose2c_kernel (round 4) — COMPACT records, the device-resident pipeline's format (kernels.h: PosePoints::compact): a stereo
 //     point is {u, v, disparity, level}; the LDS record is {u, v, ox, oy} as floats + b / disparity as a double = 24 bytes, P is
 //     rebuilt with 2 subtractions + 3 products per use and sqrt(sigma2) comes from a 16-entry table.  TWELVE ordinals fit the
 //     40 KB share (one more stays in registers): every record of the bench shape (~11.6 per thread) is on chip, nothing is
@@ -17,13 +17,11 @@
 //     plane layout, read with a three-deep register ring.
 // Key-lines (~75 per pair, at most one per thread in practice) live in the arena in both.  Same arithmetic and association
 // order in both (a thread accumulates its records in ascending ordinal), so the results agree bit for bit.
+// The arena is the caller's (launch_pose hands it in; a context owns one block per stream it launches on, ctx_internal.h); what a
+// launch needs of it is stated in pose_scratch.h.  Nothing is allocated here.
 #include <cstdlib>
 
-#include <map>
-#include <mutex>
-#include <utility>
-#include <vector>
-
+#include "pose_args.h"
 #include "pose_block.h"
 
 namespace stvo {
@@ -998,42 +996,17 @@ __global__ __launch_bounds__(NW * 64, 2) void pose2c_kernel(PoseArgs a_by_value,
     }
 }
 
-struct ArenaBuf {
-    double2* dev = nullptr;
-    size_t bytes = 0;
-    int users = 0;               // contexts that hold the stream (pose2p_retain_stream); the buffer goes with the last one
-    std::vector<void*> retired;  // superseded blocks: kept until the stream is released (a captured step graph may hold the address)
-};
-
-std::mutex g_arena_mu;
-std::map<std::pair<int, hipStream_t>, ArenaBuf> g_arenas;
-
-// the record arena of a (device, stream): grown on demand, never shrunk; the last pose2p_release_stream frees it.  Returns the
-// block itself (read under the lock): callers never hold a pointer into the map.
-double2* arena_ptr(hipStream_t s, size_t bytes) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(g_arena_mu);
-    ArenaBuf& b = g_arenas[std::make_pair(dev, s)];
-    if (b.bytes < bytes || !b.dev) {
-        if (b.dev) b.retired.push_back(b.dev);
-        b.dev = nullptr;
-        b.bytes = 0;
-        if (hipMalloc((void**)&b.dev, bytes > 256 ? bytes : 256) != hipSuccess) return nullptr;
-        b.bytes = bytes;
-    }
-    return b.dev;
-}
-
 template <int NW>
 constexpr int pose2p_static_lds() {
     return (int)(sizeof(PoseSh) + NW * 28 * 8 + NW * 4 + 2 * 260 * 4);
 }
 
 template <int NW>
-int launch_pose2p_variant(hipStream_t s, const PoseArgs& a, int wgs_per_cu) {
+int launch_pose2p_variant(hipStream_t s, const PoseArgs& a, int wgs_per_cu, double2* arena) {
     constexpr int BLOCK = NW * 64;
     constexpr int PPT = (STVO_POSE_MAX_POINTS + BLOCK - 1) / BLOCK, LPT = (STVO_POSE_MAX_LINES + BLOCK - 1) / BLOCK;
+    constexpr size_t pair_d2 = pose_arena_pair_words(false);
+    static_assert(pair_d2 == (size_t)(PPT * 3 + LPT * 7) * BLOCK, "the arena holds every ordinal of every thread");
     // LDS planes: as many record ordinals per thread as the workgroup's share of the CU's 160 KB holds (a plane of one ordinal
     // is BLOCK x 48 bytes)
     const int share = (160 * 1024) / wgs_per_cu - pose2p_static_lds<NW>();
@@ -1043,73 +1016,35 @@ int launch_pose2p_variant(hipStream_t s, const PoseArgs& a, int wgs_per_cu) {
     const bool prof = a.prof_out != nullptr;
     const void* kfn = prof ? reinterpret_cast<const void*>(&pose2p_kernel<NW, true>) : reinterpret_cast<const void*>(&pose2p_kernel<NW, false>);
     if (lds > 48 * 1024 && !lds_opt_in(kfn, lds)) return STVO_ERR_CAPACITY;
-    const size_t pair_d2 = (size_t)(PPT * 3 + LPT * 7) * BLOCK;
-    double2* ab = arena_ptr(s, (size_t)a.B * pair_d2 * sizeof(double2));
-    if (!ab) return STVO_ERR_HIP;
-    if (prof) hipLaunchKernelGGL((pose2p_kernel<NW, true>), dim3(a.B), dim3(BLOCK), (size_t)lds, s, a, k_lds, ab, pair_d2);
-    else hipLaunchKernelGGL((pose2p_kernel<NW, false>), dim3(a.B), dim3(BLOCK), (size_t)lds, s, a, k_lds, ab, pair_d2);
+    if (prof) hipLaunchKernelGGL((pose2p_kernel<NW, true>), dim3(a.B), dim3(BLOCK), (size_t)lds, s, a, k_lds, arena, pair_d2);
+    else hipLaunchKernelGGL((pose2p_kernel<NW, false>), dim3(a.B), dim3(BLOCK), (size_t)lds, s, a, k_lds, arena, pair_d2);
     return STVO_OK;
 }
 
 // the compact-record kernel: KL planes of BLOCK x 24 bytes; the arena holds the key-lines only
 template <int NW>
-int launch_pose2c_variant(hipStream_t s, const PoseArgs& a, int wgs_per_cu) {
+int launch_pose2c_variant(hipStream_t s, const PoseArgs& a, double2* arena) {
     constexpr int BLOCK = NW * 64;
     constexpr int LPT = (STVO_POSE_MAX_LINES + BLOCK - 1) / BLOCK;
     constexpr int lds = pose2c_planes<NW>() * BLOCK * 24;
     static_assert(lds + pose2p_static_lds<NW>() <= (160 * 1024) / (NW == 2 ? 4 : 2), "the planes must leave room for the co-resident pairs");
-    (void)wgs_per_cu;
+    constexpr size_t pair_d2 = pose_arena_pair_words(true);
+    static_assert(pair_d2 == (size_t)(LPT * 7) * BLOCK, "the arena holds every key-line ordinal of every thread");
     const bool prof = a.prof_out != nullptr;
     const void* kfn = prof ? reinterpret_cast<const void*>(&pose2c_kernel<NW, true>) : reinterpret_cast<const void*>(&pose2c_kernel<NW, false>);
     if (lds > 48 * 1024 && !lds_opt_in(kfn, lds)) return STVO_ERR_CAPACITY;
-    const size_t pair_d2 = (size_t)(LPT * 7) * BLOCK;
-    double2* ab = arena_ptr(s, (size_t)a.B * pair_d2 * sizeof(double2));
-    if (!ab) return STVO_ERR_HIP;
-    if (prof) hipLaunchKernelGGL((pose2c_kernel<NW, true>), dim3(a.B), dim3(BLOCK), (size_t)lds, s, a, ab, pair_d2);
-    else hipLaunchKernelGGL((pose2c_kernel<NW, false>), dim3(a.B), dim3(BLOCK), (size_t)lds, s, a, ab, pair_d2);
+    if (prof) hipLaunchKernelGGL((pose2c_kernel<NW, true>), dim3(a.B), dim3(BLOCK), (size_t)lds, s, a, arena, pair_d2);
+    else hipLaunchKernelGGL((pose2c_kernel<NW, false>), dim3(a.B), dim3(BLOCK), (size_t)lds, s, a, arena, pair_d2);
     return STVO_OK;
 }
 
 }  // namespace
 
-// A context that adopts a stream (its own, a borrowed one, the NULL stream) retains the stream's arena and releases it when it
-// lets go; the blocks are freed with the LAST holder, so contexts that share a user stream (bench.py: torch's current stream) do
-// not free each other's scratch.  The releasing caller has synchronised the stream and made its device current.
-void pose2p_retain_stream(hipStream_t s) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return;
-    std::lock_guard<std::mutex> lk(g_arena_mu);
-    ++g_arenas[std::make_pair(dev, s)].users;
-}
-
-void pose2p_release_stream(hipStream_t s) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return;
-    std::lock_guard<std::mutex> lk(g_arena_mu);
-    const auto it = g_arenas.find(std::make_pair(dev, s));
-    if (it == g_arenas.end()) return;
-    if (--it->second.users > 0) return;
-    if (it->second.dev) (void)hipFree(it->second.dev);
-    for (void* p : it->second.retired) (void)hipFree(p);
-    g_arenas.erase(it);
-}
-
-// waves per frame pair: two (four pairs per CU) once the batch holds more than two pairs per CU, four (two pairs per CU,
-// half as many records per thread) below that — with 512 pairs on 256 CUs the two-wave variant leaves half of every CU's
-// wave slots empty (configs[3] leg, 512 streams: 701 k vs 774 k frame pairs/s).  STVO_POSE2P_NW overrides (developer).
-int pose2p_waves_per_pair(int B) {
-    const int nw = dbg().pose2p_nw != DBG_UNSET && dbg().pose2p_nw > 0 ? dbg().pose2p_nw : (B > 2 * device_cu_count() ? 2 : 4);
-    return nw >= 4 ? 4 : 2;
-}
-
-int launch_pose2p(hipStream_t s, const PoseArgs& a) {
-    if (a.B <= 0) return STVO_OK;
-    if (a.eval_only) return STVO_ERR_INVALID_ARG;  // single evaluations belong to the latency kernel (launch_pose)
-    if (a.max_pts > STVO_POSE_MAX_POINTS || a.max_lines > STVO_POSE_MAX_LINES) return STVO_ERR_CAPACITY;
-    if (a.prev_rc && (!a.curr_rc || !a.q_tab)) return STVO_ERR_INVALID_ARG;
-    const int nw = pose2p_waves_per_pair(a.B);
-    if (a.prev_rc) return nw == 4 ? launch_pose2c_variant<4>(s, a, 2) : launch_pose2c_variant<2>(s, a, 4);
-    return nw == 4 ? launch_pose2p_variant<4>(s, a, 2) : launch_pose2p_variant<2>(s, a, 4);
+// launch_pose's batch route (it has checked the problem's capacity and the record form): two waves per pair share a CU among four
+// pairs, four waves among two
+int launch_pose2p(hipStream_t s, const PoseArgs& a, int waves, double2* arena) {
+    if (a.prev_rc) return waves == 4 ? launch_pose2c_variant<4>(s, a, arena) : launch_pose2c_variant<2>(s, a, arena);
+    return waves == 4 ? launch_pose2p_variant<4>(s, a, 2, arena) : launch_pose2p_variant<2>(s, a, 4, arena);
 }
 
 }  // namespace stvo

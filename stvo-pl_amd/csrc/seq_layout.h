@@ -73,7 +73,7 @@ inline StereoSetPtrs carve_stereo_set(Carver& c, int B, int K, int M, bool with_
 
 // ---- the fetch block: the by-products a caller may want on the host (stvo_seq_enable_fetch) -----------------------------------------
 // Six device arrays cut back to back, so that one pinned block mirrors them at the same offsets: [m12s_p | m12s_l | m12p | m12l] leaves
-// behind the f2f stage in one copy, [inlp | inll] behind the pose kernel in another, and a flag word follows (PoseArgs::fetch_flag).
+// behind the f2f stage in one copy, [inlp | inll] behind the pose kernel in another, and a flag word follows (PoseSync::fetch_flag).
 struct FetchBlock {
     int32_t *m12s_p, *m12s_l;  // [B][K] / [B][M] stereo matches of the left features
     int32_t *m12p, *m12l;      // f2f matches of the previous stereo features

@@ -406,13 +406,9 @@ void gather_step_facts(const stvo_seq* s, int slot, const stvo::StepFlags& fl, b
     f.grid_points_fused_ok = f.has_points && stvo::grid_points_fused_ok(g);
     if (f.track) {
         f.match_small_ok_K = stvo::match_small_ok(f.K); f.match_small_ok_M = stvo::match_small_ok(f.M);
-        f.pose_inline_sync_ok = stvo::pose_inline_sync_ok(f.B);
-        stvo::PoseArgs a{};  // what the two questions about the pose launch read of its arguments
-        std::memset(&a, 0, sizeof(a));
-        a.B = f.B; a.prev_rc = s->set[s->prev_set()].rc;
-        f.pose_batch_kernel_selected = stvo::pose_batch_kernel_selected(a);
-        f.pose_start_flag_ok = stvo::pose_start_flag_ok(a);
-        f.pose2p_waves_per_pair = f.pose_batch_kernel_selected ? stvo::pose2p_waves_per_pair(f.B) : 0;
+        const stvo::PoseRoute r = stvo::pose_route(f.B, s->set[s->prev_set()].rc != nullptr, false);  // as StepEnq::pose launches it
+        f.pose_inline_sync_ok = r.inline_sync; f.pose_batch_kernel_selected = r.batch; f.pose_start_flag_ok = r.start_flag;
+        f.pose2p_waves_per_pair = r.waves;
     }
     f.sw = stvo::dbg();
 }
@@ -520,11 +516,12 @@ int StepEnq::f2f_and_join() const {
 // ---- optimizePose
 int StepEnq::pose(StepPub& pub) const {
     const int B = s->B;
-    stvo::PoseArgs a{};
-    std::memset(&a, 0, sizeof(a));
+    stvo::PoseProblem a{};
     a.B = B; a.max_pts = s->K; a.max_lines = s->M;
     a.n_prev_pts = s->op.has_points ? ps.n : nullptr;
-    a.prev_rc = ps.rc; a.curr_rc = cs.rc; a.q_tab = s->d_qtab; a.level_scale = s->mp.orb_scale_factor; a.m12p = s->fb.m12p;
+    a.m12p = s->fb.m12p;
+    const stvo::PosePoints pts = stvo::PosePoints::compact(ps.rc, cs.rc, s->d_qtab, s->mp.orb_scale_factor);
+    stvo::PoseOptions o;
     a.n_prev_lines = s->op.has_lines ? ps.nl : nullptr;
     a.prev_sP = ps.sP; a.prev_eP = ps.eP; a.prev_spl = ps.spl; a.prev_epl = ps.epl; a.prev_s2l = ps.s2lm;
     a.curr_le = cs.le; a.m12l = m12l_use;
@@ -535,26 +532,27 @@ int StepEnq::pose(StepPub& pub) const {
     a.inl_l_out = p.inl_zero_copy ? s->fetch_mirror(s->fb.off_inll) : s->fb.inll;
     if (stvo::dbg().pose_prof != stvo::DBG_UNSET) {  // (a developer's buffer, not a schedule)
         if (!s->d_prof) HIP_TRY(ctx, hipMalloc((void**)&s->d_prof, (size_t)B * 16 * sizeof(long long)));
-        a.prof_out = s->d_prof;
+        o.prof_out = s->d_prof;
     }
+    stvo::PoseSync& y = o.sync;
     if (p.join_signal) {
-        a.wait_flag = s->d_join_flag;
-        a.wait_value = s->join_epoch;
+        y.wait_flag = s->d_join_flag;
+        y.wait_value = s->join_epoch;
     }
-    a.lazy_eig = p.lazy_eig ? 1 : 0;
+    y.lazy_eig = p.lazy_eig ? 1 : 0;
     if (p.fetch_by_pose) {
-        a.fetch_src = reinterpret_cast<const uint4*>(s->fb.m12s_p);
-        a.fetch_dst = reinterpret_cast<uint4*>(s->fetch_host);
-        a.fetch_n16 = (unsigned)(s->fb.m12_span() / 16);
-        a.fetch_flag = s->fetch_flag();
-        a.fetch_value = pub.fetch_value = ++s->fetch_epoch;
+        y.fetch_src = reinterpret_cast<const uint4*>(s->fb.m12s_p);
+        y.fetch_dst = reinterpret_cast<uint4*>(s->fetch_host);
+        y.fetch_n16 = (unsigned)(s->fb.m12_span() / 16);
+        y.fetch_flag = s->fetch_flag();
+        y.fetch_value = pub.fetch_value = ++s->fetch_epoch;
     }
     if (p.pose_flagged) {
-        a.start_flag = s->d_pose_flag;
-        a.start_value = pub.pose_flag_value = ++s->pose_epoch;
+        y.start_flag = s->d_pose_flag;
+        y.start_value = pub.pose_flag_value = ++s->pose_epoch;
     }
     mark(8, st);
-    TRY(stvo::launch_pose(st, a));
+    TRY(launch_pose_ctx(ctx, st, a, pts, o));
     mark(9, st);
     // the one place the results are written: behind it, the streams that restart or are parked read as "no pose in this step"
     if (ctl)
@@ -667,7 +665,7 @@ int stvo_seq_step_dev(stvo_seq* s, int slot) {
         s->ctl_staged = false;
         s->ctl_next ^= 1;
     }
-    if (s->d_traj_state && fl.track) {  // the trajectory behind the pose kernel, reading the results where PoseArgs::results pointed
+    if (s->d_traj_state && fl.track) {  // the trajectory behind the pose kernel, reading the results where PoseProblem::results pointed
         // (the step above is committed: a launch that fails here returns its error from a step that counts as taken, ring row included)
         stvo::launch_traj_update(ctx->stream, s->B, s->step_results(), s->traj_prm, s->d_traj_state,
                                  s->d_traj_ring + (size_t)(s->traj_steps % (unsigned long long)s->traj_log_steps) * s->B, fl.ctl);
@@ -715,7 +713,7 @@ int stvo_seq_read(stvo_seq* s, stvo_pose_result* results, int32_t* counts) {
         if (results) {
             if (track) {
                 results[b] = hr[b];
-                if (results[b].path & stvo::PATH_EIG_PENDING) {  // PoseArgs::lazy_eig: SelfAdjointEigenSolver(DT_cov).eigenvalues(), :379-380
+                if (results[b].path & stvo::PATH_EIG_PENDING) {  // PoseSync::lazy_eig: SelfAdjointEigenSolver(DT_cov).eigenvalues(), :379-380
                     pm::eig6_ql(results[b].cov, results[b].cov_eig);
                     results[b].path &= ~stvo::PATH_EIG_PENDING;
                 }

@@ -72,7 +72,7 @@ struct stvo_seq {
     double ratio_grid = 0;         // Config::minRatio12P() as the DOUBLE matchGrid compares with (matching.cpp:160,241)
     stvo_cam* d_cams = nullptr;    // [B] per-sequence calibration (device)
     double* d_inv_wh = nullptr;    // [B][2] per-sequence grid scale (device)
-    double* d_qtab = nullptr;      // [STVO_POSE_QTAB] sqrt(sigma2) of pyramid level l (kernels.h: PoseArgs::q_tab)
+    double* d_qtab = nullptr;      // [STVO_POSE_QTAB] sqrt(sigma2) of pyramid level l (kernels.h: PosePoints::q_tab)
     double* d_motion_T = nullptr;  // [B][16] use_motion_model: the next step's initial DT per sequence, written by the pose kernel's commit (stvo_seq_set_motion_model)
     // trajectory and key-frame decision per stream (stvo_seq_set_trajectory): null = off
     stvo_traj_state* d_traj_state = nullptr;   // [B]
@@ -151,7 +151,7 @@ struct stvo_seq {
     // part of the block ON the line stream and the step forks without an event; st_dirty = something the line stream would have to
     // wait for has been enqueued on the point stream since the last synchronisation.
     bool st_dirty = false;
-    // ordering inside the pose kernel instead of events (kernels.h: PoseArgs::wait_flag / fetch_*), small batches only
+    // ordering inside the pose kernel instead of events (kernels.h: PoseSync::wait_flag / fetch_*), small batches only
     unsigned* d_join_flag = nullptr;     // device word the line stream's last launch of a step is followed by a signal on
     unsigned join_epoch = 0;
     unsigned fetch_epoch = 0;            // the last value handed to a pose kernel to publish in the pinned flag once the match indices are in fetch_host
@@ -179,7 +179,7 @@ struct stvo_seq {
     // optimizePose(k - 1), the last reader of the line set and of the key-line match indices step k + 1 overwrites (three sets; odd steps
     // write the second copy m12l_alt) — and passes a gate that opens when optimizePose(k) has been dispatched: the small workgroups then
     // fill the slots that kernel's one residency round frees as its frame pairs finish, instead of sharing the issue ports with the forward
-    // scan K1m(k + 1), which they stretched by ~40 us per step.  The gate (launch_stream_gate) waits for PoseArgs::start_flag (kernels.h
+    // scan K1m(k + 1), which they stretched by ~40 us per step.  The gate (launch_stream_gate) waits for PoseSync::start_flag (kernels.h
     // says why not "has been dispatched completely"): bounded, a hint — every data dependence is carried by the events.  The point stream
     // needs no second copy of its match indices: the point f2f of step k + 1 follows optimizePose(k) in stream order.
     int32_t* m12l_alt = nullptr;  // batches only
@@ -240,7 +240,7 @@ struct stvo_seq {
     int32_t* fetch_mirror(size_t off) const { return reinterpret_cast<int32_t*>(fetch_host + off); }
     unsigned* fetch_flag() const { return reinterpret_cast<unsigned*>(fetch_host + fb.off_flag); }
     stvo::RawFrameView raw_view(int slot) const { return stvo::raw_frame<true>(raw_dev[slot], B, K, M); }  // what the kernels of a step read (SeqDev::raw)
-    // where a step's pose kernel writes its results (PoseArgs::results) and the readers behind it find them
+    // where a step's pose kernel writes its results (PoseProblem::results) and the readers behind it find them
     stvo_pose_result* step_results() const { return zero_copy ? reinterpret_cast<stvo_pose_result*>(out_host) : results; }
 };
 

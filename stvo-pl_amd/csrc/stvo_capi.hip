@@ -95,10 +95,6 @@ int stvo_ctx_create(int device_id, int max_rows, int max_batch, stvo_ctx** out) 
     bool ok = hip_ok(ctx, hipSetDevice(device_id), "hipSetDevice") &&
               hip_ok(ctx, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking), "hipStreamCreate");
     ctx->own_stream = ok;
-    if (ok) {
-        stvo::pose2p_retain_stream(ctx->stream);
-        ctx->stream_retained = true;
-    }
     const size_t knn_elems = (size_t)max_rows * (size_t)max_batch;
     // [nseg][B][rows] with nseg = 2 for full batches, up to KNN_MAX_NSEG for a single problem (knn_pick_nseg)
     const size_t knn_seg_elems =
@@ -137,14 +133,14 @@ int stvo_ctx_destroy(stvo_ctx* ctx) {
     if (ctx->arena_host) (void)hipHostFree(ctx->arena_host);
     if (ctx->probe_sink) (void)hipFree(ctx->probe_sink);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
-    if (ctx->stream_retained) stvo::pose2p_release_stream(ctx->stream);
     if (ctx->aux_stream) {
         (void)hipStreamSynchronize(ctx->aux_stream);
-        stvo::pose2p_release_stream(ctx->aux_stream);
         (void)hipStreamDestroy(ctx->aux_stream);
         (void)hipEventDestroy(ctx->ev_match_done);
         (void)hipEventDestroy(ctx->ev_pose_done);
     }
+    if (ctx->pose_arena.p) (void)hipFree(ctx->pose_arena.p);  // (behind the synchronisation of both streams)
+    if (ctx->pose_arena_aux.p) (void)hipFree(ctx->pose_arena_aux.p);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return STVO_OK;
@@ -154,12 +150,9 @@ int stvo_ctx_set_stream(stvo_ctx* ctx, void* hip_stream) {
     if (!ctx) return STVO_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->stream_retained) stvo::pose2p_release_stream(ctx->stream);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     ctx->own_stream = false;
-    ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);  // may be the NULL stream
-    stvo::pose2p_retain_stream(ctx->stream);
-    ctx->stream_retained = true;
+    ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);  // may be the NULL stream; the pose arena stays: it is the context's
     return STVO_OK;
 }
 
@@ -187,7 +180,6 @@ int stvo_ctx_set_overlap(stvo_ctx* ctx, int enable) {
         ctx->ev_match_done = em;
         ctx->ev_pose_done = ep;
         ctx->aux_stream = as;
-        stvo::pose2p_retain_stream(as);
     }
     if (!enable && ctx->aux_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->aux_stream));
     ctx->overlap = enable ? 1 : 0;
@@ -248,37 +240,34 @@ int stvo_match_nnr_mutual_batched_dev(stvo_ctx* ctx, int B, int row_stride, cons
 namespace {
 
 // stage a stvo_matched (host) into the arena as a B = 1 records-mode problem
-int stage_records(stvo_ctx* ctx, const stvo_matched* m, const double* T, stvo::PoseArgs* a, int32_t** d_inl_p,
-                  int32_t** d_inl_l) {
-    std::memset(a, 0, sizeof(*a));
+int stage_records(stvo_ctx* ctx, const stvo_matched* m, const double* T, const stvo_cam* cam, const stvo_opt_params* prm,
+                  stvo::PoseProblem* a, stvo::PosePoints* pts) {
+    *a = stvo::PoseProblem{};
     if (m->np < 0 || m->nl < 0) return STVO_ERR_INVALID_ARG;
     if (m->np > STVO_POSE_MAX_POINTS || m->nl > STVO_POSE_MAX_LINES) return STVO_ERR_CAPACITY;
     a->B = 1;
     a->max_pts = m->np > 0 ? m->np : 1;
     a->max_lines = m->nl;
     double *P, *obs, *s2p, *sP, *eP, *le, *spl, *epl, *s2l, *dT;
-    int32_t *dnp, *dnl;
+    int32_t *dnp, *dnl, *dip, *dil;
     TRY(upload(ctx, &P, m->P, (size_t)m->np * 3));
     TRY(upload(ctx, &obs, m->pl_obs, (size_t)m->np * 2));
     TRY(upload(ctx, &s2p, m->sigma2p, (size_t)m->np));
-    TRY(upload(ctx, d_inl_p, (const int32_t*)m->inlier_p, (size_t)m->np));
+    TRY(upload(ctx, &dip, (const int32_t*)m->inlier_p, (size_t)m->np));
     TRY(upload(ctx, &sP, m->sP, (size_t)m->nl * 3));
     TRY(upload(ctx, &eP, m->eP, (size_t)m->nl * 3));
     TRY(upload(ctx, &le, m->le_obs, (size_t)m->nl * 3));
     TRY(upload(ctx, &spl, m->spl, (size_t)m->nl * 2));
     TRY(upload(ctx, &epl, m->epl, (size_t)m->nl * 2));
     TRY(upload(ctx, &s2l, m->sigma2l, (size_t)m->nl));
-    TRY(upload(ctx, d_inl_l, (const int32_t*)m->inlier_l, (size_t)m->nl));
+    TRY(upload(ctx, &dil, (const int32_t*)m->inlier_l, (size_t)m->nl));
     TRY(upload(ctx, &dnp, &m->np, 1));
     TRY(upload(ctx, &dnl, &m->nl, 1));
     TRY(upload(ctx, &dT, T, 16));
     TRY(flush_uploads(ctx));
+    *pts = stvo::PosePoints::doubles(P, s2p, obs);
     a->n_prev_pts = dnp;
-    a->prev_P = P;
-    a->prev_s2p = s2p;
-    a->curr_pl = obs;
-    a->m12p = nullptr;
-    a->init_inl_p = *d_inl_p;
+    a->init_inl_p = dip;
     a->n_prev_lines = dnl;
     a->prev_sP = sP;
     a->prev_eP = eP;
@@ -286,9 +275,10 @@ int stage_records(stvo_ctx* ctx, const stvo_matched* m, const double* T, stvo::P
     a->prev_epl = epl;
     a->prev_s2l = s2l;
     a->curr_le = le;
-    a->m12l = nullptr;
-    a->init_inl_l = *d_inl_l;
+    a->init_inl_l = dil;
     a->init_T = dT;
+    a->cam = *cam;
+    a->prm = *prm;
     return STVO_OK;
 }
 
@@ -300,17 +290,15 @@ int stvo_normal_eq(stvo_ctx* ctx, const double T[16], const stvo_cam* cam, const
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->arena_off = 0;
     ctx->upload_hi = 0;
-    stvo::PoseArgs a{};
-    int32_t *dip, *dil;
-    TRY(stage_records(ctx, m, T, &a, &dip, &dil));
-    a.cam = *cam;
-    a.prm = *params;
+    stvo::PoseProblem a;
+    stvo::PosePoints pts;
+    TRY(stage_records(ctx, m, T, cam, params, &a, &pts));
     double* dout = arena_alloc<double>(ctx, 44);
     if (!dout) return STVO_ERR_CAPACITY;
-    a.eval_only = 1;
-    a.eval_robust = robust;
-    a.eval_out = dout;
-    TRY(stvo::launch_pose(ctx->stream, a));
+    stvo::PoseOptions o;
+    o.eval_out = dout;
+    o.eval_robust = robust;
+    TRY(launch_pose_ctx(ctx, ctx->stream, a, pts, o));
     TRY(check_launch(ctx));
     TRY(download_begin(ctx, dout, 44 * sizeof(double)));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -331,11 +319,9 @@ int stvo_optimize_pose(stvo_ctx* ctx, const double init_T[16], const stvo_cam* c
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->arena_off = 0;
     ctx->upload_hi = 0;
-    stvo::PoseArgs a{};
-    int32_t *dip, *dil;
-    TRY(stage_records(ctx, m, init_T, &a, &dip, &dil));
-    a.cam = *cam;
-    a.prm = *params;
+    stvo::PoseProblem a;
+    stvo::PosePoints pts;
+    TRY(stage_records(ctx, m, init_T, cam, params, &a, &pts));
     stvo_pose_result* dres = arena_alloc<stvo_pose_result>(ctx, 1);
     int32_t* dop = arena_alloc<int32_t>(ctx, (size_t)a.max_pts);
     int32_t* dol = arena_alloc<int32_t>(ctx, (size_t)(a.max_lines > 0 ? a.max_lines : 1));
@@ -343,7 +329,7 @@ int stvo_optimize_pose(stvo_ctx* ctx, const double init_T[16], const stvo_cam* c
     a.results = dres;
     a.inl_p_out = dop;
     a.inl_l_out = dol;
-    TRY(stvo::launch_pose(ctx->stream, a));
+    TRY(launch_pose_ctx(ctx, ctx->stream, a, pts));
     TRY(check_launch(ctx));
     TRY(download_begin(ctx, dres, sizeof(*out)));
     if (m->np) TRY(download_begin(ctx, dop, (size_t)m->np * 4));
@@ -362,33 +348,31 @@ namespace {
 
 constexpr int kOverlapLdsPad = 26 * 1024;  // 6 matching workgroups (24 waves) per CU instead of 8
 
-int fill_pose_args(const stvo_track_batch_dev* b, const stvo_cam* cam, const stvo_opt_params* prm, bool identity,
-                   stvo::PoseArgs* a) {
-    std::memset(a, 0, sizeof(*a));
-    a->B = b->B;
-    a->max_pts = b->max_pts;
-    a->max_lines = b->max_lines;
-    a->n_prev_pts = b->n_prev_pts;
-    a->prev_P = b->prev_P;
-    a->prev_s2p = b->prev_sigma2p;
-    a->curr_pl = b->curr_pl;
-    a->m12p = identity ? nullptr : b->m12_pts;
-    a->n_prev_lines = b->max_lines > 0 ? b->n_prev_lines : nullptr;
-    a->prev_sP = b->prev_sP;
-    a->prev_eP = b->prev_eP;
-    a->prev_spl = b->prev_spl;
-    a->prev_epl = b->prev_epl;
-    a->prev_s2l = b->prev_sigma2l;
-    a->curr_le = b->curr_le;
-    a->m12l = identity ? nullptr : b->m12_lines;
-    a->init_T = b->init_T;
-    a->cam = *cam;
-    a->prm = *prm;
-    a->results = b->results;
-    a->inl_p_out = b->inlier_pts;
-    a->inl_l_out = b->inlier_lines;
-    return STVO_OK;
+// the pose problem of a device batch; its stereo points: batch_points
+stvo::PoseProblem batch_problem(const stvo_track_batch_dev* b, const stvo_cam* cam, const stvo_opt_params* prm, bool identity) {
+    stvo::PoseProblem a{};
+    a.B = b->B;
+    a.max_pts = b->max_pts;
+    a.max_lines = b->max_lines;
+    a.n_prev_pts = b->n_prev_pts;
+    a.m12p = identity ? nullptr : b->m12_pts;
+    a.n_prev_lines = b->max_lines > 0 ? b->n_prev_lines : nullptr;
+    a.prev_sP = b->prev_sP;
+    a.prev_eP = b->prev_eP;
+    a.prev_spl = b->prev_spl;
+    a.prev_epl = b->prev_epl;
+    a.prev_s2l = b->prev_sigma2l;
+    a.curr_le = b->curr_le;
+    a.m12l = identity ? nullptr : b->m12_lines;
+    a.init_T = b->init_T;
+    a.cam = *cam;
+    a.prm = *prm;
+    a.results = b->results;
+    a.inl_p_out = b->inlier_pts;
+    a.inl_l_out = b->inlier_lines;
+    return a;
 }
+stvo::PosePoints batch_points(const stvo_track_batch_dev* b) { return stvo::PosePoints::doubles(b->prev_P, b->prev_sigma2p, b->curr_pl); }
 
 int check_batch(stvo_ctx* ctx, const stvo_track_batch_dev* b, bool need_desc) {
     if (!ctx || !b || b->B < 0 || b->max_pts <= 0 || b->max_lines < 0) return STVO_ERR_INVALID_ARG;
@@ -449,8 +433,7 @@ int stvo_track_batched_dev(stvo_ctx* ctx, const stvo_track_batch_dev* b, const s
     if (params->has_lines && b->max_lines > 0)
         match_set(b->max_lines, b->prev_ldesc, b->n_prev_lines, b->curr_ldesc, b->n_curr_lines, nnr_lines, b->m12_lines);
     if (prev_pose) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, prev_pose, 0));  // also when nothing was matched
-    stvo::PoseArgs a{};
-    fill_pose_args(b, cam, params, false, &a);
+    stvo::PoseProblem a = batch_problem(b, cam, params, false);
     // a feature kind that is switched off is never matched => matched_pt / matched_ls stay empty (:137,160)
     if (!params->has_points) a.n_prev_pts = nullptr;
     if (!params->has_lines) a.n_prev_lines = nullptr;
@@ -460,7 +443,7 @@ int stvo_track_batched_dev(stvo_ctx* ctx, const stvo_track_batch_dev* b, const s
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->ev_match_done, 0));
         pose_stream = ctx->aux_stream;
     }
-    TRY(stvo::launch_pose(pose_stream, a));
+    TRY(launch_pose_ctx(ctx, pose_stream, a, batch_points(b)));
     if (ctx->overlap) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_pose_done, ctx->aux_stream));
         ctx->pose_pending = true;
@@ -473,9 +456,7 @@ int stvo_optimize_pose_batched_dev(stvo_ctx* ctx, const stvo_track_batch_dev* b,
     if (!cam || !params) return STVO_ERR_INVALID_ARG;
     TRY(check_batch(ctx, b, false));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    stvo::PoseArgs a{};
-    fill_pose_args(b, cam, params, true, &a);
-    TRY(stvo::launch_pose(ctx->stream, a));
+    TRY(launch_pose_ctx(ctx, ctx->stream, batch_problem(b, cam, params, true), batch_points(b)));
     return check_launch(ctx);
 }
 
@@ -487,8 +468,7 @@ int stvo_time_stage_dev(stvo_ctx* ctx, const stvo_track_batch_dev* b, const stvo
     hipEvent_t e0, e1;
     HIP_TRY(ctx, hipEventCreate(&e0));
     HIP_TRY(ctx, hipEventCreate(&e1));
-    stvo::PoseArgs a{};
-    fill_pose_args(b, cam, params, false, &a);
+    const stvo::PoseProblem a = batch_problem(b, cam, params, false);
     HIP_TRY(ctx, hipEventRecord(e0, ctx->stream));
     const stvo::MatchProblem points{b->B, b->max_pts, b->prev_pdesc, b->n_prev_pts, b->curr_pdesc, b->n_curr_pts, nnr};
     const stvo::MatchScratch w = ctx->match_scratch();
@@ -501,7 +481,7 @@ int stvo_time_stage_dev(stvo_ctx* ctx, const stvo_track_batch_dev* b, const stvo
         else if (stage == 4)  // developer probe: both directions as full top-2 scans (the pre-lazy formulation)
             stvo::launch_both_dirs_scan_alone(ctx->stream, points, w, pad);
         else
-            stvo::launch_pose(ctx->stream, a);
+            (void)launch_pose_ctx(ctx, ctx->stream, a, batch_points(b));
     }
     HIP_TRY(ctx, hipEventRecord(e1, ctx->stream));
     HIP_TRY(ctx, hipEventSynchronize(e1));
@@ -513,8 +493,9 @@ int stvo_time_stage_dev(stvo_ctx* ctx, const stvo_track_batch_dev* b, const stvo
     if (stage == 1 && stvo::dbg().pose_prof != stvo::DBG_UNSET) {  // developer aid: per-phase ticks of the solver lane
         long long* dprof = nullptr;
         HIP_TRY(ctx, hipMalloc((void**)&dprof, (size_t)b->B * 16 * sizeof(long long)));
-        a.prof_out = dprof;
-        stvo::launch_pose(ctx->stream, a);
+        stvo::PoseOptions o;
+        o.prof_out = dprof;
+        (void)launch_pose_ctx(ctx, ctx->stream, a, batch_points(b), o);
         std::vector<long long> h((size_t)b->B * 16);
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the copy below rides the null stream, which does not wait for this one)
         HIP_TRY(ctx, hipMemcpy(h.data(), dprof, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
