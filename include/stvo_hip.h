@@ -708,6 +708,37 @@ int stvo_rectify_color_images_dev(stvo_rectify* rect, int n, int channels, const
 int stvo_rectify_color_to_gray_dev(stvo_rectify* rect, int n, int channels, int order, int weights, const uint8_t* src_l,
                                    const uint8_t* src_r, uint8_t* gray_l, uint8_t* gray_r, uint8_t* swapped_l, uint8_t* swapped_r);
 
+/* ---- one rectifier for mixed cameras: a calibration and an image size per pair of one launch ---------------------------- */
+
+/* A bank over K rectifiers of the same context (from stvo_rectify_create, any form, dist 0 or 1, or stvo_rectify_create_from_maps), each
+ * no larger than the slot slot_cols x slot_rows, for up to B pairs per call.  The bank BORROWS the rectifiers' resident maps and copies
+ * nothing: every rectifier must outlive the bank (destroy the bank first).  Every pair starts on calibration 0.
+ * Images are slot-shaped, the layout stvo_orb_set_image_sizes reads: buffers are [n][slot_rows][slot_cols][channels], and image b
+ * occupies the top-left cols_k x rows_k of its slot at the slot's row pitch, k being the calibration of pair b. */
+typedef struct stvo_rectify_bank stvo_rectify_bank;
+int stvo_rectify_bank_create(stvo_ctx* ctx, int B, int slot_cols, int slot_rows, stvo_rectify* const* rects, int K,
+                             stvo_rectify_bank** out);
+int stvo_rectify_bank_destroy(stvo_rectify_bank* bank);
+/* stvo_rectify_camera of rectifier k. */
+int stvo_rectify_bank_camera(const stvo_rectify_bank* bank, int k, stvo_rect_camera* out);
+/* Pair b takes calibration calib_of_pair_host[b] (0 .. K - 1) for the calls that follow.  An index out of range:
+ * STVO_ERR_INVALID_ARG and nothing changes.  calib_of_pair_host is read during the call; the split of the work it implies travels on
+ * the context's stream behind the calls already enqueued, through pinned staging that is not reused before its copy has completed: no
+ * synchronisation (the contract of stvo_orb_set_image_sizes). */
+int stvo_rectify_bank_assign(stvo_rectify_bank* bank, const int32_t* calib_of_pair_host /* [B] */);
+/* n (1 .. B) pairs, channels 1, 3 or 4, DEVICE pointers, ONE kernel launch on the context's stream for all calibrations and both sides,
+ * no synchronisation.  For every pair the crop of the destination is, bit for bit, what rectifier k alone returns for the crop of the
+ * source (stvo_rectify_images_dev / stvo_rectify_color_images_dev; with dist 0 a copy of the crop): a tap outside the image reads 0
+ * even where it lies inside the slot, and no byte of the destination outside the crop is written.  A NULL pointer, n or channels out
+ * of range, a destination that overlaps a source or the other destination: STVO_ERR_INVALID_ARG. */
+int stvo_rectify_bank_images_dev(stvo_rectify_bank* bank, int n, int channels, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l,
+                                 uint8_t* dst_r);
+/* The fused form, per pair the contract of stvo_rectify_color_to_gray_dev (every channel remapped and rounded to 8 bits, then weighted;
+ * with dist 0 the plain conversion) in the slot layout: src [n][slot_rows][slot_cols][channels] (3 or 4), planes [n][slot_rows]
+ * [slot_cols]; swapped_l / swapped_r both or neither NULL.  One launch, nothing written outside the crops, no synchronisation. */
+int stvo_rectify_bank_color_to_gray_dev(stvo_rectify_bank* bank, int n, int channels, int order, int weights, const uint8_t* src_l,
+                                        const uint8_t* src_r, uint8_t* gray_l, uint8_t* gray_r, uint8_t* swapped_l, uint8_t* swapped_r);
+
 /* ---- measurement helpers --------------------------------------------------------------------- */
 /* Times `iters` launches of the named kernel stage on the context's stream with hipEvents and
  * returns the average milliseconds per launch (used by bench.py for the roofline line).

@@ -35,7 +35,9 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_color_to_gray", "stvo_color_to_gray_dev", "stvo_rectify_color_images", "stvo_rectify_color_images_dev",
            "stvo_rectify_color_to_gray_dev", "stvo_seq_snapshot_layout", "stvo_seq_snapshot_info", "stvo_seq_export_streams_dev",
            "stvo_seq_export_streams", "stvo_seq_import_streams_dev", "stvo_seq_import_streams", "stvo_orb_set_descriptor",
-           "stvo_orb_pattern", "stvo_orb_set_image_sizes", "stvo_seq_restart_cameras"]
+           "stvo_orb_pattern", "stvo_orb_set_image_sizes", "stvo_seq_restart_cameras", "stvo_rectify_bank_create",
+           "stvo_rectify_bank_destroy", "stvo_rectify_bank_camera", "stvo_rectify_bank_assign", "stvo_rectify_bank_images_dev",
+           "stvo_rectify_bank_color_to_gray_dev"]
 
 SEQ_NSTAGE = 5  # include/stvo_hip.h: STVO_SEQ_NSTAGE
 SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_check", "pose")
@@ -339,6 +341,12 @@ def load():
     L.stvo_rectify_color_images.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
     L.stvo_rectify_color_images_dev.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
     L.stvo_rectify_color_to_gray_dev.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 6
+    L.stvo_rectify_bank_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]
+    L.stvo_rectify_bank_destroy.argtypes = [C.c_void_p]
+    L.stvo_rectify_bank_camera.argtypes = [C.c_void_p, C.c_int, C.POINTER(RectCamera)]
+    L.stvo_rectify_bank_assign.argtypes = [C.c_void_p, C.c_void_p]
+    L.stvo_rectify_bank_images_dev.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+    L.stvo_rectify_bank_color_to_gray_dev.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 6
     L.stvo_seq_push.argtypes = [C.c_void_p, C.POINTER(FrameFeatures), C.c_void_p, i32p]
     L.stvo_seq_upload.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameFeatures)]
     L.stvo_seq_upload_dev.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameFeatures)]
@@ -1288,3 +1296,91 @@ class Rectifier:
         the planes of the other channel order, both or neither."""
         self.ctx._chk(self.ctx.lib.stvo_rectify_color_to_gray_dev(self.h, n, ch, GRAY_ORDERS[order], GRAY_WEIGHTS[weights], src_l, src_r,
                                                                   gray_l, gray_r, swapped_l, swapped_r))
+
+
+class RectifierBank:
+    """One rectifier for mixed cameras (stvo_rectify_bank_*): up to B pairs per call in slots of slot_cols x slot_rows, every pair under
+    one of the K calibrations `rectifiers` (capi.Rectifier objects of the same context, each no larger than the slot).  The bank borrows
+    their resident maps: keep the rectifiers open until the bank is closed.  Buffers are slot-shaped, [n, slot_rows, slot_cols(, ch)],
+    image b the top-left cols_k x rows_k of its slot — what Orb.set_image_sizes reads.  Every pair starts on calibration 0."""
+
+    def __init__(self, ctx, B, slot_cols, slot_rows, rectifiers):
+        rectifiers = list(rectifiers)
+        if not rectifiers or any(r.ctx is not ctx or not r.h for r in rectifiers):
+            raise ValueError("RectifierBank: rectifiers is a non-empty list of open Rectifier objects of the same context")
+        self.ctx, self.B, self.slot_cols, self.slot_rows = ctx, B, slot_cols, slot_rows
+        self.rectifiers = rectifiers  # (kept alive: the bank reads their maps)
+        self.K = len(rectifiers)
+        self.sizes = [(r.cols, r.rows) for r in rectifiers]
+        self.calibs = [0] * B
+        self.h = C.c_void_p()
+        hs = (C.c_void_p * self.K)(*[r.h for r in rectifiers])
+        ctx._chk(ctx.lib.stvo_rectify_bank_create(ctx.h, B, slot_cols, slot_rows, hs, self.K, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.stvo_rectify_bank_destroy(self.h)
+            self.h = None
+
+    def assign(self, calibs):
+        """Pair b takes calibration calibs[b] (B entries, 0 .. K - 1) for the calls that follow; travels on the context's stream behind
+        the calls already enqueued, no synchronisation.  An index out of range raises and nothing changes."""
+        a = np.ascontiguousarray(calibs, np.int32).reshape(-1)
+        if a.size != self.B:
+            raise ValueError("RectifierBank.assign: one calibration index per pair (B entries)")
+        self.ctx._chk(self.ctx.lib.stvo_rectify_bank_assign(self.h, _ptr(a)))
+        self.calibs = [int(v) for v in a]
+
+    def camera(self, k):
+        """What Rectifier.camera gives for calibration k: the rectified pipeline camera (zeros for caller maps)."""
+        rc = RectCamera()
+        self.ctx._chk(self.ctx.lib.stvo_rectify_bank_camera(self.h, k, C.byref(rc)))
+        return camera_dict(rc)["cam"]
+
+    def rectify_dev(self, n, ch, src_l, src_r, dst_l, dst_r):
+        """Device pointers to slot-shaped buffers (n slots each, ch = 1, 3 or 4); one launch, asynchronous on the context's stream."""
+        self.ctx._chk(self.ctx.lib.stvo_rectify_bank_images_dev(self.h, n, ch, src_l, src_r, dst_l, dst_r))
+
+    def rectify_color_to_gray_dev(self, n, ch, src_l, src_r, gray_l, gray_r, swapped_l=None, swapped_r=None, order="bgr", weights="q14"):
+        """Raw colour slots -> the grey planes of the rectified colour images, one launch (device pointers, asynchronous); swapped_*:
+        the planes of the other channel order, both or neither."""
+        self.ctx._chk(self.ctx.lib.stvo_rectify_bank_color_to_gray_dev(self.h, n, ch, GRAY_ORDERS[order], GRAY_WEIGHTS[weights], src_l, src_r,
+                                                                       gray_l, gray_r, swapped_l, swapped_r))
+
+    def _slots(self, imgs, ch, torch):
+        """per-pair host arrays of each pair's own size -> a device tensor of slots (zeros beyond the images)"""
+        shape = (len(imgs), self.slot_rows, self.slot_cols) + ((ch,) if ch > 1 else ())
+        host = np.zeros(shape, np.uint8)
+        for b, im in enumerate(imgs):
+            cols, rows = self.sizes[self.calibs[b]]
+            im = np.asarray(im, np.uint8)
+            if im.shape != (rows, cols) + ((ch,) if ch > 1 else ()):
+                raise ValueError(f"RectifierBank: pair {b} takes images of {cols} x {rows}")
+            host[b, :rows, :cols] = im
+        return torch.as_tensor(host).cuda()
+
+    def _run(self, left, right, ch):
+        import torch  # (the device buffers of this convenience only; every computation is behind the C-ABI)
+        if len(left) != len(right) or not 1 <= len(left) <= self.B:
+            raise ValueError("RectifierBank: as many right images as left ones, 1 .. B pairs")
+        sl, sr = self._slots(left, ch, torch), self._slots(right, ch, torch)
+        dl, dr = torch.zeros_like(sl), torch.zeros_like(sr)
+        torch.cuda.synchronize()  # the copies ran on torch's stream, the library uses its own
+        self.rectify_dev(len(left), ch, sl.data_ptr(), sr.data_ptr(), dl.data_ptr(), dr.data_ptr())
+        self.ctx.synchronize()
+        out = []
+        for d in (dl.cpu().numpy(), dr.cpu().numpy()):
+            out.append([d[b, :self.sizes[self.calibs[b]][1], :self.sizes[self.calibs[b]][0]].copy() for b in range(len(left))])
+        return out[0], out[1]
+
+    def rectify(self, left, right):
+        """Host images: two lists of n <= B uint8 arrays [rows_b, cols_b] of each pair's own size (its calibration's) -> (left, right)
+        lists of the rectified images, synchronous."""
+        return self._run(left, right, 1)
+
+    def rectify_color(self, left, right):
+        """The same for colour images [rows_b, cols_b, ch], ch = 3 or 4, every channel remapped."""
+        ch = np.asarray(left[0]).shape[-1] if len(left) and np.asarray(left[0]).ndim == 3 else 0
+        if ch not in (3, 4):
+            raise ValueError("RectifierBank.rectify_color: images are [rows, cols, 3] or [rows, cols, 4]")
+        return self._run(left, right, ch)

@@ -22,13 +22,18 @@ class ImagePipeline:
     def __init__(self, ctx, B, cam, mp, op, max_kp=2048, nfeatures=2000, fast_threshold=20, edge_threshold=19, device="cuda:0", nlevels=1,
                  scale_factor=1.2, lsd=None, max_kl=128, rectify=None, fld=None, orb_score=1, adaptive_fast=None,
                  trajectory=None, trajectory_log=1, tracks=0, keyframe_sets=False, channels=1, gray_weights="q14", orb_wta_k=2,
-                 orb_patch_size=31):
+                 orb_patch_size=31, calibs=None):
         """cam: one camera dict (width / height = image size) for all B streams, or a list of B dicts, one camera AND image size per stream
         (KITTI 00-02 / 03 / 04-10 side by side): the resident image buffer is then cut in slots of the largest width x the largest height,
         stream b's images occupy the top-left of their slots (set_images takes a list of B arrays of each stream's own size), the
         detector reads every image at its own size (Orb.set_image_sizes) and the pipeline is created with the B cameras; a stream that
-        RESTARTs may take another camera (enqueue / push_images: cams).  Key-points only: with a list, lsd, fld, rectify and channels
-        other than 1 raise ValueError (their detectors, the rectifier and the colour conversion hold one size each).  nlevels / scale_factor: Config::orbNLevels /
+        RESTARTs may take another camera (enqueue / push_images: cams).  Key-points only: with a list, lsd and fld raise ValueError (their
+        detectors hold one size each), and so do a rectify that is not a capi.RectifierBank and channels other than 1 without one.
+        With a list, rectify = capi.RectifierBank and calibs = [B ints]: the frames are RAW, stream b under calibration calibs[b] of the
+        bank, whose size cam[b] must have; the slot is the bank's; enqueue first runs the bank's one launch over all streams (with
+        channels 3 / 4 the fused colour -> grey form: set_images then takes lists of colour arrays into self.color) and the detector
+        reads the rectified slots; a stream that RESTARTs may take another calibration with its camera (enqueue / push_images: calibs).
+        nlevels / scale_factor: Config::orbNLevels /
         orbScaleFactor (the key-point octaves travel with the key-points: sigma2 = 1 / scale^(2 level)).  orb_score: Config::orbScore
         (1 FAST_SCORE, 0 HARRIS_SCORE ranking of the key-points).  orb_wta_k / orb_patch_size: Config::orbWtaK / orbPatchSize
         (capi.Orb: 2 .. 4 and 2 .. 63; the descriptor stays 32 bytes under the matchers' plain Hamming distance).  lsd: capi.lsd_params(...)
@@ -62,25 +67,42 @@ class ImagePipeline:
         self.channels, self.gray_weights = channels, gray_weights
         self.ctx, self.B, self.K, self.M = ctx, B, max_kp, max_kl
         self.cams = None  # one camera per stream: the B dicts in force (a RESTART may bring another)
+        self.bank = self.calibs = None  # a capi.RectifierBank and the calibration of every stream in force
         if not isinstance(cam, dict):
             cam = list(cam)
             if len(cam) != B:
                 raise ValueError("ImagePipeline: cam is one dict or a list of B dicts")
-            for name, given in (("lsd", lsd is not None), ("fld", fld is not None), ("rectify", rectify is not None), ("channels", channels != 1)):
+            bank = rectify if isinstance(rectify, capi.RectifierBank) else None
+            for name, given in (("lsd", lsd is not None), ("fld", fld is not None), ("rectify", rectify is not None and bank is None),
+                                ("channels", channels != 1 and bank is None)):
                 if given:
-                    raise ValueError(f"ImagePipeline: {name} is not available with one camera per stream (cam as a list): key-points only")
+                    raise ValueError(f"ImagePipeline: {name} is not available with one camera per stream (cam as a list): key-points only"
+                                     " (rectify takes a capi.RectifierBank, which also takes channels 3 / 4)")
             self.cams = cam
-            self.cols, self.rows = max(c["width"] for c in cam), max(c["height"] for c in cam)  # the slot
+            if bank is not None:
+                if bank.ctx is not ctx or bank.B < B:
+                    raise ValueError("ImagePipeline: the rectifier bank must belong to the same context and hold B pairs")
+                self.cols, self.rows = bank.slot_cols, bank.slot_rows  # the slot
+                self.bank = bank
+                self.calibs = self._check_calibs(calibs, cam)
+            else:
+                self.cols, self.rows = max(c["width"] for c in cam), max(c["height"] for c in cam)  # the slot
         else:
             self.cols, self.rows = cam["width"], cam["height"]
+            if isinstance(rectify, capi.RectifierBank):
+                raise ValueError("ImagePipeline: a capi.RectifierBank goes with one camera per stream (cam as a list)")
+        if self.bank is None and calibs is not None:
+            raise ValueError("ImagePipeline: calibs goes with rectify = capi.RectifierBank and cam as a list")
         self.rectify = rectify
-        if rectify is not None and (rectify.ctx is not ctx or rectify.B < B or rectify.cols != self.cols or rectify.rows != self.rows):
+        if rectify is not None and self.bank is None and (rectify.ctx is not ctx or rectify.B < B or rectify.cols != self.cols or rectify.rows != self.rows):
             raise ValueError("ImagePipeline: the rectifier must belong to the same context, hold B pairs and match the image size")
         self.orb = capi.Orb(ctx, 2 * B, self.cols, self.rows, max_kp, nfeatures, fast_threshold, edge_threshold, nlevels, scale_factor,
                             score=orb_score, wta_k=orb_wta_k, patch_size=orb_patch_size)  # left images, then right
         if self.cams is not None:  # n = B on 2 B images: left image b and right image B + b share entry b
             try:
                 self.orb.set_image_sizes([(c["width"], c["height"]) for c in self.cams])
+                if self.bank is not None:
+                    self.bank.assign(self.calibs + [0] * (self.bank.B - B))
             except Exception:
                 self.orb.close()
                 raise
@@ -147,6 +169,28 @@ class ImagePipeline:
         self.ff = ff  # (without a line detector every line pointer stays NULL: no key-lines; oct_ll NULL: one octave)
         self.slot = 0
 
+    def _check_calibs(self, calibs, cams):
+        """calibs as a list of B calibration indices of the bank, each of the size of its stream's camera"""
+        if calibs is None or len(calibs) != self.B:
+            raise ValueError("ImagePipeline: calibs takes one calibration index of the bank per stream (B entries)")
+        calibs = [int(k) for k in calibs]
+        for b, k in enumerate(calibs):
+            if not 0 <= k < self.bank.K:
+                raise ValueError(f"ImagePipeline: calibs[{b}] = {k} is not a calibration of the bank")
+            if self.bank.sizes[k] != (cams[b]["width"], cams[b]["height"]):
+                raise ValueError(f"ImagePipeline: stream {b}'s camera is {cams[b]['width']} x {cams[b]['height']}, calibration calibs[{b}] = {k} "
+                                 f"of the bank {self.bank.sizes[k][0]} x {self.bank.sizes[k][1]}")
+        return calibs
+
+    def _calibs_after(self, control, calibs, new_cams):
+        """The B calibrations in force once the RESTART streams of `control` have taken theirs from `calibs` (B entries, None for the
+        others), checked against the cameras then in force."""
+        if self.bank is None or control is None or len(calibs) != self.B:
+            raise ValueError("ImagePipeline: calibs takes a rectifier bank, a control and B entries")
+        ctl = np.asarray(control).reshape(-1)
+        new = [k if k is not None and ctl[b] == capi.STREAM_RESTART else self.calibs[b] for b, k in enumerate(calibs)]
+        return self._check_calibs(new, new_cams if new_cams is not None else self.cams)
+
     def _cams_after(self, control, cams):
         """The B cameras in force once the RESTART streams of `control` have taken theirs from `cams` (B entries, None for the others)."""
         if self.cams is None or control is None or len(cams) != self.B:
@@ -159,7 +203,8 @@ class ImagePipeline:
 
     def set_images(self, left, right, cams=None):
         """left / right: uint8 [B, rows, cols] (numpy or torch), with channels 3 / 4 [B, rows, cols, channels]; copied into the
-        resident image buffer.  With one camera per stream also two lists of B arrays [height_b, width_b] of each stream's own size:
+        resident image buffer.  With one camera per stream also two lists of B arrays [height_b, width_b] (with channels 3 / 4, which
+        takes a rectifier bank, [height_b, width_b, channels] into self.color) of each stream's own size:
         each is placed top-left in its slot (what the slot holds beyond it is never read); cams: the B cameras whose sizes the images have,
         where they are not yet the ones in force (push_images with a RESTART)."""
         B = self.B
@@ -167,12 +212,14 @@ class ImagePipeline:
         if self.cams is not None and isinstance(left, (list, tuple)):
             if len(left) != B or len(right) != B:
                 raise ValueError("ImagePipeline.set_images: one image per stream and side")
+            dst = self.img if self.channels == 1 else self.color
+            tail = () if self.channels == 1 else (self.channels,)
             for side, imgs in ((0, left), (B, right)):
                 for b, im in enumerate(imgs):
                     t = torch.as_tensor(im)
-                    if tuple(t.shape) != (cams[b]["height"], cams[b]["width"]):
+                    if tuple(t.shape) != (cams[b]["height"], cams[b]["width"]) + tail:
                         raise ValueError(f"ImagePipeline.set_images: stream {b} takes images of {cams[b]['width']} x {cams[b]['height']}")
-                    self.img[side + b, :t.shape[0], :t.shape[1]].copy_(t, non_blocking=True)
+                    dst[side + b, :t.shape[0], :t.shape[1]].copy_(t, non_blocking=True)
             return
         if self.channels != 1:
             self.color[:B].copy_(torch.as_tensor(left).reshape(B, self.rows, self.cols, self.channels), non_blocking=True)
@@ -181,7 +228,7 @@ class ImagePipeline:
         self.img[:B].copy_(torch.as_tensor(left).reshape(B, self.rows, self.cols), non_blocking=True)
         self.img[B:].copy_(torch.as_tensor(right).reshape(B, self.rows, self.cols), non_blocking=True)
 
-    def enqueue(self, img_ptr=None, control=None, cams=None):
+    def enqueue(self, img_ptr=None, control=None, cams=None, calibs=None):
         """Detection + description of the 2 B resident images (or of the uint8 [2 B, rows, cols] device buffer at img_ptr: B left,
         then B right; with channels 3 / 4 the colour buffer [2 B, rows, cols, channels]), ingestion, one pipeline step — all
         asynchronous.  With a rectifier the images are raw and are rectified first.
@@ -189,22 +236,38 @@ class ImagePipeline:
         first, so that with adaptive_fast the restarted streams are detected at fast_threshold again (initialize sets orb_fast_th
         before it detects); the rule at the end of the step leaves the thresholds of restarted and parked streams alone.
         cams (one camera per stream only): None, or B entries — the camera dict of the sequence a RESTART stream begins, None for the
-        others: the pipeline (Sequences.restart_cameras) and the detector (Orb.set_image_sizes) take it before the detection."""
+        others: the pipeline (Sequences.restart_cameras) and the detector (Orb.set_image_sizes) take it before the detection.
+        calibs (rectifier bank only): None, or B entries — the calibration index a RESTART stream takes with its camera, None for the
+        others; the size of every stream's calibration must be its camera's, else ValueError and nothing is staged."""
         new = self._cams_after(control, cams) if cams is not None else None
+        new_k = self._calibs_after(control, calibs, new) if calibs is not None else None
+        if self.bank is not None and new_k is None and new is not None:
+            self._check_calibs(self.calibs, new)  # a camera of another size needs its calibration
         if control is not None:
             self.seq.control_next_step(control)
-            if new is not None and new != self.cams:
-                # the detector first: it validates every size, and what it has taken can be put back should the pipeline refuse —
-                # the two never disagree, and a refused call leaves no control staged
+            cams_change = new is not None and new != self.cams
+            calibs_change = new_k is not None and new_k != self.calibs
+            if cams_change or calibs_change:
+                # the detector first: it validates every size, and what it and the bank have taken can be put back should the pipeline
+                # refuse — the three never disagree, and a refused call leaves no control staged
                 ctl = np.asarray(control).reshape(-1)
                 try:
-                    self.orb.set_image_sizes([(c["width"], c["height"]) for c in new])
-                    self.seq.restart_cameras([c if ctl[b] == capi.STREAM_RESTART else None for b, c in enumerate(new)])
+                    if cams_change:
+                        self.orb.set_image_sizes([(c["width"], c["height"]) for c in new])
+                    if calibs_change:
+                        self.bank.assign(new_k + [0] * (self.bank.B - self.B))
+                    if cams_change:
+                        self.seq.restart_cameras([c if ctl[b] == capi.STREAM_RESTART else None for b, c in enumerate(new)])
                 except Exception:
                     self.orb.set_image_sizes([(c["width"], c["height"]) for c in self.cams])
+                    if calibs_change:
+                        self.bank.assign(self.calibs + [0] * (self.bank.B - self.B))
                     self.seq.control_next_step(np.zeros(self.B, np.int32))
                     raise
-                self.cams = new
+                if cams_change:
+                    self.cams = new
+                if calibs_change:
+                    self.calibs = new_k
             if self.adaptive_fast is not None:
                 self.seq.restart_fast_dev(self.fast_th, self.fast_threshold)
         ip = img_ptr if img_ptr is not None else (self.img if self.channels == 1 else self.color).data_ptr()
@@ -213,7 +276,10 @@ class ImagePipeline:
             side = self.B * self.rows * self.cols
             ga = self.img.data_ptr()
             gb = self.gray_b.data_ptr() if self.gray_b is not None else None
-            if self.rectify is not None:
+            if self.bank is not None:
+                self.bank.rectify_color_to_gray_dev(self.B, self.channels, ip, ip + side * self.channels, ga, ga + side, gb,
+                                                    gb + side if gb is not None else None, weights=self.gray_weights)
+            elif self.rectify is not None:
                 self.rectify.rectify_color_to_gray_dev(self.B, self.channels, ip, ip + side * self.channels, ga, ga + side, gb,
                                                        gb + side if gb is not None else None, weights=self.gray_weights)
             else:
@@ -222,7 +288,10 @@ class ImagePipeline:
         elif self.rectify is not None:
             side = self.B * self.rows * self.cols
             rp = self.rect_img.data_ptr()
-            self.rectify.rectify_dev(self.B, ip, ip + side, rp, rp + side)
+            if self.bank is not None:
+                self.bank.rectify_dev(self.B, 1, ip, ip + side, rp, rp + side)
+            else:
+                self.rectify.rectify_dev(self.B, ip, ip + side, rp, rp + side)
             ip = rp
         self.orb.detect_dev(ip, self.kp.data_ptr(), self.resp.data_ptr(), self.ang.data_ptr(), self.desc.data_ptr(),
                             self.n.data_ptr(), octave=self.oct.data_ptr())
@@ -237,12 +306,15 @@ class ImagePipeline:
             self.seq.adapt_fast_dev(self.adaptive_fast, self.fast_th)
         self.slot ^= 1
 
-    def push_images(self, left, right, control=None, cams=None):
-        """One frame of every stream: (pose results [B], counts [B, 4]) like Sequences.push.  control, cams: as for enqueue (the images of
-        a stream that takes another camera have that camera's size)."""
-        self.set_images(left, right, cams=self._cams_after(control, cams) if cams is not None else None)
+    def push_images(self, left, right, control=None, cams=None, calibs=None):
+        """One frame of every stream: (pose results [B], counts [B, 4]) like Sequences.push.  control, cams, calibs: as for enqueue (the
+        images of a stream that takes another camera have that camera's size)."""
+        new = self._cams_after(control, cams) if cams is not None else None
+        if calibs is not None:
+            self._calibs_after(control, calibs, new)  # refused before an image is taken
+        self.set_images(left, right, cams=new)
         torch.cuda.current_stream().synchronize()  # the copies above ran on torch's stream, the library uses its own
-        self.enqueue(control=control, cams=cams)
+        self.enqueue(control=control, cams=cams, calibs=calibs)
         return self.seq.read()
 
     def read_trajectory(self, n_last=1):
