@@ -10,37 +10,35 @@
 //                          store per plane; the thread after the last whole group does the tail (< 16 pixels) by bytes.  Needs the
 //                          source and the planes 16-byte aligned.
 //   color_to_gray_bytes    one thread = one pixel, byte loads and stores: bases that are not 16-byte aligned.
-//   rectify_color_kernel   rectify_remap_kernel's thread layout (4 consecutive output pixels, maps in registers, a loop over the
-//                          images of the block's chunk) and arithmetic ((X + 512) >> 10 per channel, a tap outside the source reads
-//                          0, the inside flag of map2) for ch channels.  GRAY = false writes the rectified colour image, which is
-//                          rectifyImagesLR on a colour Mat; GRAY = true rounds every colour channel to 8 bits as remap does, weights
-//                          them and writes the plane(s) only: the rectified colour image never reaches memory.
+//   rectify_color_kernel   the uniform remap (one rectifier for every pair of the launch) of CH = 1, 3 or 4 channels.  One thread =
+//                          4 consecutive output pixels of one side (the pixel index runs over rows * cols, so a quad may straddle
+//                          two rows): one 16-B load of map1 and one 8-B load of map2, then a loop over the images of that side in
+//                          this block's chunk with the maps held in registers; per image 4 taps per pixel and CH aligned dword
+//                          stores (byte stores where the quad is not dword-aligned in the image or runs past its end).
+//                          blockIdx.y = image chunk, blockIdx.z = side (0 left, 1 right).  GRAY = false writes the rectified image,
+//                          which is rectifyImagesLR on a Mat of CH channels; GRAY = true rounds every colour channel to 8 bits as
+//                          remap does, weights them and writes the plane(s) only: the rectified colour image never reaches memory.
+//                          The loop over the quad's 4 pixels has one of two shapes, chosen per instance (HOISTED): with one channel
+//                          the inside / border branch stands outside it and the tap offsets are 32-bit, which issues the 16 byte
+//                          loads together (69 VGPRs); with 3 or 4 channels the branch stands inside it and the offsets are 64-bit
+//                          (98 / 124 / 88 / 90 VGPRs for <3, false>, <4, false>, <3, true>, <4, true>: 4 - 5 waves per SIMD), since
+//                          the hoisted shape costs those instances 125 - 135 VGPRs and a wave.
 //
-// Grey arithmetic (cvtColor's 8-bit integer form): (w0 c0 + w1 c1 + w2 c2 + 2^(shift-1)) >> shift with (blue, green, red) weights
-// (1868, 9617, 4899) and shift 14, the table form of OpenCV 3.0 - 3.4.1, or (3735, 19235, 9798) and shift 15 of the later releases.
-// The sum stays below 2^23 + 2^14, so 32-bit arithmetic is exact.
+// rectify_px.h states the arithmetic: the remap's (X + 512) >> 10 per channel, a tap outside the source reads 0, the inside flag of
+// map2, and cvtColor's integer grey weights.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 
 #include "ctx_internal.h"
+#include "rectify_bank_plan.h"
 #include "rectify_internal.h"
 
 namespace {
 
 constexpr int COLOR_BLOCK = 256;
 constexpr int GROUP = 16;  // pixels per thread of the stream kernel
-constexpr uint32_t INSIDE = 0x8000u;
-
-struct GrayWeights {
-    uint32_t w0, w1, w2, rnd, shift;  // plane A; plane B swaps w0 and w2
-};
-
-__device__ __forceinline__ uint32_t weigh(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t w0, uint32_t w1, uint32_t w2,
-                                          const GrayWeights& w) {
-    return (w0 * c0 + w1 * c1 + w2 * c2 + w.rnd) >> w.shift;
-}
 
 template <int CH, bool TWO>
 __global__ void __launch_bounds__(COLOR_BLOCK) color_to_gray_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ pa,
@@ -87,40 +85,9 @@ __global__ void __launch_bounds__(COLOR_BLOCK) color_to_gray_bytes(const uint8_t
     if (TWO) pb[p] = (uint8_t)weigh(c0, c1, c2, w.w2, w.w1, w.w0, w);
 }
 
-__device__ __forceinline__ uint32_t blend(uint32_t s00, uint32_t s01, uint32_t s10, uint32_t s11, uint32_t m2) {
-    const uint32_t ax = m2 & 31u, ay = (m2 >> 5) & 31u;
-    const uint32_t top = __umul24(32u - ax, s00) + __umul24(ax, s01);
-    const uint32_t bot = __umul24(32u - ax, s10) + __umul24(ax, s11);
-    return (__umul24(32u - ay, top) + __umul24(ay, bot) + 512u) >> 10;
-}
-
-// The first NC channels of the pixel at p.  A 4-channel pixel is one (unaligned) 32-bit load: three byte loads per tap made the fused
-// kernel slower on B, G, R, A than remap-then-convert; a 3-channel pixel is read by bytes (a word would run past the last pixel).
-template <int CH, int NC>
-__device__ __forceinline__ void load_px(const uint8_t* __restrict__ p, uint32_t (&c)[NC]) {
-    if (CH == 4) {
-        uint32_t w;
-        __builtin_memcpy(&w, p, 4);
-#pragma unroll
-        for (int k = 0; k < NC; ++k) c[k] = (w >> (8 * k)) & 0xffu;
-    } else {
-#pragma unroll
-        for (int k = 0; k < NC; ++k) c[k] = p[k];
-    }
-}
-
-template <int CH, int NC>
-__device__ __forceinline__ void tap_px(const uint8_t* __restrict__ S, int x, int y, int cols, int rows, uint32_t (&c)[NC]) {
-    if ((unsigned)x < (unsigned)cols && (unsigned)y < (unsigned)rows) {
-        load_px<CH, NC>(S + ((size_t)y * cols + x) * CH, c);
-    } else {
-#pragma unroll
-        for (int k = 0; k < NC; ++k) c[k] = 0u;
-    }
-}
-
-// src / dst: this side's first image; source images npx * CH bytes apart.  GRAY = false: dst holds colour images (npx * CH bytes
-// apart), dstb unused.  GRAY = true: dst is plane A, dstb plane B or NULL (both sides), images npx bytes apart.
+// map1q / map2q: one side's maps padded to whole quads.  src / dst: this side's first image; source images npx * CH bytes apart.
+// GRAY = false: dst holds CH-channel images (npx * CH bytes apart), dstb and w unused.  GRAY = true: dst is plane A, dstb plane B or
+// NULL (both sides), images npx bytes apart.
 template <int CH, bool GRAY>
 __global__ void __launch_bounds__(COLOR_BLOCK) rectify_color_kernel(const int4* __restrict__ map1q_l, const uint2* __restrict__ map2q_l,
                                                                     const int4* __restrict__ map1q_r, const uint2* __restrict__ map2q_r,
@@ -129,6 +96,7 @@ __global__ void __launch_bounds__(COLOR_BLOCK) rectify_color_kernel(const int4* 
                                                                     uint8_t* __restrict__ dstb_l, uint8_t* __restrict__ dstb_r, int n,
                                                                     int per_chunk, int cols, int rows, int nquads, GrayWeights w) {
     constexpr int NC = GRAY ? 3 : CH;  // channels computed: the grey planes never read alpha
+    constexpr bool HOISTED = CH == 1;  // the shape of the loop over the quad's pixels (see the top of the file)
     const int q = blockIdx.x * COLOR_BLOCK + threadIdx.x;
     if (q >= nquads) return;
     const bool right = blockIdx.z != 0;
@@ -149,64 +117,100 @@ __global__ void __launch_bounds__(COLOR_BLOCK) rectify_color_kernel(const int4* 
 #pragma unroll
     for (int k = 0; k < 4; ++k) all_inside = all_inside && (m2s[k] & INSIDE);
     const bool full = p0 + 4 <= npx;
+    auto at = [&](int x, int y) { return ((size_t)y * cols + x) * CH; };  // a pixel's offset in its image
+    int off[4];  // HOISTED: the offset of the top-left tap (one channel: an image is below 2^31 bytes), valid where the pixel is inside
+    if constexpr (HOISTED) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int x, y;
+            map_tap(m1s[k], x, y);
+            off[k] = y * cols + x;
+        }
+    }
     for (int i = i0; i < i1; ++i) {
         const uint8_t* S = src + (size_t)i * npx * CH;
         uint32_t v[4][NC];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int x = (int)(int16_t)(m1s[k] & 0xffff), y = m1s[k] >> 16;
-            uint32_t t00[NC], t01[NC], t10[NC], t11[NC];
+        if constexpr (HOISTED) {
             if (all_inside) {
-                const uint8_t* s = S + ((size_t)y * cols + x) * CH;
-                load_px<CH, NC>(s, t00);
-                load_px<CH, NC>(s + CH, t01);
-                load_px<CH, NC>(s + row_b, t10);
-                load_px<CH, NC>(s + row_b + CH, t11);
-            } else {
-                tap_px<CH, NC>(S, x, y, cols, rows, t00);
-                tap_px<CH, NC>(S, x + 1, y, cols, rows, t01);
-                tap_px<CH, NC>(S, x, y + 1, cols, rows, t10);
-                tap_px<CH, NC>(S, x + 1, y + 1, cols, rows, t11);
-            }
 #pragma unroll
-            for (int c = 0; c < NC; ++c) v[k][c] = blend(t00[c], t01[c], t10[c], t11[c], m2s[k]);
+                for (int k = 0; k < 4; ++k) {
+                    uint32_t t00[NC], t01[NC], t10[NC], t11[NC];
+                    const uint8_t* s = S + off[k];
+                    load_px<CH, NC>(s, t00);
+                    load_px<CH, NC>(s + CH, t01);
+                    load_px<CH, NC>(s + cols, t10);
+                    load_px<CH, NC>(s + cols + CH, t11);
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) v[k][c] = blend(t00[c], t01[c], t10[c], t11[c], m2s[k]);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    int x, y;
+                    map_tap(m1s[k], x, y);
+                    uint32_t t00[NC], t01[NC], t10[NC], t11[NC];
+                    tap_px<CH, NC>(S, x, y, cols, rows, at, t00);
+                    tap_px<CH, NC>(S, x + 1, y, cols, rows, at, t01);
+                    tap_px<CH, NC>(S, x, y + 1, cols, rows, at, t10);
+                    tap_px<CH, NC>(S, x + 1, y + 1, cols, rows, at, t11);
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) v[k][c] = blend(t00[c], t01[c], t10[c], t11[c], m2s[k]);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                int x, y;
+                map_tap(m1s[k], x, y);
+                uint32_t t00[NC], t01[NC], t10[NC], t11[NC];
+                if (all_inside) {
+                    const uint8_t* s = S + ((size_t)y * cols + x) * CH;
+                    load_px<CH, NC>(s, t00);
+                    load_px<CH, NC>(s + CH, t01);
+                    load_px<CH, NC>(s + row_b, t10);
+                    load_px<CH, NC>(s + row_b + CH, t11);
+                } else {
+                    tap_px<CH, NC>(S, x, y, cols, rows, at, t00);
+                    tap_px<CH, NC>(S, x + 1, y, cols, rows, at, t01);
+                    tap_px<CH, NC>(S, x, y + 1, cols, rows, at, t10);
+                    tap_px<CH, NC>(S, x + 1, y + 1, cols, rows, at, t11);
+                }
+#pragma unroll
+                for (int c = 0; c < NC; ++c) v[k][c] = blend(t00[c], t01[c], t10[c], t11[c], m2s[k]);
+            }
         }
         if (GRAY) {
             uint8_t* D = dst + (size_t)i * npx + p0;
-            uint32_t ga[4];
+            uint32_t ga[4][1], gao[1];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) ga[k] = weigh(v[k][0], v[k][1], v[k][2], w.w0, w.w1, w.w2, w);
+            for (int k = 0; k < 4; ++k) ga[k][0] = weigh(v[k][0], v[k][1], v[k][2], w.w0, w.w1, w.w2, w);
             if (full && ((reinterpret_cast<uintptr_t>(D) & 3) == 0)) {
-                *reinterpret_cast<uint32_t*>(D) = ga[0] | (ga[1] << 8) | (ga[2] << 16) | (ga[3] << 24);
+                pack_quad<1>(ga, gao);
+                *reinterpret_cast<uint32_t*>(D) = gao[0];
             } else {
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    if (p0 + k < npx) D[k] = (uint8_t)ga[k];
+                    if (p0 + k < npx) D[k] = (uint8_t)ga[k][0];
             }
             if (dstb) {
                 uint8_t* E = dstb + (size_t)i * npx + p0;
-                uint32_t gb[4];
+                uint32_t gb[4][1], gbo[1];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) gb[k] = weigh(v[k][0], v[k][1], v[k][2], w.w2, w.w1, w.w0, w);
+                for (int k = 0; k < 4; ++k) gb[k][0] = weigh(v[k][0], v[k][1], v[k][2], w.w2, w.w1, w.w0, w);
                 if (full && ((reinterpret_cast<uintptr_t>(E) & 3) == 0)) {
-                    *reinterpret_cast<uint32_t*>(E) = gb[0] | (gb[1] << 8) | (gb[2] << 16) | (gb[3] << 24);
+                    pack_quad<1>(gb, gbo);
+                    *reinterpret_cast<uint32_t*>(E) = gbo[0];
                 } else {
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
-                        if (p0 + k < npx) E[k] = (uint8_t)gb[k];
+                        if (p0 + k < npx) E[k] = (uint8_t)gb[k][0];
                 }
             }
         } else {
             uint8_t* D = dst + ((size_t)i * npx + p0) * CH;
             if (full && ((reinterpret_cast<uintptr_t>(D) & 3) == 0)) {
-                uint32_t o[CH] = {};
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) {
-                        const int j = k * CH + c;
-                        o[j >> 2] |= v[k][c] << ((j & 3) * 8);
-                    }
+                uint32_t o[CH];
+                if constexpr (!GRAY) pack_quad<CH>(v, o);
 #pragma unroll
                 for (int c = 0; c < CH; ++c) reinterpret_cast<uint32_t*>(D)[c] = o[c];
             } else {
@@ -219,22 +223,6 @@ __global__ void __launch_bounds__(COLOR_BLOCK) rectify_color_kernel(const int4* 
             }
         }
     }
-}
-
-bool gray_weights(int order, int weights, GrayWeights* w) {
-    uint32_t blue, green, red;
-    if (weights == STVO_GRAY_Q14) {
-        blue = 1868u; green = 9617u; red = 4899u; w->shift = 14u;
-    } else if (weights == STVO_GRAY_Q15) {
-        blue = 3735u; green = 19235u; red = 9798u; w->shift = 15u;
-    } else
-        return false;
-    if (order != STVO_ORDER_BGR && order != STVO_ORDER_RGB) return false;
-    w->w0 = order == STVO_ORDER_BGR ? blue : red;
-    w->w1 = green;
-    w->w2 = order == STVO_ORDER_BGR ? red : blue;
-    w->rnd = 1u << (w->shift - 1u);
-    return true;
 }
 
 template <int CH>
@@ -291,43 +279,33 @@ struct CallBlock {
 template <int CH, bool GRAY>
 void launch_rect_ch(stvo_rectify* r, int n, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l, uint8_t* dst_r, uint8_t* dstb_l,
                     uint8_t* dstb_r, const GrayWeights& w) {
-    // image chunks as launch_remap's: enough blocks to fill 256 CUs a few times over, at least 4 images per thread where n allows
+    // image chunks by the bank's rule with every pair on this calibration (rectify_bank_plan.h)
     const int bx = (r->nquads + COLOR_BLOCK - 1) / COLOR_BLOCK;
-    const int want = std::max(1, (256 * 8 + 2 * bx - 1) / (2 * bx));
-    const int chunks = std::max(1, std::min(want, (n + 3) / 4));
-    const int per_chunk = (n + chunks - 1) / chunks;
-    const int gy = (n + per_chunk - 1) / per_chunk;
+    int per_chunk = 0;
+    const int gy = stvo::rbank_chunks(bx, n, &per_chunk);
     hipLaunchKernelGGL((rectify_color_kernel<CH, GRAY>), dim3(bx, gy, 2), dim3(COLOR_BLOCK), 0, r->ctx->stream, r->map1q(0), r->map2q(0),
                        r->map1q(1), r->map2q(1), src_l, src_r, dst_l, dst_r, dstb_l, dstb_r, n, per_chunk, r->cols, r->rows, r->nquads, w);
 }
 
-int check_color_images(const stvo_rectify* r, int n, int ch, const uint8_t* src_l, const uint8_t* src_r, const uint8_t* dst_l,
-                       const uint8_t* dst_r) {
-    if (!r || !src_l || !src_r || !dst_l || !dst_r || n <= 0 || n > r->B || (ch != 3 && ch != 4)) return STVO_ERR_INVALID_ARG;
-    const size_t bytes = (size_t)n * r->cols * r->rows * ch;
-    if (overlaps(dst_l, src_l, bytes) || overlaps(dst_l, src_r, bytes) || overlaps(dst_r, src_l, bytes) || overlaps(dst_r, src_r, bytes) ||
-        overlaps(dst_l, dst_r, bytes))
-        return STVO_ERR_INVALID_ARG;
-    return STVO_OK;
-}
+}  // namespace
 
-int launch_color_remap(stvo_rectify* r, int n, int ch, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l, uint8_t* dst_r) {
+int stvo_detail::launch_remap(stvo_rectify* r, int n, int ch, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l, uint8_t* dst_r) {
     stvo_ctx* ctx = r->ctx;
-    if (!r->cam.dist) {  // the reference copies (copyTo)
+    if (!r->cam.dist) {  // the reference copies (copyTo): a device-to-device copy on the context's stream
         const size_t bytes = (size_t)n * r->cols * r->rows * ch;
         HIP_TRY(ctx, hipMemcpyAsync(dst_l, src_l, bytes, hipMemcpyDeviceToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(dst_r, src_r, bytes, hipMemcpyDeviceToDevice, ctx->stream));
         return STVO_OK;
     }
     const GrayWeights none{};
-    if (ch == 3)
+    if (ch == 1)
+        launch_rect_ch<1, false>(r, n, src_l, src_r, dst_l, dst_r, nullptr, nullptr, none);
+    else if (ch == 3)
         launch_rect_ch<3, false>(r, n, src_l, src_r, dst_l, dst_r, nullptr, nullptr, none);
     else
         launch_rect_ch<4, false>(r, n, src_l, src_r, dst_l, dst_r, nullptr, nullptr, none);
     return check_launch(ctx);
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -365,14 +343,16 @@ int stvo_color_to_gray(stvo_ctx* ctx, int n, int rows, int cols, int channels, i
 
 int stvo_rectify_color_images_dev(stvo_rectify* r, int n, int channels, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l,
                                   uint8_t* dst_r) {
-    TRY(check_color_images(r, n, channels, src_l, src_r, dst_l, dst_r));
+    if (channels != 3 && channels != 4) return STVO_ERR_INVALID_ARG;
+    TRY(check_images(r, n, channels, src_l, src_r, dst_l, dst_r));
     HIP_TRY(r->ctx, hipSetDevice(r->ctx->device));
-    return launch_color_remap(r, n, channels, src_l, src_r, dst_l, dst_r);
+    return launch_remap(r, n, channels, src_l, src_r, dst_l, dst_r);
 }
 
 int stvo_rectify_color_images(stvo_rectify* r, int n, int channels, const uint8_t* src_l, const uint8_t* src_r, uint8_t* dst_l,
                               uint8_t* dst_r) {
-    TRY(check_color_images(r, n, channels, src_l, src_r, dst_l, dst_r));
+    if (channels != 3 && channels != 4) return STVO_ERR_INVALID_ARG;
+    TRY(check_images(r, n, channels, src_l, src_r, dst_l, dst_r));
     stvo_ctx* ctx = r->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t bytes = (size_t)n * r->cols * r->rows * channels;
@@ -384,7 +364,7 @@ int stvo_rectify_color_images(stvo_rectify* r, int n, int channels, const uint8_
     const stvo::StereoStaging S = stvo::carve_color_rectify_staging(c, n, r->cols, r->rows, channels);
     HIP_TRY(ctx, hipMemcpyAsync(S.src_l, src_l, bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(S.src_r, src_r, bytes, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch_color_remap(r, n, channels, S.src_l, S.src_r, S.dst_l, S.dst_r));
+    TRY(launch_remap(r, n, channels, S.src_l, S.src_r, S.dst_l, S.dst_r));
     HIP_TRY(ctx, hipMemcpyAsync(dst_l, S.dst_l, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(dst_r, S.dst_r, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -399,12 +379,7 @@ int stvo_rectify_color_to_gray_dev(stvo_rectify* r, int n, int channels, int ord
         return STVO_ERR_INVALID_ARG;
     const size_t px = (size_t)n * r->cols * r->rows, sb = px * channels;
     const uint8_t* planes[4] = {gray_l, gray_r, swapped_l, swapped_r};
-    const int np = swapped_l ? 4 : 2;
-    for (int a = 0; a < np; ++a) {
-        if (overlaps(planes[a], px, src_l, sb) || overlaps(planes[a], px, src_r, sb)) return STVO_ERR_INVALID_ARG;
-        for (int b = a + 1; b < np; ++b)
-            if (overlaps(planes[a], planes[b], px)) return STVO_ERR_INVALID_ARG;
-    }
+    if (!gray_planes_ok(planes, swapped_l ? 4 : 2, px, src_l, src_r, sb)) return STVO_ERR_INVALID_ARG;
     stvo_ctx* ctx = r->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!r->cam.dist) {  // the reference's copy, then the consumers' conversion: the plain conversion of each side

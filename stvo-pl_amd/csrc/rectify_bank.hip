@@ -2,7 +2,7 @@
 // launch, over K resident stvo_rectify objects whose maps the bank borrows.  Source and destination are slot-shaped
 // ([n][slot_rows][slot_cols][channels]); image b is the top-left cols_k x rows_k of its slot at the slot's row pitch, the layout
 // stvo_orb_set_image_sizes reads.  Per pair the crop of the destination is bit for bit what rectifier k alone writes for the crop of the
-// source (rectify_kernels.hip / color_kernels.hip state the arithmetic: (X + 512) >> 10 per channel, a tap outside the IMAGE reads 0 —
+// source (rectify_px.h states the arithmetic, from which every primitive here is drawn: (X + 512) >> 10 per channel, a tap outside the IMAGE reads 0 —
 // also where it lies inside the slot — and cvtColor's integer weights behind the 8-bit rounding); nothing outside the crop is written.
 //
 //   rectify_bank_kernel<CH, GRAY>  one workgroup = one item of the plan (rectify_bank_plan.h: calibration, 256 quads, a list of pairs),
@@ -34,7 +34,6 @@ namespace {
 
 using stvo::RBANK_BLOCK;
 using stvo::RectBankItem;
-constexpr uint32_t INSIDE = 0x8000u;
 constexpr int COPY_BATCH = 8;  // pairs a copying thread has in flight
 
 // one calibration as the kernel reads it (workgroup-uniform: scalar loads)
@@ -45,47 +44,6 @@ struct BankCalib {
 };
 static_assert(sizeof(BankCalib) == 48, "four pointers and four words");
 
-struct GrayWeights {
-    uint32_t w0, w1, w2, rnd, shift;  // plane A; plane B swaps w0 and w2
-};
-
-__device__ __forceinline__ uint32_t weigh(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t w0, uint32_t w1, uint32_t w2,
-                                          const GrayWeights& w) {
-    return (w0 * c0 + w1 * c1 + w2 * c2 + w.rnd) >> w.shift;
-}
-
-__device__ __forceinline__ uint32_t blend(uint32_t s00, uint32_t s01, uint32_t s10, uint32_t s11, uint32_t m2) {
-    const uint32_t ax = m2 & 31u, ay = (m2 >> 5) & 31u;
-    const uint32_t top = __umul24(32u - ax, s00) + __umul24(ax, s01);
-    const uint32_t bot = __umul24(32u - ax, s10) + __umul24(ax, s11);
-    return (__umul24(32u - ay, top) + __umul24(ay, bot) + 512u) >> 10;
-}
-
-// The first NC channels of the pixel at p (color_kernels.hip: a 4-channel pixel is one unaligned 32-bit load).
-template <int CH, int NC>
-__device__ __forceinline__ void load_px(const uint8_t* __restrict__ p, uint32_t (&c)[NC]) {
-    if (CH == 4) {
-        uint32_t w;
-        __builtin_memcpy(&w, p, 4);
-#pragma unroll
-        for (int k = 0; k < NC; ++k) c[k] = (w >> (8 * k)) & 0xffu;
-    } else {
-#pragma unroll
-        for (int k = 0; k < NC; ++k) c[k] = p[k];
-    }
-}
-
-// (x, y) against the IMAGE (cols x rows), addressed at the slot's pitch
-template <int CH, int NC>
-__device__ __forceinline__ void tap_px(const uint8_t* __restrict__ S, int x, int y, int cols, int rows, size_t pitch_b, uint32_t (&c)[NC]) {
-    if ((unsigned)x < (unsigned)cols && (unsigned)y < (unsigned)rows) {
-        load_px<CH, NC>(S + (size_t)y * pitch_b + (size_t)x * CH, c);
-    } else {
-#pragma unroll
-        for (int k = 0; k < NC; ++k) c[k] = 0u;
-    }
-}
-
 // The quad's 4 pixels of CH bytes each into the slot at D (pixel k at byte D + at[k]): CH dwords where the quad is one run of a row,
 // else the pixels that exist by bytes.  The slot's pitch is not the image's width, so the run's address is dword-aligned only in some
 // rows (pitch 1242: every other row); the dwords are stored at whatever alignment the run has, as load_px reads its 4-channel pixels
@@ -94,14 +52,8 @@ template <int CH>
 __device__ __forceinline__ void store_quad(uint8_t* __restrict__ D, const uint32_t (&at)[4], bool one_run, const bool (&live)[4],
                                            const uint32_t (&v)[4][CH]) {
     if (one_run) {
-        uint32_t o[CH] = {};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int c = 0; c < CH; ++c) {
-                const int j = k * CH + c;
-                o[j >> 2] |= v[k][c] << ((j & 3) * 8);
-            }
+        uint32_t o[CH];
+        pack_quad<CH>(v, o);
         __builtin_memcpy(D + at[0], o, 4 * CH);
     } else {
 #pragma unroll
@@ -210,8 +162,7 @@ __global__ void __launch_bounds__(RBANK_BLOCK) rectify_bank_kernel(const BankCal
     bool all_inside = true;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        mx[k] = (int)(int16_t)(m1s[k] & 0xffff);
-        my[k] = m1s[k] >> 16;
+        map_tap(m1s[k], mx[k], my[k]);
         soff[k] = dist ? (uint32_t)my[k] * pitch_b + (uint32_t)mx[k] * CH : dpx[k] * CH;
         all_inside = all_inside && (m2s[k] & INSIDE);
     }
@@ -291,12 +242,13 @@ __global__ void __launch_bounds__(RBANK_BLOCK) rectify_bank_kernel(const BankCal
         }
         return;
     }
+    auto at = [&](int x, int y) { return (size_t)y * (size_t)pitch_b + (size_t)x * CH; };  // a pixel's offset in its slot
     for (int j = 0; j < it.pair_count; ++j) {
         const int b = table_word(list + j);
         if (b >= n) break;
         const uint8_t* S = src + (size_t)b * slot_px * CH;
         uint32_t v[4][NC];
-        if (all_inside) {  // (the branch outside the loop over the pixels, as in rectify_remap_kernel: one run of 16 loads)
+        if (all_inside) {  // (the branch outside the loop over the pixels, as in the one-channel uniform kernel: one run of 16 loads)
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 uint32_t t00[NC], t01[NC], t10[NC], t11[NC];
@@ -312,32 +264,16 @@ __global__ void __launch_bounds__(RBANK_BLOCK) rectify_bank_kernel(const BankCal
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 uint32_t t00[NC], t01[NC], t10[NC], t11[NC];
-                tap_px<CH, NC>(S, mx[k], my[k], cols, rows, pitch_b, t00);
-                tap_px<CH, NC>(S, mx[k] + 1, my[k], cols, rows, pitch_b, t01);
-                tap_px<CH, NC>(S, mx[k], my[k] + 1, cols, rows, pitch_b, t10);
-                tap_px<CH, NC>(S, mx[k] + 1, my[k] + 1, cols, rows, pitch_b, t11);
+                tap_px<CH, NC>(S, mx[k], my[k], cols, rows, at, t00);
+                tap_px<CH, NC>(S, mx[k] + 1, my[k], cols, rows, at, t01);
+                tap_px<CH, NC>(S, mx[k], my[k] + 1, cols, rows, at, t10);
+                tap_px<CH, NC>(S, mx[k] + 1, my[k] + 1, cols, rows, at, t11);
 #pragma unroll
                 for (int c = 0; c < NC; ++c) v[k][c] = blend(t00[c], t01[c], t10[c], t11[c], m2s[k]);
             }
         }
         emit(b, v);
     }
-}
-
-bool gray_weights(int order, int weights, GrayWeights* w) {
-    uint32_t blue, green, red;
-    if (weights == STVO_GRAY_Q14) {
-        blue = 1868u; green = 9617u; red = 4899u; w->shift = 14u;
-    } else if (weights == STVO_GRAY_Q15) {
-        blue = 3735u; green = 19235u; red = 9798u; w->shift = 15u;
-    } else
-        return false;
-    if (order != STVO_ORDER_BGR && order != STVO_ORDER_RGB) return false;
-    w->w0 = order == STVO_ORDER_BGR ? blue : red;
-    w->w1 = green;
-    w->w2 = order == STVO_ORDER_BGR ? red : blue;
-    w->rnd = 1u << (w->shift - 1u);
-    return true;
 }
 
 }  // namespace
@@ -480,9 +416,7 @@ int stvo_rectify_bank_images_dev(stvo_rectify_bank* k, int n, int channels, cons
     if (!k || !src_l || !src_r || !dst_l || !dst_r || n <= 0 || n > k->B || (channels != 1 && channels != 3 && channels != 4))
         return STVO_ERR_INVALID_ARG;
     const size_t bytes = (size_t)n * k->slot_cols * k->slot_rows * channels;
-    if (overlaps(dst_l, src_l, bytes) || overlaps(dst_l, src_r, bytes) || overlaps(dst_r, src_l, bytes) || overlaps(dst_r, src_r, bytes) ||
-        overlaps(dst_l, dst_r, bytes))
-        return STVO_ERR_INVALID_ARG;
+    if (!stereo_ranges_ok(dst_l, dst_r, src_l, src_r, bytes)) return STVO_ERR_INVALID_ARG;
     stvo_ctx* ctx = k->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const GrayWeights none{};
@@ -503,12 +437,7 @@ int stvo_rectify_bank_color_to_gray_dev(stvo_rectify_bank* k, int n, int channel
         return STVO_ERR_INVALID_ARG;
     const size_t px = (size_t)n * k->slot_cols * k->slot_rows, sb = px * channels;
     const uint8_t* planes[4] = {gray_l, gray_r, swapped_l, swapped_r};
-    const int np = swapped_l ? 4 : 2;
-    for (int a = 0; a < np; ++a) {
-        if (overlaps(planes[a], px, src_l, sb) || overlaps(planes[a], px, src_r, sb)) return STVO_ERR_INVALID_ARG;
-        for (int b = a + 1; b < np; ++b)
-            if (overlaps(planes[a], planes[b], px)) return STVO_ERR_INVALID_ARG;
-    }
+    if (!gray_planes_ok(planes, swapped_l ? 4 : 2, px, src_l, src_r, sb)) return STVO_ERR_INVALID_ARG;
     stvo_ctx* ctx = k->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (channels == 3)

@@ -3,11 +3,12 @@
 // laid out.  stvo_rectify_bank_assign runs plan_rectify_bank into pinned staging and uploads the result; the kernel only reads it.
 // Host-pure: g++ alone compiles it; tests/cpp/rectify_bank_plan_host.cpp runs everything here without a device.
 //
-// A quad is 4 consecutive output pixels of one image (the pixel index runs over rows * cols of the image's OWN size, as in
-// rectify_remap_kernel, so the resident maps of a rectifier are read as they are).  An item is one workgroup of RBANK_BLOCK threads per
+// A quad is 4 consecutive output pixels of one image (the pixel index runs over rows * cols of the image's OWN size, as in the
+// uniform kernel, so the resident maps of a rectifier are read as they are).  An item is one workgroup of RBANK_BLOCK threads per
 // side: thread t takes quad (qblock * RBANK_BLOCK + t) of calibration `calib`, loads its maps once and walks the item's pairs
-// pairs[pair_begin .. pair_begin + pair_count) with the maps in registers.  The pairs of a calibration are cut in chunks by the rule of
-// the uniform launch (launch_remap): enough workgroups to fill 256 CUs a few times over, at least 4 images per thread where there are.
+// pairs[pair_begin .. pair_begin + pair_count) with the maps in registers.  The pairs of a calibration are cut in chunks by
+// rbank_chunks: enough workgroups to fill 256 CUs a few times over, at least 4 images per thread where there are.  The uniform launch
+// (color_kernels.hip) cuts its n pairs by the same function, as one calibration that has them all.
 #pragma once
 
 #include <cstddef>
@@ -30,7 +31,7 @@ inline int rbank_qblocks(int cols, int rows) { return (rbank_nquads(cols, rows) 
 
 // chunks the m pairs of a calibration with `qblocks` quad blocks are cut in (m >= 1), and the pairs of every chunk but the last
 inline int rbank_chunks(int qblocks, int m, int* per_chunk) {
-    const int want = (256 * 8 + 2 * qblocks - 1) / (2 * qblocks);
+    const int want = (256 * 8 + 2 * qblocks - 1) / (2 * qblocks);  // (>= 1 for every qblocks >= 1: no max(1, want))
     int chunks = (m + 3) / 4;
     if (chunks > want) chunks = want;
     if (chunks < 1) chunks = 1;

@@ -271,32 +271,10 @@ class ImagePipeline:
             if self.adaptive_fast is not None:
                 self.seq.restart_fast_dev(self.fast_th, self.fast_threshold)
         ip = img_ptr if img_ptr is not None else (self.img if self.channels == 1 else self.color).data_ptr()
-        lp = None  # what the line detector and LBD read where it is not what ORB reads
-        if self.channels != 1:
-            side = self.B * self.rows * self.cols
-            ga = self.img.data_ptr()
-            gb = self.gray_b.data_ptr() if self.gray_b is not None else None
-            if self.bank is not None:
-                self.bank.rectify_color_to_gray_dev(self.B, self.channels, ip, ip + side * self.channels, ga, ga + side, gb,
-                                                    gb + side if gb is not None else None, weights=self.gray_weights)
-            elif self.rectify is not None:
-                self.rectify.rectify_color_to_gray_dev(self.B, self.channels, ip, ip + side * self.channels, ga, ga + side, gb,
-                                                       gb + side if gb is not None else None, weights=self.gray_weights)
-            else:
-                capi.color_to_gray_dev(self.ctx, 2 * self.B, self.rows, self.cols, self.channels, ip, ga, gb, weights=self.gray_weights)
-            ip, lp = ga, gb
-        elif self.rectify is not None:
-            side = self.B * self.rows * self.cols
-            rp = self.rect_img.data_ptr()
-            if self.bank is not None:
-                self.bank.rectify_dev(self.B, 1, ip, ip + side, rp, rp + side)
-            else:
-                self.rectify.rectify_dev(self.B, ip, ip + side, rp, rp + side)
-            ip = rp
+        ip, lp = self._grey_planes(ip)
         self.orb.detect_dev(ip, self.kp.data_ptr(), self.resp.data_ptr(), self.ang.data_ptr(), self.desc.data_ptr(),
                             self.n.data_ptr(), octave=self.oct.data_ptr())
         if self.lines is not None:
-            lp = ip if lp is None else lp
             self.lines.detect_dev(lp, self.kl.data_ptr(), None, self.nl.data_ptr())
             self.lbd.compute_dev(lp, self.kl.data_ptr(), self.nl.data_ptr(), self.ldesc.data_ptr())
             self.ctx._chk(self.ctx.lib.stvo_keylines_xy_dev(self.ctx.h, 2 * self.B, self.M, self.kl.data_ptr(), self.nl.data_ptr(), self.kl_xy.data_ptr()))
@@ -305,6 +283,33 @@ class ImagePipeline:
         if self.adaptive_fast is not None:
             self.seq.adapt_fast_dev(self.adaptive_fast, self.fast_th)
         self.slot ^= 1
+
+    def _grey_planes(self, ip):
+        """The frame at ip (raw or rectified, grey or colour, as the pipeline was made) -> (the grey planes ORB reads, the grey planes the
+        line detector and LBD read): rectified first where there is a rectifier or a bank, the colour -> grey conversion fused into that
+        pass; the two differ only with colour frames and a swapped plane (gray_b)."""
+        side = self.B * self.rows * self.cols
+        if self.channels != 1:
+            ga = self.img.data_ptr()
+            gb = self.gray_b.data_ptr() if self.gray_b is not None else None
+            gb_r = gb + side if gb is not None else None
+            if self.bank is not None:
+                self.bank.rectify_color_to_gray_dev(self.B, self.channels, ip, ip + side * self.channels, ga, ga + side, gb, gb_r,
+                                                    weights=self.gray_weights)
+            elif self.rectify is not None:
+                self.rectify.rectify_color_to_gray_dev(self.B, self.channels, ip, ip + side * self.channels, ga, ga + side, gb, gb_r,
+                                                       weights=self.gray_weights)
+            else:
+                capi.color_to_gray_dev(self.ctx, 2 * self.B, self.rows, self.cols, self.channels, ip, ga, gb, weights=self.gray_weights)
+            return ga, (gb if gb is not None else ga)
+        if self.rectify is None:
+            return ip, ip
+        rp = self.rect_img.data_ptr()
+        if self.bank is not None:
+            self.bank.rectify_dev(self.B, 1, ip, ip + side, rp, rp + side)
+        else:
+            self.rectify.rectify_dev(self.B, ip, ip + side, rp, rp + side)
+        return rp, rp
 
     def push_images(self, left, right, control=None, cams=None, calibs=None):
         """One frame of every stream: (pose results [B], counts [B, 4]) like Sequences.push.  control, cams, calibs: as for enqueue (the

@@ -1,7 +1,7 @@
 """Rectification throughput (stvo_rectify_images_dev) and its cost inside the images -> poses step.
 
   python tools/bench_rectify.py [--out profiles/rectify_bench.json]     (GPU)
-  python tools/bench_rectify.py --isa                                   (no GPU: instruction mix of rectify_remap_kernel)
+  python tools/bench_rectify.py --isa                                   (no GPU: instruction mix of the one-channel remap kernel)
 
 Remap: EuRoC calibration (tests/golden/dataset_params/euroc_params.yaml), 752 x 480, n = 1, 64 and 3072 pairs per launch (2 n
 images), device buffers, hipEvent-free timing = host clock around `iters` launches ended by a device synchronise, after a warm-up.
@@ -24,11 +24,11 @@ HBM_BYTES_PER_S = 8.0e12  # MI355X peak HBM3E bandwidth (8 TB/s); the ceiling of
 
 
 def isa_mix():
-    src = os.path.join(ROOT, "stvo-pl_amd", "csrc", "rectify_kernels.hip")
+    src = os.path.join(ROOT, "stvo-pl_amd", "csrc", "color_kernels.hip")  # rectify_color_kernel<1, false>: the grey remap
     inc = os.path.join(ROOT, "stvo-pl_amd", "csrc")
     asm = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", "-I", inc, src,
                           "-o", "-"], capture_output=True, text=True, check=True).stdout
-    body = asm.split("rectify_remap_kernel", 1)[1]
+    body = asm.split("rectify_color_kernelILi1ELb0EE", 1)[1].split(":", 1)[1]
     body = body.split("s_endpgm", 1)[0]
     counts = {}
     for line in body.splitlines():
