@@ -548,6 +548,13 @@ int stvo_lbd_compute(stvo_lbd* lbd, const uint8_t* images, const stvo_keyline* l
 /* The same with DEVICE pointers, enqueued on the context's stream (no synchronisation). */
 int stvo_lbd_compute_dev(stvo_lbd* lbd, const uint8_t* images, const stvo_keyline* lines, const int32_t* n_lines, uint8_t* desc,
                          float* desc_float);
+/* One image SIZE per image for the following calls: the contract of stvo_orb_set_image_sizes (image i is sizes_host[i % n] = {cols,
+ * rows}, n divides B, top-left of its slot at the slot's pitch, the rest of the slot influences nothing).  The descriptors, and the
+ * float descriptors where asked for, of image i's key-lines are bit for bit those of a descriptor object created at (cols_i, rows_i)
+ * on the crop: the 5 x 5 blur and the Sobel reflect at the image's own border and the support region is clamped to the image's own
+ * last column and row.  STVO_ERR_INVALID_ARG and nothing changes: n <= 0, n > B, B % n != 0, an entry larger than the slot or below
+ * 8 x 8.  No synchronisation; sizes_host == NULL: every image fills its slot again, on the kernels of an object never given a table. */
+int stvo_lbd_set_image_sizes(stvo_lbd* lbd, const int32_t* sizes_host /* [n][2] = cols, rows */, int n);
 
 /* ---- LSD line detector (second half) -------------------------------------------------------- */
 
@@ -612,6 +619,29 @@ int stvo_lsd_segments(stvo_lsd* lsd, const uint8_t* images, float* segments, int
 /* test hook: the image the detector core sees — blurred and resized (the input itself at scale 1) — host buffers, synchronises:
  * images [B][rows][cols] in, scaled [B][scaled_rows][scaled_cols] out (sizes: stvo_lsd_geometry); nothing is detected */
 int stvo_lsd_scaled_image(stvo_lsd* lsd, const uint8_t* images, uint8_t* scaled);
+/* One image SIZE, and minimum line length, per image for the following calls: the contract of stvo_orb_set_image_sizes.  Image i of the B
+ * images is sizes_host[i % n] = {cols, rows}; n must divide B.  The image buffer keeps the layout [B][rows][cols] of the size given at
+ * creation (the slot): image i occupies the top-left cols_i x rows_i of its slot and keeps the slot's row pitch; the bytes of the slot
+ * outside the image influence nothing.  min_length_host[i % n] is the image's minimum line length (the reference's
+ * Config::minLineLength() x min(width, height) of the sequence's camera); min_length_host == NULL: every entry keeps the detector's
+ * min_length.  What comes back for image i is, bit for bit, what a detector created at (cols_i, rows_i) with that min_length returns
+ * for the crop — key-line records, responses, n_lines, stvo_lsd_counts, stvo_lsd_segments, and the top-left scaled cols_i x scaled
+ * rows_i of its slot of stvo_lsd_scaled_image (the slot's scaled pitch; the rest of that slot is not defined) — through every detect
+ * entry point, for lsd_refine 0 and 1 and at every n_bins: the gradient's bounds, the largest gradient and the bins, the units of the
+ * pseudo-ordering, the search's image and its smallest region, the clamps, the response divisor and the pixel count of a key-line are
+ * all the image's own.
+ *   The route: with a table set the search runs ONE wavefront per image at every batch size; the many-wave form that a detector of up
+ * to 128 images otherwise uses is not launched under a table (mixed sizes are the many-streams case; a small batch under a table pays
+ * the one-wave time: README, profiles/mixed_lines_bench.json).
+ *   STVO_ERR_INVALID_ARG and nothing changes: n <= 0, n > B, B % n != 0, an entry larger than the slot, an entry stvo_lsd_create would
+ * refuse as an image size (a side below 8, nothing left after scaling), a NaN minimum length.  STVO_ERR_UNSUPPORTED and nothing
+ * changes: a detector whose blur radius is not 3 at a scale other than 1 (stvo_lsd_geometry tells the radius; every shipped yaml but
+ * lsd_scale : 0.5 gives 3) — its fused blur + resize plans its tile per size.  sizes_host and min_length_host are read during the
+ * call; the table travels on the context's stream behind the detections already enqueued, through pinned staging that is not reused
+ * before its copy has completed: no synchronisation.  The device table is allocated at the first call; sizes_host == NULL: every image
+ * fills its slot again, on the very kernels of a detector that was never given a table. */
+int stvo_lsd_set_image_sizes(stvo_lsd* lsd, const int32_t* sizes_host /* [n][2] = cols, rows */, const double* min_length_host /* [n] or NULL */,
+                             int n);
 
 /* ---- FLD line detector (use_fld_lines = true) -------------------------------------------------------------------------- */
 

@@ -215,11 +215,16 @@ void launch_stream_signal(hipStream_t s, unsigned* flag, unsigned value);
 
 // ---- 8-bit image operations of the ORB front-end that the line detector reuses (orb_kernels.hip) ----
 // cv::GaussianBlur(7 x 7) in 8-bit fixed point with the integer kernel k7 (weights x 2^8), BORDER_REFLECT_101
-void launch_blur7_u8(hipStream_t s, int B, int cols, int rows, const uint8_t* src, uint8_t* dst, const int* k7);
+// sz (device, or nullptr: every image fills cols x rows): one size per image, image b being the top-left of its cols x rows slot at the
+// slot's pitch, sized by row (b % n_sz) * sz_stride + level of the table (orb_sizes.h) — the MIXED instance of the kernel
+struct OrbLevelSize;
+void launch_blur7_u8(hipStream_t s, int B, int cols, int rows, const uint8_t* src, uint8_t* dst, const int* k7, const OrbLevelSize* sz = nullptr,
+                     int n_sz = 0, int sz_stride = 0, int level = 0);
 // cv::resize(INTER_LINEAR) for 8-bit images, 11-bit fixed point; fx = fy = 0: resize to a given dsize (sample step ssize / dsize),
-// fx, fy > 0: resize(src, dst, Size(), fx, fy) with dsize = cvRound(ssize f) — the sample step stays 1 / f (LSD's scaled image)
+// fx, fy > 0: resize(src, dst, Size(), fx, fy) with dsize = cvRound(ssize f) — the sample step stays 1 / f (LSD's scaled image).
+// sz: as above, from row `level - 1` (the source) to row `level` (the destination and its inverse scales) of image b's entry
 void launch_resize_linear_u8(hipStream_t s, int B, int scols, int srows, int dcols, int drows, const uint8_t* src, uint8_t* dst, double fx = 0.0,
-                             double fy = 0.0);
+                             double fy = 0.0, const OrbLevelSize* sz = nullptr, int n_sz = 0, int sz_stride = 0, int level = 0);
 // ---- the same two operations fused, for every blur radius 0 .. STVO_LSD_MAX_RADIUS (lsd_scale_kernels.hip) ----
 // cv::GaussianBlur((1 + 2 radius)^2) with the integer weights (x 2^8, 32-bit: one can be 256) + cv::resize(…, Size(), scale, scale):
 // one workgroup per tile of the scaled image, the blurred bytes only in LDS.  The plan (tile, dynamic LDS) depends on the geometry

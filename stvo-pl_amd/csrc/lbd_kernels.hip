@@ -20,6 +20,8 @@
 #include "ctx_internal.h"
 #include "frontend_layout.h"
 #include "gaussian_q8.h"
+#include "lsd_sizes.h"
+#include "table_transport.h"
 
 #pragma clang fp contract(off)
 
@@ -43,6 +45,30 @@ struct LbdDev {
     float coefL[3 * LBD_W];      // (float) gaussCoefL_[k]
 };
 
+// One image size per image (stvo_lbd_set_image_sizes): image i is the top-left cols x rows of row i % n_sz of the table inside its slot,
+// whose pitch blur and dxy keep.  An argument of its own behind LbdDev, and empty for the uniform instances.
+template <bool MIXED>
+struct LbdTable {};
+template <>
+struct LbdTable<true> {
+    const OrbLevelSize* sz;
+    int n_sz;
+};
+
+// The image a workgroup works on.  MIXED = false: the slot itself — the kernel as it was.  MIXED = true: the image's size from its row
+// of the table (the image index is a block index: uniform, scalar loads; clamped into the slot) takes the place of the slot's — in the
+// Sobel kernel's own copy of its argument, so the code below the call is one text for both; in locals in the describe kernel.  The
+// uniform instances do not make the call (if constexpr) and are the code they were (profiles/mixed_lines_kernel_resources.txt).
+// LbdSlot: the slot's size, taken before the call — the stride of an image's blocks and the pitch of their rows.
+struct LbdSlot {
+    int rows, cols;
+};
+__device__ __forceinline__ void lbd_take_image(int& cols, int& rows, const LbdTable<true>& tab, int b) {
+    const OrbLevelSize* e = tab.sz + (b % tab.n_sz);
+    cols = __builtin_amdgcn_readfirstlane(min(max(e->cols, 1), cols));
+    rows = __builtin_amdgcn_readfirstlane(min(max(e->rows, 1), rows));
+}
+
 __device__ __forceinline__ int reflect101(int p, int n) {
     while (p < 0 || p >= n) {
         if (p < 0) p = -p;
@@ -61,11 +87,16 @@ __device__ __forceinline__ int reflect101(int p, int n) {
 typedef uint32_t __attribute__((aligned(1))) lbd_u32_unaligned;
 typedef int32_t lbd_i32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 constexpr int SB_R = 16, SB_T = 64;
-__global__ __launch_bounds__(SB_T) void lbd_sobel_kernel(LbdDev o) {
+template <bool MIXED>
+__global__ __launch_bounds__(SB_T) void lbd_sobel_kernel(LbdDev o, LbdTable<MIXED> tab) {
     const int b = blockIdx.z, x = (blockIdx.x * SB_T + threadIdx.x) * 4, y0 = blockIdx.y * SB_R;
+    const LbdSlot slot{o.rows, o.cols};
+    if constexpr (MIXED) lbd_take_image(o.cols, o.rows, tab, b);  // reflection, the word loads and the 16-byte store end at the image's own border
+    if constexpr (MIXED)
+        if (y0 >= o.rows) return;
     if (x >= o.cols) return;
-    const uint8_t* img = o.blur + (size_t)b * o.rows * o.cols;
-    int32_t* out = o.dxy + (size_t)b * o.rows * o.cols;
+    const uint8_t* img = o.blur + (size_t)b * slot.rows * slot.cols;
+    int32_t* out = o.dxy + (size_t)b * slot.rows * slot.cols;
     const bool inner = x >= 1 && x + 5 <= o.cols;
     int xr[6];
 #pragma unroll
@@ -79,7 +110,7 @@ __global__ __launch_bounds__(SB_T) void lbd_sobel_kernel(LbdDev o) {
     for (int r = 0; r < SB_R + 2; ++r) {
         const int yo = y0 + r - 2;  // the output row completed by this input row
         if (r >= 2 && yo >= o.rows) break;  // uniform over the workgroup
-        const uint8_t* row = img + (size_t)reflect101(y0 + r - 1, o.rows) * o.cols;
+        const uint8_t* row = img + (size_t)reflect101(y0 + r - 1, o.rows) * slot.cols;
         int p[6];
         if (inner) {
             const uint32_t wa = *reinterpret_cast<const lbd_u32_unaligned*>(row + x - 1), wb = *reinterpret_cast<const lbd_u32_unaligned*>(row + x + 1);
@@ -97,28 +128,29 @@ __global__ __launch_bounds__(SB_T) void lbd_sobel_kernel(LbdDev o) {
             sx[2][i] = p[i] + 2 * p[i + 1] + p[i + 2];
         }
         if (r >= 2) {
-            int32_t* dst = out + (size_t)yo * o.cols + x;
-            int32_t g[4];
+            int32_t* dst = out + (size_t)yo * slot.cols + x;
+            int32_t gv[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int gx = hx[0][i] + 2 * hx[1][i] + hx[2][i], gy = sx[2][i] - sx[0][i];
-                g[i] = (int32_t)(((uint32_t)gx & 0xFFFFu) | ((uint32_t)gy << 16));  // (|g| <= 1020: int16 halves)
+                gv[i] = (int32_t)(((uint32_t)gx & 0xFFFFu) | ((uint32_t)gy << 16));  // (|g| <= 1020: int16 halves)
             }
             if (x + 4 <= o.cols) {  // one 16-byte store (word-aligned: the rows of an image of odd width are not 16-byte aligned)
                 lbd_i32x4_a4 v;
-                v.x = g[0]; v.y = g[1]; v.z = g[2]; v.w = g[3];
+                v.x = gv[0]; v.y = gv[1]; v.z = gv[2]; v.w = gv[3];
                 *reinterpret_cast<lbd_i32x4_a4*>(dst) = v;
             } else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    if (x + i < o.cols) dst[i] = g[i];
+                    if (x + i < o.cols) dst[i] = gv[i];
             }
         }
     }
 }
 
 constexpr int LBD_LINES_PER_WG = 4;
-__global__ __launch_bounds__(64 * LBD_LINES_PER_WG) void lbd_describe_kernel(LbdDev o) {
+template <bool MIXED>
+__global__ __launch_bounds__(64 * LBD_LINES_PER_WG) void lbd_describe_kernel(LbdDev o, LbdTable<MIXED> tab) {
     __shared__ float s_row[LBD_LINES_PER_WG][LBD_ROWS][8];
     __shared__ float s_des[LBD_LINES_PER_WG][LBD_DESC];
     __shared__ float s_norm[LBD_LINES_PER_WG][2];
@@ -127,7 +159,8 @@ __global__ __launch_bounds__(64 * LBD_LINES_PER_WG) void lbd_describe_kernel(Lbd
     const int n = min(max(o.n_lines[b], 0), o.M);
     if (l >= n) return;  // wave-uniform (no workgroup barrier below: every synchronisation is inside the wave)
     const stvo_keyline kl = o.lines[(size_t)b * o.M + l];
-    const int32_t* pdxy = o.dxy + (size_t)b * o.rows * o.cols;
+    const LbdSlot slot{o.rows, o.cols};
+    const int32_t* pdxy = o.dxy + (size_t)b * slot.rows * slot.cols;
     float (*row)[8] = s_row[wv];
     float* des = s_des[wv];
     auto wave_sync = [] {
@@ -136,7 +169,15 @@ __global__ __launch_bounds__(64 * LBD_LINES_PER_WG) void lbd_describe_kernel(Lbd
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     };
     // ---- computeLBD :1101-1135
-    const int imageWidth = o.cols - 1, imageHeight = o.rows - 1, realWidth = o.cols;
+    int imageWidth = o.cols - 1, imageHeight = o.rows - 1;
+    const int realWidth = slot.cols;  // (the pitch of dxy's rows: the slot's)
+    if constexpr (MIXED) {
+        // the image's own last column and row, into locals: a store into this kernel's copy of its argument would move the whole of it,
+        // the weight tables it indexes by lane included, into scratch memory
+        int cols = o.cols, rows = o.rows;
+        lbd_take_image(cols, rows, tab, b);
+        imageWidth = cols - 1; imageHeight = rows - 1;
+    }
     const int halfHeight = (LBD_ROWS - 1) / 2;
     const int lengthOfLSP = (int)(short)kl.num_pixels, halfWidth = (lengthOfLSP - 1) / 2;
     const float midX = (float)(0.5 * (double)(kl.sx + kl.ex)), midY = (float)(0.5 * (double)(kl.sy + kl.ey));
@@ -275,6 +316,9 @@ struct stvo_lbd {
     stvo::LbdDev d{};
     char* dev = nullptr;  // blur | (dx, dy)
     Staging io;           // staging of the host-buffer entry point
+    // one image size per image (stvo_lbd_set_image_sizes): nothing of it exists until the first call
+    TableTransport sizes;
+    int n_sizes = 0;      // entries of the table in force; 0: every image fills its slot
 };
 
 extern "C" {
@@ -323,7 +367,28 @@ int stvo_lbd_destroy(stvo_lbd* o) {
     (void)hipStreamSynchronize(o->ctx->stream);
     if (o->dev) (void)hipFree(o->dev);
     if (o->io.p) (void)hipFree(o->io.p);
+    o->sizes.destroy();
     delete o;
+    return STVO_OK;
+}
+
+// One image size per image (stvo_hip.h): validated before anything changes, the table as table_transport.h says.
+int stvo_lbd_set_image_sizes(stvo_lbd* o, const int32_t* sizes_host, int n) {
+    if (!o) return STVO_ERR_INVALID_ARG;
+    if (!sizes_host) {  // every image fills its slot again: the uniform kernel instances, which read no table
+        o->n_sizes = 0;
+        return STVO_OK;
+    }
+    const stvo::LbdDev& d = o->d;
+    if (!stvo::lbd_image_sizes_ok(sizes_host, n, d.B, d.cols, d.rows)) return STVO_ERR_INVALID_ARG;
+    stvo_ctx* ctx = o->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    char* tab = o->sizes.begin(ctx, (size_t)d.B * sizeof(stvo::OrbLevelSize));
+    if (!tab) return STVO_ERR_HIP;
+    stvo::OrbLevelSize* rows = reinterpret_cast<stvo::OrbLevelSize*>(tab);
+    for (int i = 0; i < n; ++i) rows[i] = stvo::OrbLevelSize{sizes_host[2 * i], sizes_host[2 * i + 1], 1.0, 1.0, 1, 0};
+    TRY(o->sizes.send(ctx, (size_t)n * sizeof(stvo::OrbLevelSize)));
+    o->n_sizes = n;
     return STVO_OK;
 }
 
@@ -334,14 +399,23 @@ int stvo_lbd_compute_dev(stvo_lbd* o, const uint8_t* images, const stvo_keyline*
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     stvo::LbdDev d = o->d;
     d.img = images; d.lines = lines; d.n_lines = n_lines; d.desc = desc; d.desc_f = desc_float;
+    const stvo::LbdTable<true> tab{o->n_sizes ? reinterpret_cast<const stvo::OrbLevelSize*>(o->sizes.dev) : nullptr, o->n_sizes};
     hipStream_t s = ctx->stream;
     {   // GaussianBlur(5 x 5, sigma 1): the shared 7-tap blur with zero outer weights (the same fixed-point arithmetic: weights x 2^8 per pass, (s + 2^15) >> 16)
         const int k7[7] = {0, d.k5[0], d.k5[1], d.k5[2], d.k5[3], d.k5[4], 0};
-        stvo::launch_blur7_u8(s, d.B, d.cols, d.rows, images, d.blur, k7);
+        stvo::launch_blur7_u8(s, d.B, d.cols, d.rows, images, d.blur, k7, tab.sz, tab.n_sz, 1, 0);
     }
-    hipLaunchKernelGGL(stvo::lbd_sobel_kernel, dim3((d.cols + 4 * stvo::SB_T - 1) / (4 * stvo::SB_T), (d.rows + stvo::SB_R - 1) / stvo::SB_R, d.B), dim3(stvo::SB_T), 0, s, d);
-    hipLaunchKernelGGL(stvo::lbd_describe_kernel, dim3((d.M + stvo::LBD_LINES_PER_WG - 1) / stvo::LBD_LINES_PER_WG, d.B),
-                       dim3(64 * stvo::LBD_LINES_PER_WG), 0, s, d);
+    // one size per image: the MIXED instances on the slots' launch grids
+    const dim3 sgrid((d.cols + 4 * stvo::SB_T - 1) / (4 * stvo::SB_T), (d.rows + stvo::SB_R - 1) / stvo::SB_R, d.B);
+    const dim3 dgrid((d.M + stvo::LBD_LINES_PER_WG - 1) / stvo::LBD_LINES_PER_WG, d.B);
+    if (tab.sz) {
+        hipLaunchKernelGGL(stvo::lbd_sobel_kernel<true>, sgrid, dim3(stvo::SB_T), 0, s, d, tab);
+        hipLaunchKernelGGL(stvo::lbd_describe_kernel<true>, dgrid, dim3(64 * stvo::LBD_LINES_PER_WG), 0, s, d, tab);
+    } else {
+        const stvo::LbdTable<false> none{};
+        hipLaunchKernelGGL(stvo::lbd_sobel_kernel<false>, sgrid, dim3(stvo::SB_T), 0, s, d, none);
+        hipLaunchKernelGGL(stvo::lbd_describe_kernel<false>, dgrid, dim3(64 * stvo::LBD_LINES_PER_WG), 0, s, d, none);
+    }
     return check_launch(ctx);
 }
 

@@ -34,6 +34,9 @@
 //                        (LsdProbe) and run only while stvo_lsd_debug has them switched on; the shipped instances hold none of it
 //   lsd_keylines_kernel  the wrapper: checkLineExtremes, length, min_length, KeyLine fields (numOfPixels = the CLIPPED cv::LineIterator
 //                        count), top-N by response (stable)
+// Every kernel but lsd_grow_xcd_kernel is a template on MIXED: the MIXED instances read their image's row of a size table (one image size
+// and minimum length per image, stvo_lsd_set_image_sizes, csrc/lsd_sizes.h), the others are the kernels as they were.  Under a table the
+// search runs ONE wave per image at every batch size (lsd_grow_kernel / lsd_grow_refine_kernel); lsd_grow_xcd_kernel is not launched.
 // Byte / integer work except where the source computes in floating point; no fused multiply-adds outside the two of the sine /
 // cosine reduction, which the oracle has too.
 #include <cmath>
@@ -45,6 +48,8 @@
 #include "frontend_layout.h"
 #include "gaussian_q8.h"
 #include "line_common.h"
+#include "lsd_sizes.h"
+#include "table_transport.h"
 
 #pragma clang fp contract(off)
 
@@ -89,11 +94,50 @@ struct LsdDev {
     int32_t* n_lines;          // [B]
 };
 
+// One image size per image (stvo_lsd_set_image_sizes): image i is sized by row i % n_sz of the table.  An argument of its own behind
+// LsdDev, and empty for the uniform instances — they take the arguments they always took.
+template <bool MIXED>
+struct LsdTable {};
+template <>
+struct LsdTable<true> {
+    const LsdSizeRow* sz;
+    int n_sz;
+};
+
+// The image a workgroup works on.  MIXED = false: the slot itself — the kernel as it was, reading its argument.  MIXED = true: the
+// kernel's own copy of its argument takes the image's sizes, smallest region and minimum length from the image's row of the table in
+// place of the slot's, so the code below the call is one text for both.  Every kernel takes its image from a block index: the row is
+// uniform over the workgroup and is read with scalar loads; it is clamped into the slot, which the host has validated it to fit.
+// The uniform instances do not make the call (if constexpr): their code is the code they had, the argument's address never taken
+// (profiles/mixed_lines_kernel_resources.txt).  LsdSlot: the slot's scaled size, taken before the call.  The per-image stride of the
+// search arrays (px, k32, order, reg: the slot's w h; cnt: the slot's units) stays the slot's; INSIDE its block an image indexes them
+// compactly with its own w, so the search routines keep one w for pitch and bound (std::rint is monotone: an image's scaled size, and
+// with it its pixels and units, never exceed the slot's — lsd_sizes.h).  Only the gradient kernel reads the scaled image, at the
+// slot's pitch.
+struct LsdSlot {
+    int w, h;
+};
+__device__ __forceinline__ void lsd_take_image(LsdDev& d, const LsdTable<true>& tab, int b) {
+    const LsdSizeRow* e = tab.sz + (b % tab.n_sz);
+    d.w = __builtin_amdgcn_readfirstlane(min(max(e->w, 1), d.w));
+    d.h = __builtin_amdgcn_readfirstlane(min(max(e->h, 1), d.h));
+    d.cols = __builtin_amdgcn_readfirstlane(min(max(e->cols, 1), d.cols));
+    d.rows = __builtin_amdgcn_readfirstlane(min(max(e->rows, 1), d.rows));
+    d.min_reg_size = __builtin_amdgcn_readfirstlane(e->min_reg_size);
+    d.min_length = e->min_length;
+}
+
 // ll_angle: one thread per pixel of the scaled image
-__global__ __launch_bounds__(256) void lsd_gradient_kernel(LsdDev d) {
+template <bool MIXED>
+__global__ __launch_bounds__(256) void lsd_gradient_kernel(LsdDev d, LsdTable<MIXED> tab) {
     const int x = blockIdx.x * 256 + threadIdx.x, b = blockIdx.z;
+    const LsdSlot slot{d.w, d.h};
+    if constexpr (MIXED) lsd_take_image(d, tab, b);
+    // a workgroup wholly outside its image has no pixel and no gradient to report: it leaves as a whole, before the reduction
+    if constexpr (MIXED)
+        if ((int)blockIdx.x * 256 >= d.w || (int)blockIdx.y * LSD_ROWS >= d.h) return;
     const bool in_row = x < d.w;  // (no early return: the whole wave takes part in the reduction below)
-    const size_t base = (size_t)b * d.w * d.h;
+    const size_t base = (size_t)b * slot.w * slot.h;
     int kw = -1;
     // LSD_ROWS rows per workgroup: one row each made 2.8 M workgroups per 1024 images and the launch dispatch-bound (25 ms)
     for (int y = blockIdx.y * LSD_ROWS; y < min((int)(blockIdx.y + 1) * LSD_ROWS, d.h); ++y) {
@@ -103,8 +147,8 @@ __global__ __launch_bounds__(256) void lsd_gradient_kernel(LsdDev d) {
     double norm = 0.0;
     int kdef = -1;
     if (x < d.w - 1 && y < d.h - 1) {
-        const uint8_t* r0 = d.scaled + base + (size_t)y * d.w + x;
-        const uint8_t* r1 = r0 + d.w;
+        const uint8_t* r0 = d.scaled + base + (size_t)y * slot.w + x;  // (the scaled image keeps the slot's pitch)
+        const uint8_t* r1 = r0 + slot.w;
         const int DA = (int)r1[1] - (int)r0[0], BC = (int)r0[1] - (int)r1[0];
         const int gx = DA + BC, gy = DA - BC;
         const int k = gx * gx + gy * gy;
@@ -154,30 +198,38 @@ __device__ __forceinline__ int lsd_keybin(int k, double bin_coef, int n_bins) {
     return n_bins - 1 - bin;
 }
 
-__global__ __launch_bounds__(256) void lsd_hist_kernel(LsdDev d) {
+template <bool MIXED>
+__global__ __launch_bounds__(256) void lsd_hist_kernel(LsdDev d, LsdTable<MIXED> tab) {
     extern __shared__ unsigned s_h[];  // [4][n_bins]
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, b = blockIdx.y;
+    const LsdSlot slot{d.w, d.h};
+    if constexpr (MIXED) lsd_take_image(d, tab, b);
+    const int slot_px = slot.w * slot.h, slot_units = (slot_px + LSD_UNIT - 1) / LSD_UNIT;  // the strides of an image's blocks
     const int npx = d.w * d.h, nunits = (npx + LSD_UNIT - 1) / LSD_UNIT, unit = blockIdx.x * 4 + wv;
-    if (unit >= nunits) return;
+    if (unit >= nunits) return;  // (wave-private LDS, no workgroup barrier below)
     unsigned* h = s_h + wv * d.n_bins;
     for (int t = lane; t < d.n_bins; t += 64) h[t] = 0u;
     const double bin_coef = lsd_bin_coef(d, b);
-    const int32_t* k32 = d.k32 + (size_t)b * npx;
+    const int32_t* k32 = d.k32 + (size_t)b * slot_px;
 #pragma unroll 8
     for (int r = 0; r < LSD_UNIT_ROWS; ++r) {
         const int i = unit * LSD_UNIT + r * 64 + lane;
         const int k = i < npx ? k32[i] : -1;
         if (k >= 0) atomicAdd(&h[lsd_keybin(k, bin_coef, d.n_bins)], 1u);
     }
-    unsigned* out = d.cnt + ((size_t)b * nunits + unit) * d.n_bins;
+    unsigned* out = d.cnt + ((size_t)b * slot_units + unit) * d.n_bins;
     for (int t = lane; t < d.n_bins; t += 64) out[t] = h[t];
 }
 
-__global__ __launch_bounds__(1024) void lsd_scan_kernel(LsdDev d) {
+template <bool MIXED>
+__global__ __launch_bounds__(1024) void lsd_scan_kernel(LsdDev d, LsdTable<MIXED> tab) {
     __shared__ unsigned s_w[16];
     const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const LsdSlot slot{d.w, d.h};
+    if constexpr (MIXED) lsd_take_image(d, tab, b);
+    const int slot_px = slot.w * slot.h, slot_units = (slot_px + LSD_UNIT - 1) / LSD_UNIT;
     const int npx = d.w * d.h, nunits = (npx + LSD_UNIT - 1) / LSD_UNIT, nb = d.n_bins;
-    unsigned* cnt = d.cnt + (size_t)b * nunits * nb;
+    unsigned* cnt = d.cnt + (size_t)b * slot_units * nb;
     unsigned carry = 0u;  // pixels of all the bins in front
     for (int t0 = 0; t0 < nb; t0 += 1024) {  // (n_bins <= 2048: one or two turns)
         const int bin = t0 + t;
@@ -211,20 +263,24 @@ __global__ __launch_bounds__(1024) void lsd_scan_kernel(LsdDev d) {
         carry += all;
     }
     // the end mark: every reader walks the ranks in batches of 64 and stops at the first batch whose first rank holds LSD_NOKEY
-    if (t < 128 && carry + (unsigned)t < (unsigned)npx) d.order[(size_t)b * npx + carry + t] = LSD_NOKEY;
+    if (t < 128 && carry + (unsigned)t < (unsigned)npx) d.order[(size_t)b * slot_px + carry + t] = LSD_NOKEY;
 }
 
-__global__ __launch_bounds__(256) void lsd_scatter_kernel(LsdDev d) {
+template <bool MIXED>
+__global__ __launch_bounds__(256) void lsd_scatter_kernel(LsdDev d, LsdTable<MIXED> tab) {
     extern __shared__ unsigned s_h[];  // [4][n_bins] the next rank of every bin, for this wave's unit
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, b = blockIdx.y;
+    const LsdSlot slot{d.w, d.h};
+    if constexpr (MIXED) lsd_take_image(d, tab, b);
+    const int slot_px = slot.w * slot.h, slot_units = (slot_px + LSD_UNIT - 1) / LSD_UNIT;
     const int npx = d.w * d.h, nunits = (npx + LSD_UNIT - 1) / LSD_UNIT, unit = blockIdx.x * 4 + wv;
-    if (unit >= nunits) return;
+    if (unit >= nunits) return;  // (wave-private LDS, no workgroup barrier below)
     unsigned* h = s_h + wv * d.n_bins;
-    const unsigned* first = d.cnt + ((size_t)b * nunits + unit) * d.n_bins;
+    const unsigned* first = d.cnt + ((size_t)b * slot_units + unit) * d.n_bins;
     for (int t = lane; t < d.n_bins; t += 64) h[t] = first[t];
     const double bin_coef = lsd_bin_coef(d, b);
-    const int32_t* k32 = d.k32 + (size_t)b * npx;
-    uint32_t* order = d.order + (size_t)b * npx;
+    const int32_t* k32 = d.k32 + (size_t)b * slot_px;
+    uint32_t* order = d.order + (size_t)b * slot_px;
     const unsigned long long lt = lane == 0 ? 0ull : ~0ull >> (64 - lane);
 #pragma unroll 4
     for (int r = 0; r < LSD_UNIT_ROWS; ++r) {
@@ -760,13 +816,15 @@ __device__ __forceinline__ void lsd_store_counters(const LsdDev& d, int b, const
 
 // The search, ONE wave per image: the batch loop over the seeds in their pseudo-order, the fast growth, region2rect with its sums from
 // LDS.  The default where lsd_grow_xcd_kernel does not run (batches above LSD_WAVES_MAX_B images, STVO_LSD_WAVES=0).
-template <bool PROF>
-__global__ __launch_bounds__(64) void lsd_grow_kernel(LsdDev d) {
+template <bool PROF, bool MIXED>
+__global__ __launch_bounds__(64) void lsd_grow_kernel(LsdDev d, LsdTable<MIXED> tab) {
     __shared__ int s_ring[LSD_RING];
     __shared__ double s_term[3][64];  // region2rect: the terms of one chunk
     const int b = blockIdx.x, lane = threadIdx.x;
+    const LsdSlot slot{d.w, d.h};
+    if constexpr (MIXED) lsd_take_image(d, tab, b);
     const int w = d.w, h = d.h, npx = w * h;
-    const size_t base = (size_t)b * npx;
+    const size_t base = (size_t)b * (slot.w * slot.h);
     LsdPx* px = d.px + base;
     const int32_t* __restrict__ k32 = d.k32 + base;
     const uint32_t* __restrict__ order = d.order + base;
@@ -812,12 +870,14 @@ __global__ __launch_bounds__(64) void lsd_grow_kernel(LsdDev d) {
 //            for good, speculation against flags that only ever turn on), so the mode runs here whatever the batch.  No shipped
 //            configuration uses it (config/*.yaml: lsd_refine : 0); it is there so that a caller who sets it gets the detector it
 //            asked for rather than an error.
-template <bool REFINE, bool PROF>
-__global__ __launch_bounds__(64) void lsd_grow_refine_kernel(LsdDev d, const double density_th) {
+template <bool REFINE, bool PROF, bool MIXED>
+__global__ __launch_bounds__(64) void lsd_grow_refine_kernel(LsdDev d, const double density_th, LsdTable<MIXED> tab) {
     __shared__ int s_ring[LSD_RING];
     const int b = blockIdx.x, lane = threadIdx.x;
+    const LsdSlot slot{d.w, d.h};
+    if constexpr (MIXED) lsd_take_image(d, tab, b);
     const int w = d.w, h = d.h, npx = w * h;
-    const size_t base = (size_t)b * npx;
+    const size_t base = (size_t)b * (slot.w * slot.h);
     LsdPx* px = d.px + base;
     const int32_t* __restrict__ k32 = d.k32 + base;
     const uint32_t* __restrict__ order = d.order + base;
@@ -1606,11 +1666,13 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
 
 // LSDDetectorC::detectImpl's loop over the segments of the (single) octave (:254-303) and the cut of stereoFrame.cpp:231-240
 constexpr int KL_T = 256;
-__global__ __launch_bounds__(KL_T) void lsd_keylines_kernel(LsdDev d) {
+template <bool MIXED>
+__global__ __launch_bounds__(KL_T) void lsd_keylines_kernel(LsdDev d, LsdTable<MIXED> tab) {
     extern __shared__ float s_resp[];  // [seg_cap] responses of the kept lines, detection order
     __shared__ int s_wave[KL_T / 64];
     __shared__ int s_run;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if constexpr (MIXED) lsd_take_image(d, tab, b);  // (the clamps, the response divisor, the raster and the minimum length are the image's own)
     const int n = min(d.n_seg[b], d.seg_cap);
     const float4* seg = d.seg + (size_t)b * d.seg_cap;
     int* s_src = reinterpret_cast<int*>(s_resp + d.seg_cap);  // [seg_cap] segment of kept line k
@@ -1720,6 +1782,11 @@ struct stvo_lsd {
     size_t stamp_bytes = 0, pend_ctl_bytes = 0;  // what a call clears of the scratch below (frontend_layout.h: LsdXcdArena)
     stvo::LsdXcd xx{};        // scratch of lsd_grow_xcd_kernel (small batches, the default), or null
     int xcd_lds = 0;          // its dynamic LDS: the committer's bitmap — and at least 84 KB, so that a CU holds ONE of its workgroups (a wave per SIMD)
+    // one image size per image (stvo_lsd_set_image_sizes): nothing of it exists until the first call.  The device table holds the n rows
+    // the detector's own kernels read (LsdSizeRow), then the 2 n rows that drive the shared blur and resize (lsd_sizes.h: lsd_scale_rows)
+    TableTransport sizes;
+    int n_sizes = 0;          // entries of the table in force; 0: every image fills its slot
+    const stvo::OrbLevelSize* scale_rows() const { return reinterpret_cast<const stvo::OrbLevelSize*>(sizes.dev + (size_t)n_sizes * sizeof(stvo::LsdSizeRow)); }
 };
 
 namespace {
@@ -1729,9 +1796,11 @@ void lsd_scaled_enqueue(stvo_lsd* o, const uint8_t* images) {
     const stvo::LsdDev& d = o->d;
     hipStream_t s = o->ctx->stream;
     if (o->radius == 3) {
-        stvo::launch_blur7_u8(s, d.B, d.cols, d.rows, images, o->blur, o->kw);
-        stvo::launch_resize_linear_u8(s, d.B, d.cols, d.rows, d.w, d.h, o->blur, o->scaled, d.scale, d.scale);
-    } else {
+        // under a size table: the MIXED instances on the slots' grids, each image blurred to its own border and resized from its own size
+        const stvo::OrbLevelSize* sz = o->n_sizes ? o->scale_rows() : nullptr;
+        stvo::launch_blur7_u8(s, d.B, d.cols, d.rows, images, o->blur, o->kw, sz, o->n_sizes, 2, 0);
+        stvo::launch_resize_linear_u8(s, d.B, d.cols, d.rows, d.w, d.h, o->blur, o->scaled, d.scale, d.scale, sz, o->n_sizes, 2, 1);
+    } else {  // (no size table here: stvo_lsd_set_image_sizes refuses the detector)
         stvo::launch_blur_resize_u8(s, d.B, d.cols, d.rows, d.w, d.h, images, o->scaled, d.scale, o->radius, o->kw, o->plan);
     }
 }
@@ -1749,18 +1818,33 @@ int lsd_enqueue(stvo_lsd* o, const uint8_t* images, stvo_keyline* lines, float* 
     d.lines = lines; d.response = response; d.n_lines = n_lines;
     HIP_TRY(ctx, hipMemsetAsync(d.kmax, 0xFF, (size_t)d.B * 4, s));
     const dim3 grid((d.w + 255) / 256, (d.h + stvo::LSD_ROWS - 1) / stvo::LSD_ROWS, d.B);
-    hipLaunchKernelGGL(stvo::lsd_gradient_kernel, grid, dim3(256), 0, s, d);
-    {   // the pseudo-ordering: counting sort by bin (histogram per unit, scan per image, stable scatter)
-        const int npx = d.w * d.h, nunits = (npx + stvo::LSD_UNIT - 1) / stvo::LSD_UNIT;
-        const dim3 ug((nunits + 3) / 4, d.B);
-        const size_t lds_h = (size_t)4 * d.n_bins * 4;
-        hipLaunchKernelGGL(stvo::lsd_hist_kernel, ug, dim3(256), lds_h, s, d);
-        hipLaunchKernelGGL(stvo::lsd_scan_kernel, dim3(d.B), dim3(1024), 0, s, d);
-        hipLaunchKernelGGL(stvo::lsd_scatter_kernel, ug, dim3(256), lds_h, s, d);
+    const int nunits = (d.w * d.h + stvo::LSD_UNIT - 1) / stvo::LSD_UNIT;
+    const dim3 ug((nunits + 3) / 4, d.B);
+    const size_t lds_h = (size_t)4 * d.n_bins * 4, lds = (size_t)d.seg_cap * 8;
+    if (o->n_sizes) {
+        // One size per image: the MIXED instances of every kernel on the slots' launch grids.  The search runs ONE wave per image at every
+        // batch size (lsd_grow_kernel, lsd_grow_refine_kernel under lsd_refine = 1 or STVO_LSD_GROW=0): lsd_grow_xcd_kernel is not launched
+        // under a table — mixed sizes are the many-streams case, beyond its batch sizes anyway — and neither are the PROF instances.
+        const stvo::LsdTable<true> tab{reinterpret_cast<const stvo::LsdSizeRow*>(o->sizes.dev), o->n_sizes};
+        hipLaunchKernelGGL(stvo::lsd_gradient_kernel<true>, grid, dim3(256), 0, s, d, tab);
+        hipLaunchKernelGGL(stvo::lsd_hist_kernel<true>, ug, dim3(256), lds_h, s, d, tab);
+        hipLaunchKernelGGL(stvo::lsd_scan_kernel<true>, dim3(d.B), dim3(1024), 0, s, d, tab);
+        hipLaunchKernelGGL(stvo::lsd_scatter_kernel<true>, ug, dim3(256), lds_h, s, d, tab);
+        if (o->prm.refine == 1) hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<true, false, true>), dim3(d.B), dim3(64), 0, s, d, o->prm.density_th, tab);
+        else if (stvo::dbg().lsd_grow == 0) hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<false, false, true>), dim3(d.B), dim3(64), 0, s, d, 0.0, tab);
+        else hipLaunchKernelGGL((stvo::lsd_grow_kernel<false, true>), dim3(d.B), dim3(64), 0, s, d, tab);
+        hipLaunchKernelGGL(stvo::lsd_keylines_kernel<true>, dim3(d.B), dim3(stvo::KL_T), lds, s, d, tab);
+        return check_launch(ctx);
     }
+    const stvo::LsdTable<false> none{};  // the uniform instances: the kernels and arguments of a detector that was never given a table
+    hipLaunchKernelGGL(stvo::lsd_gradient_kernel<false>, grid, dim3(256), 0, s, d, none);
+    // the pseudo-ordering: counting sort by bin (histogram per unit, scan per image, stable scatter)
+    hipLaunchKernelGGL(stvo::lsd_hist_kernel<false>, ug, dim3(256), lds_h, s, d, none);
+    hipLaunchKernelGGL(stvo::lsd_scan_kernel<false>, dim3(d.B), dim3(1024), 0, s, d, none);
+    hipLaunchKernelGGL(stvo::lsd_scatter_kernel<false>, ug, dim3(256), lds_h, s, d, none);
     const bool prof = d.dbg != nullptr;  // stvo_lsd_debug has the probes on: the PROF instance of the route's kernel
     if (o->prm.refine == 1) {  // LSD_REFINE_STD: regions may give their pixels back — the plain one-wave kernel with refinement, for every batch size
-        hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<true, false>), dim3(d.B), dim3(64), 0, s, d, o->prm.density_th);
+        hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<true, false, false>), dim3(d.B), dim3(64), 0, s, d, o->prm.density_th, none);
     } else if (o->wdev) {  // small batches: a committing wave + speculating workgroups on the CUs of one XCD per image (lsd_grow_xcd_kernel)
         HIP_TRY(ctx, hipMemsetAsync(o->xx.stamp, 0, o->stamp_bytes, s));
         HIP_TRY(ctx, hipMemsetAsync(o->xx.pend, 0, o->pend_ctl_bytes, s));  // (the control words lie behind the table)
@@ -1768,14 +1852,13 @@ int lsd_enqueue(stvo_lsd* o, const uint8_t* images, stvo_keyline* lines, float* 
         if (prof) hipLaunchKernelGGL(stvo::lsd_grow_xcd_kernel<true>, xg, xb, o->xcd_lds, s, d, o->xx);
         else hipLaunchKernelGGL(stvo::lsd_grow_xcd_kernel<false>, xg, xb, o->xcd_lds, s, d, o->xx);
     } else if (stvo::dbg().lsd_grow == 0) {  // STVO_LSD_GROW=0: the plain one-wave kernel, nothing refined
-        if (prof) hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<false, true>), dim3(d.B), dim3(64), 0, s, d, 0.0);
-        else hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<false, false>), dim3(d.B), dim3(64), 0, s, d, 0.0);
+        if (prof) hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<false, true, false>), dim3(d.B), dim3(64), 0, s, d, 0.0, none);
+        else hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<false, false, false>), dim3(d.B), dim3(64), 0, s, d, 0.0, none);
     } else {
-        if (prof) hipLaunchKernelGGL(stvo::lsd_grow_kernel<true>, dim3(d.B), dim3(64), 0, s, d);
-        else hipLaunchKernelGGL(stvo::lsd_grow_kernel<false>, dim3(d.B), dim3(64), 0, s, d);
+        if (prof) hipLaunchKernelGGL((stvo::lsd_grow_kernel<true, false>), dim3(d.B), dim3(64), 0, s, d, none);
+        else hipLaunchKernelGGL((stvo::lsd_grow_kernel<false, false>), dim3(d.B), dim3(64), 0, s, d, none);
     }
-    const size_t lds = (size_t)d.seg_cap * 8;
-    hipLaunchKernelGGL(stvo::lsd_keylines_kernel, dim3(d.B), dim3(stvo::KL_T), lds, s, d);
+    hipLaunchKernelGGL(stvo::lsd_keylines_kernel<false>, dim3(d.B), dim3(stvo::KL_T), lds, s, d, none);
     return check_launch(ctx);
 }
 
@@ -1804,7 +1887,7 @@ int stvo_lsd_geometry(const stvo_lsd_params* prm, int cols, int rows, int32_t* s
         // 7 x 7 kernel of the ORB front-end, the others on lsd_blur_resize_kernel
         if (!(hd <= STVO_LSD_MAX_RADIUS)) return STVO_ERR_UNSUPPORTED;
         hk = (int)hd;
-        const double wd = std::rint((double)cols * prm->scale), hd2 = std::rint((double)rows * prm->scale);  // resize(..., Size(), scale, scale): cvRound
+        const double wd = stvo::lsd_scaled_extent(cols, prm->scale), hd2 = stvo::lsd_scaled_extent(rows, prm->scale);  // resize(..., Size(), scale, scale): cvRound
         if (!(wd >= 1 && hd2 >= 1)) return STVO_ERR_INVALID_ARG;  // nothing is left of the image
         if (wd >= 65536 || hd2 >= 32768) return STVO_ERR_CAPACITY;
         w = (int)wd;
@@ -1843,11 +1926,7 @@ int stvo_lsd_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, 
     d.n_bins = prm->n_bins;
     d.rho = prm->quant / std::sin(stvo::LSD_PI * prm->ang_th / 180);
     d.prec = stvo::LSD_PI * prm->ang_th / 180;
-    {
-        const double p = prm->ang_th / 180;
-        const double log_nt = 5 * (std::log10((double)d.w) + std::log10((double)d.h)) / 2 + std::log10(11.0);
-        d.min_reg_size = (int)(size_t)(-log_nt / std::log10(p));
-    }
+    d.min_reg_size = stvo::lsd_min_reg_size(d.w, d.h, prm->ang_th);
     d.min_length = prm->min_length;
     d.nfeatures = prm->nfeatures;
     d.K = max_keylines;
@@ -1865,11 +1944,14 @@ int stvo_lsd_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, 
         o->lines = a.lines; o->response = a.response; o->n_lines = a.n_lines;
     }
     if (ok && (size_t)4 * d.n_bins * 4 > 48 * 1024) {
-        ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_hist_kernel), 4 * d.n_bins * 4) &&
-             stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_scatter_kernel), 4 * d.n_bins * 4);
+        ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_hist_kernel<false>), 4 * d.n_bins * 4) &&
+             stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_scatter_kernel<false>), 4 * d.n_bins * 4) &&
+             stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_hist_kernel<true>), 4 * d.n_bins * 4) &&
+             stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_scatter_kernel<true>), 4 * d.n_bins * 4);
     }
     if (ok && (size_t)d.seg_cap * 8 > 48 * 1024)
-        ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_keylines_kernel), d.seg_cap * 8);
+        ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_keylines_kernel<false>), d.seg_cap * 8) &&
+             stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_keylines_kernel<true>), d.seg_cap * 8);
     if (ok && stvo::dbg().lsd_waves != 0 && stvo::lsd_xcd_route(prm->refine, B, npx)) {  // small batches (STVO_LSD_WAVES=0: one wave per image there too)
         // an XCD has 32 CUs and a CU holds one of the kernel's workgroups: images per XCD x (1 + speculating workgroups) <= 32
         const int per_xcd = (B + 7) / 8;
@@ -1914,7 +1996,37 @@ int stvo_lsd_destroy(stvo_lsd* o) {
     if (o->dbg) (void)hipFree(o->dbg);
     if (o->wdev) (void)hipFree(o->wdev);
     if (o->dev) (void)hipFree(o->dev);
+    o->sizes.destroy();
     delete o;
+    return STVO_OK;
+}
+
+// One image size (and minimum length) per image (stvo_hip.h).  Validated before anything changes; the table is formed with the functions
+// stvo_lsd_geometry / stvo_lsd_create form the slot's own values with (lsd_sizes.h) and travels as table_transport.h says.
+int stvo_lsd_set_image_sizes(stvo_lsd* o, const int32_t* sizes_host, const double* min_length_host, int n) {
+    if (!o) return STVO_ERR_INVALID_ARG;
+    if (!sizes_host) {  // every image fills its slot again: the uniform kernel instances, which read no table
+        o->n_sizes = 0;
+        return STVO_OK;
+    }
+    const stvo::LsdDev& d = o->d;
+    if (!stvo::lsd_image_sizes_ok(sizes_host, min_length_host, n, d.B, d.cols, d.rows, d.scale)) return STVO_ERR_INVALID_ARG;
+    // the fused blur + resize of the other radii plans its tile per size: such a detector keeps one size
+    if (d.scale != 1 && o->radius != 3) return STVO_ERR_UNSUPPORTED;
+    stvo_ctx* ctx = o->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    constexpr size_t entry = sizeof(stvo::LsdSizeRow) + 2 * sizeof(stvo::OrbLevelSize);
+    char* tab = o->sizes.begin(ctx, (size_t)d.B * entry);
+    if (!tab) return STVO_ERR_HIP;
+    stvo::LsdSizeRow* rows = reinterpret_cast<stvo::LsdSizeRow*>(tab);
+    stvo::OrbLevelSize* srows = reinterpret_cast<stvo::OrbLevelSize*>(tab + (size_t)n * sizeof(stvo::LsdSizeRow));
+    for (int i = 0; i < n; ++i) {
+        rows[i] = stvo::lsd_size_row(sizes_host[2 * i], sizes_host[2 * i + 1], d.scale, o->prm.ang_th,
+                                     stvo::lsd_entry_min_length(min_length_host, i, d.min_length));
+        stvo::lsd_scale_rows(rows[i], d.scale, srows + 2 * i);
+    }
+    TRY(o->sizes.send(ctx, (size_t)n * entry));
+    o->n_sizes = n;
     return STVO_OK;
 }
 

@@ -1144,22 +1144,29 @@ __global__ __launch_bounds__(256) void orb_describe_wta_kernel(OrbDev o, WtaArgs
 }  // namespace
 
 // the two 8-bit image operations other front-ends share (lsd_kernels.hip: the scaled image of the line detector)
-void launch_blur7_u8(hipStream_t s, int B, int cols, int rows, const uint8_t* src, uint8_t* dst, const int* k7) {
+void launch_blur7_u8(hipStream_t s, int B, int cols, int rows, const uint8_t* src, uint8_t* dst, const int* k7, const OrbLevelSize* sz, int n_sz,
+                     int sz_stride, int level) {
     OrbDev o{};
     o.B = B; o.cols = cols; o.rows = rows; o.img = src; o.blur = dst;
+    o.sz = sz; o.n_sz = n_sz; o.sz_stride = sz_stride; o.level = level;
     BlurK kk{};
     for (int i = 0; i < 7; ++i) kk.k[i] = k7[i];
     const dim3 tiles((cols + 4 * BL_T - 1) / (4 * BL_T), (rows + BL_R - 1) / BL_R, B);
-    hipLaunchKernelGGL(orb_blur_kernel<false>, tiles, dim3(BL_T), 0, s, o, kk);
+    if (sz) hipLaunchKernelGGL(orb_blur_kernel<true>, tiles, dim3(BL_T), 0, s, o, kk);
+    else hipLaunchKernelGGL(orb_blur_kernel<false>, tiles, dim3(BL_T), 0, s, o, kk);
 }
-void launch_resize_linear_u8(hipStream_t s, int B, int scols, int srows, int dcols, int drows, const uint8_t* src, uint8_t* dst, double fx, double fy) {
+void launch_resize_linear_u8(hipStream_t s, int B, int scols, int srows, int dcols, int drows, const uint8_t* src, uint8_t* dst, double fx, double fy,
+                             const OrbLevelSize* sz, int n_sz, int sz_stride, int level) {
     ResizeArgs r{};
     r.B = B; r.scols = scols; r.srows = srows; r.dcols = dcols; r.drows = drows;
     // fx, fy > 0: resize(src, dst, Size(), fx, fy) — cv::resize keeps inv_scale = fx and rounds only the output size; 0: a given dsize
     r.scale_x = 1.0 / (fx > 0 ? fx : (double)dcols / scols);
     r.scale_y = 1.0 / (fy > 0 ? fy : (double)drows / srows);
     r.src = src; r.dst = dst;
-    hipLaunchKernelGGL(orb_resize_kernel<false>, dim3((dcols + 255) / 256, drows, B), dim3(256), 0, s, r);
+    r.sz = sz; r.n_sz = n_sz; r.sz_stride = sz_stride; r.level = level;
+    const dim3 grid((dcols + 255) / 256, drows, B);
+    if (sz) hipLaunchKernelGGL(orb_resize_kernel<true>, grid, dim3(256), 0, s, r);
+    else hipLaunchKernelGGL(orb_resize_kernel<false>, grid, dim3(256), 0, s, r);
 }
 }  // namespace stvo
 

@@ -37,7 +37,7 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_seq_export_streams", "stvo_seq_import_streams_dev", "stvo_seq_import_streams", "stvo_orb_set_descriptor",
            "stvo_orb_pattern", "stvo_orb_set_image_sizes", "stvo_seq_restart_cameras", "stvo_rectify_bank_create",
            "stvo_rectify_bank_destroy", "stvo_rectify_bank_camera", "stvo_rectify_bank_assign", "stvo_rectify_bank_images_dev",
-           "stvo_rectify_bank_color_to_gray_dev"]
+           "stvo_rectify_bank_color_to_gray_dev", "stvo_lsd_set_image_sizes", "stvo_lbd_set_image_sizes"]
 
 SEQ_NSTAGE = 5  # include/stvo_hip.h: STVO_SEQ_NSTAGE
 SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_check", "pose")
@@ -320,6 +320,8 @@ def load():
                                     C.POINTER(C.c_int32), i32p]
     L.stvo_lsd_scaled_image.argtypes = [C.c_void_p, u8p, u8p]
     L.stvo_lsd_debug.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.stvo_lsd_set_image_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.stvo_lbd_set_image_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.stvo_fld_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FldParams), C.POINTER(C.c_void_p)]
     L.stvo_fld_destroy.argtypes = [C.c_void_p]
     L.stvo_fld_detect.argtypes = [C.c_void_p, u8p, C.c_void_p, C.c_void_p, i32p]
@@ -704,8 +706,24 @@ class Lsd:
         self.ctx._chk(self.ctx.lib.stvo_lsd_debug(self.h, 1 if enable else 0, _ptr(rows)))
         return rows
 
+    def set_image_sizes(self, sizes, min_lengths=None):
+        """One image size per image: sizes [n][2] = (cols, rows), image i takes sizes[i % n] (n divides B) and occupies the top-left of
+        its slot of the size given at creation, whose row pitch it keeps; min_lengths [n] (None: the detector's min_length for all) is
+        the minimum line length per entry (stvo_lsd_set_image_sizes).  sizes None: every image fills its slot."""
+        if sizes is None:
+            self.ctx._chk(self.ctx.lib.stvo_lsd_set_image_sizes(self.h, None, None, 0))
+            return
+        a = np.ascontiguousarray(sizes, np.int32)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("Lsd.set_image_sizes: sizes is [n][2] = (cols, rows)")
+        ml = None if min_lengths is None else np.ascontiguousarray(min_lengths, np.float64).reshape(-1)
+        if ml is not None and ml.size != a.shape[0]:
+            raise ValueError("Lsd.set_image_sizes: one minimum length per entry of sizes")
+        self.ctx._chk(self.ctx.lib.stvo_lsd_set_image_sizes(self.h, _ptr(a), None if ml is None else _ptr(ml), a.shape[0]))
+
     def scaled_image(self, images):
-        """The image the detector core sees (blurred and resized; the input itself at scale 1): uint8 [B, scaled rows, scaled cols]."""
+        """The image the detector core sees (blurred and resized; the input itself at scale 1): uint8 [B, scaled rows, scaled cols]
+        (under set_image_sizes: the top-left scaled size of every image, at the slot's scaled pitch)."""
         images = np.ascontiguousarray(images, np.uint8).reshape(self.B, self.rows, self.cols)
         out = np.zeros((self.B, self.geometry["rows"], self.geometry["cols"]), np.uint8)
         self.ctx._chk(self.ctx.lib.stvo_lsd_scaled_image(self.h, images.reshape(-1), out.reshape(-1)))
@@ -787,6 +805,16 @@ class Lbd:
         if self.h:
             self.ctx.lib.stvo_lbd_destroy(self.h)
             self.h = None
+
+    def set_image_sizes(self, sizes):
+        """One image size per image, as Lsd.set_image_sizes (stvo_lbd_set_image_sizes).  None: every image fills its slot."""
+        if sizes is None:
+            self.ctx._chk(self.ctx.lib.stvo_lbd_set_image_sizes(self.h, None, 0))
+            return
+        a = np.ascontiguousarray(sizes, np.int32)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("Lbd.set_image_sizes: sizes is [n][2] = (cols, rows)")
+        self.ctx._chk(self.ctx.lib.stvo_lbd_set_image_sizes(self.h, _ptr(a), a.shape[0]))
 
     def compute_dev(self, img_ptr, lines_ptr, n_ptr, desc_ptr, desc_float_ptr=None):
         """Device pointers (uint8 [B, rows, cols]; stvo_keyline [B, M]; int32 [B]; uint8 [B, M, 32]; float32 [B, M, 72] or None)."""

@@ -22,13 +22,19 @@ class ImagePipeline:
     def __init__(self, ctx, B, cam, mp, op, max_kp=2048, nfeatures=2000, fast_threshold=20, edge_threshold=19, device="cuda:0", nlevels=1,
                  scale_factor=1.2, lsd=None, max_kl=128, rectify=None, fld=None, orb_score=1, adaptive_fast=None,
                  trajectory=None, trajectory_log=1, tracks=0, keyframe_sets=False, channels=1, gray_weights="q14", orb_wta_k=2,
-                 orb_patch_size=31, calibs=None):
+                 orb_patch_size=31, calibs=None, lines_per_stream=False, lsd_min_length_ratio=None):
         """cam: one camera dict (width / height = image size) for all B streams, or a list of B dicts, one camera AND image size per stream
         (KITTI 00-02 / 03 / 04-10 side by side): the resident image buffer is then cut in slots of the largest width x the largest height,
         stream b's images occupy the top-left of their slots (set_images takes a list of B arrays of each stream's own size), the
         detector reads every image at its own size (Orb.set_image_sizes) and the pipeline is created with the B cameras; a stream that
-        RESTARTs may take another camera (enqueue / push_images: cams).  Key-points only: with a list, lsd and fld raise ValueError (their
-        detectors hold one size each), and so do a rectify that is not a capi.RectifierBank and channels other than 1 without one.
+        RESTARTs may take another camera (enqueue / push_images: cams).  Key-points only unless asked otherwise: with a list, lsd and
+        fld raise ValueError, and so do a rectify that is not a capi.RectifierBank and channels other than 1 without one.
+        lines_per_stream = True (with a list and lsd; ValueError without either) is the opt-in for key-lines on such streams: the LSD
+        detector and LBD are built at the slot size and read every image at its own size beside ORB (Lsd.set_image_sizes,
+        Lbd.set_image_sizes), with and without a rectifier bank; lsd_min_length_ratio = r gives stream b the minimum line length
+        r * min(width_b, height_b) of its own camera (the reference's Config::minLineLength() x min(width, height)), None keeps
+        lsd.min_length for all; a stream that RESTARTs hands its new size and minimum length to both with its camera.  fld stays
+        refused with a list (the FLD walk holds one size).
         With a list, rectify = capi.RectifierBank and calibs = [B ints]: the frames are RAW, stream b under calibration calibs[b] of the
         bank, whose size cam[b] must have; the slot is the bank's; enqueue first runs the bank's one launch over all streams (with
         channels 3 / 4 the fused colour -> grey form: set_images then takes lists of colour arrays into self.color) and the detector
@@ -73,11 +79,13 @@ class ImagePipeline:
             if len(cam) != B:
                 raise ValueError("ImagePipeline: cam is one dict or a list of B dicts")
             bank = rectify if isinstance(rectify, capi.RectifierBank) else None
-            for name, given in (("lsd", lsd is not None), ("fld", fld is not None), ("rectify", rectify is not None and bank is None),
+            if lines_per_stream and lsd is None:
+                raise ValueError("ImagePipeline: lines_per_stream goes with lsd (and cam as a list)")
+            for name, given in (("lsd", lsd is not None and not lines_per_stream), ("fld", fld is not None), ("rectify", rectify is not None and bank is None),
                                 ("channels", channels != 1 and bank is None)):
                 if given:
                     raise ValueError(f"ImagePipeline: {name} is not available with one camera per stream (cam as a list): key-points only"
-                                     " (rectify takes a capi.RectifierBank, which also takes channels 3 / 4)")
+                                     " (rectify takes a capi.RectifierBank, which also takes channels 3 / 4; lsd takes lines_per_stream = True)")
             self.cams = cam
             if bank is not None:
                 if bank.ctx is not ctx or bank.B < B:
@@ -89,11 +97,14 @@ class ImagePipeline:
                 self.cols, self.rows = max(c["width"] for c in cam), max(c["height"] for c in cam)  # the slot
         else:
             self.cols, self.rows = cam["width"], cam["height"]
+            if lines_per_stream:
+                raise ValueError("ImagePipeline: lines_per_stream goes with one camera per stream (cam as a list) and lsd")
             if isinstance(rectify, capi.RectifierBank):
                 raise ValueError("ImagePipeline: a capi.RectifierBank goes with one camera per stream (cam as a list)")
         if self.bank is None and calibs is not None:
             raise ValueError("ImagePipeline: calibs goes with rectify = capi.RectifierBank and cam as a list")
         self.rectify = rectify
+        self.lsd_min_length_ratio = lsd_min_length_ratio
         if rectify is not None and self.bank is None and (rectify.ctx is not ctx or rectify.B < B or rectify.cols != self.cols or rectify.rows != self.rows):
             raise ValueError("ImagePipeline: the rectifier must belong to the same context, hold B pairs and match the image size")
         self.orb = capi.Orb(ctx, 2 * B, self.cols, self.rows, max_kp, nfeatures, fast_threshold, edge_threshold, nlevels, scale_factor,
@@ -116,6 +127,12 @@ class ImagePipeline:
         self.fld = capi.Fld(ctx, 2 * B, self.cols, self.rows, fld, max_keylines=max_kl) if fld is not None else None
         self.lines = self.lsd if self.lsd is not None else self.fld  # the key-line detector, or None
         self.lbd = capi.Lbd(ctx, 2 * B, self.cols, self.rows, max_keylines=max_kl) if self.lines is not None else None
+        if self.cams is not None and self.lsd is not None:  # n = B on 2 B images, as for ORB
+            try:
+                self._set_line_sizes(self.cams)
+            except Exception:
+                self.orb.close(); self.lsd.close(); self.lbd.close()
+                raise
         self.seq = capi.Sequences(ctx, B, max_kp, max_kl if self.lines is not None else 64, cam, mp, op)
         self.trajectory = trajectory
         if trajectory is not None:
@@ -182,6 +199,13 @@ class ImagePipeline:
                                  f"of the bank {self.bank.sizes[k][0]} x {self.bank.sizes[k][1]}")
         return calibs
 
+    def _set_line_sizes(self, cams):
+        """the size, and minimum line length, of every stream's camera to the line detector and the line descriptor"""
+        sizes = [(c["width"], c["height"]) for c in cams]
+        r = self.lsd_min_length_ratio
+        self.lsd.set_image_sizes(sizes, None if r is None else [r * min(w, h) for w, h in sizes])
+        self.lbd.set_image_sizes(sizes)
+
     def _calibs_after(self, control, calibs, new_cams):
         """The B calibrations in force once the RESTART streams of `control` have taken theirs from `calibs` (B entries, None for the
         others), checked against the cameras then in force."""
@@ -236,7 +260,8 @@ class ImagePipeline:
         first, so that with adaptive_fast the restarted streams are detected at fast_threshold again (initialize sets orb_fast_th
         before it detects); the rule at the end of the step leaves the thresholds of restarted and parked streams alone.
         cams (one camera per stream only): None, or B entries — the camera dict of the sequence a RESTART stream begins, None for the
-        others: the pipeline (Sequences.restart_cameras) and the detector (Orb.set_image_sizes) take it before the detection.
+        others: the pipeline (Sequences.restart_cameras) and the detectors (Orb.set_image_sizes, and with lines_per_stream
+        Lsd.set_image_sizes with the stream's minimum length and Lbd.set_image_sizes) take it before the detection.
         calibs (rectifier bank only): None, or B entries — the calibration index a RESTART stream takes with its camera, None for the
         others; the size of every stream's calibration must be its camera's, else ValueError and nothing is staged."""
         new = self._cams_after(control, cams) if cams is not None else None
@@ -248,18 +273,22 @@ class ImagePipeline:
             cams_change = new is not None and new != self.cams
             calibs_change = new_k is not None and new_k != self.calibs
             if cams_change or calibs_change:
-                # the detector first: it validates every size, and what it and the bank have taken can be put back should the pipeline
-                # refuse — the three never disagree, and a refused call leaves no control staged
+                # the detectors first: they validate every size, and what they and the bank have taken can be put back should the
+                # pipeline refuse — none of them ever disagree, and a refused call leaves no control staged
                 ctl = np.asarray(control).reshape(-1)
                 try:
                     if cams_change:
                         self.orb.set_image_sizes([(c["width"], c["height"]) for c in new])
+                        if self.lsd is not None:
+                            self._set_line_sizes(new)
                     if calibs_change:
                         self.bank.assign(new_k + [0] * (self.bank.B - self.B))
                     if cams_change:
                         self.seq.restart_cameras([c if ctl[b] == capi.STREAM_RESTART else None for b, c in enumerate(new)])
                 except Exception:
                     self.orb.set_image_sizes([(c["width"], c["height"]) for c in self.cams])
+                    if self.lsd is not None:
+                        self._set_line_sizes(self.cams)
                     if calibs_change:
                         self.bank.assign(self.calibs + [0] * (self.bank.B - self.B))
                     self.seq.control_next_step(np.zeros(self.B, np.int32))
