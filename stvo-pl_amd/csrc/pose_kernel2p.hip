@@ -75,49 +75,60 @@ __global__ __launch_bounds__(NW * 64, 2) void pose2p_kernel(PoseArgs a, const in
     unsigned pmatched = 0u, pinl = 0u;
     const int n_prev_p = a.n_prev_pts != nullptr ? min(a.n_prev_pts[f], a.max_pts) : 0;
     const size_t pbase = (size_t)f * a.max_pts;
-    // branch-free, clamped loads: the PPT match indices (and below the PPT records) of a thread are all in flight at once —
-    // the prologue is a chain of dependent HBM round trips otherwise (index -> record -> LDS)
-    int jj[PPT];
+    // branch-free, clamped loads: the 2 PPT match indices and inlier flags of a thread, and the 2 LPT of its lines, are all in
+    // flight at once — the prologue is a chain of dependent HBM round trips otherwise (index -> record -> LDS).  Written as
+    // `a.m12p ? a.m12p[i] : i` each load sits in a branch of its own and is waited for alone; an absent array (identity matches,
+    // all-inlier masks) is therefore replaced by memory that is always valid for the pair (its own prev_P slot: 4 bytes of a
+    // 24-byte point per index; its first word for the lines), the load is issued regardless and the alternative is selected after it.
+    const size_t lbase = (size_t)f * a.max_lines;
+    const int li0 = BLOCK - 1 - tid;  // line k of this thread: li0 + k BLOCK
+    const bool has_l = a.n_prev_lines != nullptr && a.max_lines > 0;
+    const bool use_m12l = a.m12l != nullptr && has_l, use_init_l = a.init_inl_l != nullptr && has_l;
+    const int n_prev_l = has_l ? a.n_prev_lines[f] : 0;
+    int jj[PPT], jl[LPT];
+    unsigned lmatched = 0u, linl = 0u;
     {
-        int init[PPT];
+        int init[PPT], initl[LPT];
+        const int32_t* const own = reinterpret_cast<const int32_t*>(a.prev_P + pbase * 3);
+        const int32_t* const mp = a.m12p ? a.m12p + pbase : own;
+        const int32_t* const ip = a.init_inl_p ? a.init_inl_p + pbase : own;
+        const int32_t* const ml = use_m12l ? a.m12l + lbase : own;
+        const int32_t* const il = use_init_l ? a.init_inl_l + lbase : own;
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
             const int i = tid + k * BLOCK;
             const int ic = i < n_prev_p ? i : 0;
-            jj[k] = a.m12p ? a.m12p[pbase + ic] : ic;
-            init[k] = a.init_inl_p ? a.init_inl_p[pbase + ic] : 1;
+            jj[k] = mp[ic];
+            init[k] = ip[ic];
         }
-#pragma unroll
-        for (int k = 0; k < PPT; ++k) {
-            const int i = tid + k * BLOCK;
-            if (i < n_prev_p && jj[k] >= 0) {
-                pmatched |= 1u << k;
-                if (init[k] != 0) pinl |= 1u << k;
-            } else {
-                jj[k] = 0;
-            }
-        }
-    }
-    unsigned lmatched = 0u, linl = 0u;
-    const int n_prev_l = (a.n_prev_lines != nullptr && a.max_lines > 0) ? a.n_prev_lines[f] : 0;
-    const size_t lbase = (size_t)f * a.max_lines;
-    const int li0 = BLOCK - 1 - tid;  // line k of this thread: li0 + k BLOCK
-    int jl[LPT];
-    {   // branch-free, clamped loads as for the points: all LPT match indices of the thread in one round trip
-        int initl[LPT];
 #pragma unroll
         for (int k = 0; k < LPT; ++k) {
             const int li = li0 + k * BLOCK;
             const int lc = (li < n_prev_l && li < a.max_lines) ? li : 0;
-            jl[k] = (a.m12l && a.max_lines > 0) ? a.m12l[lbase + lc] : lc;
-            initl[k] = (a.init_inl_l && a.max_lines > 0) ? a.init_inl_l[lbase + lc] : 1;
+            jl[k] = ml[use_m12l ? lc : 0];
+            initl[k] = il[use_init_l ? lc : 0];
+        }
+        __builtin_amdgcn_sched_barrier(0);  // (every load above is issued before the first value is looked at)
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) {
+            const int i = tid + k * BLOCK;
+            const int j = a.m12p ? jj[k] : i;
+            if (i < n_prev_p && j >= 0) {
+                pmatched |= 1u << k;
+                if (a.init_inl_p == nullptr || init[k] != 0) pinl |= 1u << k;
+                jj[k] = j;
+            } else {
+                jj[k] = 0;
+            }
         }
 #pragma unroll
         for (int k = 0; k < LPT; ++k) {
             const int li = li0 + k * BLOCK;
-            if (li < n_prev_l && li < a.max_lines && jl[k] >= 0) {
+            const int j = use_m12l ? jl[k] : li;
+            if (li < n_prev_l && li < a.max_lines && j >= 0) {
                 lmatched |= 1u << k;
-                if (initl[k] != 0) linl |= 1u << k;
+                if (!use_init_l || initl[k] != 0) linl |= 1u << k;
+                jl[k] = j;
             } else {
                 jl[k] = 0;
             }
@@ -484,7 +495,8 @@ __global__ __launch_bounds__(NW * 64, 2) void pose2c_kernel(PoseArgs a_by_value,
     // The ~35 pointers and scalars of PoseArgs are read from the kernel-argument segment WHERE THEY ARE USED, through a pointer the
     // compiler cannot see through: as ordinary by-value arguments they are all loaded at the top of the kernel and stay live — most
     // of them until the epilogue — in SGPRs the evaluation loop needs (it then reloads spilled scalars with v_readlane on every
-    // trip: 9 of its 137 vector instructions).  PoseArgs is the first kernel argument: offset 0 of the segment.
+    // trip: 9 of its 137 vector instructions).  PoseArgs is the first kernel argument: offset 0 of the segment.  The PROLOGUE reads what
+    // it needs once, through one such pointer, into locals that end with it (below): there the re-reading cost a branch per use.
     (void)a_by_value;
     typedef const PoseArgs __attribute__((address_space(4))) KArgs;
     KArgs* const kargs = (KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -520,73 +532,122 @@ __global__ __launch_bounds__(NW * 64, 2) void pose2c_kernel(PoseArgs a_by_value,
     const long long t_begin = tick();
     if (blockIdx.x == 0 && threadIdx.x == 0 && ka().start_flag)  // this launch has begun to take the CUs (kernels.h)
         __hip_atomic_store(ka().start_flag, ka().start_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    stvo_cam cam_f;
-    if (ka().cams) {
-        cam_f = ka().cams[f];
-    } else {
-        cam_f.fx = ka().cam.fx; cam_f.fy = ka().cam.fy; cam_f.cx = ka().cam.cx; cam_f.cy = ka().cam.cy; cam_f.b = ka().cam.b;
+    // ---------------- prologue: three dependent round trips to memory ----------------
+    //   1. the counts, every match index and inlier flag of the thread's point and line slots, cams[f], init_T;
+    //   2. the records those indices point to: 2 PPT point records and the 14 fields of line slot 0;
+    //   3. the fields of line slots 1 .. LPT - 1 — only for a pair with more than BLOCK prev key-lines.
+    // The prologue's kernel arguments are read ONCE, into locals that die with it (the evaluation loop keeps its SGPRs, which is what
+    // ka() is for): the compiler then sees one uniform value per argument.  Read anew at every use, each `m12p ? m12p[i] : i` is a
+    // real branch on a freshly loaded pointer and each index load is waited for on its own — some thirty dependent round trips
+    // (profiles/pose_prologue_isa.txt).  An absent array (identity matches, all-inlier masks, one camera, no initial pose, no counts) is replaced by memory that is
+    // always valid for the pair, the load is issued regardless and the alternative is selected where the value is used: the pair's
+    // own prev_rc slot (4 bytes of a 16-byte record per index) for the per-point arrays, q_tab (16 doubles) for the rest.
+    KArgs& pa = ka();
+    const int max_pts = pa.max_pts, max_lines = pa.max_lines;
+    const int32_t* const a_n_prev_pts = pa.n_prev_pts;
+    const int32_t* const a_m12p = pa.m12p;
+    const int32_t* const a_init_inl_p = pa.init_inl_p;
+    const int32_t* const a_n_prev_lines = pa.n_prev_lines;
+    const int32_t* const a_m12l = pa.m12l;
+    const int32_t* const a_init_inl_l = pa.init_inl_l;
+    const float4* const a_prev_rc = pa.prev_rc;
+    const float4* const a_curr_rc = pa.curr_rc;
+    const double* const a_init_T = pa.init_T;
+    const stvo_cam* const a_cams = pa.cams;
+    const double* const a_q_tab = pa.q_tab;
+    const size_t pbase = (size_t)f * max_pts;
+    const size_t lbase = (size_t)f * max_lines;
+    const int li0 = BLOCK - 1 - tid;
+    const bool has_l = a_n_prev_lines != nullptr && max_lines > 0;  // (block-uniform) the pair has key-line arrays at all
+    const bool use_m12l = a_m12l != nullptr && has_l, use_init_l = a_init_inl_l != nullptr && has_l;
+    const int last = max(max_pts - 1, 0), last_l = max(max_lines - 1, 0);
+    const int32_t* const spare = reinterpret_cast<const int32_t*>(a_q_tab);
+
+    // ---- round trip 1: nothing here depends on anything loaded (addresses clamped to the pair's slot, not to its counts) ----
+    const stvo_cam cam_ld = *(a_cams ? a_cams + f : reinterpret_cast<const stvo_cam*>(a_q_tab));
+    const int n_p_ld = *(a_n_prev_pts ? a_n_prev_pts + f : spare);
+    const int n_l_ld = *(has_l ? a_n_prev_lines + f : spare);
+    const double init_T_ld = (a_init_T ? a_init_T + (size_t)f * 16 : a_q_tab)[lane & 15];  // element `lane` of the initial pose (wave 0 stores it)
+    int jj[PPT], init[PPT], jl[LPT], initl[LPT];
+    {
+        const int32_t* const own = reinterpret_cast<const int32_t*>(a_prev_rc + pbase);
+        const int32_t* const mp = a_m12p ? a_m12p + pbase : own;
+        const int32_t* const ip = a_init_inl_p ? a_init_inl_p + pbase : own;
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) {  // 2 PPT loads back to back
+            const int ic = min(tid + k * BLOCK, last);
+            jj[k] = mp[ic];
+            init[k] = ip[ic];
+        }
+        const int32_t* const ml = use_m12l ? a_m12l + lbase : spare;
+        const int32_t* const il = use_init_l ? a_init_inl_l + lbase : spare;
+#pragma unroll
+        for (int k = 0; k < LPT; ++k) {  // and the 2 LPT of the lines behind them
+            const int lc = min(li0 + k * BLOCK, last_l);
+            jl[k] = ml[use_m12l ? lc : 0];
+            initl[k] = il[use_init_l ? lc : 0];
+        }
     }
+    __builtin_amdgcn_sched_barrier(0);  // (every load above is issued before the first value is looked at)
+    stvo_cam cam_f;
+    cam_f.fx = a_cams ? cam_ld.fx : pa.cam.fx; cam_f.fy = a_cams ? cam_ld.fy : pa.cam.fy; cam_f.cx = a_cams ? cam_ld.cx : pa.cam.cx;
+    cam_f.cy = a_cams ? cam_ld.cy : pa.cam.cy; cam_f.b = a_cams ? cam_ld.b : pa.cam.b;
     const pm::Cam5 cam{cam_f.fx, cam_f.fy, cam_f.cx, cam_f.cy};
     const double cam_b = cam_f.b;
-    const double homog_th = ka().prm.homog_th, inv_homog = 1.0 / homog_th;
+    const double homog_th = pa.prm.homog_th, inv_homog = 1.0 / homog_th;
 
     // ---------------- ownership (as pose2p_kernel): thread t owns prev points t + k BLOCK and prev line BLOCK - 1 - t ----------------
     unsigned pmatched = 0u, pinl = 0u;
-    const int n_prev_p = ka().n_prev_pts != nullptr ? min(ka().n_prev_pts[f], ka().max_pts) : 0;
-    const size_t pbase = (size_t)f * ka().max_pts;
-    int jj[PPT];
-    {
-        int init[PPT];
-        const int last = ka().max_pts - 1;
+    const int n_prev_p = a_n_prev_pts != nullptr ? min(n_p_ld, max_pts) : 0;
 #pragma unroll
-        for (int k = 0; k < PPT; ++k) {  // (addresses clamped to the pair's slot, not to its count: the loads do not wait for n_prev_pts)
-            const int i = tid + k * BLOCK;
-            const int ic = i < last ? i : last;
-            jj[k] = ka().m12p ? ka().m12p[pbase + ic] : ic;
-            init[k] = ka().init_inl_p ? ka().init_inl_p[pbase + ic] : 1;
-        }
-#pragma unroll
-        for (int k = 0; k < PPT; ++k) {
-            const int i = tid + k * BLOCK;
-            if (i < n_prev_p && jj[k] >= 0) {
-                pmatched |= 1u << k;
-                if (init[k] != 0) pinl |= 1u << k;
-            } else {
-                jj[k] = 0;
-            }
+    for (int k = 0; k < PPT; ++k) {  // validity is applied here, where the loaded values are consumed
+        const int i = tid + k * BLOCK;
+        const int j = a_m12p ? jj[k] : i;
+        if (i < n_prev_p && j >= 0) {
+            pmatched |= 1u << k;
+            if (a_init_inl_p == nullptr || init[k] != 0) pinl |= 1u << k;
+            jj[k] = j;
+        } else {
+            jj[k] = 0;
         }
     }
     unsigned lmatched = 0u, linl = 0u;
-    const int n_prev_l = (ka().n_prev_lines != nullptr && ka().max_lines > 0) ? ka().n_prev_lines[f] : 0;
-    const size_t lbase = (size_t)f * ka().max_lines;
-    const int li0 = BLOCK - 1 - tid;
-    int jl[LPT];
-    {
-        int initl[LPT];
+    const int n_prev_l = has_l ? n_l_ld : 0;
 #pragma unroll
-        for (int k = 0; k < LPT; ++k) {
-            const int li = li0 + k * BLOCK;
-            const int lc = (li < n_prev_l && li < ka().max_lines) ? li : 0;
-            jl[k] = (ka().m12l && ka().max_lines > 0) ? ka().m12l[lbase + lc] : lc;
-            initl[k] = (ka().init_inl_l && ka().max_lines > 0) ? ka().init_inl_l[lbase + lc] : 1;
-        }
-#pragma unroll
-        for (int k = 0; k < LPT; ++k) {
-            const int li = li0 + k * BLOCK;
-            if (li < n_prev_l && li < ka().max_lines && jl[k] >= 0) {
-                lmatched |= 1u << k;
-                if (initl[k] != 0) linl |= 1u << k;
-            } else {
-                jl[k] = 0;
-            }
+    for (int k = 0; k < LPT; ++k) {
+        const int li = li0 + k * BLOCK;
+        const int j = use_m12l ? jl[k] : li;
+        if (li < n_prev_l && li < max_lines && j >= 0) {
+            lmatched |= 1u << k;
+            if (!use_init_l || initl[k] != 0) linl |= 1u << k;
+            jl[k] = j;
+        } else {
+            jl[k] = 0;
         }
     }
     const int n_mine = __popc(pmatched);
-    unsigned* const sel = reinterpret_cast<unsigned*>(&s_hist[0][0]);  // BlockOps::select2's scratch: zero before its first use
-    int sel_rot = 0;
-    for (int i = tid; i < 2 * Ops::HIST_W; i += BLOCK) sel[i] = 0u;  // (the barriers of the counts below come first)
-    const int n_m_p = Ops::template sum_int<true>(n_mine, s_ired);
-    const int n_m_l = Ops::template sum_int<true>(__popc(lmatched), s_ired);
+
+    // key-lines: the arena, plane layout [ordinal][7 parts][thread] (as pose2p_kernel).  gather_line: the 14 fields of line slot k
+    // from addresses clamped to the pair's slot, whatever the counts say; store_line, the predicated part: the matched line's record
+    double2* ar_l = arena + (size_t)f * arena_pair;
+    auto gather_line = [&](int k, double* v) {
+        const size_t i = lbase + (size_t)min(li0 + k * BLOCK, last_l), j = lbase + (size_t)jl[k];
+        v[0] = pa.prev_sP[i * 3 + 0]; v[1] = pa.prev_sP[i * 3 + 1]; v[2] = pa.prev_sP[i * 3 + 2];
+        v[3] = pa.prev_eP[i * 3 + 0]; v[4] = pa.prev_eP[i * 3 + 1]; v[5] = pa.prev_eP[i * 3 + 2];
+        v[6] = pa.curr_le[j * 3 + 0]; v[7] = pa.curr_le[j * 3 + 1]; v[8] = pa.curr_le[j * 3 + 2];
+        v[9] = pa.prev_spl[i * 2 + 0]; v[10] = pa.prev_spl[i * 2 + 1];
+        v[11] = pa.prev_epl[i * 2 + 0]; v[12] = pa.prev_epl[i * 2 + 1];
+        v[13] = pa.prev_s2l[i];
+    };
+    auto store_line = [&](int k, const double* v) {
+        if ((lmatched >> k) & 1u) {
+            const int r = __popc(lmatched & ((1u << k) - 1u));
+            double2* q = ar_l + (size_t)(r * 7) * BLOCK + tid;
+#pragma unroll
+            for (int p = 0; p < 6; ++p) q[p * BLOCK] = make_double2(v[2 * p], v[2 * p + 1]);
+            q[6 * BLOCK] = make_double2(v[12], sqrt(v[13]));  // the record carries sqrt(sigma2) (pm::line_term_q)
+        }
+    };
 
     // ---------------- staging: every matched record of the thread, once, ordinal by ordinal ----------------
     const unsigned m_o = n_mine >= 32 ? 0xFFFFFFFFu : ((1u << n_mine) - 1u);
@@ -594,45 +655,62 @@ __global__ __launch_bounds__(NW * 64, 2) void pose2c_kernel(PoseArgs a_by_value,
     unsigned long long lv = 0ull;
     float4 xa = make_float4(0.f, 0.f, 0.f, 0.f);
     double xb = 1.0;
+    // ---- round trip 2, issued as soon as jj is known: both records of every slot (32 x 16 bytes per thread at two waves) and the
+    // fields of line slot 0, where a pair's ~75 key-lines live — unconditional loads from clamped (valid) addresses
+    float4 pv[PPT], cv[PPT];
+    double l0[14];
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const int ik = tid + k * BLOCK;
+        pv[k] = a_prev_rc[pbase + (size_t)(ik < n_prev_p ? ik : 0)];  // (index 0 for the slots past the count: one cache line)
+        cv[k] = a_curr_rc[pbase + (size_t)jj[k]];
+    }
+    if (has_l) gather_line(0, l0);
+    __builtin_amdgcn_sched_barrier(0);
+    // the counts need only pmatched / lmatched: their four barriers pass while the records are in flight
+    unsigned* const sel = reinterpret_cast<unsigned*>(&s_hist[0][0]);  // BlockOps::select2's scratch: zero before its first use
+    int sel_rot = 0;
+    for (int i = tid; i < 2 * Ops::HIST_W; i += BLOCK) sel[i] = 0u;  // (the barriers of the counts below come first)
+    const int n_m_p = Ops::template sum_int<true>(n_mine, s_ired);
+    const int n_m_l = Ops::template sum_int<true>(__popc(lmatched), s_ired);
+    __builtin_amdgcn_sched_barrier(0);
     {
         int r = 0;
-        constexpr int STAGE_CH = PPT;  // both records of every slot in flight at once: one round trip (32 x 16 bytes per thread)
 #pragma unroll
-        for (int k0 = 0; k0 < PPT; k0 += STAGE_CH) {
-            float4 pv[STAGE_CH], cv[STAGE_CH];
-#pragma unroll
-            for (int c = 0; c < STAGE_CH; ++c) {  // unconditional loads from clamped (valid) addresses: all in flight at once
-                const int k = k0 + c;
-                if (k >= PPT) continue;
-                const int ik = tid + k * BLOCK;
-                pv[c] = ka().prev_rc[pbase + (size_t)(ik < n_prev_p ? ik : 0)];  // (index 0 for the slots past the count: one cache line)
-                cv[c] = ka().curr_rc[pbase + (size_t)jj[k]];
-            }
-#pragma unroll
-            for (int c = 0; c < STAGE_CH; ++c) {
-                const int k = k0 + c;
-                if (k >= PPT) continue;
-                if ((pmatched >> k) & 1u) {
-                    const int level = (int)pv[c].w;
-                    const bool in_tab = level >= 0 && level < STVO_POSE_QTAB - 1;
-                    const float4 av = make_float4(pv[c].x, pv[c].y, cv[c].x, cv[c].y);
-                    const double bd = cam_b / (double)pv[c].z;  // backProjection's quotient (src/pinholeStereoCamera.cpp:224)
-                    if (r < KL) {
-                        s_ra[r * BLOCK + tid] = av;
-                        s_rb[r * BLOCK + tid] = bd;
-                    } else if (HAS_REG && r == KL) {
-                        xa = av;
-                        xb = bd;
-                    }
-                    lv |= (unsigned long long)(in_tab ? level : STVO_POSE_QTAB - 1) << (4 * r);
-                    if (r > (HAS_REG ? KL : KL - 1) || !in_tab) slow_o |= 1u << r;
-                    if ((pinl >> k) & 1u) inl_o |= 1u << r;
-                    ++r;
+        for (int k = 0; k < PPT; ++k) {
+            if ((pmatched >> k) & 1u) {
+                const int level = (int)pv[k].w;
+                const bool in_tab = level >= 0 && level < STVO_POSE_QTAB - 1;
+                const float4 av = make_float4(pv[k].x, pv[k].y, cv[k].x, cv[k].y);
+                const double bd = cam_b / (double)pv[k].z;  // backProjection's quotient (src/pinholeStereoCamera.cpp:224)
+                if (r < KL) {
+                    s_ra[r * BLOCK + tid] = av;
+                    s_rb[r * BLOCK + tid] = bd;
+                } else if (HAS_REG && r == KL) {
+                    xa = av;
+                    xb = bd;
                 }
+                lv |= (unsigned long long)(in_tab ? level : STVO_POSE_QTAB - 1) << (4 * r);
+                if (r > (HAS_REG ? KL : KL - 1) || !in_tab) slow_o |= 1u << r;
+                if ((pinl >> k) & 1u) inl_o |= 1u << r;
+                ++r;
             }
-            __builtin_amdgcn_sched_barrier(0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (has_l) {
+        store_line(0, l0);
+        // ---- round trip 3, rare: a pair with more than BLOCK prev key-lines has some in the slots above 0 ----
+        if (LPT > 1 && n_prev_l > BLOCK) {
+            double lk[LPT > 1 ? LPT - 1 : 1][14];
+#pragma unroll
+            for (int k = 1; k < LPT; ++k) gather_line(k, lk[k - 1]);
+#pragma unroll
+            for (int k = 1; k < LPT; ++k) store_line(k, lk[k - 1]);
         }
     }
+    // (a thread reads back only what it wrote itself: program order is enough, no fence)
+
     // the number of LDS planes any lane of this WAVE uses: the trip count of the evaluation loops (wave-uniform, an SGPR)
     int n_trip = n_mine < KL ? n_mine : KL;
 #pragma unroll
@@ -644,9 +722,7 @@ __global__ __launch_bounds__(NW * 64, 2) void pose2c_kernel(PoseArgs a_by_value,
     bool dealt = false;
     unsigned inl_w = 0u;
 
-    // key-lines: the arena, plane layout [ordinal][7 parts][thread] (as pose2p_kernel)
-    double2* ar_l = arena + (size_t)f * arena_pair;
-    auto load_line = [&](int k) -> pm::LineRec {
+    auto load_line = [&](int k) -> pm::LineRec {  // a key-line record back from the arena
         int r = __popc(lmatched & ((1u << k) - 1u));
         asm volatile("" : "+v"(r));  // no hoisted 64-bit addresses across the iteration loop
         const double2* q = ar_l + (size_t)(r * 7) * BLOCK + tid;
@@ -657,22 +733,6 @@ __global__ __launch_bounds__(NW * 64, 2) void pose2c_kernel(PoseArgs a_by_value,
         L.sigma2 = v6.y;
         return L;
     };
-#pragma unroll
-    for (int k = 0; k < LPT; ++k)
-        if ((lmatched >> k) & 1u) {
-            const size_t i = lbase + (size_t)(li0 + k * BLOCK);
-            const size_t j = lbase + (size_t)jl[k];
-            const int r = __popc(lmatched & ((1u << k) - 1u));
-            double2* q = ar_l + (size_t)(r * 7) * BLOCK + tid;
-            q[0] = make_double2(ka().prev_sP[i * 3 + 0], ka().prev_sP[i * 3 + 1]);
-            q[BLOCK] = make_double2(ka().prev_sP[i * 3 + 2], ka().prev_eP[i * 3 + 0]);
-            q[2 * BLOCK] = make_double2(ka().prev_eP[i * 3 + 1], ka().prev_eP[i * 3 + 2]);
-            q[3 * BLOCK] = make_double2(ka().curr_le[j * 3 + 0], ka().curr_le[j * 3 + 1]);
-            q[4 * BLOCK] = make_double2(ka().curr_le[j * 3 + 2], ka().prev_spl[i * 2 + 0]);
-            q[5 * BLOCK] = make_double2(ka().prev_spl[i * 2 + 1], ka().prev_epl[i * 2 + 0]);
-            q[6 * BLOCK] = make_double2(ka().prev_epl[i * 2 + 1], sqrt(ka().prev_s2l[i]));  // the record carries sqrt(sigma2) (pm::line_term_q)
-        }
-    // (a thread reads back only what it wrote itself: program order is enough, no fence)
 
     {
         const int nip = Ops::template sum_int<true>(__popc(inl_o), s_ired);
@@ -684,11 +744,10 @@ __global__ __launch_bounds__(NW * 64, 2) void pose2c_kernel(PoseArgs a_by_value,
             sh->n_inl_l = nil;
             sh->good = 1;
             sh->err_out = -1.0;  // :313
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const double v = ka().init_T ? ka().init_T[(size_t)f * 16 + i] : ((i % 5 == 0) ? 1.0 : 0.0);
-                sh->DT[i] = v;
-                sh->DT0[i] = v;
+            if (lane < 16) {  // one element per lane, loaded in round trip 1 (the barrier below publishes it)
+                const double v = a_init_T ? init_T_ld : ((lane % 5 == 0) ? 1.0 : 0.0);
+                sh->DT[lane] = v;
+                sh->DT0[lane] = v;
             }
 #pragma unroll
             for (int i = 0; i < 36; ++i) {
