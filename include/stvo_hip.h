@@ -587,8 +587,11 @@ typedef struct stvo_lsd_params {
     double density_th;     /* Config::lsdDensityTh()   0.6 (read with refine 1) */
     double min_length;     /* LSDOptions::min_length = min_line_length x min(cols, rows) (stereoFrame.cpp:78) */
     int32_t nfeatures;     /* Config::lsdNFeatures()   300, 0: keep all */
-    int32_t reserved;
+    int32_t flags;         /* STVO_LSD_* bits below; other bits are ignored; 0: none (the field was `reserved`, never read) */
 } stvo_lsd_params;
+/* stvo_lsd_params::flags, bit 0: stvo_lsd_set_image_sizes also takes this detector when its scale is not 1 and its blur radius not 3
+ * (lsd_scale : 0.5 among them).  It changes nothing at creation and nothing while no size table is set. */
+#define STVO_LSD_SIZES_ANY_RADIUS 1
 typedef struct stvo_lsd stvo_lsd;
 /* HOST ONLY, no context: what stvo_lsd_create derives from the parameters and the image size, and the same verdict on them
  * (STVO_ERR_INVALID_ARG / STVO_ERR_UNSUPPORTED / STVO_ERR_CAPACITY exactly where stvo_lsd_create returns them; it takes its own
@@ -636,7 +639,12 @@ int stvo_lsd_scaled_image(stvo_lsd* lsd, const uint8_t* images, uint8_t* scaled)
  *   STVO_ERR_INVALID_ARG and nothing changes: n <= 0, n > B, B % n != 0, an entry larger than the slot, an entry stvo_lsd_create would
  * refuse as an image size (a side below 8, nothing left after scaling), a NaN minimum length.  STVO_ERR_UNSUPPORTED and nothing
  * changes: a detector whose blur radius is not 3 at a scale other than 1 (stvo_lsd_geometry tells the radius; every shipped yaml but
- * lsd_scale : 0.5 gives 3) — its fused blur + resize plans its tile per size.  sizes_host and min_length_host are read during the
+ * lsd_scale : 0.5 gives 3) that was created WITHOUT STVO_LSD_SIZES_ANY_RADIUS in stvo_lsd_params::flags.  With the flag such a
+ * detector is taken at every built radius 0 .. STVO_LSD_MAX_RADIUS under the same contract: its fused blur + resize then runs every
+ * image under the slot's tile plan, whose LDS bounds the need of every image that fits the slot, reading nothing outside the image's
+ * crop and writing nothing outside the top-left scaled size of its slot; the scaled image does not depend on the tile, so the crop
+ * comes back as a detector of its own size — with its own tile — returns it.  At radius 3 and at scale 1 the flag changes nothing.
+ * sizes_host and min_length_host are read during the
  * call; the table travels on the context's stream behind the detections already enqueued, through pinned staging that is not reused
  * before its copy has completed: no synchronisation.  The device table is allocated at the first call; sizes_host == NULL: every image
  * fills its slot again, on the very kernels of a detector that was never given a table. */

@@ -12,6 +12,7 @@
 #include "../../include/stvo_hip.h"
 #include "debug_switches.h"
 #include "grid_scratch.h"
+#include "lsd_scale_plan.h"
 #include "match_scratch.h"
 #include "point_tail.h"
 #include "pose_scratch.h"
@@ -228,13 +229,13 @@ void launch_resize_linear_u8(hipStream_t s, int B, int scols, int srows, int dco
 // ---- the same two operations fused, for every blur radius 0 .. STVO_LSD_MAX_RADIUS (lsd_scale_kernels.hip) ----
 // cv::GaussianBlur((1 + 2 radius)^2) with the integer weights (x 2^8, 32-bit: one can be 256) + cv::resize(…, Size(), scale, scale):
 // one workgroup per tile of the scaled image, the blurred bytes only in LDS.  The plan (tile, dynamic LDS) depends on the geometry
-// alone and is made once; false: no tile fits the LDS (scales far below 0.01).
-struct BlurResizePlan {
-    int tw_log, th_log, lds_bytes;
-};
-bool plan_blur_resize_u8(int scols, int srows, double scale, int radius, BlurResizePlan* p);
+// alone and is made once (lsd_scale_plan.h: BlurResizePlan, plan_blur_resize_u8; false: no tile fits the LDS, scales far below 0.01).
+// sz (device, or nullptr: every image fills scols x srows): one size per image, image b being the top-left of its slot at the slot's
+// pitch — source and scaled — sized by row b % n_sz of the detector's table (lsd_sizes.h), under the SLOT's plan, which bounds the
+// need of every image that fits the slot (lsd_scale_plan.h) — the MIXED instance of the kernel
+struct LsdSizeRow;
 void launch_blur_resize_u8(hipStream_t s, int B, int scols, int srows, int dcols, int drows, const uint8_t* src, uint8_t* dst, double scale,
-                           int radius, const int* weights, const BlurResizePlan& p);
+                           int radius, const int* weights, const BlurResizePlan& p, const LsdSizeRow* sz = nullptr, int n_sz = 0);
 
 // ---- K3: grid-windowed stereo matchers, batched over frame pairs (blockIdx.y) ----------------------
 constexpr int GRID_LW = STVO_GRID_COLS + 16, GRID_LCELLS = STVO_GRID_ROWS * GRID_LW, GRID_LSTART_STRIDE = GRID_LCELLS + 4;

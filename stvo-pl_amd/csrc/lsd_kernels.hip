@@ -37,6 +37,8 @@
 // Every kernel but lsd_grow_xcd_kernel is a template on MIXED: the MIXED instances read their image's row of a size table (one image size
 // and minimum length per image, stvo_lsd_set_image_sizes, csrc/lsd_sizes.h), the others are the kernels as they were.  Under a table the
 // search runs ONE wave per image at every batch size (lsd_grow_kernel / lsd_grow_refine_kernel); lsd_grow_xcd_kernel is not launched.
+// The scaled image under a table: ORB's MIXED blur and resize at radius 3, the MIXED instance of lsd_blur_resize_kernel at every other
+// radius — for a detector created with STVO_LSD_SIZES_ANY_RADIUS (lsd_scale_kernels.hip, lsd_scale_plan.h).
 // Byte / integer work except where the source computes in floating point; no fused multiply-adds outside the two of the sine /
 // cosine reduction, which the oracle has too.
 #include <cmath>
@@ -94,15 +96,8 @@ struct LsdDev {
     int32_t* n_lines;          // [B]
 };
 
-// One image size per image (stvo_lsd_set_image_sizes): image i is sized by row i % n_sz of the table.  An argument of its own behind
-// LsdDev, and empty for the uniform instances — they take the arguments they always took.
-template <bool MIXED>
-struct LsdTable {};
-template <>
-struct LsdTable<true> {
-    const LsdSizeRow* sz;
-    int n_sz;
-};
+// One image size per image (stvo_lsd_set_image_sizes): LsdTable<MIXED> (lsd_sizes.h), an argument of its own behind LsdDev and empty for
+// the uniform instances — they take the arguments they always took.
 
 // The image a workgroup works on.  MIXED = false: the slot itself — the kernel as it was, reading its argument.  MIXED = true: the
 // kernel's own copy of its argument takes the image's sizes, smallest region and minimum length from the image's row of the table in
@@ -1800,8 +1795,11 @@ void lsd_scaled_enqueue(stvo_lsd* o, const uint8_t* images) {
         const stvo::OrbLevelSize* sz = o->n_sizes ? o->scale_rows() : nullptr;
         stvo::launch_blur7_u8(s, d.B, d.cols, d.rows, images, o->blur, o->kw, sz, o->n_sizes, 2, 0);
         stvo::launch_resize_linear_u8(s, d.B, d.cols, d.rows, d.w, d.h, o->blur, o->scaled, d.scale, d.scale, sz, o->n_sizes, 2, 1);
-    } else {  // (no size table here: stvo_lsd_set_image_sizes refuses the detector)
-        stvo::launch_blur_resize_u8(s, d.B, d.cols, d.rows, d.w, d.h, images, o->scaled, d.scale, o->radius, o->kw, o->plan);
+    } else {
+        // under a size table (a detector created with STVO_LSD_SIZES_ANY_RADIUS): the MIXED instance under the slot's plan, which bounds
+        // every image that fits the slot (lsd_scale_plan.h)
+        const stvo::LsdSizeRow* sz = o->n_sizes ? reinterpret_cast<const stvo::LsdSizeRow*>(o->sizes.dev) : nullptr;
+        stvo::launch_blur_resize_u8(s, d.B, d.cols, d.rows, d.w, d.h, images, o->scaled, d.scale, o->radius, o->kw, o->plan, sz, o->n_sizes);
     }
 }
 
@@ -2011,8 +2009,9 @@ int stvo_lsd_set_image_sizes(stvo_lsd* o, const int32_t* sizes_host, const doubl
     }
     const stvo::LsdDev& d = o->d;
     if (!stvo::lsd_image_sizes_ok(sizes_host, min_length_host, n, d.B, d.cols, d.rows, d.scale)) return STVO_ERR_INVALID_ARG;
-    // the fused blur + resize of the other radii plans its tile per size: such a detector keeps one size
-    if (d.scale != 1 && o->radius != 3) return STVO_ERR_UNSUPPORTED;
+    // the fused blur + resize of the other radii runs every image under the slot's tile plan (lsd_scale_plan.h: the bound) — for a
+    // detector that asked for it at creation; without the flag such a detector keeps one size, as it always did
+    if (d.scale != 1 && o->radius != 3 && !(o->prm.flags & STVO_LSD_SIZES_ANY_RADIUS)) return STVO_ERR_UNSUPPORTED;
     stvo_ctx* ctx = o->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     constexpr size_t entry = sizeof(stvo::LsdSizeRow) + 2 * sizeof(stvo::OrbLevelSize);

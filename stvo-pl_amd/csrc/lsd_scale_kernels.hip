@@ -16,8 +16,18 @@
 // A down-scale neither writes nor reads a full-size blurred image.  The radius is a template argument (one instance per radius: the
 // tap loops unroll, the weights — 32-bit values from the kernel-argument segment — sit in scalar registers and the LDS reads carry
 // immediate offsets; with the radius as a launch argument every tap waited for a scalar load of its weight), the tile a launch
-// argument chosen by the host so that the LDS fits.
+// argument chosen by the host so that the LDS fits (lsd_scale_plan.h).
+//
+// One image size per image (stvo_lsd_set_image_sizes on a detector created with STVO_LSD_SIZES_ANY_RADIUS): the MIXED instance, in the
+// form of lsd_kernels.hip — the table (LsdTable<MIXED>, lsd_sizes.h) an argument of its own, empty for the uniform instance, one body.  A workgroup takes its image
+// from blockIdx.z and that image's row of the table with scalar loads; the row replaces the BOUNDS only (the source size for the taps,
+// the reflection and the word-load clamp; the scaled size for the tile's extent and the store), the pitches and the strides per image
+// stay the slot's, source and scaled.  The launch is the slot's — its grid, its tile, its LDS, which bounds the need of every tile of
+// every image that fits the slot (lsd_scale_plan.h) — and a workgroup whose tile lies outside its image's scaled size leaves as a
+// whole before the first barrier.  Nothing is read outside the image's crop and nothing written outside the top-left w_i x h_i of its
+// slot of the scaled buffer.  The uniform instances are the code they were (profiles/mixed_lsd_scale_kernel_resources.txt).
 #include "kernels.h"
+#include "lsd_sizes.h"
 
 #pragma clang fp contract(off)
 
@@ -25,7 +35,6 @@ namespace stvo {
 namespace {
 
 constexpr int BR_T = 256;                 // threads of a workgroup
-constexpr int BR_LDS_BUDGET = 64 * 1024;  // dynamic LDS a tile may take (no opt-in needed; the default 64 x 16 tile takes 34 KB at h = 5 / scale 0.5)
 
 typedef uint32_t __attribute__((aligned(1))) u32_unaligned;  // a word at any byte address (gfx950 global memory allows it)
 
@@ -70,23 +79,6 @@ struct BlurResizeArgs {
     int k[STVO_LSD_MAX_TAPS]; // the integer weights
 };
 
-// The geometry of a tile in LDS, the same arithmetic on the host (an upper bound sizes the launch) and in the kernel.  nx x ny: the
-// source pixels between the tile's first and last bilinear tap; ncp x nr: the columns / rows in which blurred bytes are kept.
-struct BrLayout {
-    int sr;         // staged rows: ny + 2 radius
-    int scp;        // pitch of a staged row in bytes: the columns a run of 4 sums reads (4 ceil(nx / 4) + 2 radius, in whole words)
-    int ncp;        // pitch of the sums and of the blurred bytes, a multiple of 4: nx columns for a contiguous run, 2 per output column for the pairs
-    long long bytes;
-};
-__host__ __device__ inline BrLayout br_layout(int nx, int ny, int ncp, int nr, int hk, int tw, int th) {
-    BrLayout l;
-    l.sr = ny + 2 * hk;
-    l.scp = (4 * ((nx + 3) / 4) + 2 * hk + 4) & ~3;
-    l.ncp = ncp;
-    l.bytes = 4ll * l.sr * ncp + 16 * (tw + th) + (long long)l.sr * l.scp + (((long long)nr * ncp + 3) & ~3ll);
-    return l;
-}
-
 // R sums of 1 + 2 HK taps each over R + 2 HK consecutive values: sum u covers v[u .. u + 2 HK].  Weights <= 2^8, bytes < 2^8, row
 // sums < 2^24: the 24-bit multiplies are exact; the sums are integers, so their order is free.
 template <int HK, int R>
@@ -98,12 +90,23 @@ __device__ __forceinline__ void tap_sums(const uint32_t (&v)[R + 2 * HK], const 
     }
 }
 
-template <int HK>  // radius: 1 + 2 HK taps
-__global__ __launch_bounds__(BR_T) void lsd_blur_resize_kernel(BlurResizeArgs a) {
+template <int HK, bool MIXED>  // radius: 1 + 2 HK taps; MIXED: the bounds of every image from its row of the table
+__global__ __launch_bounds__(BR_T) void lsd_blur_resize_kernel(BlurResizeArgs a, LsdTable<MIXED> tab) {
     extern __shared__ __attribute__((aligned(16))) unsigned char br_lds[];
     const int tid = threadIdx.x;
     const int tw = 1 << a.tw_log, th = 1 << a.th_log;
     const int dx0 = blockIdx.x << a.tw_log, dy0 = blockIdx.y << a.th_log, b = blockIdx.z;
+    // the slot's pitches and strides per image, before the image's own bounds take the place of a.scols .. a.drows in the kernel's copy
+    // of its argument (so the text below is one for both instances; the uniform instance does none of this)
+    const int spitch = a.scols, sheight = a.srows, dpitch = a.dcols, dheight = a.drows;
+    if constexpr (MIXED) {  // the row is uniform over the workgroup; it is clamped into the slot, which the host has validated it to fit
+        const LsdSizeRow* e = tab.sz + (b % tab.n_sz);
+        a.scols = __builtin_amdgcn_readfirstlane(min(max(e->cols, 8), a.scols));
+        a.srows = __builtin_amdgcn_readfirstlane(min(max(e->rows, 1), a.srows));
+        a.dcols = __builtin_amdgcn_readfirstlane(min(max(e->w, 1), a.dcols));
+        a.drows = __builtin_amdgcn_readfirstlane(min(max(e->h, 1), a.drows));
+        if (dx0 >= a.dcols || dy0 >= a.drows) return;  // a tile of the slot's grid outside this image: block-uniform, before any barrier
+    }
     const int ntw = min(tw, a.dcols - dx0), nth = min(th, a.drows - dy0);
     constexpr int hk = HK;
     int cmin, cmax, rmin, rmax, t0, t1, t2;  // (the taps are monotonic in d: the first and the last output bound the window)
@@ -111,6 +114,8 @@ __global__ __launch_bounds__(BR_T) void lsd_blur_resize_kernel(BlurResizeArgs a)
     resize_taps<true>(dx0 + ntw - 1, a.step_x, a.scols, t0, cmax, t1, t2);
     resize_taps<false>(dy0, a.step_y, a.srows, rmin, t0, t1, t2);
     resize_taps<false>(dy0 + nth - 1, a.step_y, a.srows, t0, rmax, t1, t2);
+    // (lsd_scale_plan.h: br_tile_layout states these four lines for the host, and says why they stay here; tests/test_lsd_scale_plan_host.py
+    // holds the two texts together)
     const int nx = cmax - cmin + 1, ny = rmax - rmin + 1;
     const bool xlist = nx > 2 * ntw, ylist = ny > 2 * nth;  // the taps as pairs per output (scale < 0.5), not as one contiguous run
     const int nr = ylist ? 2 * nth : ny;
@@ -134,7 +139,7 @@ __global__ __launch_bounds__(BR_T) void lsd_blur_resize_kernel(BlurResizeArgs a)
             s_yt[d - ntw] = make_int4(i0 - rmin, i1 - i0, w0, w1);
         }
     }
-    const uint8_t* img = a.src + (size_t)b * a.srows * a.scols;
+    const uint8_t* img = a.src + (size_t)b * sheight * spitch;
     // staging, a word of the window per thread and four of them in flight: away from the image border a word of the window is a word
     // of the image (at any byte address); at the border, and in the padding of a row, it is put together byte by byte
     {
@@ -148,7 +153,7 @@ __global__ __launch_bounds__(BR_T) void lsd_blur_resize_kernel(BlurResizeArgs a)
             for (int m = 0; m < 4; ++m) {
                 const int t = min(t0 + m * BR_T, nwords - 1), r = t / scp4;
                 gx[m] = cmin - hk + 4 * (t - r * scp4);
-                row[m] = img + (size_t)reflect101(rmin - hk + r, a.srows) * a.scols;
+                row[m] = img + (size_t)reflect101(rmin - hk + r, a.srows) * spitch;
                 w[m] = *reinterpret_cast<const u32_unaligned*>(row[m] + min(max(gx[m], 0), a.scols - 4));
             }
 #pragma unroll
@@ -223,7 +228,7 @@ __global__ __launch_bounds__(BR_T) void lsd_blur_resize_kernel(BlurResizeArgs a)
         }
     }
     __syncthreads();
-    uint8_t* out = a.dst + (size_t)b * a.drows * a.dcols;
+    uint8_t* out = a.dst + (size_t)b * dheight * dpitch;
     for (int t = tid; t < (th << a.tw_log); t += BR_T) {
         const int lx = t & (tw - 1), ly = t >> a.tw_log;
         if (lx >= ntw || ly >= nth) continue;
@@ -234,38 +239,14 @@ __global__ __launch_bounds__(BR_T) void lsd_blur_resize_kernel(BlurResizeArgs a)
         const int S0 = (int)s_bl[qy0 * ncp + jx0] * a0 + (int)s_bl[qy0 * ncp + jx1] * a1;
         const int S1 = (int)s_bl[qy1 * ncp + jx0] * a0 + (int)s_bl[qy1 * ncp + jx1] * a1;
         const int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
-        out[(size_t)(dy0 + ly) * a.dcols + dx0 + lx] = (uint8_t)min(max(v, 0), 255);
+        out[(size_t)(dy0 + ly) * dpitch + dx0 + lx] = (uint8_t)min(max(v, 0), 255);
     }
 }
 
 }  // namespace
 
-// The tile of the scaled image and the dynamic LDS of its launch: 64 x 16 unless the source window of such a tile (it grows with
-// 1 / scale) exceeds the budget, then the longer side is halved; false: not even one output pixel per workgroup fits.
-bool plan_blur_resize_u8(int scols, int srows, double scale, int radius, BlurResizePlan* p) {
-    const double step = 1.0 / scale;
-    for (int twl = 6, thl = 4;;) {
-        const int tw = 1 << twl, th = 1 << thl;
-        // first and last tap of a tile: floor() of positions (tile - 1) step apart, + 1 for the second tap, + 1 for the two floors,
-        // + 1 for the roundings to float — never more than the image
-        const double sx = std::ceil((tw - 1) * step) + 4, sy = std::ceil((th - 1) * step) + 4;
-        const int nx = (int)(sx < scols ? sx : scols), ny = (int)(sy < srows ? sy : srows);
-        // (a contiguous run is at most 2 tile columns rounded up to 4, the pairs are 2 per column)
-        const int run = 4 * ((nx + 3) / 4), most = 2 * tw > 4 ? 2 * tw : 4;
-        const int ncp = run < most ? run : most, nr = ny < 2 * th ? ny : 2 * th;
-        const long long bytes = br_layout(nx, ny, ncp, nr, radius, tw, th).bytes;
-        if (bytes <= BR_LDS_BUDGET) {
-            p->tw_log = twl; p->th_log = thl; p->lds_bytes = (int)bytes;
-            return true;
-        }
-        if (twl == 0 && thl == 0) return false;
-        if (twl >= thl) --twl;
-        else --thl;
-    }
-}
-
 void launch_blur_resize_u8(hipStream_t s, int B, int scols, int srows, int dcols, int drows, const uint8_t* src, uint8_t* dst, double scale,
-                           int radius, const int* weights, const BlurResizePlan& p) {
+                           int radius, const int* weights, const BlurResizePlan& p, const LsdSizeRow* sz, int n_sz) {
     BlurResizeArgs a{};
     a.B = B; a.scols = scols; a.srows = srows; a.dcols = dcols; a.drows = drows;
     a.tw_log = p.tw_log; a.th_log = p.th_log; a.lds_bytes = p.lds_bytes;
@@ -273,13 +254,22 @@ void launch_blur_resize_u8(hipStream_t s, int B, int scols, int srows, int dcols
     a.src = src; a.dst = dst;
     for (int i = 0; i < 1 + 2 * radius; ++i) a.k[i] = weights[i];
     const int tw = 1 << p.tw_log, th = 1 << p.th_log;
-    typedef void (*kernel_t)(BlurResizeArgs);
-    static const kernel_t kernels[STVO_LSD_MAX_RADIUS + 1] = {
-        lsd_blur_resize_kernel<0>,  lsd_blur_resize_kernel<1>,  lsd_blur_resize_kernel<2>,  lsd_blur_resize_kernel<3>,
-        lsd_blur_resize_kernel<4>,  lsd_blur_resize_kernel<5>,  lsd_blur_resize_kernel<6>,  lsd_blur_resize_kernel<7>,
-        lsd_blur_resize_kernel<8>,  lsd_blur_resize_kernel<9>,  lsd_blur_resize_kernel<10>, lsd_blur_resize_kernel<11>,
-        lsd_blur_resize_kernel<12>, lsd_blur_resize_kernel<13>, lsd_blur_resize_kernel<14>, lsd_blur_resize_kernel<15>};
-    hipLaunchKernelGGL(kernels[radius], dim3((dcols + tw - 1) / tw, (drows + th - 1) / th, B), dim3(BR_T), (size_t)p.lds_bytes, s, a);
+    const dim3 grid((dcols + tw - 1) / tw, (drows + th - 1) / th, B);
+#define BR_KERNELS(M)                                                                                                             \
+    {lsd_blur_resize_kernel<0, M>,  lsd_blur_resize_kernel<1, M>,  lsd_blur_resize_kernel<2, M>,  lsd_blur_resize_kernel<3, M>,   \
+     lsd_blur_resize_kernel<4, M>,  lsd_blur_resize_kernel<5, M>,  lsd_blur_resize_kernel<6, M>,  lsd_blur_resize_kernel<7, M>,   \
+     lsd_blur_resize_kernel<8, M>,  lsd_blur_resize_kernel<9, M>,  lsd_blur_resize_kernel<10, M>, lsd_blur_resize_kernel<11, M>,  \
+     lsd_blur_resize_kernel<12, M>, lsd_blur_resize_kernel<13, M>, lsd_blur_resize_kernel<14, M>, lsd_blur_resize_kernel<15, M>}
+    if (sz && n_sz > 0) {  // one size per image: the slot's grid, tile and LDS
+        typedef void (*kernel_t)(BlurResizeArgs, LsdTable<true>);
+        static const kernel_t kernels[STVO_LSD_MAX_RADIUS + 1] = BR_KERNELS(true);
+        hipLaunchKernelGGL(kernels[radius], grid, dim3(BR_T), (size_t)p.lds_bytes, s, a, LsdTable<true>{sz, n_sz});
+        return;
+    }
+    typedef void (*kernel_t)(BlurResizeArgs, LsdTable<false>);
+    static const kernel_t kernels[STVO_LSD_MAX_RADIUS + 1] = BR_KERNELS(false);
+    hipLaunchKernelGGL(kernels[radius], grid, dim3(BR_T), (size_t)p.lds_bytes, s, a, LsdTable<false>{});
+#undef BR_KERNELS
 }
 
 }  // namespace stvo

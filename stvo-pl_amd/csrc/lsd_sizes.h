@@ -26,6 +26,17 @@ struct LsdSizeRow {
 };
 static_assert(sizeof(LsdSizeRow) == 32, "the kernels read a row as 32 bytes");
 
+// One image size per image (stvo_lsd_set_image_sizes) as the kernels take it: image i is sized by row i % n_sz of the table.  A kernel
+// argument of its own behind the kernel's arguments, and empty for the uniform instances — they take the arguments they always took
+// (lsd_kernels.hip and lsd_scale_kernels.hip).
+template <bool MIXED>
+struct LsdTable {};
+template <>
+struct LsdTable<true> {
+    const LsdSizeRow* sz;
+    int n_sz;
+};
+
 // one axis of the scaled image, as a double: the callers look at its range before they narrow it
 inline double lsd_scaled_extent(int n, double scale) { return scale != 1 ? std::rint((double)n * scale) : (double)n; }
 

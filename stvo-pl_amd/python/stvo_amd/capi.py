@@ -633,12 +633,18 @@ KEYLINE_DTYPE = np.dtype([("sx", "<f4"), ("sy", "<f4"), ("ex", "<f4"), ("ey", "<
 class LsdParams(C.Structure):  # stvo_lsd_params
     _fields_ = [("refine", C.c_int32), ("n_bins", C.c_int32), ("scale", C.c_double), ("sigma_scale", C.c_double), ("quant", C.c_double),
                 ("ang_th", C.c_double), ("log_eps", C.c_double), ("density_th", C.c_double), ("min_length", C.c_double),
-                ("nfeatures", C.c_int32), ("reserved", C.c_int32)]
+                ("nfeatures", C.c_int32), ("flags", C.c_int32)]
 
 
-def lsd_params(min_length=0.0, nfeatures=300, refine=0, scale=1.2, sigma_scale=0.6, quant=2.0, ang_th=22.5, n_bins=1024):
-    """src/config.cpp:104-112 (every shipped yaml has the same values)."""
-    return LsdParams(refine, n_bins, scale, sigma_scale, quant, ang_th, 1.0, 0.6, min_length, nfeatures, 0)
+LSD_SIZES_ANY_RADIUS = 1  # STVO_LSD_SIZES_ANY_RADIUS
+
+
+def lsd_params(min_length=0.0, nfeatures=300, refine=0, scale=1.2, sigma_scale=0.6, quant=2.0, ang_th=22.5, n_bins=1024,
+               sizes_any_radius=False):
+    """src/config.cpp:104-112 (every shipped yaml has the same values).  sizes_any_radius: Lsd.set_image_sizes also takes the detector
+    at a scale other than 1 with a blur radius other than 3 (STVO_LSD_SIZES_ANY_RADIUS; nothing else changes)."""
+    return LsdParams(refine, n_bins, scale, sigma_scale, quant, ang_th, 1.0, 0.6, min_length, nfeatures,
+                     LSD_SIZES_ANY_RADIUS if sizes_any_radius else 0)
 
 
 LSD_MAX_RADIUS = 15  # STVO_LSD_MAX_RADIUS

@@ -31,7 +31,8 @@ class ImagePipeline:
         fld raise ValueError, and so do a rectify that is not a capi.RectifierBank and channels other than 1 without one.
         lines_per_stream = True (with a list and lsd; ValueError without either) is the opt-in for key-lines on such streams: the LSD
         detector and LBD are built at the slot size and read every image at its own size beside ORB (Lsd.set_image_sizes,
-        Lbd.set_image_sizes), with and without a rectifier bank; lsd_min_length_ratio = r gives stream b the minimum line length
+        Lbd.set_image_sizes), with and without a rectifier bank, at every built lsd_scale (the pipeline sets LSD_SIZES_ANY_RADIUS on its
+        own copy of lsd: lsd_scale 0.5 and the other blur radii run the fused blur + resize per image too); lsd_min_length_ratio = r gives stream b the minimum line length
         r * min(width_b, height_b) of its own camera (the reference's Config::minLineLength() x min(width, height)), None keeps
         lsd.min_length for all; a stream that RESTARTs hands its new size and minimum length to both with its camera.  fld stays
         refused with a list (the FLD walk holds one size).
@@ -123,6 +124,9 @@ class ImagePipeline:
         if lp is not None and (lp.nfeatures == 0 or lp.nfeatures > max_kl):
             import warnings
             warnings.warn(f"ImagePipeline: line nfeatures = {lp.nfeatures} against a capacity of {max_kl} key-lines per image: the strongest {max_kl} are kept")
+        if lsd is not None and lines_per_stream:  # the opt-in has been given: a size per image at every built blur radius, on a copy
+            lsd = capi.LsdParams.from_buffer_copy(lsd)
+            lsd.flags |= capi.LSD_SIZES_ANY_RADIUS
         self.lsd = capi.Lsd(ctx, 2 * B, self.cols, self.rows, lsd, max_keylines=max_kl) if lsd is not None else None
         self.fld = capi.Fld(ctx, 2 * B, self.cols, self.rows, fld, max_keylines=max_kl) if fld is not None else None
         self.lines = self.lsd if self.lsd is not None else self.fld  # the key-line detector, or None
