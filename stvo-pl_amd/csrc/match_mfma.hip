@@ -28,6 +28,11 @@
 //   * bit -> K element mapping: K step kk covers descriptor words 2 kk (lower wave half) and 2 kk + 1 (upper); dword d of a
 //     lane's fragment holds bits d, d + 4, ..., d + 28 of its word as nibbles: ((w << (3 - d)) & 0x88888888) | 0x66666666 —
 //     and + shift-or per eight elements in the forward scan (expand_fp4_lshl_or).  Any mapping works as long as both operands use the same one (a sum over k).
+//   * the tile loop of the forward scan exists in two forms: the GENERAL barrier group (any tile count, conditional fetch and staging, the
+//     first group and the last two or three of a segment) and the STEADY loop between them (all tiles it touches are full: nothing
+//     conditional, two groups per turn).  One-op nibble codes that leave a bit where it is in its nibble (0 / 0.5, 0 / 1, 0 / 2, +1 / -1
+//     against query magnitudes 4, 2, 1, 1, scales 2^6, a per-query constant 4096 (192 - 2 popcount(q & 0x77..7)) in every key) were built
+//     and are exact on the hardware, but measured slower, not faster: NOTES.md, profiles/k1m_codes_ab.json.
 #include <type_traits>
 
 #include "kernels.h"
@@ -154,7 +159,8 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
     const int dir = dir0 + (local / nseg) / tiles;
     const int slot = (local / nseg) % tiles;
     const size_t frame_off = (size_t)b * row_stride;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, col = lane & 31, hf = lane >> 5;
+    // (the wave's number as a scalar: what is derived from it — its first row, wave_active — holds no vector register through the scan)
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), col = lane & 31, hf = lane >> 5;
     const uint32_t* __restrict__ Q = reinterpret_cast<const uint32_t*>((dir == 0 ? d1 : d2) + frame_off * STVO_DESC_BYTES);
     // A slot that knows its tile before the counts arrive fetches its query rows while n1 / n2 are still on their way (rows
     // past the count are inside the frame's slot, are scanned like any other row and never stored).  An end slot learns its
@@ -275,11 +281,12 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
     // FOLD: 0 = the first tile of a scan (nothing to fold yet), 1 = the tile behind it, 2 = every later tile.
     // ODD: the second tile of a pair — its keys are relative to the pair's first row (C operand cidx + 32), and in front of its folds,
     // which take the pair's first tile, (best, second) move from the previous pair's frame to this one.
-    auto mma_fold = [&](auto nb_c, auto fold_c, auto odd_c, acc_t (&cur)[QB], acc_t (&prev)[QB], int t) {
+    // KNOWN: the caller has tested wave_active already (the steady loop: once, in front of the loop).
+    auto mma_fold = [&](auto known_c, auto nb_c, auto fold_c, auto odd_c, acc_t (&cur)[QB], acc_t (&prev)[QB], int t) {
         constexpr int NB = decltype(nb_c)::value, FOLD = decltype(fold_c)::value;
-        constexpr bool ODD = decltype(odd_c)::value;
+        constexpr bool ODD = decltype(odd_c)::value, KNOWN = decltype(known_c)::value;
         constexpr bool fold_prev = FOLD > 0;  // tile t - 1 is a full tile here
-        if (wave_active) {
+        if (KNOWN || wave_active) {
             const v4i* frag = s_tile[t & (NBUF - 1)];
             if (ODD && FOLD == 2) rebase(NB);  // (in the first pair they hold no key yet)
             key_t node[NB][5];
@@ -313,6 +320,14 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
                         asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 2" : "+v"(prev[0]));
 #pragma unroll
                         for (int qb = 1; qb < NB; ++qb) asm volatile("" : "+v"(prev[qb]));  // (behind the fence: volatile asm keeps its order)
+                    }
+                    // In the steady loop two tiles share a basic block, and nothing but data keeps this tile's folds behind its first
+                    // matrix instruction, which the structural distance above counts on (without the tie the scheduler drew five of
+                    // them in front of it: 12 wait states, no margin).  Tie the previous tile's registers to that instruction's
+                    // result: no instruction, no register (21 wait states).
+                    if (KNOWN && kk == 0) {
+#pragma unroll
+                        for (int qb = 0; qb < NB; ++qb) asm("" : "+v"(prev[qb]) : "v"(cur[0]));
                     }
 #pragma unroll
                     for (int qb = 0; qb < NB; ++qb) {
@@ -388,8 +403,8 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
                 if (t + 2 * MF_TPB + i < ntiles) w_far[i] = fetch(t + 2 * MF_TPB + i);
             }
             static_assert(MF_TPB == 2, "the accumulator sets alternate tile by tile, two tiles per group");
-            mma_fold(nb_c, std::integral_constant<int, (FIRST ? 0 : 2)>{}, std::false_type{}, accA, accB, t);
-            mma_fold(nb_c, std::integral_constant<int, (FIRST ? 1 : 2)>{}, std::true_type{}, accB, accA, t + 1);
+            mma_fold(std::false_type{}, nb_c, std::integral_constant<int, (FIRST ? 0 : 2)>{}, std::false_type{}, accA, accB, t);
+            mma_fold(std::false_type{}, nb_c, std::integral_constant<int, (FIRST ? 1 : 2)>{}, std::true_type{}, accB, accA, t + 1);
 #pragma unroll
             for (int i = 0; i < MF_TPB; ++i) {
                 if (t + MF_TPB + i < ntiles) stage(t + MF_TPB + i, w_near[i]);
@@ -398,11 +413,38 @@ __global__ __launch_bounds__(MF_BLOCK, (QB == 1 ? 4 : QB == 2 ? 3 : 1)) void ham
             __syncthreads();
             t += MF_TPB;
         };
+        // The STEADY group: tiles t .. t + 3 MF_TPB - 1 are all full tiles of the segment, so the fetch two groups ahead and the
+        // staging one group ahead are unconditional and no lane tests its row: the conditions of the general group are false only
+        // in a segment's last groups, yet cost it ~45 scalar and branch instructions every time (1647 train rows: 22 of the 26
+        // groups run here; K1m 988 -> 941 us at 3072 frames, profiles/k1m_codes_ab.json).  `near` / `far` trade places from one
+        // group to the next — the loop holds two groups, no move carries the words.  Only a wave that multiplies comes here
+        // (tested once, in front of the loop); an idle wave of a two-block tile stays with the general group, which stages the
+        // same tiles and meets the others at the same barrier, one per group.
+        auto steady_group = [&](uint32_t (&near)[MF_TPB], uint32_t (&far)[MF_TPB]) {
+#pragma unroll
+            for (int i = 0; i < MF_TPB; ++i)
+                far[i] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(T) +
+                                                            (voff0 + (uint32_t)(t + 2 * MF_TPB + i) * (MF_TILE * STVO_DESC_BYTES)));
+            mma_fold(std::true_type{}, nb_c, std::integral_constant<int, 2>{}, std::false_type{}, accA, accB, t);
+            mma_fold(std::true_type{}, nb_c, std::integral_constant<int, 2>{}, std::true_type{}, accB, accA, t + 1);
+#pragma unroll
+            for (int i = 0; i < MF_TPB; ++i) stage(t + MF_TPB + i, near[i]);
+            __syncthreads();
+            t += MF_TPB;
+        };
         if (MF_TPB <= ntiles) group(std::true_type{});
-        while (t + MF_TPB <= ntiles) group(std::false_type{});
+        // (the one-block form of a small tile keeps the general group only; wave_active is wave-uniform and constant over the scan)
+        if (NB == QB && wave_active) {
+            uint32_t w_other[MF_TPB];
+            while (t + 4 * MF_TPB <= nfull) {  // two groups per turn: the second one fetches tiles t + 3 MF_TPB .. t + 4 MF_TPB - 1
+                steady_group(w_near, w_other);
+                steady_group(w_other, w_near);
+            }
+        }
+        while (t + MF_TPB <= ntiles) group(std::false_type{});  // the segment's last two or three groups
         if (t < ntiles) {  // its tile is staged already (t is even here)
-            if (t == 0) mma_fold(nb_c, std::integral_constant<int, 0>{}, std::false_type{}, accA, accB, t);
-            else mma_fold(nb_c, std::integral_constant<int, 2>{}, std::false_type{}, accA, accB, t);
+            if (t == 0) mma_fold(std::false_type{}, nb_c, std::integral_constant<int, 0>{}, std::false_type{}, accA, accB, t);
+            else mma_fold(std::false_type{}, nb_c, std::integral_constant<int, 2>{}, std::false_type{}, accA, accB, t);
         }
         if (wave_active && ntiles > 0) {  // drain: the last tile, rows past the segment end carry no key
             const int jt = j0 + (ntiles - 1) * MF_TILE;
