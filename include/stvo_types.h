@@ -227,7 +227,11 @@ typedef struct stvo_kf_header {
 } stvo_kf_header;
 
 /* A key-line as the LBD descriptor consumes it: the line_descriptor::KeyLine fields BinaryDescriptor::computeImpl copies into its
- * OctaveSingleLine (3rdparty/line_descriptor/src/binary_descriptor_custom.cpp:592-609), octave 0. */
+ * OctaveSingleLine (3rdparty/line_descriptor/src/binary_descriptor_custom.cpp:592-609), octave 0.
+ * Domain of the descriptor: every sample coordinate of the support region (63 rows across, (short) num_pixels along) inside
+ * +-32767 before it is clamped into the image, and angle inside [-2 pi, 2 pi].  Beyond that the source's (short) cast of the rounded
+ * coordinate is undefined and no result is promised.  Of the end points only the mid-point is used; num_pixels is taken through a
+ * (short) cast as the source takes it (32768 walks nothing, 65537 walks one step), and a walk of no step gives a NaN descriptor. */
 typedef struct stvo_keyline {
     float sx, sy, ex, ey;  /* sPointInOctaveX / Y, ePointInOctaveX / Y */
     float angle;           /* KeyLine::angle = atan2(ey - sy, ex - sx), radians */
