@@ -658,7 +658,8 @@ int stvo_lsd_set_image_sizes(stvo_lsd* lsd, const int32_t* sizes_host /* [n][2] 
  * (OpenCV contrib 3.x — third-party code the reference does not hold) as restated in tests/cpp/fld_ref.c (parity unpinned, DESIGN.md
  * §10): Canny (aperture 3, L1, th1 == th2), the edge chains, extractSegments, the length / border filters and the orientation by the
  * brighter side.  Images up to 2^20 pixels, at least 16 x 16.  Canny, the 8-connected components of the edge map and the segment
- * fitting are data-parallel kernels; the chain walk runs one lane per component (exact: a chain never leaves its component). */
+ * fitting are data-parallel kernels; the chain walk runs one lane per component (exact: a chain never leaves its component).  One
+ * size for all images, or one size and threshold per image (stvo_fld_set_image_sizes below). */
 typedef struct stvo_fld_params {
     int32_t length_threshold;    /* (int)(min_line_length x min(cols, rows)) (stereoFrameHandler.cpp:39, truncated), >= 1 */
     float distance_threshold;    /* 1.414213562f */
@@ -686,6 +687,27 @@ int stvo_fld_counts(stvo_fld* fld, int32_t* n_segments);
  * edges [B][rows][cols] = 0 / 255. */
 int stvo_fld_segments(stvo_fld* fld, const uint8_t* images, float* segments, int cap, int32_t* n_segments);
 int stvo_fld_edges(stvo_fld* fld, const uint8_t* images, uint8_t* edges);
+/* One image SIZE, and length threshold, per image for the following calls: the contract of stvo_lsd_set_image_sizes.  Image i of the B
+ * images is sizes_host[i % n] = {cols, rows}; n must divide B.  The image buffer keeps the layout [B][rows][cols] of the size given at
+ * creation (the slot): image i occupies the top-left cols_i x rows_i of its slot and keeps the slot's row pitch; the bytes of the slot
+ * outside the image influence nothing.  length_threshold_host[i % n] is the image's length threshold (the reference's
+ * (int)(Config::minLineLength() x min(width, height)) of the sequence's camera); length_threshold_host == NULL: every entry keeps the
+ * detector's.  What comes back for image i is, bit for bit, what a detector created at (cols_i, rows_i) with that threshold returns for
+ * the crop — key-line records, responses, n_lines, stvo_fld_counts, stvo_fld_segments; stvo_fld_edges gives the crop's edge map
+ * top-left in a slot-shaped output whose rest is 0 — through stvo_fld_detect and stvo_fld_detect_dev: the Sobel border, the corner
+ * quirk, the neighbourhoods of the components and of the walk, the clamps and border filters of a segment, the chain length, the
+ * response divisor and the pixel count of a key-line are all the image's own.
+ *   The stores of chains and segments were cut at creation for (the slot's pixels, the detector's threshold) and an image places its
+ * segments by its OWN threshold, so an entry is taken only if cols_i rows_i / (L_i + 1) + 1 <= slot pixels / (L + 1) + 1; L_i >= L
+ * always satisfies it: create a detector meant for mixed sizes with the smallest threshold it will be given.
+ *   STVO_ERR_INVALID_ARG and nothing changes: n <= 0, n > B, B % n != 0, an entry larger than the slot, a side below 16, a threshold
+ * below 1.  STVO_ERR_CAPACITY and nothing changes: an entry the store rule refuses (stvo_ctx_last_error names it and both capacities).
+ * sizes_host and length_threshold_host are read during the call; the table travels on the context's stream behind the detections
+ * already enqueued, through pinned staging that is not reused before its copy has completed: no synchronisation.  The device table is
+ * allocated at the first call; sizes_host == NULL: every image fills its slot again, on the very kernels of a detector that was never
+ * given a table. */
+int stvo_fld_set_image_sizes(stvo_fld* fld, const int32_t* sizes_host /* [n][2] = cols, rows */,
+                             const int32_t* length_threshold_host /* [n] or NULL */, int n);
 
 /* ---- stereo rectification (input preparation of Dataset::nextFrame, src/dataset.cpp:147-157) ---------------------------- */
 

@@ -31,13 +31,23 @@
 // written to [s, e) of an image-sized store; a chain of n points gives at most n / (L + 1) segments, so the segments of the chain at
 // point offset o go to slots [o / (L + 1), (o + n) / (L + 1)) of a store of npx / (L + 1) + 1 slots.  No store can fill; the walk
 // still flags an overflow (stvo_fld_detect then returns STVO_ERR_CAPACITY) rather than drop a point.
+//
+// Every kernel is a template on MIXED: the MIXED instances read their image's row of a size table (one image size and length threshold
+// per image, stvo_fld_set_image_sizes, csrc/fld_sizes.h), the others are the kernels as they were (fld_take_image below says what an
+// image replaces and what stays the slot's).  Under a table an image's chain of n points at offset o goes to segment slots
+// [o / (L_i + 1), (o + n) / (L_i + 1)) with its OWN threshold, in the stores cut for (the slot's pixels, the detector's L): the host
+// takes an entry only if its own store fits them (fld_sizes.h: the store rule).
 #include <cmath>
+#include <cstring>
 #include <new>
+#include <vector>
 
 #include "ctx_internal.h"
 #include "fast_atan2.h"
+#include "fld_sizes.h"
 #include "frontend_layout.h"
 #include "line_common.h"
+#include "table_transport.h"
 
 #pragma clang fp contract(off)
 
@@ -75,49 +85,91 @@ struct FldDev {
     int32_t* n_lines;
 };
 
+// One image size and length threshold per image (stvo_fld_set_image_sizes): FldTable<MIXED> (fld_sizes.h), an argument of its own behind
+// FldDev and empty for the uniform instances — they take the arguments they always took.
+//
+// The image a workgroup works on.  MIXED = false: the slot itself — the kernel as it was, reading its argument.  MIXED = true: the
+// kernel's own copy of its argument takes the image's size, pixels, edge words, sort units and threshold from the image's row of the
+// table in place of the slot's, so the code below the call is one text for both.  Every kernel takes its image from a block index: the
+// row is uniform over the workgroup and read with scalar loads.  The uniform instances do not make the call (if constexpr): their code
+// is the code they had (profiles/mixed_fld_kernel_resources.txt).  FldSlot: the slot's pitch and per-image strides, taken before the
+// call.  The strides BETWEEN images (the image buffer, lab, tmp, list, pts, ch_at: the slot's npx; ebits, sbits, wsum: its nw; cnt: its
+// nunits; ch, sg: the stores' capacity; dseg) stay the slot's; INSIDE its block an image indexes compactly with its own cols (pixel p =
+// y cols_i + x for labels, roots, edge bits and chain seeds: the detection order is the crop's own raster order).  Only Canny and
+// orient_segment read the image bytes, at the slot's row pitch with the image's bounds.
+//
+// Why a table can never index outside the slot, and why the union-find terminates under one.  The host has validated the rows
+// (fld_sizes.h), and the call clamps all the same: cols, rows, npx, nw and nunits into [.., the slot's], the threshold to the
+// detector's where the stores cut for the slot would not hold the image under its own (the store rule), so a stale or torn table still
+// addresses the slot's blocks only.  Every kernel of one detection reads the same table: it travels on the stream between detections,
+// never between two kernels of one.  fld_canny_kernel initialises lab[p] = p for exactly the pixels p < npx_i (and the edge, seed and
+// sum words w < nw_i); the union, the flatten, the sort and the walk of that launch read a label only at an edge pixel p < npx_i or at a
+// neighbour inside the image's own bounds, whose compact index is below npx_i too — initialised by THIS launch, whatever an earlier
+// launch under a larger or smaller table left beyond.  Labels only ever take the value of another such index and only decrease, so
+// uf_find follows a strictly decreasing chain inside [0, npx_i) and ends; every other loop whose trip count comes from the table (the
+// units of the scan, the words of the walk's LDS copy and of the order scan, the walk's blocks of 32 sorted positions up to n_edge <=
+// npx_i) takes it after the clamp.
+struct FldSlot {
+    int cols, npx, nw, nunits;
+};
+__device__ __forceinline__ void fld_take_image(FldDev& d, const FldTable<true>& tab, int b) {
+    const FldSizeRow* e = tab.sz + (b % tab.n_sz);
+    d.cols = __builtin_amdgcn_readfirstlane(min(max(e->cols, 1), d.cols));
+    d.rows = __builtin_amdgcn_readfirstlane(min(max(e->rows, 1), d.rows));
+    d.npx = __builtin_amdgcn_readfirstlane(min(d.cols * d.rows, d.npx));  // (cols_i rows_i: what the row holds, once validated)
+    d.nw = __builtin_amdgcn_readfirstlane(min(max(e->nw, (d.npx + 31) >> 5), d.nw));
+    d.nunits = __builtin_amdgcn_readfirstlane(min(max(e->nunits, 1), d.nunits));
+    const int L = __builtin_amdgcn_readfirstlane(max(e->L, 1));
+    d.L = d.npx / (L + 1) + 1 <= d.sg_cap ? L : d.L;  // the store rule (fld_sizes.h); the detector's own always fits
+}
+
 // ---- the edge map ----
-__device__ __forceinline__ void sobel_at(const uint8_t* im, int cols, int rows, int x, int y, int& dx, int& dy) {
+// (im: the image at row pitch `pitch`; cols, rows: its bounds — the replicated border is the image's own)
+__device__ __forceinline__ void sobel_at(const uint8_t* im, int pitch, int cols, int rows, int x, int y, int& dx, int& dy) {
     const int xm = max(x - 1, 0), xp = min(x + 1, cols - 1), ym = max(y - 1, 0), yp = min(y + 1, rows - 1);
-    const uint8_t *r0 = im + (size_t)ym * cols, *r1 = im + (size_t)y * cols, *r2 = im + (size_t)yp * cols;
+    const uint8_t *r0 = im + (size_t)ym * pitch, *r1 = im + (size_t)y * pitch, *r2 = im + (size_t)yp * pitch;
     dx = ((int)r0[xp] + 2 * (int)r1[xp] + (int)r2[xp]) - ((int)r0[xm] + 2 * (int)r1[xm] + (int)r2[xm]);
     dy = ((int)r2[xm] + 2 * (int)r2[x] + (int)r2[xp]) - ((int)r0[xm] + 2 * (int)r0[x] + (int)r0[xp]);
 }
-__device__ __forceinline__ int mag_at(const uint8_t* im, int cols, int rows, int x, int y) {
+__device__ __forceinline__ int mag_at(const uint8_t* im, int pitch, int cols, int rows, int x, int y) {
     if (x < 0 || y < 0 || x >= cols || y >= rows) return 0;
     int dx, dy;
-    sobel_at(im, cols, rows, x, y, dx, dy);
+    sobel_at(im, pitch, cols, rows, x, y, dx, dy);
     return abs(dx) + abs(dy);
 }
 
-__global__ __launch_bounds__(256) void fld_canny_kernel(FldDev d) {
+template <bool MIXED>
+__global__ __launch_bounds__(256) void fld_canny_kernel(FldDev d, FldTable<MIXED> tab) {
     const int b = blockIdx.y, lane = threadIdx.x & 63;
     const int p = blockIdx.x * 256 + threadIdx.x;
-    const uint8_t* im = d.img + (size_t)b * d.npx;
+    const FldSlot slot{d.cols, d.npx, d.nw, d.nunits};
+    if constexpr (MIXED) fld_take_image(d, tab, b);
+    const uint8_t* im = d.img + (size_t)b * slot.npx;
     bool e = false;
     if (p < d.npx) {
         const int y = p / d.cols, x = p - y * d.cols;
         int dx, dy;
-        sobel_at(im, d.cols, d.rows, x, y, dx, dy);
+        sobel_at(im, slot.cols, d.cols, d.rows, x, y, dx, dy);
         const int m = abs(dx) + abs(dy);
         if (m > d.low) {
             const int TG22 = (int)(0.4142135623730950488 * (1 << 15) + 0.5);
             const int xs = abs(dx), ys = abs(dy) << 15, tg22x = xs * TG22;
             if (ys < tg22x) {
-                e = m > mag_at(im, d.cols, d.rows, x - 1, y) && m >= mag_at(im, d.cols, d.rows, x + 1, y);
+                e = m > mag_at(im, slot.cols, d.cols, d.rows, x - 1, y) && m >= mag_at(im, slot.cols, d.cols, d.rows, x + 1, y);
             } else if (ys > tg22x + (xs << 16)) {
-                e = m > mag_at(im, d.cols, d.rows, x, y - 1) && m >= mag_at(im, d.cols, d.rows, x, y + 1);
+                e = m > mag_at(im, slot.cols, d.cols, d.rows, x, y - 1) && m >= mag_at(im, slot.cols, d.cols, d.rows, x, y + 1);
             } else {
                 const int s = (dx ^ dy) < 0 ? -1 : 1;
-                e = m > mag_at(im, d.cols, d.rows, x - s, y - 1) && m > mag_at(im, d.cols, d.rows, x + s, y + 1);
+                e = m > mag_at(im, slot.cols, d.cols, d.rows, x - s, y - 1) && m > mag_at(im, slot.cols, d.cols, d.rows, x + s, y + 1);
             }
         }
         if ((y < 6 && x < 6) || (y >= d.rows - 5 && x >= d.cols - 5)) e = false;  // lineDetection: canny(0..5, 0..5) = 0, the far corner too
-        d.lab[(size_t)b * d.npx + p] = p;
+        d.lab[(size_t)b * slot.npx + p] = p;
     }
     const unsigned long long bal = __ballot(e);
     const int w = ((blockIdx.x * 256 + (threadIdx.x & ~63)) >> 5) + (lane >> 5);
     if ((lane & 31) == 0 && w < d.nw) {
-        const size_t q = (size_t)b * d.nw + w;
+        const size_t q = (size_t)b * slot.nw + w;
         d.ebits[q] = (uint32_t)(bal >> (lane & 32));
         d.sbits[q] = 0u;
         d.wsum[q] = 0u;
@@ -150,12 +202,15 @@ __device__ void uf_unite(int32_t* L, int a, int b) {
     }
 }
 
-__global__ __launch_bounds__(256) void fld_union_kernel(FldDev d) {
+template <bool MIXED>
+__global__ __launch_bounds__(256) void fld_union_kernel(FldDev d, FldTable<MIXED> tab) {
     const int b = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
+    const FldSlot slot{d.cols, d.npx, d.nw, d.nunits};
+    if constexpr (MIXED) fld_take_image(d, tab, b);
     if (p >= d.npx) return;
-    const uint32_t* eb = d.ebits + (size_t)b * d.nw;
+    const uint32_t* eb = d.ebits + (size_t)b * slot.nw;
     if (!ebit(eb, p)) return;
-    int32_t* L = d.lab + (size_t)b * d.npx;
+    int32_t* L = d.lab + (size_t)b * slot.npx;
     const int y = p / d.cols, x = p - y * d.cols;
     if (x > 0 && ebit(eb, p - 1)) uf_unite(L, p, p - 1);
     if (y > 0) {
@@ -166,47 +221,56 @@ __global__ __launch_bounds__(256) void fld_union_kernel(FldDev d) {
     }
 }
 
-__global__ __launch_bounds__(256) void fld_flatten_kernel(FldDev d) {
+template <bool MIXED>
+__global__ __launch_bounds__(256) void fld_flatten_kernel(FldDev d, FldTable<MIXED> tab) {
     const int b = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= d.npx || !ebit(d.ebits + (size_t)b * d.nw, p)) return;
-    int32_t* L = d.lab + (size_t)b * d.npx;
+    const FldSlot slot{d.cols, d.npx, d.nw, d.nunits};
+    if constexpr (MIXED) fld_take_image(d, tab, b);
+    if (p >= d.npx || !ebit(d.ebits + (size_t)b * slot.nw, p)) return;
+    int32_t* L = d.lab + (size_t)b * slot.npx;
     L[p] = uf_find(L, p);
 }
 
 // ---- the edge pixels by root: stable counting sort, pass 0 by the low 10 bits (all pixels, raster order), pass 1 by the high ----
-__device__ __forceinline__ bool sort_elem(const FldDev& d, int b, int pass, int i, uint32_t& val, int& digit) {
-    const int32_t* L = d.lab + (size_t)b * d.npx;
+__device__ __forceinline__ bool sort_elem(const FldDev& d, const FldSlot& slot, int b, int pass, int i, uint32_t& val, int& digit) {
+    const int32_t* L = d.lab + (size_t)b * slot.npx;
     if (pass == 0) {
-        if (i >= d.npx || !ebit(d.ebits + (size_t)b * d.nw, i)) return false;
+        if (i >= d.npx || !ebit(d.ebits + (size_t)b * slot.nw, i)) return false;
         val = (uint32_t)i;
         digit = L[i] & (FLD_BINS - 1);
     } else {
         if (i >= d.n_edge[b]) return false;
-        val = d.tmp[(size_t)b * d.npx + i];
+        val = d.tmp[(size_t)b * slot.npx + i];
         digit = (L[val] >> 10) & (FLD_BINS - 1);
     }
     return true;
 }
 
-__global__ __launch_bounds__(256) void fld_hist_kernel(FldDev d, int pass) {
+template <bool MIXED>
+__global__ __launch_bounds__(256) void fld_hist_kernel(FldDev d, int pass, FldTable<MIXED> tab) {
     __shared__ unsigned s_h[4][FLD_BINS];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, b = blockIdx.y, unit = blockIdx.x * 4 + wv;
+    const FldSlot slot{d.cols, d.npx, d.nw, d.nunits};
+    if constexpr (MIXED) fld_take_image(d, tab, b);
     if (unit >= d.nunits) return;
     unsigned* h = s_h[wv];
     for (int t = lane; t < FLD_BINS; t += 64) h[t] = 0u;
     for (int r = 0; r < FLD_UNIT_ROWS; ++r) {
         uint32_t v;
         int dg;
-        if (sort_elem(d, b, pass, unit * FLD_UNIT + r * 64 + lane, v, dg)) atomicAdd(&h[dg], 1u);
+        if (sort_elem(d, slot, b, pass, unit * FLD_UNIT + r * 64 + lane, v, dg)) atomicAdd(&h[dg], 1u);
     }
-    unsigned* out = d.cnt + ((size_t)b * d.nunits + unit) * FLD_BINS;
+    unsigned* out = d.cnt + ((size_t)b * slot.nunits + unit) * FLD_BINS;
     for (int t = lane; t < FLD_BINS; t += 64) out[t] = h[t];
 }
 
-__global__ __launch_bounds__(1024) void fld_scan_kernel(FldDev d, int pass) {
+template <bool MIXED>
+__global__ __launch_bounds__(1024) void fld_scan_kernel(FldDev d, int pass, FldTable<MIXED> tab) {
     __shared__ unsigned s_w[16];
     const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    unsigned* cnt = d.cnt + (size_t)b * d.nunits * FLD_BINS;
+    const FldSlot slot{d.cols, d.npx, d.nw, d.nunits};
+    if constexpr (MIXED) fld_take_image(d, tab, b);
+    unsigned* cnt = d.cnt + (size_t)b * slot.nunits * FLD_BINS;
     unsigned tot = 0u;
     for (int u = 0; u < d.nunits; ++u) tot += cnt[(size_t)u * FLD_BINS + t];
     unsigned inc = tot;
@@ -232,19 +296,22 @@ __global__ __launch_bounds__(1024) void fld_scan_kernel(FldDev d, int pass) {
     if (pass == 0 && t == 0) d.n_edge[b] = (int)all;
 }
 
-__global__ __launch_bounds__(256) void fld_scatter_kernel(FldDev d, int pass) {
+template <bool MIXED>
+__global__ __launch_bounds__(256) void fld_scatter_kernel(FldDev d, int pass, FldTable<MIXED> tab) {
     __shared__ unsigned s_h[4][FLD_BINS];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, b = blockIdx.y, unit = blockIdx.x * 4 + wv;
+    const FldSlot slot{d.cols, d.npx, d.nw, d.nunits};
+    if constexpr (MIXED) fld_take_image(d, tab, b);
     if (unit >= d.nunits) return;
     unsigned* h = s_h[wv];
-    const unsigned* first = d.cnt + ((size_t)b * d.nunits + unit) * FLD_BINS;
+    const unsigned* first = d.cnt + ((size_t)b * slot.nunits + unit) * FLD_BINS;
     for (int t = lane; t < FLD_BINS; t += 64) h[t] = first[t];
-    uint32_t* out = (pass == 0 ? d.tmp : d.list) + (size_t)b * d.npx;
+    uint32_t* out = (pass == 0 ? d.tmp : d.list) + (size_t)b * slot.npx;
     const unsigned long long lt = lane == 0 ? 0ull : ~0ull >> (64 - lane);
     for (int r = 0; r < FLD_UNIT_ROWS; ++r) {
         uint32_t v = 0;
         int dg = 0;
-        const bool valid = sort_elem(d, b, pass, unit * FLD_UNIT + r * 64 + lane, v, dg);
+        const bool valid = sort_elem(d, slot, b, pass, unit * FLD_UNIT + r * 64 + lane, v, dg);
         unsigned long long m = __ballot(valid);  // ... the lanes of the row with this lane's digit
         if (!m) continue;                        // uniform
 #pragma unroll
@@ -266,18 +333,21 @@ __global__ __launch_bounds__(256) void fld_scatter_kernel(FldDev d, int pass) {
 __device__ __forceinline__ bool lbit(const uint32_t* s, int p) { return (s[p >> 5] >> (p & 31)) & 1u; }
 __device__ __forceinline__ void lclear(uint32_t* s, int p) { atomicAnd(&s[p >> 5], ~(1u << (p & 31))); }
 
-__global__ __launch_bounds__(FLD_WALK_T) void fld_walk_kernel(FldDev d) {
-    extern __shared__ uint32_t s_e[];  // [nw] the edge map of this image
+template <bool MIXED>
+__global__ __launch_bounds__(FLD_WALK_T) void fld_walk_kernel(FldDev d, FldTable<MIXED> tab) {
+    extern __shared__ uint32_t s_e[];  // [nw] the edge map of this image (the launch gives the slot's nw words)
     __shared__ int s_next, s_nch;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const uint32_t* eb = d.ebits + (size_t)b * d.nw;
+    const FldSlot slot{d.cols, d.npx, d.nw, d.nunits};
+    if constexpr (MIXED) fld_take_image(d, tab, b);
+    const uint32_t* eb = d.ebits + (size_t)b * slot.nw;
     for (int w = tid; w < d.nw; w += FLD_WALK_T) s_e[w] = eb[w];
     if (tid == 0) { s_next = 0; s_nch = 0; }
     __syncthreads();
     const int E = d.n_edge[b], cols = d.cols, rows = d.rows, L = d.L;
-    const uint32_t* lst = d.list + (size_t)b * d.npx;
-    const int32_t* lab = d.lab + (size_t)b * d.npx;
-    uint32_t* pts = d.pts + (size_t)b * d.npx;
+    const uint32_t* lst = d.list + (size_t)b * slot.npx;
+    const int32_t* lab = d.lab + (size_t)b * slot.npx;
+    uint32_t* pts = d.pts + (size_t)b * slot.npx;
     FldChain* ch = d.ch + (size_t)b * d.ch_cap;
     const int dyv[8] = {1, 1, 1, 0, -1, -1, -1, 0}, dxv[8] = {1, 0, -1, -1, -1, 0, 1, 1};
     for (;;) {
@@ -340,8 +410,8 @@ __global__ __launch_bounds__(FLD_WALK_T) void fld_walk_kernel(FldDev d) {
                     FldChain c;
                     c.seed = q; c.off = c0; c.n = n; c.nseg = 0;
                     ch[idx] = c;
-                    d.ch_at[(size_t)b * d.npx + q] = idx;
-                    atomicOr(&d.sbits[(size_t)b * d.nw + (q >> 5)], 1u << (q & 31));
+                    d.ch_at[(size_t)b * slot.npx + q] = idx;
+                    atomicOr(&d.sbits[(size_t)b * slot.nw + (q >> 5)], 1u << (q & 31));
                 }
             }
         }
@@ -470,7 +540,7 @@ __device__ __forceinline__ bool keep_segment(float4 s, int L, int cols, int rows
              (s.y >= (float)rows - 5.0f && s.w >= (float)rows - 5.0f));
 }
 // additionalOperationsOnSegment: the end points swapped when the right side is brighter
-__device__ float4 orient_segment(const uint8_t* im, int cols, int rows, float4 s) {
+__device__ float4 orient_segment(const uint8_t* im, int pitch, int cols, int rows, float4 s) {
     const double ang = (double)(float)((double)__fdiv_rn(fast_atan2_deg(s.w - s.y, s.z - s.x), 180.0f) * FLD_PI);
     const double dx = (double)s.z - (double)s.x, dy = (double)s.w - (double)s.y;
     double sn, cs;
@@ -490,20 +560,23 @@ __device__ float4 orient_segment(const uint8_t* im, int cols, int rows, float4 s
         ry = ry <= 5 ? 5 : (ry >= rows - 5 ? rows - 5 : ry);
         lx = lx <= 5 ? 5 : (lx >= cols - 5 ? cols - 5 : lx);
         ly = ly <= 5 ? 5 : (ly >= rows - 5 ? rows - 5 : ly);
-        iR += im[(size_t)ry * cols + rx];
-        iL += im[(size_t)ly * cols + lx];
+        iR += im[(size_t)ry * pitch + rx];
+        iL += im[(size_t)ly * pitch + lx];
     }
     return iR > iL ? make_float4(s.z, s.w, s.x, s.y) : s;
 }
 
-__global__ __launch_bounds__(256) void fld_segments_kernel(FldDev d) {
+template <bool MIXED>
+__global__ __launch_bounds__(256) void fld_segments_kernel(FldDev d, FldTable<MIXED> tab) {
     const int b = blockIdx.y;
+    const FldSlot slot{d.cols, d.npx, d.nw, d.nunits};
+    if constexpr (MIXED) fld_take_image(d, tab, b);
     const int nch = d.n_ch[b], L = d.L, cols = d.cols, rows = d.rows;
     const double th = (double)d.dist_th;
-    const uint8_t* im = d.img + (size_t)b * d.npx;
+    const uint8_t* im = d.img + (size_t)b * slot.npx;
     for (int c = blockIdx.x * 256 + threadIdx.x; c < nch; c += FLD_SEG_BLOCKS * 256) {
         FldChain chn = d.ch[(size_t)b * d.ch_cap + c];
-        const uint32_t* P = d.pts + (size_t)b * d.npx + chn.off;
+        const uint32_t* P = d.pts + (size_t)b * slot.npx + chn.off;
         const int total = chn.n;
         float4* out = d.sg + (size_t)b * d.sg_cap + chn.off / (L + 1);
         int kept = 0;
@@ -545,20 +618,23 @@ __global__ __launch_bounds__(256) void fld_segments_kernel(FldDev d) {
             incident_point(l, e1x, e1y, cols, rows);
             incident_point(l, e2x, e2y, cols, rows);
             const float4 s = make_float4(e1x, e1y, e2x, e2y);
-            if (keep_segment(s, L, cols, rows)) out[kept++] = orient_segment(im, cols, rows, s);
+            if (keep_segment(s, L, cols, rows)) out[kept++] = orient_segment(im, slot.cols, cols, rows, s);
             i = i + j;
         }
         d.ch[(size_t)b * d.ch_cap + c].nseg = kept;
-        if (kept) atomicAdd(&d.wsum[(size_t)b * d.nw + (chn.seed >> 5)], (unsigned)kept);
+        if (kept) atomicAdd(&d.wsum[(size_t)b * slot.nw + (chn.seed >> 5)], (unsigned)kept);
     }
 }
 
 // ---- detection order: scan of the per-word segment counts, then every chain's segments to their place ----
-__global__ __launch_bounds__(1024) void fld_order_kernel(FldDev d) {
+template <bool MIXED>
+__global__ __launch_bounds__(1024) void fld_order_kernel(FldDev d, FldTable<MIXED> tab) {
     __shared__ unsigned s_w[16];
     __shared__ unsigned s_total;
     const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    uint32_t* ws = d.wsum + (size_t)b * d.nw;
+    const FldSlot slot{d.cols, d.npx, d.nw, d.nunits};
+    if constexpr (MIXED) fld_take_image(d, tab, b);
+    uint32_t* ws = d.wsum + (size_t)b * slot.nw;
     const int per = (d.nw + 1023) / 1024, w0 = min(t * per, d.nw), w1 = min(w0 + per, d.nw);
     unsigned tot = 0u;
     for (int w = w0; w < w1; ++w) tot += ws[w];
@@ -586,8 +662,8 @@ __global__ __launch_bounds__(1024) void fld_order_kernel(FldDev d) {
     __syncthreads();
     const int nch = d.n_ch[b];
     const FldChain* ch = d.ch + (size_t)b * d.ch_cap;
-    const uint32_t* sb = d.sbits + (size_t)b * d.nw;
-    const int32_t* at = d.ch_at + (size_t)b * d.npx;
+    const uint32_t* sb = d.sbits + (size_t)b * slot.nw;
+    const int32_t* at = d.ch_at + (size_t)b * slot.npx;
     for (int c = t; c < nch; c += 1024) {
         const FldChain q = ch[c];
         if (q.nseg == 0) continue;
@@ -611,9 +687,11 @@ __device__ __forceinline__ double sort_length(float4 e) {  // sort_flines_by_len
     return sqrt(a * a + c * c);
 }
 
-__global__ __launch_bounds__(FLD_KL_T) void fld_keylines_kernel(FldDev d) {
+template <bool MIXED>
+__global__ __launch_bounds__(FLD_KL_T) void fld_keylines_kernel(FldDev d, FldTable<MIXED> tab) {
     extern __shared__ double s_len[];  // [FLD_SEG_CAP]
     const int b = blockIdx.x, tid = threadIdx.x;
+    if constexpr (MIXED) fld_take_image(d, tab, b);  // (the response divisor and the raster of the pixel count are the image's own)
     const int m = min(d.n_seg[b], FLD_SEG_CAP);
     const float4* seg = d.dseg + (size_t)b * FLD_SEG_CAP;
     for (int i = tid; i < m; i += FLD_KL_T) s_len[i] = sort_length(seg[i]);
@@ -656,29 +734,47 @@ struct stvo_fld {
     float* response = nullptr;
     int32_t* n_lines = nullptr;
     int walk_lds = 0;
+    // one image size and threshold per image (stvo_fld_set_image_sizes): nothing of it exists until the first call.  The device table
+    // holds the n rows the kernels read (FldSizeRow); `rows` is the host's copy of the table in force (stvo_fld_edges unpacks with it)
+    stvo_detail::TableTransport sizes;
+    std::vector<stvo::FldSizeRow> rows;
+    int n_sizes = 0;          // entries of the table in force; 0: every image fills its slot
 };
 
 namespace {
 
+template <bool MIXED>
+void fld_launch(stvo_fld* o, const stvo::FldDev& d, dim3 pg, dim3 ug, stvo::FldTable<MIXED> tab) {
+    hipStream_t s = o->ctx->stream;
+    hipLaunchKernelGGL(stvo::fld_canny_kernel<MIXED>, pg, dim3(256), 0, s, d, tab);
+    hipLaunchKernelGGL(stvo::fld_union_kernel<MIXED>, pg, dim3(256), 0, s, d, tab);
+    hipLaunchKernelGGL(stvo::fld_flatten_kernel<MIXED>, pg, dim3(256), 0, s, d, tab);
+    for (int pass = 0; pass < 2; ++pass) {
+        hipLaunchKernelGGL(stvo::fld_hist_kernel<MIXED>, ug, dim3(256), 0, s, d, pass, tab);
+        hipLaunchKernelGGL(stvo::fld_scan_kernel<MIXED>, dim3(d.B), dim3(1024), 0, s, d, pass, tab);
+        hipLaunchKernelGGL(stvo::fld_scatter_kernel<MIXED>, ug, dim3(256), 0, s, d, pass, tab);
+    }
+    hipLaunchKernelGGL(stvo::fld_walk_kernel<MIXED>, dim3(d.B), dim3(stvo::FLD_WALK_T), o->walk_lds, s, d, tab);
+    hipLaunchKernelGGL(stvo::fld_segments_kernel<MIXED>, dim3(stvo::FLD_SEG_BLOCKS, d.B), dim3(256), 0, s, d, tab);
+    hipLaunchKernelGGL(stvo::fld_order_kernel<MIXED>, dim3(d.B), dim3(1024), 0, s, d, tab);
+    hipLaunchKernelGGL(stvo::fld_keylines_kernel<MIXED>, dim3(d.B), dim3(stvo::FLD_KL_T), (size_t)stvo::FLD_SEG_CAP * 8, s, d, tab);
+}
+
 int fld_enqueue(stvo_fld* o, const uint8_t* images, stvo_keyline* lines, float* response, int32_t* n_lines) {
     stvo_ctx* ctx = o->ctx;
-    hipStream_t s = ctx->stream;
     stvo::FldDev d = o->d;
     d.img = images;
     d.lines = lines; d.response = response; d.n_lines = n_lines;
     const dim3 pg((d.npx + 255) / 256, d.B), ug((d.nunits + 3) / 4, d.B);
-    hipLaunchKernelGGL(stvo::fld_canny_kernel, pg, dim3(256), 0, s, d);
-    hipLaunchKernelGGL(stvo::fld_union_kernel, pg, dim3(256), 0, s, d);
-    hipLaunchKernelGGL(stvo::fld_flatten_kernel, pg, dim3(256), 0, s, d);
-    for (int pass = 0; pass < 2; ++pass) {
-        hipLaunchKernelGGL(stvo::fld_hist_kernel, ug, dim3(256), 0, s, d, pass);
-        hipLaunchKernelGGL(stvo::fld_scan_kernel, dim3(d.B), dim3(1024), 0, s, d, pass);
-        hipLaunchKernelGGL(stvo::fld_scatter_kernel, ug, dim3(256), 0, s, d, pass);
+    if (o->n_sizes) {
+        // One size per image: the MIXED instances of every kernel on the slot's launch grids and LDS; threads beyond an image's pixels or
+        // units leave as those beyond the slot's do.
+        const stvo::FldTable<true> tab{reinterpret_cast<const stvo::FldSizeRow*>(o->sizes.dev), o->n_sizes};
+        fld_launch<true>(o, d, pg, ug, tab);
+    } else {
+        const stvo::FldTable<false> none{};  // the uniform instances: the kernels and arguments of a detector that was never given a table
+        fld_launch<false>(o, d, pg, ug, none);
     }
-    hipLaunchKernelGGL(stvo::fld_walk_kernel, dim3(d.B), dim3(stvo::FLD_WALK_T), o->walk_lds, s, d);
-    hipLaunchKernelGGL(stvo::fld_segments_kernel, dim3(stvo::FLD_SEG_BLOCKS, d.B), dim3(256), 0, s, d);
-    hipLaunchKernelGGL(stvo::fld_order_kernel, dim3(d.B), dim3(1024), 0, s, d);
-    hipLaunchKernelGGL(stvo::fld_keylines_kernel, dim3(d.B), dim3(stvo::FLD_KL_T), (size_t)stvo::FLD_SEG_CAP * 8, s, d);
     return check_launch(ctx);
 }
 
@@ -727,8 +823,12 @@ int stvo_fld_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, 
         o->lines = a.lines; o->response = a.response; o->n_lines = a.n_lines;
     }
     o->walk_lds = d.nw * 4;
-    if (ok && o->walk_lds > 48 * 1024) ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::fld_walk_kernel), o->walk_lds);
-    if (ok) ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::fld_keylines_kernel), stvo::FLD_SEG_CAP * 8);
+    if (ok && o->walk_lds > 48 * 1024)
+        ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::fld_walk_kernel<false>), o->walk_lds) &&
+             stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::fld_walk_kernel<true>), o->walk_lds);
+    if (ok)
+        ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::fld_keylines_kernel<false>), stvo::FLD_SEG_CAP * 8) &&
+             stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::fld_keylines_kernel<true>), stvo::FLD_SEG_CAP * 8);
     if (!ok) {
         stvo_fld_destroy(o);
         return STVO_ERR_HIP;
@@ -744,7 +844,44 @@ int stvo_fld_destroy(stvo_fld* o) {
         (void)hipStreamSynchronize(o->ctx->stream);
     }
     if (o->dev) (void)hipFree(o->dev);
+    o->sizes.destroy();
     delete o;
+    return STVO_OK;
+}
+
+// One image size and length threshold per image (stvo_hip.h).  Validated before anything changes; the table is formed with the
+// functions stvo_fld_create forms the slot's own values with (fld_sizes.h) and travels as table_transport.h says.
+int stvo_fld_set_image_sizes(stvo_fld* o, const int32_t* sizes_host, const int32_t* length_threshold_host, int n) {
+    if (!o) return STVO_ERR_INVALID_ARG;
+    if (!sizes_host) {  // every image fills its slot again: the uniform kernel instances, which read no table
+        o->n_sizes = 0;
+        o->rows.clear();
+        return STVO_OK;
+    }
+    const stvo::FldDev& d = o->d;
+    stvo_ctx* ctx = o->ctx;
+    int entry = 0, need = 0, have = 0;
+    switch (stvo::fld_image_sizes_verdict(sizes_host, length_threshold_host, n, d.B, d.cols, d.rows, d.L, &entry, &need, &have)) {
+        case stvo::FLD_SIZES_OK: break;
+        case stvo::FLD_SIZES_CAPACITY:
+            std::snprintf(ctx->last_error, sizeof(ctx->last_error),
+                          "stvo_fld_set_image_sizes: entry %d (%d x %d, length threshold %d) needs a store of %d segments, the detector's "
+                          "(%d x %d, length threshold %d) holds %d: create the detector with the smallest threshold it will be given",
+                          entry, sizes_host[2 * entry], sizes_host[2 * entry + 1], stvo::fld_entry_threshold(length_threshold_host, entry, d.L),
+                          need, d.cols, d.rows, d.L, have);
+            return STVO_ERR_CAPACITY;
+        default: return STVO_ERR_INVALID_ARG;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<stvo::FldSizeRow> rows((size_t)n);
+    for (int i = 0; i < n; ++i)
+        rows[i] = stvo::fld_size_row(sizes_host[2 * i], sizes_host[2 * i + 1], stvo::fld_entry_threshold(length_threshold_host, i, d.L));
+    char* tab = o->sizes.begin(ctx, (size_t)d.B * sizeof(stvo::FldSizeRow));
+    if (!tab) return STVO_ERR_HIP;
+    std::memcpy(tab, rows.data(), (size_t)n * sizeof(stvo::FldSizeRow));
+    TRY(o->sizes.send(ctx, (size_t)n * sizeof(stvo::FldSizeRow)));
+    o->rows.swap(rows);
+    o->n_sizes = n;
     return STVO_OK;
 }
 
@@ -811,6 +948,18 @@ int stvo_fld_edges(stvo_fld* o, const uint8_t* images, uint8_t* edges) {
     std::vector<uint32_t> bits((size_t)d.B * d.nw);
     HIP_TRY(ctx, hipMemcpyAsync(bits.data(), d.ebits, bits.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     TRY(fld_check(o));
+    if (o->n_sizes) {  // under a table the bits are compact at the image's own cols: its edge map top-left in the slot, 0 around it
+        std::memset(edges, 0, (size_t)d.B * d.npx);
+        for (int b = 0; b < d.B; ++b) {
+            const stvo::FldSizeRow& e = o->rows[(size_t)(b % o->n_sizes)];
+            for (int y = 0; y < e.rows; ++y)
+                for (int x = 0; x < e.cols; ++x) {
+                    const int p = y * e.cols + x;
+                    edges[(size_t)b * d.npx + (size_t)y * d.cols + x] = ((bits[(size_t)b * d.nw + (p >> 5)] >> (p & 31)) & 1u) ? 255 : 0;
+                }
+        }
+        return STVO_OK;
+    }
     for (int b = 0; b < d.B; ++b)
         for (int p = 0; p < d.npx; ++p)
             edges[(size_t)b * d.npx + p] = ((bits[(size_t)b * d.nw + (p >> 5)] >> (p & 31)) & 1u) ? 255 : 0;

@@ -37,7 +37,7 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_seq_export_streams", "stvo_seq_import_streams_dev", "stvo_seq_import_streams", "stvo_orb_set_descriptor",
            "stvo_orb_pattern", "stvo_orb_set_image_sizes", "stvo_seq_restart_cameras", "stvo_rectify_bank_create",
            "stvo_rectify_bank_destroy", "stvo_rectify_bank_camera", "stvo_rectify_bank_assign", "stvo_rectify_bank_images_dev",
-           "stvo_rectify_bank_color_to_gray_dev", "stvo_lsd_set_image_sizes", "stvo_lbd_set_image_sizes"]
+           "stvo_rectify_bank_color_to_gray_dev", "stvo_lsd_set_image_sizes", "stvo_lbd_set_image_sizes", "stvo_fld_set_image_sizes"]
 
 SEQ_NSTAGE = 5  # include/stvo_hip.h: STVO_SEQ_NSTAGE
 SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_check", "pose")
@@ -329,6 +329,7 @@ def load():
     L.stvo_fld_counts.argtypes = [C.c_void_p, i32p]
     L.stvo_fld_segments.argtypes = [C.c_void_p, u8p, f32p, C.c_int, i32p]
     L.stvo_fld_edges.argtypes = [C.c_void_p, u8p, u8p]
+    L.stvo_fld_set_image_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.stvo_keylines_xy_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.stvo_seq_destroy.argtypes = [C.c_void_p]
     L.stvo_rectify_compute.argtypes = [C.POINTER(RectCalib), C.POINTER(RectCamera), C.c_void_p, C.c_void_p]
@@ -749,7 +750,7 @@ def fld_params(length_threshold, nfeatures=300, distance_threshold=1.414213562, 
 
 
 class Fld:
-    """The FLD key-line detector for B images of one size (stvo_fld_*)."""
+    """The FLD key-line detector for B images of one size, or one size per image under set_image_sizes (stvo_fld_*)."""
 
     def __init__(self, ctx, B, cols, rows, prm, max_keylines=512):
         self.ctx, self.B, self.cols, self.rows, self.M = ctx, B, cols, rows, max_keylines
@@ -773,6 +774,21 @@ class Fld:
         self.ctx._chk(self.ctx.lib.stvo_fld_detect(self.h, images.reshape(-1), rec.ctypes.data_as(C.c_void_p), resp.ctypes.data_as(C.c_void_p), n))
         return [(rec[b, :n[b]].copy(), resp[b, :n[b]].copy()) for b in range(self.B)]
 
+    def set_image_sizes(self, sizes, length_thresholds=None):
+        """One image size per image: sizes [n][2] = (cols, rows), image i takes sizes[i % n] (n divides B) and occupies the top-left of
+        its slot of the size given at creation, whose row pitch it keeps; length_thresholds [n] (None: the detector's for all) is the
+        length threshold per entry (stvo_fld_set_image_sizes).  sizes None: every image fills its slot."""
+        if sizes is None:
+            self.ctx._chk(self.ctx.lib.stvo_fld_set_image_sizes(self.h, None, None, 0))
+            return
+        a = np.ascontiguousarray(sizes, np.int32)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("Fld.set_image_sizes: sizes is [n][2] = (cols, rows)")
+        lt = None if length_thresholds is None else np.ascontiguousarray(length_thresholds, np.int32).reshape(-1)
+        if lt is not None and lt.size != a.shape[0]:
+            raise ValueError("Fld.set_image_sizes: one length threshold per entry of sizes")
+        self.ctx._chk(self.ctx.lib.stvo_fld_set_image_sizes(self.h, _ptr(a), None if lt is None else _ptr(lt), a.shape[0]))
+
     def detect_dev(self, img_ptr, lines_ptr, resp_ptr, n_ptr):
         """Device pointers (uint8 [B, rows, cols]; stvo_keyline [B, M]; float32 [B, M] or None; int32 [B]); asynchronous."""
         self.ctx._chk(self.ctx.lib.stvo_fld_detect_dev(self.h, img_ptr, lines_ptr, resp_ptr, n_ptr))
@@ -792,7 +808,8 @@ class Fld:
         return [seg[b, :min(n[b], cap)].copy() for b in range(self.B)], n
 
     def edges(self, images):
-        """The edge map the chains are walked on: uint8 [B, rows, cols] 0 / 255."""
+        """The edge map the chains are walked on: uint8 [B, rows, cols] 0 / 255 (under set_image_sizes: every image's own edge map
+        top-left in its slot, 0 around it)."""
         images = self._images(images)
         out = np.zeros((self.B, self.rows, self.cols), np.uint8)
         self.ctx._chk(self.ctx.lib.stvo_fld_edges(self.h, images.reshape(-1), out.reshape(-1)))

@@ -22,7 +22,7 @@ class ImagePipeline:
     def __init__(self, ctx, B, cam, mp, op, max_kp=2048, nfeatures=2000, fast_threshold=20, edge_threshold=19, device="cuda:0", nlevels=1,
                  scale_factor=1.2, lsd=None, max_kl=128, rectify=None, fld=None, orb_score=1, adaptive_fast=None,
                  trajectory=None, trajectory_log=1, tracks=0, keyframe_sets=False, channels=1, gray_weights="q14", orb_wta_k=2,
-                 orb_patch_size=31, calibs=None, lines_per_stream=False, lsd_min_length_ratio=None):
+                 orb_patch_size=31, calibs=None, lines_per_stream=False, lsd_min_length_ratio=None, fld_min_length_ratio=None):
         """cam: one camera dict (width / height = image size) for all B streams, or a list of B dicts, one camera AND image size per stream
         (KITTI 00-02 / 03 / 04-10 side by side): the resident image buffer is then cut in slots of the largest width x the largest height,
         stream b's images occupy the top-left of their slots (set_images takes a list of B arrays of each stream's own size), the
@@ -34,8 +34,14 @@ class ImagePipeline:
         Lbd.set_image_sizes), with and without a rectifier bank, at every built lsd_scale (the pipeline sets LSD_SIZES_ANY_RADIUS on its
         own copy of lsd: lsd_scale 0.5 and the other blur radii run the fused blur + resize per image too); lsd_min_length_ratio = r gives stream b the minimum line length
         r * min(width_b, height_b) of its own camera (the reference's Config::minLineLength() x min(width, height)), None keeps
-        lsd.min_length for all; a stream that RESTARTs hands its new size and minimum length to both with its camera.  fld stays
-        refused with a list (the FLD walk holds one size).
+        lsd.min_length for all; a stream that RESTARTs hands its new size and minimum length to both with its camera.
+        lines_per_stream = True with a list and fld (not both detectors) is the same opt-in for the FLD detector of use_fld_lines: it
+        and LBD are built at the slot size and read every stream's images at that stream's own size (Fld.set_image_sizes);
+        fld_min_length_ratio = r gives stream b the length threshold int(r * min(width_b, height_b)) of its own camera (the reference's
+        llength_th truncated by createFastLineDetector(int)), None keeps fld.length_threshold for all; the detector is created at the
+        smallest threshold among fld.length_threshold and the initial streams', which sizes its stores: a camera that a RESTART brings
+        later and whose image those stores cannot hold under its own threshold raises ValueError before anything is staged.  With a
+        rectifier bank and channels 3 / 4 FLD and its LBD read the swapped-weight plane gray_b in the slot layout.
         With a list, rectify = capi.RectifierBank and calibs = [B ints]: the frames are RAW, stream b under calibration calibs[b] of the
         bank, whose size cam[b] must have; the slot is the bank's; enqueue first runs the bank's one launch over all streams (with
         channels 3 / 4 the fused colour -> grey form: set_images then takes lists of colour arrays into self.color) and the detector
@@ -80,13 +86,15 @@ class ImagePipeline:
             if len(cam) != B:
                 raise ValueError("ImagePipeline: cam is one dict or a list of B dicts")
             bank = rectify if isinstance(rectify, capi.RectifierBank) else None
-            if lines_per_stream and lsd is None:
-                raise ValueError("ImagePipeline: lines_per_stream goes with lsd (and cam as a list)")
-            for name, given in (("lsd", lsd is not None and not lines_per_stream), ("fld", fld is not None), ("rectify", rectify is not None and bank is None),
-                                ("channels", channels != 1 and bank is None)):
+            if lines_per_stream and lsd is None and fld is None:
+                raise ValueError("ImagePipeline: lines_per_stream goes with lsd or fld (and cam as a list)")
+            if lsd is not None and fld is not None:
+                raise ValueError("ImagePipeline: one line detector, lsd or fld")
+            for name, given in (("lsd", lsd is not None and not lines_per_stream), ("fld", fld is not None and not lines_per_stream),
+                                ("rectify", rectify is not None and bank is None), ("channels", channels != 1 and bank is None)):
                 if given:
                     raise ValueError(f"ImagePipeline: {name} is not available with one camera per stream (cam as a list): key-points only"
-                                     " (rectify takes a capi.RectifierBank, which also takes channels 3 / 4; lsd takes lines_per_stream = True)")
+                                     " (rectify takes a capi.RectifierBank, which also takes channels 3 / 4; lsd and fld take lines_per_stream = True)")
             self.cams = cam
             if bank is not None:
                 if bank.ctx is not ctx or bank.B < B:
@@ -99,13 +107,14 @@ class ImagePipeline:
         else:
             self.cols, self.rows = cam["width"], cam["height"]
             if lines_per_stream:
-                raise ValueError("ImagePipeline: lines_per_stream goes with one camera per stream (cam as a list) and lsd")
+                raise ValueError("ImagePipeline: lines_per_stream goes with one camera per stream (cam as a list) and lsd or fld")
             if isinstance(rectify, capi.RectifierBank):
                 raise ValueError("ImagePipeline: a capi.RectifierBank goes with one camera per stream (cam as a list)")
         if self.bank is None and calibs is not None:
             raise ValueError("ImagePipeline: calibs goes with rectify = capi.RectifierBank and cam as a list")
         self.rectify = rectify
         self.lsd_min_length_ratio = lsd_min_length_ratio
+        self.fld_min_length_ratio = fld_min_length_ratio
         if rectify is not None and self.bank is None and (rectify.ctx is not ctx or rectify.B < B or rectify.cols != self.cols or rectify.rows != self.rows):
             raise ValueError("ImagePipeline: the rectifier must belong to the same context, hold B pairs and match the image size")
         self.orb = capi.Orb(ctx, 2 * B, self.cols, self.rows, max_kp, nfeatures, fast_threshold, edge_threshold, nlevels, scale_factor,
@@ -120,6 +129,7 @@ class ImagePipeline:
                 raise
         if lsd is not None and fld is not None:
             raise ValueError("ImagePipeline: one line detector, lsd or fld")
+        fld_in = fld
         lp = lsd if lsd is not None else fld
         if lp is not None and (lp.nfeatures == 0 or lp.nfeatures > max_kl):
             import warnings
@@ -127,15 +137,20 @@ class ImagePipeline:
         if lsd is not None and lines_per_stream:  # the opt-in has been given: a size per image at every built blur radius, on a copy
             lsd = capi.LsdParams.from_buffer_copy(lsd)
             lsd.flags |= capi.LSD_SIZES_ANY_RADIUS
+        if fld is not None and lines_per_stream:  # the stores are cut for the smallest threshold the detector is given (stvo_fld_set_image_sizes)
+            fld = capi.FldParams.from_buffer_copy(fld)
+            fld.length_threshold = min([fld.length_threshold] + [L for L in self._fld_thresholds(self.cams, fld.length_threshold)])
         self.lsd = capi.Lsd(ctx, 2 * B, self.cols, self.rows, lsd, max_keylines=max_kl) if lsd is not None else None
         self.fld = capi.Fld(ctx, 2 * B, self.cols, self.rows, fld, max_keylines=max_kl) if fld is not None else None
         self.lines = self.lsd if self.lsd is not None else self.fld  # the key-line detector, or None
         self.lbd = capi.Lbd(ctx, 2 * B, self.cols, self.rows, max_keylines=max_kl) if self.lines is not None else None
-        if self.cams is not None and self.lsd is not None:  # n = B on 2 B images, as for ORB
+        self.fld_length_threshold = fld_in.length_threshold if fld_in is not None else None  # the caller's, for streams without a ratio
+        self.fld_store_threshold = fld.length_threshold if fld is not None else None      # the detector's: what its stores were cut for
+        if self.cams is not None and self.lines is not None:  # n = B on 2 B images, as for ORB
             try:
                 self._set_line_sizes(self.cams)
             except Exception:
-                self.orb.close(); self.lsd.close(); self.lbd.close()
+                self.orb.close(); self.lines.close(); self.lbd.close()
                 raise
         self.seq = capi.Sequences(ctx, B, max_kp, max_kl if self.lines is not None else 64, cam, mp, op)
         self.trajectory = trajectory
@@ -203,11 +218,23 @@ class ImagePipeline:
                                  f"of the bank {self.bank.sizes[k][0]} x {self.bank.sizes[k][1]}")
         return calibs
 
+    def _fld_thresholds(self, cams, own):
+        """the FLD length threshold of every stream's camera: int(ratio * min(width, height)) — llength_th as createFastLineDetector(int)
+        truncates it (src/stereoFrameHandler.cpp:39, src/stereoFrame.cpp:257) — or the caller's where no ratio was given"""
+        r = self.fld_min_length_ratio
+        return [int(own) if r is None else int(r * min(c["width"], c["height"])) for c in cams]
+
     def _set_line_sizes(self, cams):
-        """the size, and minimum line length, of every stream's camera to the line detector and the line descriptor"""
+        """the size, and minimum line length or length threshold, of every stream's camera to the line detector and the line descriptor"""
         sizes = [(c["width"], c["height"]) for c in cams]
-        r = self.lsd_min_length_ratio
-        self.lsd.set_image_sizes(sizes, None if r is None else [r * min(w, h) for w, h in sizes])
+        if self.fld is not None:
+            try:
+                self.fld.set_image_sizes(sizes, self._fld_thresholds(cams, self.fld_length_threshold))
+            except capi.StvoError as e:  # the store rule, or a size or threshold the detector does not take: nothing has changed
+                raise ValueError(f"ImagePipeline: the FLD detector refuses a stream's camera: {e}") from e
+        else:
+            r = self.lsd_min_length_ratio
+            self.lsd.set_image_sizes(sizes, None if r is None else [r * min(w, h) for w, h in sizes])
         self.lbd.set_image_sizes(sizes)
 
     def _calibs_after(self, control, calibs, new_cams):
@@ -227,6 +254,13 @@ class ImagePipeline:
         new = [c if c is not None and ctl[b] == capi.STREAM_RESTART else self.cams[b] for b, c in enumerate(cams)]
         if any(c["width"] > self.cols or c["height"] > self.rows for c in new):
             raise ValueError("ImagePipeline: a camera's images are larger than the slot the pipeline was built with")
+        if self.fld is not None:  # the store rule of stvo_fld_set_image_sizes, before anything is staged
+            have = self.cols * self.rows // (self.fld_store_threshold + 1) + 1
+            for b, (c, L) in enumerate(zip(new, self._fld_thresholds(new, self.fld_length_threshold))):
+                need = c["width"] * c["height"] // (max(L, 0) + 1) + 1
+                if L < 1 or need > have:
+                    raise ValueError(f"ImagePipeline: stream {b}'s camera ({c['width']} x {c['height']}, FLD length threshold {L}) needs a store of "
+                                     f"{need} segments, the detector (created at threshold {self.fld_store_threshold}) holds {have}")
         return new
 
     def set_images(self, left, right, cams=None):
@@ -265,7 +299,8 @@ class ImagePipeline:
         before it detects); the rule at the end of the step leaves the thresholds of restarted and parked streams alone.
         cams (one camera per stream only): None, or B entries — the camera dict of the sequence a RESTART stream begins, None for the
         others: the pipeline (Sequences.restart_cameras) and the detectors (Orb.set_image_sizes, and with lines_per_stream
-        Lsd.set_image_sizes with the stream's minimum length and Lbd.set_image_sizes) take it before the detection.
+        Lsd.set_image_sizes with the stream's minimum length, or Fld.set_image_sizes with its length threshold, and Lbd.set_image_sizes)
+        take it before the detection; a camera the FLD stores cannot hold raises ValueError before anything is staged.
         calibs (rectifier bank only): None, or B entries — the calibration index a RESTART stream takes with its camera, None for the
         others; the size of every stream's calibration must be its camera's, else ValueError and nothing is staged."""
         new = self._cams_after(control, cams) if cams is not None else None
@@ -283,7 +318,7 @@ class ImagePipeline:
                 try:
                     if cams_change:
                         self.orb.set_image_sizes([(c["width"], c["height"]) for c in new])
-                        if self.lsd is not None:
+                        if self.lines is not None:
                             self._set_line_sizes(new)
                     if calibs_change:
                         self.bank.assign(new_k + [0] * (self.bank.B - self.B))
@@ -291,7 +326,7 @@ class ImagePipeline:
                         self.seq.restart_cameras([c if ctl[b] == capi.STREAM_RESTART else None for b, c in enumerate(new)])
                 except Exception:
                     self.orb.set_image_sizes([(c["width"], c["height"]) for c in self.cams])
-                    if self.lsd is not None:
+                    if self.lines is not None:
                         self._set_line_sizes(self.cams)
                     if calibs_change:
                         self.bank.assign(self.calibs + [0] * (self.bank.B - self.B))
