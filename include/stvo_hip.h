@@ -633,9 +633,11 @@ int stvo_lsd_scaled_image(stvo_lsd* lsd, const uint8_t* images, uint8_t* scaled)
  * entry point, for lsd_refine 0 and 1 and at every n_bins: the gradient's bounds, the largest gradient and the bins, the units of the
  * pseudo-ordering, the search's image and its smallest region, the clamps, the response divisor and the pixel count of a key-line are
  * all the image's own.
- *   The route: with a table set the search runs ONE wavefront per image at every batch size; the many-wave form that a detector of up
- * to 128 images otherwise uses is not launched under a table (mixed sizes are the many-streams case; a small batch under a table pays
- * the one-wave time: README, profiles/mixed_lines_bench.json).
+ *   The route: two are built, and stvo_lsd_set_table_route (below) chooses.  STVO_LSD_TABLE_ONE_WAVE, the default: with a table set
+ * the search runs ONE wavefront per image at every batch size; the many-wave form that a detector of up to 128 images otherwise uses
+ * is not launched (a small batch under a table then pays the one-wave time: README, profiles/mixed_lines_bench.json).
+ * STVO_LSD_TABLE_BY_BATCH: a table does not change the route — a detector that launches the many-wave form with no table launches its
+ * table-reading instance under one (README, profiles/lsd_table_route_bench.json).  Either way image i comes back bit for bit the same.
  *   STVO_ERR_INVALID_ARG and nothing changes: n <= 0, n > B, B % n != 0, an entry larger than the slot, an entry stvo_lsd_create would
  * refuse as an image size (a side below 8, nothing left after scaling), a NaN minimum length.  STVO_ERR_UNSUPPORTED and nothing
  * changes: a detector whose blur radius is not 3 at a scale other than 1 (stvo_lsd_geometry tells the radius; every shipped yaml but
@@ -650,6 +652,23 @@ int stvo_lsd_scaled_image(stvo_lsd* lsd, const uint8_t* images, uint8_t* scaled)
  * fills its slot again, on the very kernels of a detector that was never given a table. */
 int stvo_lsd_set_image_sizes(stvo_lsd* lsd, const int32_t* sizes_host /* [n][2] = cols, rows */, const double* min_length_host /* [n] or NULL */,
                              int n);
+/* What a size table does to the route of the search, for the detections enqueued after the call.  HOST ONLY: no device work, no
+ * synchronisation.  STVO_LSD_TABLE_ONE_WAVE (the default): one wavefront per image under a table.  STVO_LSD_TABLE_BY_BATCH: the route
+ * is the one the detector takes with no table — the many-wave search for a detector that holds its scratch (at most 128 images,
+ * lsd_refine 0, a scaled image within the many-wave form's limit, not under STVO_LSD_WAVES=0); any other detector takes the call and
+ * stays on one wave.  The results do not depend on the route.  The value survives stvo_lsd_set_image_sizes, NULL included, and means
+ * nothing while no table is set.  Another value: STVO_ERR_INVALID_ARG and nothing changes. */
+#define STVO_LSD_TABLE_ONE_WAVE 0
+#define STVO_LSD_TABLE_BY_BATCH 1
+int stvo_lsd_set_table_route(stvo_lsd* lsd, int route);
+/* HOST ONLY: the search kernel the next detection launches, as things stand (parameters, batch size, table, table route, developer
+ * switches).  STVO_LSD_SEARCH_ONE_WAVE: one wavefront per image, the fast growth.  STVO_LSD_SEARCH_ONE_WAVE_PLAIN: one wavefront per
+ * image on the plain statement of the growth, with (lsd_refine 1) or without (STVO_LSD_GROW=0) refinement.
+ * STVO_LSD_SEARCH_MANY_WAVES: a committing wave and speculating workgroups per image. */
+#define STVO_LSD_SEARCH_ONE_WAVE 0
+#define STVO_LSD_SEARCH_ONE_WAVE_PLAIN 1
+#define STVO_LSD_SEARCH_MANY_WAVES 2
+int stvo_lsd_search_route(stvo_lsd* lsd, int32_t* route);
 
 /* ---- FLD line detector (use_fld_lines = true) -------------------------------------------------------------------------- */
 

@@ -34,9 +34,11 @@
 //                        (LsdProbe) and run only while stvo_lsd_debug has them switched on; the shipped instances hold none of it
 //   lsd_keylines_kernel  the wrapper: checkLineExtremes, length, min_length, KeyLine fields (numOfPixels = the CLIPPED cv::LineIterator
 //                        count), top-N by response (stable)
-// Every kernel but lsd_grow_xcd_kernel is a template on MIXED: the MIXED instances read their image's row of a size table (one image size
-// and minimum length per image, stvo_lsd_set_image_sizes, csrc/lsd_sizes.h), the others are the kernels as they were.  Under a table the
-// search runs ONE wave per image at every batch size (lsd_grow_kernel / lsd_grow_refine_kernel); lsd_grow_xcd_kernel is not launched.
+// Every kernel is a template on MIXED: the MIXED instances read their image's row of a size table (one image size and minimum length
+// per image, stvo_lsd_set_image_sizes, csrc/lsd_sizes.h), the others are the kernels as they were.  Which search kernel a detection
+// launches is decided in ONE place, csrc/lsd_route.h: under a table ONE wave per image at every batch size by default (lsd_grow_kernel /
+// lsd_grow_refine_kernel), or — stvo_lsd_set_table_route(STVO_LSD_TABLE_BY_BATCH) — the no-table rule, lsd_grow_xcd_kernel<false, true>
+// for a detector that holds the small-batch arena.
 // The scaled image under a table: ORB's MIXED blur and resize at radius 3, the MIXED instance of lsd_blur_resize_kernel at every other
 // radius — for a detector created with STVO_LSD_SIZES_ANY_RADIUS (lsd_scale_kernels.hip, lsd_scale_plan.h).
 // Byte / integer work except where the source computes in floating point; no fused multiply-adds outside the two of the sine /
@@ -50,6 +52,7 @@
 #include "frontend_layout.h"
 #include "gaussian_q8.h"
 #include "line_common.h"
+#include "lsd_route.h"
 #include "lsd_sizes.h"
 #include "table_transport.h"
 
@@ -1095,8 +1098,8 @@ enum { CM_T_SELF, CM_T_WAIT, CM_T_TAKE, CM_TOOK, CM_SELF, CM_BAD, CM_WAITED, CM_
 enum { DP_ITER, DP_CHUNKS, DP_GIVEN, DP_NOIDLE, DP_BLOCKED, DP_N };
 enum { SP_BUSY, SP_REGIONS };
 
-template <bool PROF>
-__global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, LsdXcd x) {
+template <bool PROF, bool MIXED>
+__global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, LsdXcd x, LsdTable<MIXED> tab) {
     __shared__ int s_ring[LSD_XW][LSD_WRING];
     __shared__ double s_term[LSD_XW][3][64];
     __shared__ int s_scan, s_done, s_qhead, s_qtail, s_cwords;
@@ -1106,8 +1109,15 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
     if (b >= d.B) return;
     int xcc;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
+    // Under a table (MIXED) two sizes meet here.  The SLOT's pixel count spx is the STRIDE of everything cut per image at creation:
+    // the blocks of px / k32 / order / pend and, per wave, of stamp / wlist.  The IMAGE's own w, h, npx (its row of the table, known
+    // only now that b is) are every BOUND and every pitch inside a block, where an image lies compactly as in the one-wave kernels:
+    // the walks of the ranks, the dispatcher's scan, x / y of a pixel index, the neighbour bounds, the list capacities, region2rect.
+    // The uniform instances do not make the call and spx is npx: their code is the code they had.
+    const int spx = d.w * d.h;
+    if constexpr (MIXED) lsd_take_image(d, tab, b);
     const int w = d.w, h = d.h, npx = w * h;
-    const size_t base = (size_t)b * npx;
+    const size_t base = (size_t)b * spx;
     LsdPx* px = d.px + base;
     const int32_t* __restrict__ k32 = d.k32 + base;
     const uint32_t* __restrict__ order = d.order + base;
@@ -1116,6 +1126,8 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
     long long* mbox = reinterpret_cast<long long*>(ctl + XC_MBOX);
     const int nw = 1 + x.nsb * LSD_XW;
     // dynamic LDS of the committer's workgroup: its flags, one bit per pixel | the feeder's record ring | the records' descriptors
+    // (MIXED: carved for the IMAGE's npx — one bit per pixel it can index, fewer words to clear; the allocation is cut for the slot
+    // and npx <= spx, so the records behind the bitmap end inside it, and the three waves of the workgroup carve alike)
     extern __shared__ unsigned s_bits[];
     const int nbw = (((npx + 31) / 32) + 3) & ~3;  // (whole 16-byte units: the descriptors behind are int4)
     int* const s_px = reinterpret_cast<int*>(s_bits + nbw);  // [LSD_FEED_PX] per record: its pixel indices, the record's number (mod 256) in the top byte
@@ -1133,7 +1145,15 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
         __syncthreads();
     }
     // keys and table entries of LSD_SB batches per round trip, the next such span requested before this one is worked on (the
-    // committer and the feeder walk the ranks alike)
+    // committer and the feeder walk the ranks alike).
+    // The end of the ranks: lsd_scan_kernel writes LSD_NOKEY into the 128 ranks behind the image's last defined pixel (those below npx:
+    // the image's own under a table), and a rank >= npx reads as LSD_NOKEY here.  Behind the mark `order` may hold the keys of an earlier
+    // detection — one with more defined pixels, or under a table a LARGER image of the same slot, whose pixel indices this image does
+    // not have.  No reader acts on them: the committer and the feeder take batches at multiples of 64 in rank order and stop at the
+    // first batch whose first rank holds LSD_NOKEY — the batch that straddles the last defined rank has the mark in all its later
+    // lanes, the next one begins inside the mark; the dispatcher's chunks begin anywhere, but no further than 64 ranks behind the last
+    // defined one (front <= the end of a chunk that began at a defined rank; the committer's rank is defined), so inside the 128.  The
+    // requests run up to two spans ahead into stale ranks: those keys are loaded (r < npx <= the slot's pixels) and never looked at.
     constexpr int LSD_SB = 4;
     uint32_t kn[LSD_SB], kc[LSD_SB];
     long long en[LSD_SB], ec[LSD_SB];
@@ -1170,7 +1190,7 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
         // and pixel list from the L2 and left a record in rank order.  A seed without a record (its region was not finished when the
         // feeder passed, or the feeder is behind) takes the path through the table.
         __builtin_amdgcn_s_setprio(3);
-        int32_t* wlist = x.wlist + (size_t)b * nw * npx;
+        int32_t* wlist = x.wlist + (size_t)b * nw * spx;
         if (lane == 0) __hip_atomic_store(ctl + XC_ALIVE, xcc + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         int n_seg = 0;
         LsdProbe<PROF> pr(b == 0);  // tools/lsd_probe.py: where the committer's time goes
@@ -1367,7 +1387,7 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                     if (p) {
                         const int off = (int)(p & 0x1FFFFF), n = (int)((p >> 21) & 0x1FFFFF), pw = (int)((p >> 42) & 0x7F);
                         if (n > 0) {
-                            const int32_t* pl = x.wlist + ((size_t)b * nw + pw) * npx + off;  // 4 words of segment, then the pixels
+                            const int32_t* pl = x.wlist + ((size_t)b * nw + pw) * spx + off;  // 4 words of segment, then the pixels
                             const int w0 = lane < n + 4 ? ld_l2(pl + lane) : 0;
                             const bool has = lane >= 4 && lane < n + 4;
                             const int q0 = (w0 >> 16) * w + (w0 & 0xFFFF);
@@ -1483,7 +1503,7 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
                     if (J[k] >= 0) {
                         const long long p = readlane_i64(ent, J[k]);
                         const int off = (int)(p & 0x1FFFFF), n = (int)((p >> 21) & 0x1FFFFF), pw = (int)((p >> 42) & 0x7F);
-                        PL[k] = x.wlist + ((size_t)b * nw + pw) * npx + off;
+                        PL[k] = x.wlist + ((size_t)b * nw + pw) * spx + off;
                         if (lane < n + 4) W[k] = ld_l2(PL[k] + lane);
                     }
                 }
@@ -1604,8 +1624,8 @@ __global__ __launch_bounds__(LSD_XW * 64) void lsd_grow_xcd_kernel(LsdDev d, Lsd
             if (alive != xcc + 1) return;
         }
         const int v = 1 + (role - 1) * LSD_XW + wv;  // this wave among the image's waves
-        int32_t* stamp = x.stamp + ((size_t)b * nw + v) * npx;
-        int32_t* wl = x.wlist + ((size_t)b * nw + v) * npx;
+        int32_t* stamp = x.stamp + ((size_t)b * nw + v) * spx;
+        int32_t* wl = x.wlist + ((size_t)b * nw + v) * spx;
         int id = 0, off = 0;
         LsdProbe<PROF> pr(b == 0);
         LsdProbe<false> quiet(false);
@@ -1781,6 +1801,7 @@ struct stvo_lsd {
     // the detector's own kernels read (LsdSizeRow), then the 2 n rows that drive the shared blur and resize (lsd_sizes.h: lsd_scale_rows)
     TableTransport sizes;
     int n_sizes = 0;          // entries of the table in force; 0: every image fills its slot
+    int table_route = STVO_LSD_TABLE_ONE_WAVE;  // stvo_lsd_set_table_route: what a table does to the search's route (lsd_route.h)
     const stvo::OrbLevelSize* scale_rows() const { return reinterpret_cast<const stvo::OrbLevelSize*>(sizes.dev + (size_t)n_sizes * sizeof(stvo::LsdSizeRow)); }
 };
 
@@ -1803,6 +1824,16 @@ void lsd_scaled_enqueue(stvo_lsd* o, const uint8_t* images) {
     }
 }
 
+static_assert(STVO_LSD_SEARCH_ONE_WAVE == stvo::LSD_SEARCH_ONE_WAVE && STVO_LSD_SEARCH_ONE_WAVE_PLAIN == stvo::LSD_SEARCH_ONE_WAVE_PLAIN &&
+                  STVO_LSD_SEARCH_MANY_WAVES == stvo::LSD_SEARCH_MANY_WAVES && STVO_LSD_TABLE_ONE_WAVE == stvo::LSD_TABLE_ONE_WAVE &&
+                  STVO_LSD_TABLE_BY_BATCH == stvo::LSD_TABLE_BY_BATCH,
+              "lsd_route.h restates the values of stvo_hip.h");
+
+// the facts lsd_route.h decides on, as they stand for the next detection
+stvo::LsdRouteFacts lsd_route_facts(const stvo_lsd* o) {
+    return stvo::LsdRouteFacts{o->prm.refine, o->wdev != nullptr, o->n_sizes != 0, o->table_route, stvo::dbg().lsd_grow, o->d.dbg != nullptr};
+}
+
 int lsd_enqueue(stvo_lsd* o, const uint8_t* images, stvo_keyline* lines, float* response, int32_t* n_lines) {
     stvo_ctx* ctx = o->ctx;
     hipStream_t s = ctx->stream;
@@ -1819,17 +1850,21 @@ int lsd_enqueue(stvo_lsd* o, const uint8_t* images, stvo_keyline* lines, float* 
     const int nunits = (d.w * d.h + stvo::LSD_UNIT - 1) / stvo::LSD_UNIT;
     const dim3 ug((nunits + 3) / 4, d.B);
     const size_t lds_h = (size_t)4 * d.n_bins * 4, lds = (size_t)d.seg_cap * 8;
+    const stvo::LsdRoute route = stvo::lsd_search_route(lsd_route_facts(o));  // the search kernel: decided in lsd_route.h, launched below
+    const dim3 xg(8 * ((d.B + 7) / 8) * (1 + o->xx.nsb)), xb(stvo::LSD_XW * 64);
     if (o->n_sizes) {
-        // One size per image: the MIXED instances of every kernel on the slots' launch grids.  The search runs ONE wave per image at every
-        // batch size (lsd_grow_kernel, lsd_grow_refine_kernel under lsd_refine = 1 or STVO_LSD_GROW=0): lsd_grow_xcd_kernel is not launched
-        // under a table — mixed sizes are the many-streams case, beyond its batch sizes anyway — and neither are the PROF instances.
+        // One size per image: the MIXED instances of every kernel on the slots' launch grids.  No PROF instance exists under a table.
         const stvo::LsdTable<true> tab{reinterpret_cast<const stvo::LsdSizeRow*>(o->sizes.dev), o->n_sizes};
         hipLaunchKernelGGL(stvo::lsd_gradient_kernel<true>, grid, dim3(256), 0, s, d, tab);
         hipLaunchKernelGGL(stvo::lsd_hist_kernel<true>, ug, dim3(256), lds_h, s, d, tab);
         hipLaunchKernelGGL(stvo::lsd_scan_kernel<true>, dim3(d.B), dim3(1024), 0, s, d, tab);
         hipLaunchKernelGGL(stvo::lsd_scatter_kernel<true>, ug, dim3(256), lds_h, s, d, tab);
-        if (o->prm.refine == 1) hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<true, false, true>), dim3(d.B), dim3(64), 0, s, d, o->prm.density_th, tab);
-        else if (stvo::dbg().lsd_grow == 0) hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<false, false, true>), dim3(d.B), dim3(64), 0, s, d, 0.0, tab);
+        if (route.search == STVO_LSD_SEARCH_MANY_WAVES) {  // STVO_LSD_TABLE_BY_BATCH: its scratch is cut for the slots and cleared whole
+            HIP_TRY(ctx, hipMemsetAsync(o->xx.stamp, 0, o->stamp_bytes, s));
+            HIP_TRY(ctx, hipMemsetAsync(o->xx.pend, 0, o->pend_ctl_bytes, s));
+            hipLaunchKernelGGL((stvo::lsd_grow_xcd_kernel<false, true>), xg, xb, o->xcd_lds, s, d, o->xx, tab);
+        } else if (route.search == STVO_LSD_SEARCH_ONE_WAVE_PLAIN && route.refine) hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<true, false, true>), dim3(d.B), dim3(64), 0, s, d, o->prm.density_th, tab);
+        else if (route.search == STVO_LSD_SEARCH_ONE_WAVE_PLAIN) hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<false, false, true>), dim3(d.B), dim3(64), 0, s, d, 0.0, tab);
         else hipLaunchKernelGGL((stvo::lsd_grow_kernel<false, true>), dim3(d.B), dim3(64), 0, s, d, tab);
         hipLaunchKernelGGL(stvo::lsd_keylines_kernel<true>, dim3(d.B), dim3(stvo::KL_T), lds, s, d, tab);
         return check_launch(ctx);
@@ -1840,16 +1875,15 @@ int lsd_enqueue(stvo_lsd* o, const uint8_t* images, stvo_keyline* lines, float* 
     hipLaunchKernelGGL(stvo::lsd_hist_kernel<false>, ug, dim3(256), lds_h, s, d, none);
     hipLaunchKernelGGL(stvo::lsd_scan_kernel<false>, dim3(d.B), dim3(1024), 0, s, d, none);
     hipLaunchKernelGGL(stvo::lsd_scatter_kernel<false>, ug, dim3(256), lds_h, s, d, none);
-    const bool prof = d.dbg != nullptr;  // stvo_lsd_debug has the probes on: the PROF instance of the route's kernel
-    if (o->prm.refine == 1) {  // LSD_REFINE_STD: regions may give their pixels back — the plain one-wave kernel with refinement, for every batch size
+    const bool prof = route.prof;  // stvo_lsd_debug has the probes on: the PROF instance of the route's kernel
+    if (route.search == STVO_LSD_SEARCH_ONE_WAVE_PLAIN && route.refine) {  // LSD_REFINE_STD: regions may give their pixels back — the plain one-wave kernel with refinement, for every batch size
         hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<true, false, false>), dim3(d.B), dim3(64), 0, s, d, o->prm.density_th, none);
-    } else if (o->wdev) {  // small batches: a committing wave + speculating workgroups on the CUs of one XCD per image (lsd_grow_xcd_kernel)
+    } else if (route.search == STVO_LSD_SEARCH_MANY_WAVES) {  // small batches: a committing wave + speculating workgroups on the CUs of one XCD per image (lsd_grow_xcd_kernel)
         HIP_TRY(ctx, hipMemsetAsync(o->xx.stamp, 0, o->stamp_bytes, s));
         HIP_TRY(ctx, hipMemsetAsync(o->xx.pend, 0, o->pend_ctl_bytes, s));  // (the control words lie behind the table)
-        const dim3 xg(8 * ((d.B + 7) / 8) * (1 + o->xx.nsb)), xb(stvo::LSD_XW * 64);
-        if (prof) hipLaunchKernelGGL(stvo::lsd_grow_xcd_kernel<true>, xg, xb, o->xcd_lds, s, d, o->xx);
-        else hipLaunchKernelGGL(stvo::lsd_grow_xcd_kernel<false>, xg, xb, o->xcd_lds, s, d, o->xx);
-    } else if (stvo::dbg().lsd_grow == 0) {  // STVO_LSD_GROW=0: the plain one-wave kernel, nothing refined
+        if (prof) hipLaunchKernelGGL((stvo::lsd_grow_xcd_kernel<true, false>), xg, xb, o->xcd_lds, s, d, o->xx, none);
+        else hipLaunchKernelGGL((stvo::lsd_grow_xcd_kernel<false, false>), xg, xb, o->xcd_lds, s, d, o->xx, none);
+    } else if (route.search == STVO_LSD_SEARCH_ONE_WAVE_PLAIN) {  // STVO_LSD_GROW=0: the plain one-wave kernel, nothing refined
         if (prof) hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<false, true, false>), dim3(d.B), dim3(64), 0, s, d, 0.0, none);
         else hipLaunchKernelGGL((stvo::lsd_grow_refine_kernel<false, false, false>), dim3(d.B), dim3(64), 0, s, d, 0.0, none);
     } else {
@@ -1960,8 +1994,9 @@ int stvo_lsd_create(stvo_ctx* ctx, int B, int cols, int rows, int max_keylines, 
         stvo::carve_lsd_xcd_arena(wsize, B, npx, nw);
         o->xcd_lds = (int)(((((npx + 31) / 32) + 3) & ~size_t(3)) * 4) + stvo::LSD_FEED_PX * 4 + stvo::LSD_FEED_Q * 32;
         if (o->xcd_lds < 84 * 1024) o->xcd_lds = 84 * 1024;
-        ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_grow_xcd_kernel<false>), o->xcd_lds) &&
-             stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_grow_xcd_kernel<true>), o->xcd_lds) &&
+        ok = stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_grow_xcd_kernel<false, false>), o->xcd_lds) &&
+             stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_grow_xcd_kernel<true, false>), o->xcd_lds) &&
+             stvo::lds_opt_in(reinterpret_cast<const void*>(stvo::lsd_grow_xcd_kernel<false, true>), o->xcd_lds) &&  // (the opt-in is per function)
              hip_ok(ctx, hipMalloc((void**)&o->wdev, wsize.off), "hipMalloc lsd xcd");
         if (ok) {
             stvo::Carver cw(o->wdev);
@@ -2026,6 +2061,19 @@ int stvo_lsd_set_image_sizes(stvo_lsd* o, const int32_t* sizes_host, const doubl
     }
     TRY(o->sizes.send(ctx, (size_t)n * entry));
     o->n_sizes = n;
+    return STVO_OK;
+}
+
+// What a size table does to the route of the search (stvo_hip.h).  Host only: a field the next lsd_enqueue reads.
+int stvo_lsd_set_table_route(stvo_lsd* o, int route) {
+    if (!o || !stvo::lsd_table_route_ok(route)) return STVO_ERR_INVALID_ARG;
+    o->table_route = route;
+    return STVO_OK;
+}
+
+int stvo_lsd_search_route(stvo_lsd* o, int32_t* route) {
+    if (!o || !route) return STVO_ERR_INVALID_ARG;
+    *route = stvo::lsd_search_route(lsd_route_facts(o)).search;
     return STVO_OK;
 }
 

@@ -37,7 +37,8 @@ EXPORTS = ["stvo_backend_name", "stvo_abi_version", "stvo_error_string", "stvo_c
            "stvo_seq_export_streams", "stvo_seq_import_streams_dev", "stvo_seq_import_streams", "stvo_orb_set_descriptor",
            "stvo_orb_pattern", "stvo_orb_set_image_sizes", "stvo_seq_restart_cameras", "stvo_rectify_bank_create",
            "stvo_rectify_bank_destroy", "stvo_rectify_bank_camera", "stvo_rectify_bank_assign", "stvo_rectify_bank_images_dev",
-           "stvo_rectify_bank_color_to_gray_dev", "stvo_lsd_set_image_sizes", "stvo_lbd_set_image_sizes", "stvo_fld_set_image_sizes"]
+           "stvo_rectify_bank_color_to_gray_dev", "stvo_lsd_set_image_sizes", "stvo_lbd_set_image_sizes", "stvo_fld_set_image_sizes",
+           "stvo_lsd_set_table_route", "stvo_lsd_search_route"]
 
 SEQ_NSTAGE = 5  # include/stvo_hip.h: STVO_SEQ_NSTAGE
 SEQ_STAGE_NAMES = ("stereo_points_stage", "grid_scan", "hamming_knn2", "reverse_check", "pose")
@@ -321,6 +322,8 @@ def load():
     L.stvo_lsd_scaled_image.argtypes = [C.c_void_p, u8p, u8p]
     L.stvo_lsd_debug.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.stvo_lsd_set_image_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.stvo_lsd_set_table_route.argtypes = [C.c_void_p, C.c_int]
+    L.stvo_lsd_search_route.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.stvo_lbd_set_image_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.stvo_fld_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FldParams), C.POINTER(C.c_void_p)]
     L.stvo_fld_destroy.argtypes = [C.c_void_p]
@@ -638,6 +641,8 @@ class LsdParams(C.Structure):  # stvo_lsd_params
 
 
 LSD_SIZES_ANY_RADIUS = 1  # STVO_LSD_SIZES_ANY_RADIUS
+LSD_TABLE_ONE_WAVE, LSD_TABLE_BY_BATCH = 0, 1  # STVO_LSD_TABLE_*: what a size table does to the route of the search (Lsd.set_table_route)
+LSD_SEARCH_ONE_WAVE, LSD_SEARCH_ONE_WAVE_PLAIN, LSD_SEARCH_MANY_WAVES = 0, 1, 2  # STVO_LSD_SEARCH_*: the search kernel (Lsd.search_route)
 
 
 def lsd_params(min_length=0.0, nfeatures=300, refine=0, scale=1.2, sigma_scale=0.6, quant=2.0, ang_th=22.5, n_bins=1024,
@@ -727,6 +732,20 @@ class Lsd:
         if ml is not None and ml.size != a.shape[0]:
             raise ValueError("Lsd.set_image_sizes: one minimum length per entry of sizes")
         self.ctx._chk(self.ctx.lib.stvo_lsd_set_image_sizes(self.h, _ptr(a), None if ml is None else _ptr(ml), a.shape[0]))
+
+    def set_table_route(self, route):
+        """What a size table does to the route of the search from the next detection on (stvo_lsd_set_table_route, host only):
+        LSD_TABLE_ONE_WAVE (the default) — one wavefront per image under a table; LSD_TABLE_BY_BATCH — the route the detector takes with
+        no table, the many-wave search for a detector of up to 128 images.  The results are the same bytes.  It survives
+        set_image_sizes; StvoError for another value, and the route in force stays."""
+        self.ctx._chk(self.ctx.lib.stvo_lsd_set_table_route(self.h, int(route)))
+
+    def search_route(self):
+        """The search kernel the next detection launches (stvo_lsd_search_route, host only): LSD_SEARCH_ONE_WAVE, LSD_SEARCH_ONE_WAVE_PLAIN
+        (lsd_refine 1, STVO_LSD_GROW=0) or LSD_SEARCH_MANY_WAVES."""
+        r = C.c_int32(-1)
+        self.ctx._chk(self.ctx.lib.stvo_lsd_search_route(self.h, C.byref(r)))
+        return r.value
 
     def scaled_image(self, images):
         """The image the detector core sees (blurred and resized; the input itself at scale 1): uint8 [B, scaled rows, scaled cols]

@@ -22,7 +22,8 @@ class ImagePipeline:
     def __init__(self, ctx, B, cam, mp, op, max_kp=2048, nfeatures=2000, fast_threshold=20, edge_threshold=19, device="cuda:0", nlevels=1,
                  scale_factor=1.2, lsd=None, max_kl=128, rectify=None, fld=None, orb_score=1, adaptive_fast=None,
                  trajectory=None, trajectory_log=1, tracks=0, keyframe_sets=False, channels=1, gray_weights="q14", orb_wta_k=2,
-                 orb_patch_size=31, calibs=None, lines_per_stream=False, lsd_min_length_ratio=None, fld_min_length_ratio=None):
+                 orb_patch_size=31, calibs=None, lines_per_stream=False, lsd_min_length_ratio=None, fld_min_length_ratio=None,
+                 lsd_many_waves=False):
         """cam: one camera dict (width / height = image size) for all B streams, or a list of B dicts, one camera AND image size per stream
         (KITTI 00-02 / 03 / 04-10 side by side): the resident image buffer is then cut in slots of the largest width x the largest height,
         stream b's images occupy the top-left of their slots (set_images takes a list of B arrays of each stream's own size), the
@@ -35,6 +36,10 @@ class ImagePipeline:
         own copy of lsd: lsd_scale 0.5 and the other blur radii run the fused blur + resize per image too); lsd_min_length_ratio = r gives stream b the minimum line length
         r * min(width_b, height_b) of its own camera (the reference's Config::minLineLength() x min(width, height)), None keeps
         lsd.min_length for all; a stream that RESTARTs hands its new size and minimum length to both with its camera.
+        lsd_many_waves = True (with a list, lsd and lines_per_stream; ValueError anywhere else) sets LSD_TABLE_BY_BATCH on that detector
+        (Lsd.set_table_route): up to 64 streams — 128 images per launch — then run the many-wave search under their size table, as the
+        same streams under one camera do; more streams stay on one wave per image.  The same bytes either way; False (the default)
+        keeps one wave per image at every B.
         lines_per_stream = True with a list and fld (not both detectors) is the same opt-in for the FLD detector of use_fld_lines: it
         and LBD are built at the slot size and read every stream's images at that stream's own size (Fld.set_image_sizes);
         fld_min_length_ratio = r gives stream b the length threshold int(r * min(width_b, height_b)) of its own camera (the reference's
@@ -112,6 +117,8 @@ class ImagePipeline:
                 raise ValueError("ImagePipeline: a capi.RectifierBank goes with one camera per stream (cam as a list)")
         if self.bank is None and calibs is not None:
             raise ValueError("ImagePipeline: calibs goes with rectify = capi.RectifierBank and cam as a list")
+        if lsd_many_waves and not (self.cams is not None and lsd is not None and lines_per_stream):
+            raise ValueError("ImagePipeline: lsd_many_waves goes with one camera per stream (cam as a list), lsd and lines_per_stream = True")
         self.rectify = rectify
         self.lsd_min_length_ratio = lsd_min_length_ratio
         self.fld_min_length_ratio = fld_min_length_ratio
@@ -148,6 +155,8 @@ class ImagePipeline:
         self.fld_store_threshold = fld.length_threshold if fld is not None else None      # the detector's: what its stores were cut for
         if self.cams is not None and self.lines is not None:  # n = B on 2 B images, as for ORB
             try:
+                if lsd_many_waves:  # the size table below does not move the search off the route of the batch size
+                    self.lsd.set_table_route(capi.LSD_TABLE_BY_BATCH)
                 self._set_line_sizes(self.cams)
             except Exception:
                 self.orb.close(); self.lines.close(); self.lbd.close()
